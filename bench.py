@@ -8,17 +8,19 @@ gray, synth-kitti renderer), all resident in HBM before the clock starts.
         ONE sequence (front end batched over the B pairs, then the ordered tail frame by frame);
         B = 4541 // (warmup + steps), the remainder rides in the first warm-up step so that the
         whole sequence is tracked and ATE is over all of it.  The timed region runs the product's
-        default schedule (no profiling hooks); per-kernel HIP-event times come from a separate,
-        untimed pass over the first frames, the tail's critical path from in-kernel wall-clock
-        stamps of the timed region itself.
+        default schedule (no profiling hooks); with --full, per-kernel HIP-event times come from a
+        separate, untimed pass over the first frames, the tail's critical path from in-kernel
+        wall-clock stamps of the timed region itself.
   --workload frontend (BASELINE configs[1], batched): ORB on both images + sparse epipolar
         stereo for B pairs per step, rotating through the resident sequence.
   --shard: BASELINE configs[3] as the reference would run it - ONE sequence, ONE process, --gpus G
         contexts (one per GPU when the box has G GPUs, otherwise all on GPU 0): pair k's front end
         on context k mod G, the ordered tail on context 0 (svo_track_sharded_dev).
-The default line also carries named legs: "frontend", "multi_sequence", "sharded", "semantic_elas"
-(configs[4] as a whole), "elas", "msa", and the CPU baseline (the oracle's single-thread port on a
-bounded prefix; its tail alone over ALL tracked frames for the counter / ATE comparison).
+A plain run sets up, warms up, times --steps steps and prints the line (--dump-outputs DIR: the last
+timed step's outputs as .npy files).  With --full the line also carries the roofline, named legs:
+"frontend", "multi_sequence", "sharded", "semantic_elas" (configs[4] as a whole), "elas", "msa", and
+the CPU baseline (the oracle's single-thread port on a bounded prefix; its tail alone over ALL tracked
+frames for the counter / ATE comparison).
 N > 1: `python bench.py --gpus N` starts the N ranks itself (torch.distributed.run as a child
 process, before this process touches a GPU) unless it already runs under one; one process per GPU
 (backend nccl = RCCL, used ONLY for the barrier and the max-over-ranks clock).  The tracking chain
@@ -135,9 +137,52 @@ def pmc_valu(kernel):
         return None
 
 
+def render_views(synth, T_wc, eye_offset_x, frames, view, seed, dev, noise_sigma=2.0):
+    """synth.render_view for a chunk of frames at once: the same elementwise operations in the same order, with the frame as
+    a leading dimension (the per-frame values broadcast from (c, 1, 1)), so every pixel is bit for bit the one
+    synth.render_sequence renders.  The renderer issues ~300 small kernels per view; one view at a time, the 9,082 views of
+    the headline's sequence took a minute of launches before the clock started."""
+    import math
+    import torch
+    cam = synth.KITTI00
+    T = T_wc.to(dev, torch.float32)
+    R, C = T[:, :3, :3], T[:, :3, 3] + T[:, :3, 0] * eye_offset_x
+
+    def b(x):                                            # (c,) per-frame value -> (c, 1, 1)
+        return x[:, None, None]
+    v, u = torch.meshgrid(torch.arange(cam["H"], device=dev, dtype=torch.float32),
+                          torch.arange(cam["W"], device=dev, dtype=torch.float32), indexing="ij")
+    dcx, dcy = (u - cam["cx"]) / cam["fx"], (v - cam["cy"]) / cam["fy"]
+    dwx = b(R[:, 0, 0]) * dcx + b(R[:, 0, 1]) * dcy + b(R[:, 0, 2])
+    dwy = b(R[:, 1, 0]) * dcx + b(R[:, 1, 1]) * dcy + b(R[:, 1, 2])
+    dwz = b(R[:, 2, 0]) * dcx + b(R[:, 2, 1]) * dcy + b(R[:, 2, 2])
+    y_ground, y_canopy = 1.65, -4.0
+    eps = 1e-6
+    down = dwy > eps
+    up = dwy < -eps
+    t = torch.where(down, b(y_ground - C[:, 1]) / torch.where(down, dwy, torch.ones_like(dwy)),
+                    torch.where(up, b(y_canopy - C[:, 1]) / torch.where(up, dwy, -torch.ones_like(dwy)),
+                                torch.full_like(dwy, 1e6)))
+    t = torch.clamp(t, 0.1, 1e6)
+    px, pz = b(C[:, 0]) + t * dwx, b(C[:, 2]) + t * dwz
+    img_g = synth._texture(px, pz, 0, t, cam["fx"], seed)
+    img_c = synth._texture(px, pz, 1, t, cam["fx"], seed)
+    img = torch.where(down, img_g, torch.where(up, img_c, torch.full_like(img_g, 128.0)))
+    haze = torch.clamp(t / 300.0, 0.0, 1.0)
+    img = img * (1 - haze) + 128.0 * haze
+    if noise_sigma > 0:
+        ui, vi = u.to(torch.int64), v.to(torch.int64)
+        fr = b(torch.as_tensor(frames, dtype=torch.int64, device=dev) * 2 + view)
+        n = (synth._hash01(ui, vi, fr, torch.full_like(ui, 11)) + synth._hash01(ui, vi, fr, torch.full_like(ui, 23)) +
+             synth._hash01(ui, vi, fr, torch.full_like(ui, 37)) + synth._hash01(ui, vi, fr, torch.full_like(ui, 41)) - 2.0)
+        img = img + n * (noise_sigma / math.sqrt(4.0 / 12.0))
+    return torch.clamp(torch.round(img), 0, 255).to(torch.uint8)
+
+
 def render_frames(synth, n, dev, seed, start=0):
     """n consecutive frames resident on `dev`, padded to PITCH; + ground truth.  synth-kitti by
-    default; real KITTI 00 frames when KITTI_ROOT is set (layout of the reference's main.cpp:20-57).
+    default (synth.render_sequence's frames, rendered a chunk at a time by render_views); real KITTI 00
+    frames when KITTI_ROOT is set (layout of the reference's main.cpp:20-57).
     Rendered / loaded in chunks so that only the padded uint8 frames stay resident."""
     import numpy as np
     import torch
@@ -147,6 +192,7 @@ def render_frames(synth, n, dev, seed, start=0):
     Ts = []
     kio = importlib.import_module("stereo_semantic_vo_amd.kitti_io") if root else None
     gt = kio.load_poses(root, "00") if root else None
+    T_all = None if root else synth.trajectory(start + n)[start:]
     for c0 in range(0, n, 64):
         c = min(64, n - c0)
         if root:
@@ -155,7 +201,10 @@ def render_frames(synth, n, dev, seed, start=0):
             T = torch.from_numpy(gt[start + c0:start + c0 + c] if gt is not None else np.tile(np.eye(4), (c, 1, 1)))
             L, R = torch.from_numpy(Ln).to(dev), torch.from_numpy(Rn).to(dev)
         else:
-            L, R, T = synth.render_sequence(c, seed=seed, device=dev, start=start + c0)
+            T = T_all[c0:c0 + c]
+            frames = list(range(start + c0, start + c0 + c))
+            L = render_views(synth, T, 0.0, frames, 0, seed, dev)
+            R = render_views(synth, T, synth.KITTI00["bf"] / synth.KITTI00["fx"], frames, 1, seed, dev)
         dL[c0:c0 + c, :, :W] = L
         dR[c0:c0 + c, :, :W] = R
         Ts.append(T)
@@ -1139,6 +1188,37 @@ def emit(out):
     sys.stdout.flush()
 
 
+DUMP_LIMIT = 64 << 20   # bytes: --dump-outputs writes at most this much (a fixed, seeded sample of rows beyond it)
+
+
+def dump_outputs(path, pkg, track, multi, d_res, B, extra, nsteps, frontend=None):
+    """--dump-outputs: what the timed path's last step handed its caller, one float32 / float64 .npy per array, rows = frames
+    (pairs) of that step.  track: its svo_track_batch_dev records (svo_track_multi_step_dev's with --sequences), one file per
+    field of TRACK_DTYPE (track_Tcw float32, the counters as float64); frontend: the left keypoint counts and the per-keypoint
+    stereo depths of its B pairs.  The inputs are the seeded sequence, so two builds compare output for output."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    s = nsteps - 1
+    if track:
+        off, nb = (s * B, B) if multi else (s * B + (extra if s > 0 else 0), B + (extra if s == 0 else 0))
+        rec = d_res[off:off + nb].cpu().numpy().view(pkg.TRACK_DTYPE).reshape(-1)
+        arrays = {"track_" + f: rec[f].astype(np.float32 if rec.dtype[f].base.kind == "f" else np.float64) for f in rec.dtype.names}
+    else:
+        d_n, d_depth = frontend
+        arrays = {"frontend_n_kp_left": d_n.cpu().numpy().astype(np.float64), "frontend_depth": d_depth.cpu().numpy().astype(np.float32)}
+    rows = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:                       # the same rows of every array, chosen by a fixed seed
+        keep = np.sort(np.random.default_rng(0).choice(rows, max(1, DUMP_LIMIT // (total // rows + 8)), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["sampled_rows"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    progress("outputs of the last timed step (%d rows) written to %s" % (rows, path))
+
+
 # ------------------------------------------------------------------------------------------------ main
 def spawn_ranks(args):
     """`python bench.py --gpus N` outside a launcher: start the N ranks as a CHILD process group before this process makes
@@ -1284,7 +1364,18 @@ def main():
                     help="track workload: S concurrent sequences per GPU (svo_track_multi_step_dev), one frame of each per step")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL; default) or gloo (single-GPU dry runs)")
     ap.add_argument("--share-gpu", action="store_true", help="all ranks / contexts use cuda:0 (dry run of the N>1 path on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the in-kernel stamps of the tail's critical path, the per-kernel profile pass "
+                         "and roofline, the CPU baselines and the all-frames oracle comparison, the legs, and rank 0's sharded run for "
+                         "N > 1 (the --no-* options switch parts of it off).  Without it a run sets up, warms up, times the steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_profile = args.no_cpu_baseline = args.no_legs = args.no_shard_leg = True
+    if args.dump_outputs and args.shard:
+        raise SystemExit("bench.py: --dump-outputs is not supported with --shard")
     global DETAIL_PATH
     DETAIL_PATH = args.detail_path
     if args.watchdog > 0:
@@ -1449,9 +1540,12 @@ def main():
     dt = time.perf_counter() - t0
     progress("timed region done")
     dt = shard.max_over_ranks(dt, dist, dev if args.dist_backend == "nccl" else "cpu")
-    # in-kernel wall-clock stamps of the last timed step's frames (always written, free)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pkg, track, multi, d_res if track else None, B, extra, nsteps,
+                     None if track else (d_n, d_depth))
+    # in-kernel wall-clock stamps of the last timed step's frames (always written, free; read with --full)
     chain = None
-    if track and not multi and rank == 0:
+    if args.full and track and not multi and rank == 0:
         try:
             chain = tail_chain_from_stamps(svo.debug_track_frames(0, B))
         except Exception as e:  # noqa: BLE001
@@ -1526,7 +1620,7 @@ def main():
             "scaling": "weak", "vs_baseline": None, "dtype": "u8",
             "data": "kitti00" if os.environ.get("KITTI_ROOT") else "synthetic", "config": cfg,
         }
-        if track and not multi:
+        if args.full and track and not multi:
             try:
                 cfg["stream_probe"] = {"candidates_tried": int(svo.debug_stream_probe()[0]), "two_chains_vs_one_percent": int(svo.debug_stream_probe()[1])}
             except Exception:  # noqa: BLE001

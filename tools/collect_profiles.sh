@@ -19,7 +19,7 @@ FULL=1
 if [ "$WL" = "track" ]; then
   ARGS="--workload track --frames 1000 --steps 4 --warmup 1 --no-cpu-baseline --no-profile --no-legs $*"
 elif [ "$WL" = "legs" ]; then
-  ARGS="--workload track --frames 600 --steps 2 --warmup 1 --no-cpu-baseline --no-profile $*"
+  ARGS="--workload track --frames 600 --steps 2 --warmup 1 --full --no-cpu-baseline --no-profile $*"
   FULL=0
 else
   ARGS="--workload frontend --frames 1536 --steps 10 --warmup 2 --no-cpu-baseline --no-profile --no-legs $*"
