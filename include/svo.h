@@ -35,7 +35,7 @@ extern "C" {
 #define SVO_ABI_VERSION 7   /* 7 (round 6): + svo_track_batch_host, svo_track_sharded_host, svo_frontend_batch_host (pipelined host-fed entries:
                               images start in host memory, uploads run on a copy stream ahead of the front end, records come back to
                               host memory; svo_boxes_host), svo_create_ex (per-context stream mode), svo_stream_mode; svo_sync also
-                              completes the host-fed calls' outputs.
+                              completes the host-fed calls' outputs.  Later: version 4's two-launch RANSAC switch is no longer accepted (SVO_E_INVALID).
                               6 (round 5, late): + svo_debug_stream_pipes.  BEHAVIOUR: a context's four main streams are hardware queues of their own,
                               created back to back at svo_create (four dispatch pipes; see svo_debug_stream_pipes) - they are BLOCKING
                               streams (they order against the NULL stream, as every hipExtStreamCreateWithCUMask stream does) without a
@@ -44,7 +44,7 @@ extern "C" {
                               svo_debug_stream_probe's second value is now a ratio in per cent (see there); "epnp_exact" accepts every
                               non-zero value again (ABI 3's meaning); svo_destroy waits for batched / sharded work in flight.
                               4 (round 4): + svo_track_epnp_fallbacks, svo_debug_stream_probe; "epnp_exact" defaults to 2 (the
-                              order-preserving solver); options gate_group, hyp_first, dense_cu_percent, dense_two_launch,
+                              order-preserving solver); options gate_group, hyp_first, dense_cu_percent, a two-launch RANSAC switch,
                               epnp_force_seq, shard_force_staged; svo_track_sharded_dev overlaps consecutive calls.
                               No signature of version 3 changed.  BEHAVIOUR changes a version-3 caller sees: (i) the tracker's
                               default RANSAC solver is the bit-comparable one - 8.8 k instead of 14.4 k frames/s on the headline
@@ -252,10 +252,7 @@ void svo_destroy(svo_ctx* ctx);
  *   leaves when the loop can never reach it - 8 CUs' float64 pipelines per ordinary frame instead of 100 taken from the dense
  *   kernels, still two launches per frame (configs[4]: 6.1-6.5 k -> 6.4-6.6 k frames/s at 256 frames per call).  2 = also with
  *   eight or more sequences per step (measured slower: 99.5 k instead of 100.9 k pairs/s; a switch).  0 = off.  Same records.
- * "epnp_force_seq" (default 0, tests): 1 = mode 2 takes its sequential fallback for every sample.
- * "dense_two_launch" (default 0): svo_track_batch_dev with depth_source = 1: the tail beside the dense stage launches its RANSAC
- *   samples as in the many-sequence mode (see "hyp_first") - fewer CUs taken from ELAS on ordinary frames.  Measured: no gain
- *   (6.4 k -> 6.2 k frames/s); kept as a switch.  Same records. */
+ * "epnp_force_seq" (default 0, tests): 1 = mode 2 takes its sequential fallback for every sample. */
 int svo_set_option(svo_ctx* ctx, const char* key, int value);
 /* Block until everything enqueued on the ctx stream has finished. */
 int svo_sync(svo_ctx* ctx);

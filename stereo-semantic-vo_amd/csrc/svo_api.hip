@@ -387,7 +387,6 @@ extern "C" int svo_set_option(svo_ctx* ctx, const char* key, int value) {
   if (!strcmp(key, "pose_flag")) { ctx->opt_pose_flag = value != 0; return SVO_OK; }
   if (!strcmp(key, "gate_group")) { ctx->opt_gate_group = value != 0; return SVO_OK; }
   if (!strcmp(key, "hyp_first")) { if (value < 4 || value > 16 || (value & 3)) return SVO_E_INVALID; ctx->opt_hyp_first = value; return SVO_OK; }
-  if (!strcmp(key, "dense_two_launch")) { ctx->opt_dense_two_launch = value != 0; return SVO_OK; }
   if (!strcmp(key, "epnp_exact")) {
     // 0 the statistical solver, 2 the order-preserving one (default); every other value is ABI 3's "non-zero": the one-lane checker
     ctx->opt_epnp_exact = value == 0 ? 0 : value == 2 ? 2 : 1;
@@ -482,7 +481,7 @@ extern "C" int svo_orb_extract(svo_ctx* ctx, const uint8_t* gray, int stride, sv
   hipSetDevice(ctx->device);
   int rc = upload_image(ctx, gray, stride, 0);
   if (rc) return rc;
-  rc = svo_launch_orb(ctx, ctx->d_stage, ctx->d_stage, ctx->stage_pitch, 1, 1);
+  rc = svo_launch_orb(ctx, ctx->stream, svo_fe_own(ctx), ctx->d_stage, ctx->d_stage, ctx->stage_pitch, 1, 1);
   if (rc) return rc;
   int32_t cnt = 0;
   SVO_HIP(ctx, hipMemcpyAsync(&cnt, ctx->d_nkp, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -554,9 +553,10 @@ extern "C" int svo_stereo_frame_ex(svo_ctx* ctx, const uint8_t* grayL, int strid
   if (rc) return rc;
   const uint8_t* dL = ctx->d_stage;
   const uint8_t* dR = ctx->d_stage + (size_t)ctx->g.H * ctx->stage_pitch;
-  rc = svo_launch_orb(ctx, dL, dR, ctx->stage_pitch, 1, 2);
+  const SvoFeBufs fb = svo_fe_own(ctx);
+  rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 2);
   if (rc) return rc;
-  rc = svo_launch_stereo(ctx, dL, dR, ctx->stage_pitch, 1, cam);
+  rc = svo_launch_stereo(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, cam);
   if (rc) return rc;
   int32_t cnt[2] = {0, 0};
   const size_t K = ctx->max_kp;
@@ -856,37 +856,23 @@ extern "C" int svo_debug_epnp5(svo_ctx* ctx, const double Xw5[15], const double 
 
 // ---- throughput mode ---------------------------------------------------------------------
 // The front end of pairs p0 .. p0 + b - 1 of a batch on stream `st`, in image slots 2 p0 .. 2 p0 + 2 b - 1 of the working
-// set (left images first, then the right ones), results copied to the caller's arrays.  The launchers read the
-// context's working-set pointers and stream: they are pointed at the slice for the duration of the call.
+// set (left images first, then the right ones), results copied to the caller's arrays.
 static int frontend_slice(svo_ctx* ctx, hipStream_t st, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int p0, int b,
                           const svo_camera* cam, svo_kp* d_kpL, uint8_t* d_descL, int32_t* d_nL, float* d_uR, float* d_depth) {
-  const SvoGeom& g = ctx->g;
-  const size_t K = ctx->max_kp, base = 2 * (size_t)p0, img = (size_t)g.H * stride;
-  struct Saved {
-    uint8_t* pyr; uint32_t* corners; int32_t *counters, *hist; SvoSel* sel; int32_t* selcnt; svo_kp* kp; uint8_t* desc; int32_t* nkp;
-    float *uR, *depth; int32_t* sad; hipStream_t stream;
-  } sv{ctx->d_pyr, ctx->d_corners, ctx->d_counters, ctx->d_hist, ctx->d_sel, ctx->d_selcnt, ctx->d_kp, ctx->d_desc, ctx->d_nkp,
-       ctx->d_uR, ctx->d_depth, ctx->d_sad, ctx->stream};
-  ctx->d_pyr += base * g.pyr_bytes; ctx->d_corners += base * g.corner_entries; ctx->d_counters += base * SVO_NLEVELS;
-  ctx->d_hist += base * SVO_NLEVELS * 256; ctx->d_sel += base * SVO_NLEVELS * SVO_QMAX; ctx->d_selcnt += base * SVO_NLEVELS;
-  ctx->d_kp += base * K; ctx->d_desc += base * K * 32; ctx->d_nkp += base;
-  ctx->d_uR += (size_t)p0 * K; ctx->d_depth += (size_t)p0 * K; ctx->d_sad += (size_t)p0 * K;
-  ctx->stream = st;
-  int rc = svo_launch_orb(ctx, d_grayL + p0 * img, d_grayR + p0 * img, stride, b, 2 * b);
-  if (rc == SVO_OK) rc = svo_launch_stereo(ctx, d_grayL + p0 * img, d_grayR + p0 * img, stride, b, cam);
+  const size_t K = ctx->max_kp, img = (size_t)ctx->g.H * stride;
+  const SvoFeBufs fb = svo_fe_own(ctx).at(ctx->g, K, 2 * (size_t)p0, p0);
+  int rc = svo_launch_orb(ctx, st, fb, d_grayL + p0 * img, d_grayR + p0 * img, stride, b, 2 * b);
+  if (rc == SVO_OK) rc = svo_launch_stereo(ctx, st, fb, d_grayL + p0 * img, d_grayR + p0 * img, stride, b, cam);
   if (rc == SVO_OK) {
     auto d2d = [&](void* dst, const void* src, size_t bytes) {
       if (dst && hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) rc = SVO_E_HIP;
     };
-    d2d(d_kpL ? d_kpL + (size_t)p0 * K : nullptr, ctx->d_kp, sizeof(svo_kp) * K * b);
-    d2d(d_descL ? d_descL + (size_t)p0 * K * 32 : nullptr, ctx->d_desc, 32 * K * b);
-    d2d(d_nL ? d_nL + p0 : nullptr, ctx->d_nkp, 4 * (size_t)b);
-    d2d(d_uR ? d_uR + (size_t)p0 * K : nullptr, ctx->d_uR, 4 * K * b);
-    d2d(d_depth ? d_depth + (size_t)p0 * K : nullptr, ctx->d_depth, 4 * K * b);
+    d2d(d_kpL ? d_kpL + (size_t)p0 * K : nullptr, fb.kp, sizeof(svo_kp) * K * b);
+    d2d(d_descL ? d_descL + (size_t)p0 * K * 32 : nullptr, fb.desc, 32 * K * b);
+    d2d(d_nL ? d_nL + p0 : nullptr, fb.nkp, 4 * (size_t)b);
+    d2d(d_uR ? d_uR + (size_t)p0 * K : nullptr, fb.uR, 4 * K * b);
+    d2d(d_depth ? d_depth + (size_t)p0 * K : nullptr, fb.depth, 4 * K * b);
   }
-  ctx->d_pyr = sv.pyr; ctx->d_corners = sv.corners; ctx->d_counters = sv.counters; ctx->d_hist = sv.hist; ctx->d_sel = sv.sel;
-  ctx->d_selcnt = sv.selcnt; ctx->d_kp = sv.kp; ctx->d_desc = sv.desc; ctx->d_nkp = sv.nkp; ctx->d_uR = sv.uR; ctx->d_depth = sv.depth;
-  ctx->d_sad = sv.sad; ctx->stream = sv.stream;
   return rc;
 }
 

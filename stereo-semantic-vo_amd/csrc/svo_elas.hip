@@ -1165,12 +1165,12 @@ int elas_phase_a(svo_ctx* ctx, hipStream_t s, const ElasTab* d_tab, int B, int p
   svo_elas_params pk = p;   // what the kernels see: the lattice step already adjusted (elas.cpp:379-381)
   pk.candidate_stepsize = p.candidate_stepsize + (p.subsampling ? p.candidate_stepsize % 2 : 0);
   {
-    SvoTimer t(ctx, "k_elas_desc");
+    SvoTimer t(ctx, "k_elas_desc", s);
     hipLaunchKernelGGL(k_elas_desc, dim3((W + DT_X - 1) / DT_X, (H + DT_Y - 1) / DT_Y, 2 * B), dim3(256), 0, s, d_tab,
                        pitch, W, H, p.subsampling);
   }
   if (Wc > 1 && Hc > 1) {
-    SvoTimer t(ctx, "k_elas_support");
+    SvoTimer t(ctx, "k_elas_support", s);
     const int ncand = (Wc - 1) * (Hc - 1);
     hipLaunchKernelGGL(k_elas_support, dim3((ncand + 3) / 4, B), dim3(256), 0, s, d_tab, W, H, Wc, Hc, pk);
   }
@@ -1239,7 +1239,7 @@ void elas_triangulate(int cap_tri, const svo_elas_taps* taps, ElasWork& w, bool 
 // disparity grids.  In the one-pair path this runs while the host triangulates.
 int elas_phase_b_grids(svo_ctx* ctx, hipStream_t s, const ElasTab* d_tab, int B, int max_nsp, int gw, int gh,
                        const svo_elas_params& p) {
-  SvoTimer t(ctx, "k_elas_grid");
+  SvoTimer t(ctx, "k_elas_grid", s);
   hipLaunchKernelGGL(k_elas_grid_mark, dim3((std::max(max_nsp, 1) + 255) / 256, B), dim3(256), 0, s, d_tab, p.grid_size,
                      p.disp_max, gw, gh);
   hipLaunchKernelGGL(k_elas_grid_diffuse, dim3((gw * gh * 8 + 255) / 256, 2, B), dim3(256), 0, s, d_tab, gw, gh);
@@ -1261,15 +1261,15 @@ int elas_phase_b(svo_ctx* ctx, hipStream_t s, const ElasTab* d_tab, int B, int m
   int rc;
   if (max_nt > 0) {
     {
-      SvoTimer t(ctx, "k_elas_planes");
+      SvoTimer t(ctx, "k_elas_planes", s);
       hipLaunchKernelGGL(k_elas_planes, dim3((max_nt + 63) / 64, 2, ub), dim3(64), 0, s, d_tab);
     }
-    SvoTimer t(ctx, "k_elas_raster");
+    SvoTimer t(ctx, "k_elas_raster", s);
     hipLaunchKernelGGL(k_elas_raster, dim3((max_nt + 3) / 4, 2, ub), dim3(256), 0, s, d_tab, W, H, sub);
   }
   const dim3 pix((Wd + 255) / 256, Hd, ub), pix2((Wd + 255) / 256, Hd, 2 * ub);
   {
-    SvoTimer t(ctx, "k_elas_match");
+    SvoTimer t(ctx, "k_elas_match", s);
     hipLaunchKernelGGL(k_elas_match, pix2, dim3(256), 0, s, d_tab, d_P, W, H, gw, gh, gd, plane_radius, p);
   }
   if (taps) {
@@ -1301,7 +1301,7 @@ int elas_phase_b(svo_ctx* ctx, hipStream_t s, const ElasTab* d_tab, int B, int m
     if ((rc = tap(ctx, s, taps->D2_raw, tap_e->raw1, n))) return rc;
   }
   {
-    SvoTimer t(ctx, "k_elas_lr");
+    SvoTimer t(ctx, "k_elas_lr", s);
     hipLaunchKernelGGL(k_elas_lr, pix, dim3(256), 0, s, d_tab, Wd, Hd, p.lr_threshold, sub);
   }
   if (taps) { if ((rc = tap(ctx, s, taps->D1_lr, tap_e->out0, n))) return rc; if ((rc = tap(ctx, s, taps->D2_lr, tap_e->out1, n))) return rc; }
@@ -1323,7 +1323,7 @@ int elas_phase_b(svo_ctx* ctx, hipStream_t s, const ElasTab* d_tab, int B, int m
   const char* cc_env = getenv("SVO_ELAS_CC_STRIPS");
   const bool use_strips = strip_ok && strip_lds <= 150 * 1024 && Hd > CCS_ROWS && (!cc_env || atoi(cc_env) != 0);
   for (int side = 0; side < nsides; ++side) {
-    SvoTimer t(ctx, "k_cc_segments");
+    SvoTimer t(ctx, "k_cc_segments", s);
     if (use_strips) {
       const int nstrips = (Hd + CCS_ROWS - 1) / CCS_ROWS;
       hipLaunchKernelGGL(k_cc_strip, dim3(nstrips, ub), dim3(256), strip_lds, s, d_tab, side, Wd, Hd, p.speckle_sim_threshold);
@@ -1340,7 +1340,7 @@ int elas_phase_b(svo_ctx* ctx, hipStream_t s, const ElasTab* d_tab, int B, int m
   }
   if (taps) { if ((rc = tap(ctx, s, taps->D1_seg, tap_e->out0, n))) return rc; if ((rc = tap(ctx, s, taps->D2_seg, tap_e->out1, n))) return rc; }
   for (int side = 0; side < nsides; ++side) {
-    SvoTimer t(ctx, "k_elas_gap");
+    SvoTimer t(ctx, "k_elas_gap", s);
     hipLaunchKernelGGL(k_elas_gap, dim3(Hd, ub), dim3(256), 0, s, d_tab, side, Wd, 1, Wd, gap_width, p.add_corners);
     int C = 32;   // columns per tile: val (4 B) + next-valid (2 B) per pixel within 60 KB of dynamic LDS
     while (C > 1 && (size_t)Hd * C * 6 > 60 * 1024) C >>= 1;
@@ -1350,14 +1350,14 @@ int elas_phase_b(svo_ctx* ctx, hipStream_t s, const ElasTab* d_tab, int B, int m
   if (taps) { if ((rc = tap(ctx, s, taps->D1_gap, tap_e->out0, n))) return rc; if ((rc = tap(ctx, s, taps->D2_gap, tap_e->out1, n))) return rc; }
   if (p.filter_adaptive_mean)
     for (int side = 0; side < nsides; ++side) {
-      SvoTimer t(ctx, "k_elas_mean");
+      SvoTimer t(ctx, "k_elas_mean", s);
       hipLaunchKernelGGL(k_elas_mean_h, pix, dim3(256), 0, s, d_tab, side, Wd, Hd, sub);
       hipLaunchKernelGGL(k_elas_mean_v, pix, dim3(256), 0, s, d_tab, side, Wd, Hd, sub);
     }
   if (taps) { if ((rc = tap(ctx, s, taps->D1_mean, tap_e->out0, n))) return rc; if ((rc = tap(ctx, s, taps->D2_mean, tap_e->out1, n))) return rc; }
   if (p.filter_median)
     for (int side = 0; side < nsides; ++side) {
-      SvoTimer t(ctx, "k_elas_median");
+      SvoTimer t(ctx, "k_elas_median", s);
       hipLaunchKernelGGL(k_elas_median_h, pix, dim3(256), 0, s, d_tab, side, Wd, Hd);
       hipLaunchKernelGGL(k_elas_median_v, pix, dim3(256), 0, s, d_tab, side, Wd, Hd);
     }
@@ -1512,21 +1512,18 @@ int svo_elas_run_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pit
   return elas_core(ctx, st, dL, dR, pitch, W, H, *params, nullptr, dD1, dD2, produced);
 }
 
-// svo_elas_batch_dev with a hook: hook(user, f0, b) runs on the calling thread right after the last GPU phase of the pairs
-// f0 .. f0 + b - 1 has been ENQUEUED on the ctx stream (their `produced` flags are final) - the batched tracker hangs the
-// per-keypoint depth lookups and the ordered tail of those frames on it, so that they run while later chunks are still in the
-// dense stage (BASELINE configs[4] as a pipeline).
-int svo_elas_batch_dev_hooked(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H,
-                              int B, const svo_elas_params* params, float* d_D1, float* d_D2, int32_t* produced,
-                              int (*hook)(void*, int, int), void* user);
 extern "C" int svo_elas_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H,
                                   int B, const svo_elas_params* params, float* d_D1, float* d_D2, int32_t* produced) {
-  return svo_elas_batch_dev_hooked(ctx, d_L, d_R, stride, W, H, B, params, d_D1, d_D2, produced, nullptr, nullptr);
+  if (!ctx) return SVO_E_INVALID;
+  return svo_elas_batch_dev_hooked(ctx, ctx->stream, d_L, d_R, stride, W, H, B, params, d_D1, d_D2, produced, nullptr, nullptr);
 }
-int svo_elas_batch_dev_hooked(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H,
+// svo_elas_batch_dev on stream `s`, with a hook: hook(user, f0, b) runs on the calling thread right after the last GPU phase of the
+// pairs f0 .. f0 + b - 1 has been ENQUEUED on `s` (their `produced` flags are final) - the batched tracker hangs the per-keypoint
+// depth lookups and the ordered tail of those frames on it, so that they run while later chunks are still in the dense stage
+// (BASELINE configs[4] as a pipeline).
+int svo_elas_batch_dev_hooked(svo_ctx* ctx, hipStream_t s, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H,
                               int B, const svo_elas_params* params, float* d_D1, float* d_D2, int32_t* produced,
                               int (*hook)(void*, int, int), void* user) {
-  if (!ctx) return SVO_E_INVALID;
   if (!d_L || !d_R || !d_D1 || !d_D2 || !params || B < 1) { ctx->last_error = "svo_elas_batch_dev: invalid argument"; return SVO_E_INVALID; }
   const svo_elas_params p = *params;
   int rc = elas_check(ctx, W, H, stride, p);
@@ -1540,7 +1537,7 @@ int svo_elas_batch_dev_hooked(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d
   const ElasState* s0 = eb->slots[0];
   const int Wc = s0->Wc, Hc = s0->Hc, gw = s0->gw, gh = s0->gh, wh = Wc * Hc;
   if (eb->cap < B || eb->can_elems != wh) {
-    SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SVO_HIP(ctx, hipStreamSynchronize(s));
     eb->release_tables();
     SVO_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&eb->d_tab), sizeof(ElasTab) * (size_t)B));
     SVO_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&eb->h_tab), sizeof(ElasTab) * (size_t)B, hipHostMallocDefault));
@@ -1551,7 +1548,6 @@ int svo_elas_batch_dev_hooked(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d
   if (!eb->d_P) SVO_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&eb->d_P), 256 * sizeof(int32_t)));
   const size_t nd = p.subsampling ? (size_t)(W / 2) * (H / 2) : (size_t)W * H;
   const size_t img = (size_t)stride * H;
-  hipStream_t s = ctx->stream;
 
   // The batch is cut into chunks that move through  A (GPU) -> host stages -> B (GPU)  as a pipeline: while the
   // host threads work on chunk c, the GPU runs phase A of chunk c+1 and phase B of chunk c-1.
@@ -1612,8 +1608,7 @@ int svo_elas_batch_dev_hooked(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d
             // them waited 30 ms per 256-frame call, configs[4] 4.8 k instead of 6.8 k frames/s)
           int attempts = 0, percent = 0;
           const int rcp = svo_pick_stream(ctx, [](hipStream_t* q) { return svo_stream_create(q, 0); },
-                                          {s, ctx->stream != s ? ctx->stream : nullptr, ctx->stream_idx}, &ctx->stream_elas_a, &attempts, &percent,
-                                          {s, ctx->stream != s ? ctx->stream : nullptr, ctx->stream_idx}, {s});
+                                          {s, ctx->stream_idx}, &ctx->stream_elas_a, &attempts, &percent, {s, ctx->stream_idx}, {s});
           if (rcp) return rcp;
         }
         ctx->stream_elas_a_pct = pct;

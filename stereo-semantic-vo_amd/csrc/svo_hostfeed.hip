@@ -6,7 +6,7 @@
 //
 //   host images --(pinned: copied where they lie | pageable: rows gathered into a pinned ring by worker threads)-->
 //   copy stream: H2D into image set p (two sets alternate between calls)  --event per 8 pairs-->
-//   front-end stream: sub-batches wait for the event of their last pair (svo_track_batch_dev / svo_track_sharded_dev, unchanged)
+//   front-end stream: sub-batches wait for the event of their last pair (svo_track_batch_fed / svo_track_sharded_fed: the _dev entries' work)
 //   ... ordered tail ...  pose stream: records D2H into a pinned buffer --> the caller's array at svo_sync (or two calls later)
 #include <string.h>
 
@@ -346,9 +346,8 @@ extern "C" int svo_track_batch_host(svo_ctx* ctx, const uint8_t* grayL, const ui
   if ((rc = feed_boxes(ctx, p, boxes, B, &bx))) return rc;
   if ((rc = feed_upload(ctx, p, grayL, grayR, stride, 0, 1, B))) return rc;
   const size_t ib = img_bytes(ctx);
-  ctx->feed_pair_event = hf->pair_ev.data();
-  rc = svo_track_batch_dev(ctx, hf->d_img[p], hf->d_img[p] + (size_t)hf->cap * ib, ctx->stage_pitch, B, bx.boxes ? &bx : nullptr, hf->d_res[p]);
-  ctx->feed_pair_event = nullptr;
+  rc = svo_track_batch_fed(ctx, hf->d_img[p], hf->d_img[p] + (size_t)hf->cap * ib, ctx->stage_pitch, B, bx.boxes ? &bx : nullptr, hf->d_res[p],
+                           hf->pair_ev.data());
   if (rc) return rc;
   // who read the images of this set: the front-end stream (sparse depth), the dense stage's streams and the main stream otherwise
   int nf = 0;
@@ -380,6 +379,7 @@ extern "C" int svo_track_sharded_host(svo_ctx* const* ctxs, int G, const uint8_t
   int rc = SVO_OK;
   // every context uploads ITS pairs (k = g, g + G, ...) to ITS device on ITS copy stream: SURVEY 8e's "pair k -> GPU k mod G"
   std::vector<const uint8_t*> dl((size_t)G), dr((size_t)G);
+  std::vector<const hipEvent_t*> ready((size_t)G, nullptr);   // context g's pair i is resident after ready[g][i]
   std::vector<int> par((size_t)G);
   for (int g = 0; g < G && rc == SVO_OK; ++g) {
     svo_ctx* c = ctxs[g];
@@ -392,18 +392,16 @@ extern "C" int svo_track_sharded_host(svo_ctx* const* ctxs, int G, const uint8_t
     if ((rc = flush_set(c, hf, p))) break;
     const int nb = (B - g + G - 1) / G;
     if (nb > 0 && (rc = feed_upload(c, p, grayL, grayR, stride, g, G, nb))) break;
-    if (nb <= 0) hf->pair_ev.clear();
     dl[g] = hf->d_img[p];
     dr[g] = hf->d_img[p] + (size_t)hf->cap * img_bytes(c);
-    c->feed_pair_event = hf->pair_ev.empty() ? nullptr : hf->pair_ev.data();
+    if (nb > 0) ready[g] = hf->pair_ev.data();
   }
   hipSetDevice(c0->device);
   HostFeed* h0 = feed_of(c0);
   svo_boxes_dev bx{nullptr, nullptr, 0};
   if (rc == SVO_OK) rc = feed_boxes(c0, par[0], boxes, B, &bx);
   if (rc == SVO_OK)
-    rc = svo_track_sharded_dev(ctxs, G, dl.data(), dr.data(), c0->stage_pitch, B, bx.boxes ? &bx : nullptr, h0->d_res[par[0]]);
-  for (int g = 0; g < G; ++g) if (ctxs[g]) ctxs[g]->feed_pair_event = nullptr;
+    rc = svo_track_sharded_fed(ctxs, G, dl.data(), dr.data(), c0->stage_pitch, B, bx.boxes ? &bx : nullptr, h0->d_res[par[0]], ready.data());
   if (rc) return rc;
   for (int g = 0; g < G; ++g) {
     svo_ctx* c = ctxs[g];

@@ -54,6 +54,37 @@ struct SvoSel {
 // One launch of k_pyr_fused: levels l0 .. l0 + nl - 1 from level l0 - 1, strips of rt rows of the last level
 struct SvoPyrGroup { int l0, nl, rt, cap0, cap1; size_t lds; };
 
+// The arrays svo_launch_orb / svo_launch_stereo work in: the working set (image slot i: pyramid, raw corners, counters, histogram,
+// selection) and the outputs (image slot i: keypoints, descriptors, count; pair p: right x, depth, best SAD).  svo_fe_own(ctx) is the
+// context's own set; a caller that runs the front end on a part of a batch, or into other output arrays, derives its view from it.
+struct SvoFeBufs {
+  uint8_t* pyr = nullptr; uint32_t* corners = nullptr; int32_t *counters = nullptr, *hist = nullptr;
+  SvoSel* sel = nullptr; int32_t* selcnt = nullptr;
+  svo_kp* kp = nullptr; uint8_t* desc = nullptr; int32_t* nkp = nullptr;
+  float *uR = nullptr, *depth = nullptr; int32_t* sad = nullptr;
+  // the outputs from image slot i and pair p on (K keypoints per image); the working set stays where it is
+  SvoFeBufs outputs_at(size_t K, size_t i, size_t p) const {
+    SvoFeBufs b = *this;
+    b.kp += i * K; b.desc += i * K * SVO_DESC_BYTES; b.nkp += i;
+    b.uR += p * K; b.depth += p * K; b.sad += p * K;
+    return b;
+  }
+  // the working set from image slot i on as well (a slice of a batch that runs beside the other slices)
+  SvoFeBufs at(const SvoGeom& g, size_t K, size_t i, size_t p) const {
+    SvoFeBufs b = outputs_at(K, i, p);
+    b.pyr += i * g.pyr_bytes; b.corners += i * g.corner_entries; b.counters += i * SVO_NLEVELS;
+    b.hist += i * SVO_NLEVELS * 256; b.sel += i * SVO_NLEVELS * SVO_QMAX; b.selcnt += i * SVO_NLEVELS;
+    return b;
+  }
+  // the output arrays `o` holds in place of these (those `o` leaves null stay)
+  SvoFeBufs with_outputs(const SvoFeBufs& o) const {
+    SvoFeBufs b = *this;
+    b.kp = o.kp ? o.kp : kp; b.desc = o.desc ? o.desc : desc; b.nkp = o.nkp ? o.nkp : nkp;
+    b.uR = o.uR ? o.uR : uR; b.depth = o.depth ? o.depth : depth; b.sad = o.sad ? o.sad : sad;
+    return b;
+  }
+};
+
 struct SvoProfileEntry {
   std::string name;
   double total_ms = 0;
@@ -100,18 +131,16 @@ struct svo_ctx {
   void* d_track = nullptr;      // n_seq TrackState records
   int n_seq = 0;
   // svo_track_multi_step_dev with svo_set_option("multi_pipeline", 1): the front end of step t + 1 runs beside the tail of
-  // step t; its outputs alternate between two private sets (ms_*[parity])
+  // step t; its keypoints, descriptors, counts and depths alternate between two private sets (ms_out[parity]; right x and
+  // SAD go to the context's own arrays)
   int opt_multi_pipeline = 0, ms_parity = 0, ms_cap = 0;
   bool ms_tail_recorded[2] = {false, false};
-  svo_kp* ms_kp[2] = {nullptr, nullptr};
-  uint8_t* ms_desc[2] = {nullptr, nullptr};
-  int32_t* ms_nkp[2] = {nullptr, nullptr};
-  float* ms_depth[2] = {nullptr, nullptr};
+  SvoFeBufs ms_out[2];
   hipEvent_t ms_fe_done[2] = {nullptr, nullptr}, ms_tail_done[2] = {nullptr, nullptr};
   // svo_track_batch_dev: the front end's outputs exist twice and alternate between calls, so that the first sub-batches of call
-  // c + 1 run while the tail of call c is still reading its set (set 0 = the context's own arrays, set 1 allocated on demand)
-  svo_kp* tb_kp = nullptr; uint8_t* tb_desc = nullptr; int32_t* tb_nkp = nullptr;
-  float *tb_uR = nullptr, *tb_depth = nullptr; int32_t* tb_sad = nullptr;
+  // c + 1 run while the tail of call c is still reading its set (set 0 = the context's own arrays: tb_out[0] stays empty;
+  // tb_out[1] allocated on demand)
+  SvoFeBufs tb_out[2];
   hipEvent_t tb_done[2] = {nullptr, nullptr};   // the tail of the call that last used set p has finished
   bool tb_used[2] = {false, false};
   int tb_parity = 0;
@@ -121,8 +150,6 @@ struct svo_ctx {
   hipEvent_t ev_elas_setup = nullptr;
   hipEvent_t shard_wait = nullptr;   // borrowed: the gather event of the sharded tracker call that last read this context's result arrays
   void* d_gate_pre = nullptr;   // GatePre records (brute-force matches + F solved ahead of the index chain), like d_work
-  bool hyp_two_launch = false;  // set by an entry for the duration of its tail_enqueue calls: RANSAC samples as 16 + (those the bound can reach)
-  int opt_dense_two_launch = 0; // depth_source = 1: the tail beside the dense stage uses the two-launch RANSAC (fewer CUs taken from ELAS)
   int idx_probe_attempts = -1;  // how many candidate streams the index chain's stream was chosen from (-1: not chosen yet, 0: probe off)
   int idx_probe_spins = 0;      // the chosen candidate's probe result: two chains together / one alone, per cent (~100 side by side, ~200 serialised)
   int opt_hyp_first = 8;        // many sequences: RANSAC samples per sequence in the first (and second) launch of a step
@@ -179,8 +206,6 @@ struct svo_ctx {
   bool timeout_reported = false;                  // svo_sync returned SVO_E_TIMEOUT for this context once (sticky flag 4, svo_track_check_timeout)
   uint32_t create_flags = 0;                      // svo_create_ex
   void* hostfeed = nullptr;                       // HostFeed (svo_hostfeed.hip): copy stream, image sets, pinned staging of the host-fed entries
-  const hipEvent_t* feed_pair_event = nullptr;    // set by a host-fed entry for the duration of its inner call: pair i of the call (this context's
-                                                  //   local index) is resident in HBM after feed_pair_event[i] (recorded on the feed's copy stream)
   bool profiling = false;
   std::vector<SvoProfileEntry> prof;
   void* prof_impl = nullptr;  // SvoProfState (svo_api.hip)
@@ -204,12 +229,21 @@ static inline hipError_t svo_memcpy_sync(svo_ctx* ctx, void* dst, const void* sr
   return e;
 }
 
+static inline SvoFeBufs svo_fe_own(const svo_ctx* ctx) {
+  SvoFeBufs b;
+  b.pyr = ctx->d_pyr; b.corners = ctx->d_corners; b.counters = ctx->d_counters; b.hist = ctx->d_hist;
+  b.sel = ctx->d_sel; b.selcnt = ctx->d_selcnt;
+  b.kp = ctx->d_kp; b.desc = ctx->d_desc; b.nkp = ctx->d_nkp; b.uR = ctx->d_uR; b.depth = ctx->d_depth; b.sad = ctx->d_sad;
+  return b;
+}
+
 // ---- stage launchers (each enqueues on ctx->stream, no sync) -------------------
+// The front end's two enqueue on `st` instead and work in the arrays of `b` (image 0 of the batch in image slot 0 of `b`).
 // Images of a batch: index i < B is left image i, i >= B is right image i-B (nimg = B or 2B).
-int svo_launch_orb(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride,
-                   int B, int nimg);
-int svo_launch_stereo(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride,
-                      int B, const svo_camera* cam);
+int svo_launch_orb(svo_ctx* ctx, hipStream_t st, const SvoFeBufs& b, const uint8_t* d_grayL, const uint8_t* d_grayR,
+                   int stride, int B, int nimg);
+int svo_launch_stereo(svo_ctx* ctx, hipStream_t st, const SvoFeBufs& b, const uint8_t* d_grayL, const uint8_t* d_grayR,
+                      int stride, int B, const svo_camera* cam);
 int svo_launch_descriptor_distance(svo_ctx* ctx, const uint8_t* a, const uint8_t* b, int count,
                                    int32_t* dist);
 int svo_launch_hamming_argmin(svo_ctx* ctx, const uint8_t* q, int M, const uint8_t* t, int N,
@@ -266,9 +300,15 @@ int svo_pick_stream(svo_ctx* ctx, const std::function<hipError_t(hipStream_t*)>&
 // a large grid in dispatch on `blocker` beside a chain of short kernels on `victim`: the chain's time in per cent of its time alone
 int svo_probe_block_percent(hipStream_t blocker, hipStream_t victim);
 int svo_track_fe_batch_stream(svo_ctx* ctx);   // svo_track.hip: creates ctx->stream_fe_batch (a stream that runs beside the tail's two chains)
-int svo_elas_batch_dev_hooked(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
+int svo_elas_batch_dev_hooked(svo_ctx* ctx, hipStream_t s, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
                               const svo_elas_params* params, float* d_D1, float* d_D2, int32_t* produced,
-                              int (*hook)(void*, int, int), void* user);   // svo_elas.hip   // wait for the tails svo_track_batch_dev left in flight (svo_api.hip)
+                              int (*hook)(void*, int, int), void* user);   // svo_elas.hip: svo_elas_batch_dev on stream `s`
+// svo_track.hip: svo_track_batch_dev / svo_track_sharded_dev for the host-fed entries (svo_hostfeed.hip), whose images arrive on a
+// copy stream: pair i of the call is resident in HBM after pair_ready[i] (context g's own pair i: pair_ready[g][i])
+int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
+                        const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready);
+int svo_track_sharded_fed(svo_ctx* const* ctxs, int G, const uint8_t* const* d_grayL, const uint8_t* const* d_grayR, int stride, int B,
+                          const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* const* pair_ready);
 hipError_t svo_stream_create_masked(hipStream_t* st, int device, int percent);
 int svo_frontend_nslices(const svo_ctx* ctx, int B);   // how svo_frontend_batch_dev slices a batch (svo_api.hip)
 int svo_launch_disp2depth(svo_ctx* ctx, const float* disp, int count, float bf, float* depth);

@@ -930,49 +930,48 @@ __global__ __launch_bounds__(64) void k_describe(SvoGeom g, ImgSrc s, const SvoS
 }
 
 // ---------------------------------------------------------------------------------
-int svo_launch_orb(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride,
-                   int B, int nimg) {
+int svo_launch_orb(svo_ctx* ctx, hipStream_t st, const SvoFeBufs& b, const uint8_t* d_grayL, const uint8_t* d_grayR,
+                   int stride, int B, int nimg) {
   const SvoGeom& g = ctx->g;
   if (nimg > ctx->max_images || B < 1) return SVO_E_CAPACITY;
-  ImgSrc s{d_grayL, d_grayR, stride, B, ctx->d_pyr};
-  hipStream_t st = ctx->stream;
-  SVO_HIP(ctx, hipMemsetAsync(ctx->d_counters, 0, sizeof(int32_t) * (size_t)nimg * SVO_NLEVELS, st));
+  ImgSrc s{d_grayL, d_grayR, stride, B, b.pyr};
+  SVO_HIP(ctx, hipMemsetAsync(b.counters, 0, sizeof(int32_t) * (size_t)nimg * SVO_NLEVELS, st));
   {
     const bool fused = ctx->opt_pyr_fused && !ctx->pyr_plan.empty();
-    SvoTimer t(ctx, fused ? "k_pyr_fused" : "k_pyr_level");   // one timer around the pyramid's launches (three fused ones, or seven)
+    SvoTimer t(ctx, fused ? "k_pyr_fused" : "k_pyr_level", st);   // one timer around the pyramid's launches (three fused ones, or seven)
     if (fused) {
       for (const SvoPyrGroup& pg : ctx->pyr_plan) {
         const int lt = pg.l0 + pg.nl - 1;
         const dim3 grid((g.h[lt] + pg.rt - 1) / pg.rt, nimg);
         if (pg.nl == 2)
-          hipLaunchKernelGGL(k_pyr_fused<2>, grid, dim3(256), pg.lds, st, g, s, pg.l0, pg.rt, pg.cap0, pg.cap1, ctx->d_pyr, ctx->d_xofs,
+          hipLaunchKernelGGL(k_pyr_fused<2>, grid, dim3(256), pg.lds, st, g, s, pg.l0, pg.rt, pg.cap0, pg.cap1, b.pyr, ctx->d_xofs,
                              ctx->d_xalpha, ctx->d_yofs, ctx->d_ybeta);
         else
-          hipLaunchKernelGGL(k_pyr_fused<3>, grid, dim3(256), pg.lds, st, g, s, pg.l0, pg.rt, pg.cap0, pg.cap1, ctx->d_pyr, ctx->d_xofs,
+          hipLaunchKernelGGL(k_pyr_fused<3>, grid, dim3(256), pg.lds, st, g, s, pg.l0, pg.rt, pg.cap0, pg.cap1, b.pyr, ctx->d_xofs,
                              ctx->d_xalpha, ctx->d_yofs, ctx->d_ybeta);
       }
     } else {
       for (int l = 1; l < SVO_NLEVELS; ++l) {
         dim3 grid((g.w[l] / 4 + 64) / 64, (g.h[l] + 15) / 16, nimg);
-        hipLaunchKernelGGL(k_pyr_level, grid, dim3(64, 4, 1), 0, st, g, s, l, ctx->d_pyr, ctx->d_xofs,
+        hipLaunchKernelGGL(k_pyr_level, grid, dim3(64, 4, 1), 0, st, g, s, l, b.pyr, ctx->d_xofs,
                            ctx->d_xalpha, ctx->d_yofs, ctx->d_ybeta);
       }
     }
   }
   {
-    SvoTimer t(ctx, "k_fast");
+    SvoTimer t(ctx, "k_fast", st);
     hipLaunchKernelGGL(k_fast, dim3(g.tile_base[SVO_NLEVELS], nimg), dim3(256), 0, st, g, s,
-                       ctx->d_corners, ctx->d_counters, ctx->d_hist, ctx->opt_fast_cand_cap);
+                       b.corners, b.counters, b.hist, ctx->opt_fast_cand_cap);
   }
   {
-    SvoTimer t(ctx, "k_select");
-    hipLaunchKernelGGL(k_select, dim3(SVO_NLEVELS, nimg), dim3(256), 0, st, g, s, ctx->d_corners,
-                       ctx->d_counters, ctx->d_hist, ctx->d_sel, ctx->d_selcnt);
+    SvoTimer t(ctx, "k_select", st);
+    hipLaunchKernelGGL(k_select, dim3(SVO_NLEVELS, nimg), dim3(256), 0, st, g, s, b.corners,
+                       b.counters, b.hist, b.sel, b.selcnt);
   }
   {
-    SvoTimer t(ctx, "k_describe");
-    hipLaunchKernelGGL(k_describe, dim3(ctx->max_kp, nimg), dim3(64), 0, st, g, s, ctx->d_sel,
-                       ctx->d_selcnt, ctx->d_kp, ctx->d_desc, ctx->d_nkp, ctx->max_kp);
+    SvoTimer t(ctx, "k_describe", st);
+    hipLaunchKernelGGL(k_describe, dim3(ctx->max_kp, nimg), dim3(64), 0, st, g, s, b.sel,
+                       b.selcnt, b.kp, b.desc, b.nkp, ctx->max_kp);
   }
   SVO_HIP(ctx, hipGetLastError());
   return SVO_OK;

@@ -342,20 +342,20 @@ __global__ void k_unproject(const float* __restrict__ uvz, int n, svo_camera cam
   }
 }
 
-int svo_launch_stereo(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride,
-                      int B, const svo_camera* cam) {
+int svo_launch_stereo(svo_ctx* ctx, hipStream_t st, const SvoFeBufs& b, const uint8_t* d_grayL, const uint8_t* d_grayR,
+                      int stride, int B, const svo_camera* cam) {
   if (B > ctx->max_batch || ctx->max_kp > 1024) return SVO_E_CAPACITY;
-  StereoSrc s{d_grayL, d_grayR, stride, B, ctx->d_pyr};
+  StereoSrc s{d_grayL, d_grayR, stride, B, b.pyr};
   {
-    SvoTimer t(ctx, "k_stereo_match");
+    SvoTimer t(ctx, "k_stereo_match", st);
     hipLaunchKernelGGL(k_stereo_match, dim3((ctx->max_kp + KP_PER_WG - 1) / KP_PER_WG, B), dim3(256),
-                       0, ctx->stream, ctx->g, s, ctx->d_kp, ctx->d_desc, ctx->d_nkp, ctx->max_kp,
-                       cam->bf, cam->fx, ctx->d_uR, ctx->d_depth, ctx->d_sad);
+                       0, st, ctx->g, s, b.kp, b.desc, b.nkp, ctx->max_kp,
+                       cam->bf, cam->fx, b.uR, b.depth, b.sad);
   }
   {
-    SvoTimer t(ctx, "k_stereo_median");
-    hipLaunchKernelGGL(k_stereo_median, dim3(B), dim3(256), 0, ctx->stream, ctx->max_kp, ctx->d_uR,
-                       ctx->d_depth, ctx->d_sad);
+    SvoTimer t(ctx, "k_stereo_median", st);
+    hipLaunchKernelGGL(k_stereo_median, dim3(B), dim3(256), 0, st, ctx->max_kp, b.uR,
+                       b.depth, b.sad);
   }
   SVO_HIP(ctx, hipGetLastError());
   return SVO_OK;

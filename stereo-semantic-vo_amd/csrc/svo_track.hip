@@ -1478,18 +1478,40 @@ __global__ __launch_bounds__(TPF_NT) void k_tp_tail_ord(TrackState* st, TrackWor
 // Host side
 // --------------------------------------------------------------------------------------------
 static void shard_gather_free(svo_ctx* ctx);
-static void track_batch_sets_free(svo_ctx* ctx) {
-  if (ctx->tb_kp) hipFree(ctx->tb_kp);
-  if (ctx->tb_desc) hipFree(ctx->tb_desc);
-  if (ctx->tb_nkp) hipFree(ctx->tb_nkp);
-  if (ctx->tb_uR) hipFree(ctx->tb_uR);
-  if (ctx->tb_depth) hipFree(ctx->tb_depth);
-  if (ctx->tb_sad) hipFree(ctx->tb_sad);
-  ctx->tb_kp = nullptr; ctx->tb_desc = nullptr; ctx->tb_nkp = nullptr; ctx->tb_uR = nullptr; ctx->tb_depth = nullptr; ctx->tb_sad = nullptr;
+// The alternating front-end output sets (ms_out, tb_out): n sets of keypoints, descriptors and counts for `images` image slots and
+// depths - with `stereo_aux` also right x and SAD - for `pairs` pairs, K keypoints each.  A failed allocation leaves all n sets empty.
+static void fe_sets_free(SvoFeBufs* sets, int n) {
+  for (int q = 0; q < n; ++q) {
+    SvoFeBufs& o = sets[q];
+    if (o.kp) hipFree(o.kp);
+    if (o.desc) hipFree(o.desc);
+    if (o.nkp) hipFree(o.nkp);
+    if (o.uR) hipFree(o.uR);
+    if (o.depth) hipFree(o.depth);
+    if (o.sad) hipFree(o.sad);
+    o = SvoFeBufs{};
+  }
+}
+static int fe_sets_alloc(SvoFeBufs* sets, int n, size_t images, size_t pairs, size_t K, bool stereo_aux) {
+  fe_sets_free(sets, n);
+  for (int q = 0; q < n; ++q) {
+    SvoFeBufs& o = sets[q];
+    if (hipMalloc(reinterpret_cast<void**>(&o.kp), sizeof(svo_kp) * images * K) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&o.desc), 32 * images * K) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&o.nkp), sizeof(int32_t) * images) != hipSuccess ||
+        (stereo_aux && hipMalloc(reinterpret_cast<void**>(&o.uR), sizeof(float) * pairs * K) != hipSuccess) ||
+        hipMalloc(reinterpret_cast<void**>(&o.depth), sizeof(float) * pairs * K) != hipSuccess ||
+        (stereo_aux && hipMalloc(reinterpret_cast<void**>(&o.sad), sizeof(int32_t) * pairs * K) != hipSuccess)) {
+      (void)hipGetLastError();
+      fe_sets_free(sets, n);
+      return SVO_E_NOMEM;
+    }
+  }
+  return SVO_OK;
 }
 void svo_track_release(svo_ctx* ctx) {
   shard_gather_free(ctx);
-  track_batch_sets_free(ctx);
+  fe_sets_free(ctx->tb_out, 2);
   for (int q = 0; q < 2; ++q) {
     if (ctx->tb_done[q]) { hipEventDestroy(ctx->tb_done[q]); ctx->tb_done[q] = nullptr; }
     ctx->tb_used[q] = false;
@@ -1509,12 +1531,8 @@ void svo_track_release(svo_ctx* ctx) {
   if (ctx->stream_fe_batch) { hipStreamDestroy(ctx->stream_fe_batch); ctx->stream_fe_batch = nullptr; }
   if (ctx->stream_dense) { hipStreamDestroy(ctx->stream_dense); ctx->stream_dense = nullptr; }
   if (ctx->h_prod) { hipHostFree(ctx->h_prod); ctx->h_prod = nullptr; }
+  fe_sets_free(ctx->ms_out, 2);
   for (int p = 0; p < 2; ++p) {
-    if (ctx->ms_kp[p]) hipFree(ctx->ms_kp[p]);
-    if (ctx->ms_desc[p]) hipFree(ctx->ms_desc[p]);
-    if (ctx->ms_nkp[p]) hipFree(ctx->ms_nkp[p]);
-    if (ctx->ms_depth[p]) hipFree(ctx->ms_depth[p]);
-    ctx->ms_kp[p] = nullptr; ctx->ms_desc[p] = nullptr; ctx->ms_nkp[p] = nullptr; ctx->ms_depth[p] = nullptr;
     if (ctx->ms_fe_done[p]) { hipEventDestroy(ctx->ms_fe_done[p]); ctx->ms_fe_done[p] = nullptr; }
     if (ctx->ms_tail_done[p]) { hipEventDestroy(ctx->ms_tail_done[p]); ctx->ms_tail_done[p] = nullptr; }
     ctx->ms_tail_recorded[p] = false;
@@ -1722,7 +1740,7 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
     const svo_kp* kpf = kp + row(f) * kstride;
     const float* depf = depth + row(f) * kstride;
     ctx->profiling = prof && (f % 32 == 0 || frames < 32);
-    if (ctx->opt_epnp_exact == 2 && ny == 1 && !ctx->hyp_two_launch && ctx->opt_tail_fused && (ctx->opt_depth_source == 0 || ctx->opt_tail_fused == 2)) {
+    if (ctx->opt_epnp_exact == 2 && ny == 1 && ctx->opt_tail_fused && (ctx->opt_depth_source == 0 || ctx->opt_tail_fused == 2)) {
       // one sequence, the default solver: samples and frame part in ONE launch (k_tp_tail_ord).  Not beside a dense stereo stage
       // (depth_source 1 / 2): a fused launch's sample workgroups carry the frame part's 67 KB of LDS and three idle waves each,
       // which the dense kernels running on the same CUs pay for (configs[4]: 6.05 k frames/s fused, 6.85 k with two launches)
@@ -1747,8 +1765,8 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
     }
     if (ctx->opt_epnp_exact == 2) {
       SvoTimer t(ctx, "k_tp_hyp_ord");
-      if (ny >= 8 || ctx->hyp_two_launch) {
-        // many sequences (or a dense stage beside the tail): throughput counts.  cv::solvePnPRansac visits a median of 4 samples
+      if (ny >= 8) {
+        // many sequences: throughput counts.  cv::solvePnPRansac visits a median of 4 samples
         // on these sequences, 96 % of the frames 8 or fewer, 99.9 % 16 or fewer: F samples per sequence first ("hyp_first",
         // default 8), then F more, then the rest - the workgroups of a later launch replay the adaptive rule over the earlier
         // samples and leave at once when the loop can never reach theirs
@@ -1915,8 +1933,9 @@ extern "C" int svo_track_frame(svo_ctx* ctx, const uint8_t* grayL, int strideL,
   if (n_boxes > 0)
     SVO_HIP(ctx, hipMemcpyAsync(st->boxes, h_box + 4, 16 * (size_t)n_boxes, hipMemcpyHostToDevice, ctx->stream));
   const svo_boxes_dev bx{st->boxes, &st->n_boxes, SVO_MAX_BOXES};
+  const SvoFeBufs fb = svo_fe_own(ctx);
   if (ctx->opt_depth_source == 1) {
-    if ((rc = svo_launch_orb(ctx, dL, dR, ctx->stage_pitch, 1, 1))) return rc;   // left image only
+    if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 1))) return rc;   // left image only
     svo_elas_params ep;
     svo_elas_default_params(0, &ep);
     float *dD1 = nullptr, *dD2 = nullptr;
@@ -1928,7 +1947,7 @@ extern "C" int svo_track_frame(svo_ctx* ctx, const uint8_t* grayL, int strideL,
                        (const int32_t*)nullptr);
   } else if (ctx->opt_depth_source == 2) {
     // the reference's live configuration: frame::MB = MSA::solve(left, right, 48, 1) (src/Tracking.cc:225-228)
-    if ((rc = svo_launch_orb(ctx, dL, dR, ctx->stage_pitch, 1, 1))) return rc;
+    if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 1))) return rc;
     if ((rc = dense_reserve(ctx, 1))) return rc;
     if ((rc = svo_msa_run_dev(ctx, dL, dR, ctx->stage_pitch, g.W, g.H, 48, ctx->d_dense))) return rc;
     SvoTimer t(ctx, "k_tk_dense_depth");
@@ -1936,8 +1955,8 @@ extern "C" int svo_track_frame(svo_ctx* ctx, const uint8_t* grayL, int strideL,
                        ctx->d_nkp, ctx->d_dense, g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, (size_t)0,
                        (const int32_t*)nullptr);
   } else {
-    if ((rc = svo_launch_orb(ctx, dL, dR, ctx->stage_pitch, 1, 2))) return rc;
-    if ((rc = svo_launch_stereo(ctx, dL, dR, ctx->stage_pitch, 1, &ctx->cam))) return rc;
+    if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 2))) return rc;
+    if ((rc = svo_launch_stereo(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, &ctx->cam))) return rc;
   }
   svo_track_result* d_res = reinterpret_cast<svo_track_result*>(ctx->d_scratch);
   rc = tail_enqueue(ctx, ctx->d_kp, ctx->d_desc, ctx->d_nkp, ctx->d_depth, ctx->max_kp, 1, 1, d_res, n_boxes > 0 ? &bx : nullptr);
@@ -1965,31 +1984,12 @@ extern "C" int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, co
     // Pipelined steps (svo_set_option("multi_pipeline", 1)): the front end is stateless, so step t + 1's may run while
     // step t's tail is still busy - on its own stream, into the other of two private output sets.  Contract: between
     // consecutive steps nothing else is enqueued on this context (svo_sync and reading results are fine).
-    const size_t K = ctx->max_kp, I = 2 * (size_t)n_seq;
     if (ctx->ms_cap < n_seq) {
       SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
       if (ctx->stream_fe) SVO_HIP(ctx, hipStreamSynchronize(ctx->stream_fe));
+      ctx->ms_cap = 0;   // a failed allocation below leaves empty sets and no capacity behind, never freed memory
+      if ((rc = fe_sets_alloc(ctx->ms_out, 2, 2 * (size_t)n_seq, n_seq, ctx->max_kp, false))) return rc;
       for (int p = 0; p < 2; ++p) {
-        if (ctx->ms_kp[p]) hipFree(ctx->ms_kp[p]);
-        if (ctx->ms_desc[p]) hipFree(ctx->ms_desc[p]);
-        if (ctx->ms_nkp[p]) hipFree(ctx->ms_nkp[p]);
-        if (ctx->ms_depth[p]) hipFree(ctx->ms_depth[p]);
-        ctx->ms_kp[p] = nullptr; ctx->ms_desc[p] = nullptr; ctx->ms_nkp[p] = nullptr; ctx->ms_depth[p] = nullptr;
-        ctx->ms_cap = 0;   // a failed allocation below leaves null pointers and no capacity behind, never freed memory
-        if (hipMalloc(reinterpret_cast<void**>(&ctx->ms_kp[p]), sizeof(svo_kp) * I * K) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&ctx->ms_desc[p]), 32 * I * K) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&ctx->ms_nkp[p]), sizeof(int32_t) * I) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&ctx->ms_depth[p]), sizeof(float) * (size_t)n_seq * K) != hipSuccess) {
-          (void)hipGetLastError();
-          for (int q = 0; q < 2; ++q) {
-            if (ctx->ms_kp[q]) hipFree(ctx->ms_kp[q]);
-            if (ctx->ms_desc[q]) hipFree(ctx->ms_desc[q]);
-            if (ctx->ms_nkp[q]) hipFree(ctx->ms_nkp[q]);
-            if (ctx->ms_depth[q]) hipFree(ctx->ms_depth[q]);
-            ctx->ms_kp[q] = nullptr; ctx->ms_desc[q] = nullptr; ctx->ms_nkp[q] = nullptr; ctx->ms_depth[q] = nullptr;
-          }
-          return SVO_E_NOMEM;
-        }
         if (!ctx->ms_fe_done[p]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->ms_fe_done[p], hipEventDisableTiming));
         if (!ctx->ms_tail_done[p]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->ms_tail_done[p], hipEventDisableTiming));
         ctx->ms_tail_recorded[p] = false;
@@ -2010,34 +2010,30 @@ extern "C" int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, co
       SVO_HIP(ctx, hipEventRecord(ctx->ev_frontend, ctx->stream));                  // first use: after whatever came before
       SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_fe, ctx->ev_frontend, 0));
     }
-    svo_kp* kp0 = ctx->d_kp; uint8_t* desc0 = ctx->d_desc; int32_t* nkp0 = ctx->d_nkp; float* depth0 = ctx->d_depth;
-    hipStream_t s_main = ctx->stream;
-    ctx->d_kp = ctx->ms_kp[p]; ctx->d_desc = ctx->ms_desc[p]; ctx->d_nkp = ctx->ms_nkp[p]; ctx->d_depth = ctx->ms_depth[p];
-    ctx->stream = ctx->stream_fe;
-    rc = svo_launch_orb(ctx, d_grayL, d_grayR, stride, n_seq, 2 * n_seq);
-    if (rc == SVO_OK) rc = svo_launch_stereo(ctx, d_grayL, d_grayR, stride, n_seq, &ctx->cam);
-    ctx->stream = s_main;
-    ctx->d_kp = kp0; ctx->d_desc = desc0; ctx->d_nkp = nkp0; ctx->d_depth = depth0;
+    const SvoFeBufs fb = svo_fe_own(ctx).with_outputs(ctx->ms_out[p]);   // (right x and SAD: the context's own arrays)
+    rc = svo_launch_orb(ctx, ctx->stream_fe, fb, d_grayL, d_grayR, stride, n_seq, 2 * n_seq);
+    if (rc == SVO_OK) rc = svo_launch_stereo(ctx, ctx->stream_fe, fb, d_grayL, d_grayR, stride, n_seq, &ctx->cam);
     if (rc) return rc;
     SVO_HIP(ctx, hipEventRecord(ctx->ms_fe_done[p], ctx->stream_fe));
     SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ms_fe_done[p], 0));
-    if ((rc = tail_enqueue(ctx, ctx->ms_kp[p], ctx->ms_desc[p], ctx->ms_nkp[p], ctx->ms_depth[p], ctx->max_kp, 1, n_seq, d_results, boxes))) return rc;
+    if ((rc = tail_enqueue(ctx, fb.kp, fb.desc, fb.nkp, fb.depth, ctx->max_kp, 1, n_seq, d_results, boxes))) return rc;
     SVO_HIP(ctx, hipEventRecord(ctx->ms_tail_done[p], ctx->stream));
     ctx->ms_tail_recorded[p] = true;
     ctx->ms_parity ^= 1;
     ctx->track_frame++;
     return SVO_OK;
   }
-  rc = svo_launch_orb(ctx, d_grayL, d_grayR, stride, n_seq, 2 * n_seq);
+  const SvoFeBufs fb = svo_fe_own(ctx);
+  rc = svo_launch_orb(ctx, ctx->stream, fb, d_grayL, d_grayR, stride, n_seq, 2 * n_seq);
   if (rc) return rc;
-  if ((rc = svo_launch_stereo(ctx, d_grayL, d_grayR, stride, n_seq, &ctx->cam))) return rc;
+  if ((rc = svo_launch_stereo(ctx, ctx->stream, fb, d_grayL, d_grayR, stride, n_seq, &ctx->cam))) return rc;
   if ((rc = tail_enqueue(ctx, ctx->d_kp, ctx->d_desc, ctx->d_nkp, ctx->d_depth, ctx->max_kp, 1, n_seq, d_results, boxes))) return rc;
   ctx->track_frame++;
   return SVO_OK;
 }
 
-extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR,
-                                   int stride, int B, const svo_boxes_dev* boxes, svo_track_result* d_results) {
+int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
+                        const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready) {
   if (!ctx || !d_grayL || !d_grayR || !d_results || B < 1 || stride < ctx->g.W) return SVO_E_INVALID;
   if (B > ctx->max_batch) return SVO_E_CAPACITY;
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;
@@ -2081,7 +2077,7 @@ extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const u
     SVO_HIP(ctx, hipEventRecord(ctx->ev_frontend, ctx->stream));
     SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_dense, ctx->ev_frontend, 0));
     struct Hook {
-      svo_ctx* ctx; hipStream_t s_main; const svo_boxes_dev* boxes; svo_track_result* d_results; float* dD1; int32_t* d_prod;
+      svo_ctx* ctx; const svo_boxes_dev* boxes; svo_track_result* d_results; float* dD1; int32_t* d_prod;
       size_t n, K; int chunk;
       static int run(void* u, int f0, int b) {
         Hook& h = *static_cast<Hook*>(u);
@@ -2093,20 +2089,18 @@ extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const u
           ctx->ev_sub.push_back(e);
         }
         if (hipMemcpyAsync(h.d_prod + f0, ctx->h_prod + f0, sizeof(int32_t) * (size_t)b, hipMemcpyHostToDevice, sd) != hipSuccess) return SVO_E_HIP;
-        hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256, b), dim3(256), 0, sd, ctx->d_kp + f0 * h.K, ctx->d_nkp + f0,
-                           h.dD1 + h.n * f0, ctx->g.W, ctx->cam.bf, ctx->d_uR + f0 * h.K, ctx->d_depth + f0 * h.K, ctx->max_kp, h.n, h.d_prod + f0);
+        const SvoFeBufs o = svo_fe_own(ctx).outputs_at(h.K, f0, f0);
+        hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256, b), dim3(256), 0, sd, o.kp, o.nkp,
+                           h.dD1 + h.n * f0, ctx->g.W, ctx->cam.bf, o.uR, o.depth, ctx->max_kp, h.n, h.d_prod + f0);
         if (hipEventRecord(ctx->ev_sub[h.chunk], sd) != hipSuccess) return SVO_E_HIP;
         const int p = ctx->tb_parity;
         std::vector<hipEvent_t> wait(b, nullptr);
         wait[0] = ctx->ev_sub[h.chunk];
         svo_boxes_dev bj{nullptr, nullptr, 0};
         if (h.boxes && h.boxes->boxes && h.boxes->n) bj = svo_boxes_dev{h.boxes->boxes + (size_t)f0 * h.boxes->stride * 4, h.boxes->n + f0, h.boxes->stride};
-        ctx->stream = h.s_main;          // (the dense stage runs with the ctx stream swapped for its own)
-        int rc = tail_enqueue(ctx, ctx->d_kp + f0 * h.K, ctx->d_desc + f0 * h.K * 32, ctx->d_nkp + f0, ctx->d_depth + f0 * h.K, ctx->max_kp, b, 1,
-                              h.d_results + f0, bj.boxes ? &bj : nullptr, wait.data(), nullptr, p,
-                              ctx->tb_used[p] ? ctx->tb_done[p] : ctx->ev_frontend, true);
+        int rc = tail_enqueue(ctx, o.kp, o.desc, o.nkp, o.depth, ctx->max_kp, b, 1, h.d_results + f0, bj.boxes ? &bj : nullptr, wait.data(),
+                              nullptr, p, ctx->tb_used[p] ? ctx->tb_done[p] : ctx->ev_frontend, true);
         if (rc == SVO_OK && hipEventRecord(ctx->tb_done[p], ctx->stream) != hipSuccess) rc = SVO_E_HIP;   // the pose chain is the last reader of this half
-        ctx->stream = sd;
         if (rc) return rc;
         ctx->tb_used[p] = true;
         ctx->tb_parity ^= 1;
@@ -2114,22 +2108,19 @@ extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const u
         ++h.chunk;
         return SVO_OK;
       }
-    } hook{ctx, ctx->stream, boxes, d_results, dD1, d_prod, n, K, 0};
-    if (ctx->feed_pair_event) SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_dense, ctx->feed_pair_event[B - 1], 0));   // host-fed: the call's uploads
-    ctx->stream = ctx->stream_dense;
-    ctx->hyp_two_launch = ctx->opt_dense_two_launch != 0;   // (the hook's tail_enqueue calls: 16 CUs per frame instead of 100 on ordinary frames)
-    rc = svo_launch_orb(ctx, d_grayL, d_grayR, stride, B, B);   // left images only
+    } hook{ctx, boxes, d_results, dD1, d_prod, n, K, 0};
+    if (pair_ready) SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_dense, pair_ready[B - 1], 0));   // host-fed: the call's uploads
+    rc = svo_launch_orb(ctx, ctx->stream_dense, svo_fe_own(ctx), d_grayL, d_grayR, stride, B, B);   // left images only
     if (rc == SVO_OK)
-      rc = svo_elas_batch_dev_hooked(ctx, d_grayL, d_grayR, stride, ctx->g.W, ctx->g.H, B, &ep, dD1, dD2, ctx->h_prod, &Hook::run, &hook);
-    ctx->hyp_two_launch = false;
-    ctx->stream = hook.s_main;
+      rc = svo_elas_batch_dev_hooked(ctx, ctx->stream_dense, d_grayL, d_grayR, stride, ctx->g.W, ctx->g.H, B, &ep, dD1, dD2, ctx->h_prod,
+                                     &Hook::run, &hook);
     return rc;
   } else if (ctx->opt_depth_source == 2) {
     // MSA maps, up to eight frames in flight (most of a solve is the host tree builds)
     const size_t n = (size_t)ctx->g.W * ctx->g.H;
     if ((rc = dense_reserve(ctx, B))) return rc;
-    if (ctx->feed_pair_event) SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->feed_pair_event[B - 1], 0));   // host-fed: the call's uploads
-    if ((rc = svo_launch_orb(ctx, d_grayL, d_grayR, stride, B, B))) return rc;   // left images only
+    if (pair_ready) SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, pair_ready[B - 1], 0));   // host-fed: the call's uploads
+    if ((rc = svo_launch_orb(ctx, ctx->stream, svo_fe_own(ctx), d_grayL, d_grayR, stride, B, B))) return rc;   // left images only
     if ((rc = svo_msa_run_many_dev(ctx, d_grayL, d_grayR, stride, (size_t)ctx->g.H * stride, ctx->g.W, ctx->g.H, 48, B,
                                    ctx->d_dense)))
       return rc;
@@ -2160,19 +2151,8 @@ extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const u
     // stream holds).  The front end's working set (pyramids, corner lists) is shared: stream_fe runs the calls' sub-batches
     // one after the other anyway.
     const int p = ctx->tb_parity;
-    if (p == 1 && !ctx->tb_kp) {
-      const size_t I = (size_t)ctx->max_images, Kk = (size_t)ctx->max_kp, Bm = (size_t)ctx->max_batch;
-      if (hipMalloc(reinterpret_cast<void**>(&ctx->tb_kp), sizeof(svo_kp) * I * Kk) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&ctx->tb_desc), 32 * I * Kk) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&ctx->tb_nkp), 4 * I) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&ctx->tb_uR), 4 * Bm * Kk) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&ctx->tb_depth), 4 * Bm * Kk) != hipSuccess ||
-          hipMalloc(reinterpret_cast<void**>(&ctx->tb_sad), 4 * Bm * Kk) != hipSuccess) {
-        (void)hipGetLastError();
-        track_batch_sets_free(ctx);
-        return SVO_E_NOMEM;
-      }
-    }
+    if (p == 1 && !ctx->tb_out[1].kp && (rc = fe_sets_alloc(&ctx->tb_out[1], 1, ctx->max_images, ctx->max_batch, ctx->max_kp, true)))
+      return rc;
     for (int q = 0; q < 2; ++q)
       if (!ctx->tb_done[q]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->tb_done[q], hipEventDisableTiming));
     if (ctx->tb_used[p]) {
@@ -2182,30 +2162,23 @@ extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const u
       SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_fe_batch, ctx->ev_frontend, 0));
     }
     std::vector<hipEvent_t> wait(B, nullptr);
-    svo_kp* const own_kp = ctx->d_kp; uint8_t* const own_desc = ctx->d_desc; int32_t* const own_nkp = ctx->d_nkp;
-    float* const own_uR = ctx->d_uR; float* const own_depth = ctx->d_depth; int32_t* const own_sad = ctx->d_sad;
-    svo_kp* kp0 = p ? ctx->tb_kp : own_kp; uint8_t* desc0 = p ? ctx->tb_desc : own_desc; int32_t* nkp0 = p ? ctx->tb_nkp : own_nkp;
-    float* uR0 = p ? ctx->tb_uR : own_uR; float* depth0 = p ? ctx->tb_depth : own_depth; int32_t* sad0 = p ? ctx->tb_sad : own_sad;
-    hipStream_t s_main = ctx->stream;
+    const SvoFeBufs set = svo_fe_own(ctx).with_outputs(ctx->tb_out[p]);   // (set 0: tb_out[0] is empty, the context's own outputs)
     const size_t K = ctx->max_kp, img = (size_t)ctx->g.H * stride;
-    ctx->stream = ctx->stream_fe_batch;
+    hipStream_t fs = ctx->stream_fe_batch;
     for (int j = 0; j < nsub && rc == SVO_OK; ++j) {
       const int f0 = j * SUB, b = std::min(SUB, B - f0);
-      ctx->d_kp = kp0 + f0 * K; ctx->d_desc = desc0 + f0 * K * 32; ctx->d_nkp = nkp0 + f0;
-      ctx->d_uR = uR0 + f0 * K; ctx->d_depth = depth0 + f0 * K; ctx->d_sad = sad0 + f0 * K;
-      if (ctx->feed_pair_event && hipStreamWaitEvent(ctx->stream_fe_batch, ctx->feed_pair_event[f0 + b - 1], 0) != hipSuccess) rc = SVO_E_HIP;   // host-fed: this sub-batch's uploads
+      const SvoFeBufs fb = set.outputs_at(K, f0, f0);
+      if (pair_ready && hipStreamWaitEvent(fs, pair_ready[f0 + b - 1], 0) != hipSuccess) rc = SVO_E_HIP;   // host-fed: this sub-batch's uploads
       if (rc) break;
-      rc = svo_launch_orb(ctx, d_grayL + f0 * img, d_grayR + f0 * img, stride, b, 2 * b);
-      if (rc == SVO_OK) rc = svo_launch_stereo(ctx, d_grayL + f0 * img, d_grayR + f0 * img, stride, b, &ctx->cam);
-      if (rc == SVO_OK && hipEventRecord(ctx->ev_sub[j], ctx->stream_fe_batch) != hipSuccess) rc = SVO_E_HIP;
+      rc = svo_launch_orb(ctx, fs, fb, d_grayL + f0 * img, d_grayR + f0 * img, stride, b, 2 * b);
+      if (rc == SVO_OK) rc = svo_launch_stereo(ctx, fs, fb, d_grayL + f0 * img, d_grayR + f0 * img, stride, b, &ctx->cam);
+      if (rc == SVO_OK && hipEventRecord(ctx->ev_sub[j], fs) != hipSuccess) rc = SVO_E_HIP;
       wait[f0] = ctx->ev_sub[j];
     }
-    ctx->stream = s_main;
-    ctx->d_kp = own_kp; ctx->d_desc = own_desc; ctx->d_nkp = own_nkp; ctx->d_uR = own_uR; ctx->d_depth = own_depth; ctx->d_sad = own_sad;
     if (rc) return rc;
     // (the index chain: its inputs arrive through the sub-batch events; its half of the work records was last read by the pose
     // chain of the call before the previous one - the same event the front end waited for)
-    if ((rc = tail_enqueue(ctx, kp0, desc0, nkp0, depth0, ctx->max_kp, B, 1, d_results, boxes, wait.data(), nullptr, p,
+    if ((rc = tail_enqueue(ctx, set.kp, set.desc, set.nkp, set.depth, ctx->max_kp, B, 1, d_results, boxes, wait.data(), nullptr, p,
                            ctx->tb_used[p] ? ctx->tb_done[p] : ctx->ev_frontend, true)))
       return rc;
     SVO_HIP(ctx, hipEventRecord(ctx->tb_done[p], ctx->stream));   // the pose chain is the last reader of this call's set
@@ -2217,6 +2190,11 @@ extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const u
   if ((rc = tail_enqueue(ctx, ctx->d_kp, ctx->d_desc, ctx->d_nkp, ctx->d_depth, ctx->max_kp, B, 1, d_results, boxes))) return rc;
   ctx->track_frame += B;
   return SVO_OK;
+}
+
+extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR,
+                                   int stride, int B, const svo_boxes_dev* boxes, svo_track_result* d_results) {
+  return svo_track_batch_fed(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, nullptr);
 }
 
 // The ordered tail alone, for front-end results produced elsewhere (another context, another GPU): frame f's keypoints
@@ -2458,8 +2436,8 @@ int svo_shard_quiesce(svo_ctx* ctx) {
   return SVO_OK;
 }
 
-extern "C" int svo_track_sharded_dev(svo_ctx* const* ctxs, int G, const uint8_t* const* d_grayL, const uint8_t* const* d_grayR,
-                                     int stride, int B, const svo_boxes_dev* boxes, svo_track_result* d_results) {
+int svo_track_sharded_fed(svo_ctx* const* ctxs, int G, const uint8_t* const* d_grayL, const uint8_t* const* d_grayR, int stride, int B,
+                          const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* const* pair_ready) {
   if (!ctxs || G < 1 || !d_grayL || !d_grayR || B < 1 || !d_results) return SVO_E_INVALID;
   svo_ctx* c0 = ctxs[0];
   if (!c0 || !c0->d_track || c0->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset(ctxs[0]) first
@@ -2587,12 +2565,9 @@ extern "C" int svo_track_sharded_dev(svo_ctx* const* ctxs, int G, const uint8_t*
   int rc = SVO_OK;
   // sub-batch by sub-batch, every context's share of it (contexts on the tail's device share ONE stream: all of context 0's
   // sub-batches in front of context 1's first would hold the tail up for the whole of context 0's front end)
-  struct Own { svo_kp* kp; uint8_t* desc; int32_t* nkp; float* uR; float* depth; int32_t* sad; hipStream_t stream; };
-  std::vector<Own> own(G);
   std::vector<hipStream_t> fsv(G, nullptr);
   for (int g = 0; g < G && rc == SVO_OK; ++g) {
     svo_ctx* c = ctxs[g];
-    own[g] = Own{c->d_kp, c->d_desc, c->d_nkp, c->d_uR, c->d_depth, c->d_sad, c->stream};
     if ((B - g + G - 1) / G <= 0) continue;
     hipSetDevice(c->device);
     { const int rcq = svo_track_quiesce(c, false); if (rcq) { hipSetDevice(c0->device); return rcq; } }   // (a batched call of this context may still read its result arrays; its own earlier calls are ordered by the stream waits below)
@@ -2609,24 +2584,20 @@ extern "C" int svo_track_sharded_dev(svo_ctx* const* ctxs, int G, const uint8_t*
       svo_ctx* c = ctxs[g];
       hipStream_t fs = fsv[g];
       hipSetDevice(c->device);
-      c->stream = fs;
-      c->d_kp = own[g].kp + (size_t)f0 * K; c->d_desc = own[g].desc + (size_t)f0 * wd; c->d_nkp = own[g].nkp + f0;
-      c->d_uR = own[g].uR + (size_t)f0 * K; c->d_depth = own[g].depth + (size_t)f0 * K; c->d_sad = own[g].sad + (size_t)f0 * K;
-      if (c->feed_pair_event && hipStreamWaitEvent(fs, c->feed_pair_event[f0 + b - 1], 0) != hipSuccess) rc = SVO_E_HIP;   // host-fed: this sub-batch's uploads (context g's copy stream, its device)
-      if (rc == SVO_OK) rc = svo_launch_orb(c, d_grayL[g] + f0 * img, d_grayR[g] + f0 * img, stride, b, 2 * b);
-      if (rc == SVO_OK) rc = svo_launch_stereo(c, d_grayL[g] + f0 * img, d_grayR[g] + f0 * img, stride, b, &c0->cam);
+      const SvoFeBufs fb = svo_fe_own(c).outputs_at(K, f0, f0);
+      if (pair_ready && hipStreamWaitEvent(fs, pair_ready[g][f0 + b - 1], 0) != hipSuccess) rc = SVO_E_HIP;   // host-fed: this sub-batch's uploads (context g's copy stream, its device)
+      if (rc == SVO_OK) rc = svo_launch_orb(c, fs, fb, d_grayL[g] + f0 * img, d_grayR[g] + f0 * img, stride, b, 2 * b);
+      if (rc == SVO_OK) rc = svo_launch_stereo(c, fs, fb, d_grayL[g] + f0 * img, d_grayR[g] + f0 * img, stride, b, &c0->cam);
       if (rc == SVO_OK && !direct[g]) {
         // bounce, first half: this sub-batch's results into the context's region of the pinned buffer, on its own stream
         uint8_t* h = sg->h_stage + region_bytes * g;
-        if (hipMemcpyAsync(h + wk * f0, c->d_kp, wk * b, hipMemcpyDeviceToHost, fs) != hipSuccess ||
-            hipMemcpyAsync(h + wk * rper + wd * f0, c->d_desc, wd * b, hipMemcpyDeviceToHost, fs) != hipSuccess ||
-            hipMemcpyAsync(h + (wk + wd) * rper + wf * f0, c->d_depth, wf * b, hipMemcpyDeviceToHost, fs) != hipSuccess ||
-            hipMemcpyAsync(h + (wk + wd + wf) * rper + 4 * (size_t)f0, c->d_nkp, 4 * (size_t)b, hipMemcpyDeviceToHost, fs) != hipSuccess)
+        if (hipMemcpyAsync(h + wk * f0, fb.kp, wk * b, hipMemcpyDeviceToHost, fs) != hipSuccess ||
+            hipMemcpyAsync(h + wk * rper + wd * f0, fb.desc, wd * b, hipMemcpyDeviceToHost, fs) != hipSuccess ||
+            hipMemcpyAsync(h + (wk + wd) * rper + wf * f0, fb.depth, wf * b, hipMemcpyDeviceToHost, fs) != hipSuccess ||
+            hipMemcpyAsync(h + (wk + wd + wf) * rper + 4 * (size_t)f0, fb.nkp, 4 * (size_t)b, hipMemcpyDeviceToHost, fs) != hipSuccess)
           rc = SVO_E_HIP;
       }
       if (rc == SVO_OK && hipEventRecord(c->ev_sub[j], fs) != hipSuccess) rc = SVO_E_HIP;
-      c->stream = own[g].stream;
-      c->d_kp = own[g].kp; c->d_desc = own[g].desc; c->d_nkp = own[g].nkp; c->d_uR = own[g].uR; c->d_depth = own[g].depth; c->d_sad = own[g].sad;
     }
   }
   hipSetDevice(c0->device);
@@ -2684,6 +2655,11 @@ extern "C" int svo_track_sharded_dev(svo_ctx* const* ctxs, int G, const uint8_t*
   sg->parity ^= 1;
   c0->track_frame += B;
   return SVO_OK;
+}
+
+extern "C" int svo_track_sharded_dev(svo_ctx* const* ctxs, int G, const uint8_t* const* d_grayL, const uint8_t* const* d_grayR,
+                                     int stride, int B, const svo_boxes_dev* boxes, svo_track_result* d_results) {
+  return svo_track_sharded_fed(ctxs, G, d_grayL, d_grayR, stride, B, boxes, d_results, nullptr);
 }
 
 // Parity probe: cv::solvePnPRansac's outcome for the frame just tracked (winning sample, consensus, samples visited)
