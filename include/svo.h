@@ -17,7 +17,8 @@
  *     return after the result is in the caller's memory.
  *   - Return 0 (SVO_OK) or a negative svo_status.  Nothing here falls back to a
  *     CPU path: if no HIP device is usable, svo_create fails with SVO_E_NODEVICE.
- *   - Images are 8-bit gray, row-major, `stride` bytes per row.
+ *   - Images are 8-bit gray, row-major, `stride` bytes per row - except in the entries named _bgr, which take the 8UC3
+ *     BGR images the reference reads (interleaved B, G, R bytes, `stride` >= 3 * W bytes per row; "colour input" below).
  *   - Keypoints use the 28-byte layout of cv::KeyPoint (pt.x, pt.y, size, angle,
  *     response, octave, class_id) so `frame::keypoints_l` can alias the buffer.
  *   - Descriptors are n x 32 bytes row-major, like `frame::f_descriptor`
@@ -32,7 +33,9 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 7   /* 7 (round 6): + svo_track_batch_host, svo_track_sharded_host, svo_frontend_batch_host (pipelined host-fed entries:
+#define SVO_ABI_VERSION 7   /* 7, backward-compatible additions: svo_bgr_to_gray, svo_track_frame_bgr, svo_track_batch_bgr_dev,
+                              svo_track_batch_bgr_host (8UC3 BGR input, see "colour input" below); no existing entry changed.
+                              7 (round 6): + svo_track_batch_host, svo_track_sharded_host, svo_frontend_batch_host (pipelined host-fed entries:
                               images start in host memory, uploads run on a copy stream ahead of the front end, records come back to
                               host memory; svo_boxes_host), svo_create_ex (per-context stream mode), svo_stream_mode; svo_sync also
                               completes the host-fed calls' outputs.  Later: version 4's two-launch RANSAC switch is no longer accepted (SVO_E_INVALID).
@@ -204,8 +207,9 @@ void svo_destroy(svo_ctx* ctx);
  * steps nothing else is enqueued on the context (svo_sync and reading results are fine); svo_track_multi_reset restarts it.
  * "depth_source" (default 0): where svo_track_frame / svo_track_batch_dev take keypoint depth from - 0 the sparse
  * epipolar matcher (north star), 1 a dense ELAS map (svo_elas_*), 2 a dense MSA map (svo_msa_solve with d = 48: the
- * reference's live configuration, src/Tracking.cc:225-228 + src/frame.cc:82-91), both read per keypoint as
- * frame::computekeypoint_r / disp2Depth do.
+ * reference's live configuration, src/Tracking.cc:225-228 + src/frame.cc:82-91 - on the reference's colour input through the _bgr
+ * entries; the gray entries hand MSA B = G = R copies of the gray), both read per keypoint as frame::computekeypoint_r /
+ * disp2Depth do.
  * "fe_cu_percent" (default 12 = 32 of the 256 CUs, 10..100): share of the compute units (whole 32-bit words of the CU mask; measured
  * with tools/microbench/cu_mask_probe: the first word is FOUR CUs ON EACH of the eight XCDs, not one XCD) the front-end stream of
  * svo_track_batch_dev may use.  Its kernels would otherwise fill every CU while the ordered tail runs beside them, and the
@@ -484,6 +488,33 @@ int svo_track_sharded_host(svo_ctx* const* ctxs, int G, const uint8_t* grayL, co
  * following call returned.  Its rate is what the PCIe link delivers (0.93 MB per 1241x376 pair). */
 int svo_frontend_batch_host(svo_ctx* ctx, const uint8_t* grayL, const uint8_t* grayR, int stride, int B,
                             const svo_camera* cam, svo_kp* kpL, uint8_t* descL, int32_t* nL, float* uR, float* depth);
+
+/* ---- colour input (main.cpp:160-161: KITTI image_2 / image_3 read with CV_LOAD_IMAGE_UNCHANGED, 8UC3 BGR) ----------------
+ * The reference's tracker consumes colour in two places: cv::ORB reduces it to gray (COLOR_BGR2GRAY, src/frame.cc:75-79), and
+ * frame::MB hands it to MSA::solve (src/frame.cc:82-91), whose cost, 3x3 median and tree weights use the three channels.  The
+ * entries below take colour pairs and convert them ON THE DEVICE with cv::cvtColor(COLOR_BGR2GRAY)'s fixed point for 8U,
+ * gray = (1868 B + 9617 G + 4899 R + 8192) >> 14 (B = G = R = v gives v); from that gray on, ORB, the sparse matcher and ELAS
+ * (depth_source 0 / 1) run exactly as in their gray counterparts - ELAS on gray is the only definition there is, the reference
+ * never calls libelas.  With depth_source 2 MSA gets the true colour pair (the gray entries give it B = G = R copies of the
+ * gray), and computes its own 0.299 / 0.587 / 0.114 gray from it, as the reference does.  Argument checks, contracts and overlap
+ * rules are those of the gray counterparts, with stride >= 3 * W; gray and colour calls may follow each other within one
+ * sequence, each frame's record being what its own pixels imply.  A context allocates its colour staging on the first colour
+ * call.  svo_track_sharded_*, svo_track_multi_step_dev and svo_frontend_batch_* stay gray-only. */
+
+/* BGR -> gray with cv::cvtColor(COLOR_BGR2GRAY)'s fixed-point weights; host buffers in and out (any width x height, rows
+ * bgr_stride >= 3 * width and gray_stride >= width bytes apart).  Synchronises. */
+int svo_bgr_to_gray(svo_ctx* ctx, const uint8_t* bgr, int width, int height, int bgr_stride, uint8_t* gray, int gray_stride);
+/* svo_track_frame for 8UC3 BGR host images (main.cpp:160-161). */
+int svo_track_frame_bgr(svo_ctx* ctx, const uint8_t* bgrL, int strideL, const uint8_t* bgrR, int strideR, double timestamp,
+                        const int32_t* boxes, int n_boxes, svo_track_result* res);
+/* svo_track_batch_dev for B BGR pairs in HBM (pair b at d_bgrL + b * H * stride), stride >= 3 * W.  The gray of each front-end
+ * sub-batch is written just before it, on the front end's stream, into staging of the context's own (max_batch pairs). */
+int svo_track_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_bgrL, const uint8_t* d_bgrR, int stride, int B,
+                            const svo_boxes_dev* boxes, svo_track_result* d_results);
+/* svo_track_batch_host for B BGR pairs in host memory (pinned or pageable), same contract.  Each upload chunk of eight pairs is
+ * converted on the copy stream before its event, so a front-end sub-batch still waits for its own pairs only. */
+int svo_track_batch_bgr_host(svo_ctx* ctx, const uint8_t* bgrL, const uint8_t* bgrR, int stride, int B,
+                             const svo_boxes_host* boxes, svo_track_result* results);
 
 /* Sticky flag of the device tracker (synchronises).  4: see SVO_E_TIMEOUT.  1: capacity - *flag != 0 once a frame needed more than the 4096 live
  * map points the pool holds, or a map point stayed alive for more than 2^20 creations (its slot in the position table

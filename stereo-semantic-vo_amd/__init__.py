@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "svo_elas_default_params", "svo_elas_process", "svo_elas_process_ex", "svo_elas_delaunay",
     "svo_ctmf", "svo_track_multi_reset", "svo_track_multi_step_dev", "svo_track_tail_dev", "svo_track_overflowed", "svo_track_epnp_fallbacks", "svo_debug_stream_probe", "svo_debug_stream_pipes", "svo_track_sharded_dev", "svo_elas_batch_dev", "svo_msa_init", "svo_msa_tree", "svo_msa_tree_dp", "svo_msa_wta", "svo_msa_lrcheck", "svo_msa_solve", "svo_msa_batch_dev",
     "svo_create_ex", "svo_stream_mode", "svo_track_batch_host", "svo_track_sharded_host", "svo_frontend_batch_host",
+    "svo_bgr_to_gray", "svo_track_frame_bgr", "svo_track_batch_bgr_dev", "svo_track_batch_bgr_host",
 ]
 
 # svo_create_ex flags (include/svo.h)
@@ -335,6 +336,34 @@ class Svo:
         self._chk(self.lib.svo_track_frame(self.h, _p(grayL), self.W, _p(grayR), self.W,
                                            C.c_double(timestamp), _p(bx), nb, _p(res)))
         return res[0]
+
+    # ---- colour input (8UC3 BGR, as the reference's driver reads KITTI image_2 / image_3) ------------------------------------
+    def bgr_to_gray(self, bgr):
+        """svo_bgr_to_gray: (H, W, 3) uint8 BGR -> (H, W) gray with cv::cvtColor(COLOR_BGR2GRAY)'s fixed point, on the device."""
+        a = _u8(bgr)
+        H, W = a.shape[:2]
+        out = np.zeros((H, W), np.uint8)
+        self._chk(self.lib.svo_bgr_to_gray(self.h, _p(a), W, H, 3 * W, _p(out), W))
+        return out
+
+    def track_frame_bgr(self, bgrL, bgrR, timestamp=0.0, boxes=None):
+        """svo_track_frame_bgr: track_frame for a (H, W, 3) BGR pair."""
+        bgrL = _u8(bgrL); bgrR = _u8(bgrR)
+        res = np.zeros(1, TRACK_DTYPE)
+        bx = None if boxes is None or len(boxes) == 0 else np.ascontiguousarray(boxes, np.int32)
+        nb = 0 if bx is None else len(bx)
+        self._chk(self.lib.svo_track_frame_bgr(self.h, _p(bgrL), 3 * self.W, _p(bgrR), 3 * self.W,
+                                               C.c_double(timestamp), _p(bx), nb, _p(res)))
+        return res[0]
+
+    def track_batch_bgr_dev(self, d_bgrL, d_bgrR, stride, B, d_results, boxes=None):
+        """svo_track_batch_bgr_dev: track_batch_dev for B BGR pairs in HBM (pair b at d_bgrL + b * H * stride, stride >= 3 W)."""
+        self._chk(self.lib.svo_track_batch_bgr_dev(self.h, _p(d_bgrL), _p(d_bgrR), int(stride), int(B), _bx(boxes),
+                                                   _p(d_results)))
+
+    def track_batch_bgr_host(self, bgrL, bgrR, stride, B, results, boxes=None):
+        """svo_track_batch_bgr_host: track_batch_host for B BGR pairs in host memory (pinned or pageable), same contract."""
+        self._chk(self.lib.svo_track_batch_bgr_host(self.h, _p(bgrL), _p(bgrR), int(stride), int(B), _bx(boxes), _p(results)))
 
     def debug_track_gate(self):
         F = np.zeros(9); n = C.c_int32(0)

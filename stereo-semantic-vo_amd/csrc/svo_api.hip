@@ -313,6 +313,7 @@ extern "C" void svo_destroy(svo_ctx* ctx) {
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
   (void)hipGetLastError();
   svo_hostfeed_release(ctx);
+  svo_colour_release(ctx);
   svo_track_release(ctx);
   svo_elas_release(ctx);
   svo_msa_release(ctx);

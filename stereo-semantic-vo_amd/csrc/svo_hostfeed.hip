@@ -48,11 +48,25 @@ struct HostFeed {
   uint8_t* h_fe[2] = {nullptr, nullptr};
   hipEvent_t fe_done[2] = {nullptr, nullptr};
   struct FeOut { svo_kp* kp; uint8_t* desc; int32_t* n; float* uR; float* depth; int B; } fe_pending[2] = {};
+  // svo_track_batch_bgr_host: colour image sets beside the gray ones (cap left, then cap right colour images, H x bgr_pitch each) and
+  // their pinned staging - allocated by the first colour call; the gray sets then receive k_bgr2gray's output
+  uint8_t* d_bgr[2] = {nullptr, nullptr};
+  uint8_t* h_bgr[2] = {nullptr, nullptr};
+  int bgr_pitch = 0;
 };
 
 HostFeed* feed_of(svo_ctx* ctx) { return reinterpret_cast<HostFeed*>(ctx->hostfeed); }
 
 size_t img_bytes(const svo_ctx* ctx) { return (size_t)ctx->g.H * ctx->stage_pitch; }
+size_t bgr_bytes(const svo_ctx* ctx, const HostFeed* hf) { return (size_t)ctx->g.H * hf->bgr_pitch; }
+
+void free_bgr_sets(HostFeed* hf) {
+  for (int p = 0; p < 2; ++p) {
+    if (hf->d_bgr[p]) hipFree(hf->d_bgr[p]);
+    if (hf->h_bgr[p]) hipHostFree(hf->h_bgr[p]);
+    hf->d_bgr[p] = nullptr; hf->h_bgr[p] = nullptr;
+  }
+}
 
 bool is_pinned(const void* p) {
   hipPointerAttribute_t a;
@@ -92,6 +106,7 @@ int feed_reserve(svo_ctx* ctx, int pairs) {
     hf->d_fe[p] = nullptr; hf->h_fe[p] = nullptr;
     hf->used[p] = false;
   }
+  free_bgr_sets(hf);
   hf->cap = 0;
   const size_t box_bytes = (size_t)pairs * (SVO_MAX_BOXES * 16 + 4);
   for (int p = 0; p < 2; ++p) {
@@ -118,10 +133,20 @@ int feed_reserve(svo_ctx* ctx, int pairs) {
 
 // Pair i of this call (i = 0 .. n - 1) is the caller's frame `first + i * step` (sharded: first = g, step = G).  Uploads them
 // into image set p in chunks of FEED_CHUNK pairs on the copy stream; hf->pair_ev[i] = the event after which pair i is resident.
-int feed_upload(svo_ctx* ctx, int p, const uint8_t* grayL, const uint8_t* grayR, int stride, int first, int step, int n) {
+// bgr: the caller's images are 8UC3 BGR - they go to set p's colour images, and each chunk's gray is written into the gray set by
+// k_bgr2gray on the copy stream before the chunk's event (so that a sub-batch still waits for its own pairs only).
+int feed_upload(svo_ctx* ctx, int p, const uint8_t* grayL, const uint8_t* grayR, int stride, int first, int step, int n, bool bgr = false) {
   HostFeed* hf = feed_of(ctx);
-  const int W = ctx->g.W, H = ctx->g.H, pitch = ctx->stage_pitch;
-  const size_t ib = img_bytes(ctx), fb = (size_t)H * stride;
+  const int H = ctx->g.H;
+  const int W = bgr ? 3 * ctx->g.W : ctx->g.W, pitch = bgr ? hf->bgr_pitch : ctx->stage_pitch;   // (bytes per row, row pitch of the set)
+  const size_t ib = bgr ? bgr_bytes(ctx, hf) : img_bytes(ctx), fb = (size_t)H * stride;
+  const size_t gib = img_bytes(ctx);
+  auto to_gray = [&](int i0, int b) {
+    if (!bgr) return;
+    svo_launch_bgr2gray(hf->copy, hf->d_bgr[p] + i0 * ib, pitch, ib, hf->d_img[p] + i0 * gib, ctx->stage_pitch, gib, ctx->g.W, H, b);
+    svo_launch_bgr2gray(hf->copy, hf->d_bgr[p] + ((size_t)hf->cap + i0) * ib, pitch, ib, hf->d_img[p] + ((size_t)hf->cap + i0) * gib,
+                        ctx->stage_pitch, gib, ctx->g.W, H, b);
+  };
   const int nchunk = (n + FEED_CHUNK - 1) / FEED_CHUNK;
   while ((int)hf->ev_up[p].size() < nchunk) {
     hipEvent_t e;
@@ -130,8 +155,8 @@ int feed_upload(svo_ctx* ctx, int p, const uint8_t* grayL, const uint8_t* grayR,
   }
   // the set's last readers (front end / dense stage of the call two back) first
   for (int k = 0; k < hf->n_free[p]; ++k) SVO_HIP(ctx, hipStreamWaitEvent(hf->copy, hf->img_free[p][k], 0));
-  uint8_t* dL = hf->d_img[p];
-  uint8_t* dR = hf->d_img[p] + (size_t)hf->cap * ib;
+  uint8_t* dL = bgr ? hf->d_bgr[p] : hf->d_img[p];
+  uint8_t* dR = dL + (size_t)hf->cap * ib;
   const bool pinned = is_pinned(grayL) && is_pinned(grayR);
   hf->pair_ev.assign((size_t)n, nullptr);
   if (pinned) {
@@ -160,6 +185,7 @@ int feed_upload(svo_ctx* ctx, int p, const uint8_t* grayL, const uint8_t* grayR,
           }
         }
       }
+      to_gray(i0, b);
       SVO_HIP(ctx, hipEventRecord(hf->ev_up[p][c], hf->copy));
       for (int i = i0; i < i0 + b; ++i) hf->pair_ev[i] = hf->ev_up[p][c];
     }
@@ -168,19 +194,21 @@ int feed_upload(svo_ctx* ctx, int p, const uint8_t* grayL, const uint8_t* grayR,
   // Pageable source: rows gathered into the pinned ring by worker threads (a copy straight from pageable memory blocks the
   // caller and moves ~14 ms per image on this stack, docs/NEXT_ROUNDS.md), chunk by chunk; this thread enqueues each chunk's
   // linear H2D as soon as it is staged - staging of chunk c + 1 runs beside the upload of chunk c.
-  if (!hf->h_img[p]) {
-    if (hipHostMalloc(reinterpret_cast<void**>(&hf->h_img[p]), 2 * (size_t)hf->cap * ib) != hipSuccess) {
+  uint8_t*& ring = bgr ? hf->h_bgr[p] : hf->h_img[p];
+  if (!ring) {
+    if (hipHostMalloc(reinterpret_cast<void**>(&ring), 2 * (size_t)hf->cap * ib) != hipSuccess) {
       (void)hipGetLastError();
+      ring = nullptr;
       ctx->last_error = "host feed: out of pinned memory for the staging ring";
       return SVO_E_NOMEM;
     }
-    memset(hf->h_img[p], 0, 2 * (size_t)hf->cap * ib);
+    memset(ring, 0, 2 * (size_t)hf->cap * ib);
   } else if (hf->used[p] && !hf->ev_up[p].empty()) {
     // the uploads that last read this half of the ring (two calls back)
     for (hipEvent_t e : hf->ev_up[p]) SVO_HIP(ctx, hipEventSynchronize(e));
   }
-  uint8_t* hL = hf->h_img[p];
-  uint8_t* hR = hf->h_img[p] + (size_t)hf->cap * ib;
+  uint8_t* hL = ring;
+  uint8_t* hR = ring + (size_t)hf->cap * ib;
   std::vector<std::atomic<int>> staged((size_t)nchunk);
   for (auto& s : staged) s.store(0, std::memory_order_relaxed);
   const int T = std::max(1, std::min({4, svo_host_cpus() - 1, nchunk}));   // staging threads (this thread enqueues)
@@ -220,7 +248,7 @@ int feed_upload(svo_ctx* ctx, int p, const uint8_t* grayL, const uint8_t* grayR,
       const int i0 = c * FEED_CHUNK, b = std::min(FEED_CHUNK, n - i0);
       if (hipMemcpyAsync(dL + i0 * ib, hL + i0 * ib, ib * b, hipMemcpyHostToDevice, hf->copy) != hipSuccess ||
           hipMemcpyAsync(dR + i0 * ib, hR + i0 * ib, ib * b, hipMemcpyHostToDevice, hf->copy) != hipSuccess ||
-          hipEventRecord(hf->ev_up[p][c], hf->copy) != hipSuccess) {
+          (to_gray(i0, b), hipEventRecord(hf->ev_up[p][c], hf->copy) != hipSuccess)) {
         ctx->last_error = std::string("host feed upload: ") + hipGetErrorString(hipGetLastError());
         rc = SVO_E_HIP;
       }
@@ -325,14 +353,17 @@ void svo_hostfeed_release(svo_ctx* ctx) {
     if (hf->res_done[p]) hipEventDestroy(hf->res_done[p]);
     if (hf->fe_done[p]) hipEventDestroy(hf->fe_done[p]);
   }
+  free_bgr_sets(hf);
   if (hf->copy) hipStreamDestroy(hf->copy);
   delete hf;
   ctx->hostfeed = nullptr;
 }
 
-extern "C" int svo_track_batch_host(svo_ctx* ctx, const uint8_t* grayL, const uint8_t* grayR, int stride, int B,
-                                    const svo_boxes_host* boxes, svo_track_result* results) {
-  if (!ctx || !grayL || !grayR || !results || B < 1 || stride < ctx->g.W) return SVO_E_INVALID;
+namespace {
+// svo_track_batch_host (bgr = false) and svo_track_batch_bgr_host (bgr = true: 8UC3 BGR images, `stride` >= 3 W)
+int track_batch_host(svo_ctx* ctx, const uint8_t* grayL, const uint8_t* grayR, int stride, int B, const svo_boxes_host* boxes,
+                     svo_track_result* results, bool bgr) {
+  if (!ctx || !grayL || !grayR || !results || B < 1 || stride < (bgr ? 3 : 1) * ctx->g.W) return SVO_E_INVALID;
   if (B > ctx->max_batch) return SVO_E_CAPACITY;
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset first
   hipSetDevice(ctx->device);
@@ -340,14 +371,27 @@ extern "C" int svo_track_batch_host(svo_ctx* ctx, const uint8_t* grayL, const ui
   int rc = feed_reserve(ctx, ctx->max_batch);
   if (rc) return rc;
   HostFeed* hf = feed_of(ctx);
+  if (bgr && !hf->d_bgr[0]) {
+    // the colour sets (first colour call): nothing of the gray sets is in flight on them, nothing to wait for
+    hf->bgr_pitch = (3 * ctx->g.W + 255) & ~255;
+    for (int q = 0; q < 2; ++q)
+      if (hipMalloc(reinterpret_cast<void**>(&hf->d_bgr[q]), 2 * (size_t)hf->cap * bgr_bytes(ctx, hf)) != hipSuccess) {
+        (void)hipGetLastError();
+        free_bgr_sets(hf);
+        ctx->last_error = "host feed: out of memory for the colour image sets";
+        return SVO_E_NOMEM;
+      }
+  }
   const int p = hf->parity;
   if ((rc = flush_set(ctx, hf, p))) return rc;          // what the call two back left in this set's pinned buffers
   svo_boxes_dev bx;
   if ((rc = feed_boxes(ctx, p, boxes, B, &bx))) return rc;
-  if ((rc = feed_upload(ctx, p, grayL, grayR, stride, 0, 1, B))) return rc;
+  if ((rc = feed_upload(ctx, p, grayL, grayR, stride, 0, 1, B, bgr))) return rc;
   const size_t ib = img_bytes(ctx);
+  SvoBgrSrc src;   // (colour: the gray is already written on the copy stream, chunk by chunk; MSA reads the colour set)
+  if (bgr) { src.L = hf->d_bgr[p]; src.R = hf->d_bgr[p] + (size_t)hf->cap * bgr_bytes(ctx, hf); src.stride = hf->bgr_pitch; }
   rc = svo_track_batch_fed(ctx, hf->d_img[p], hf->d_img[p] + (size_t)hf->cap * ib, ctx->stage_pitch, B, bx.boxes ? &bx : nullptr, hf->d_res[p],
-                           hf->pair_ev.data());
+                           hf->pair_ev.data(), bgr ? &src : nullptr);
   if (rc) return rc;
   // who read the images of this set: the front-end stream (sparse depth), the dense stage's streams and the main stream otherwise
   int nf = 0;
@@ -363,6 +407,17 @@ extern "C" int svo_track_batch_host(svo_ctx* ctx, const uint8_t* grayL, const ui
   hf->used[p] = true;
   hf->parity ^= 1;
   return SVO_OK;
+}
+}  // namespace
+
+extern "C" int svo_track_batch_host(svo_ctx* ctx, const uint8_t* grayL, const uint8_t* grayR, int stride, int B,
+                                    const svo_boxes_host* boxes, svo_track_result* results) {
+  return track_batch_host(ctx, grayL, grayR, stride, B, boxes, results, false);
+}
+
+extern "C" int svo_track_batch_bgr_host(svo_ctx* ctx, const uint8_t* bgrL, const uint8_t* bgrR, int stride, int B,
+                                        const svo_boxes_host* boxes, svo_track_result* results) {
+  return track_batch_host(ctx, bgrL, bgrR, stride, B, boxes, results, true);
 }
 
 extern "C" int svo_track_sharded_host(svo_ctx* const* ctxs, int G, const uint8_t* grayL, const uint8_t* grayR, int stride, int B,

@@ -206,6 +206,7 @@ struct svo_ctx {
   bool timeout_reported = false;                  // svo_sync returned SVO_E_TIMEOUT for this context once (sticky flag 4, svo_track_check_timeout)
   uint32_t create_flags = 0;                      // svo_create_ex
   void* hostfeed = nullptr;                       // HostFeed (svo_hostfeed.hip): copy stream, image sets, pinned staging of the host-fed entries
+  void* colour = nullptr;                         // SvoColour (svo_colour.hip): staging of the colour entries, allocated by the first colour call
   bool profiling = false;
   std::vector<SvoProfileEntry> prof;
   void* prof_impl = nullptr;  // SvoProfState (svo_api.hip)
@@ -305,8 +306,29 @@ int svo_elas_batch_dev_hooked(svo_ctx* ctx, hipStream_t s, const uint8_t* d_L, c
                               int (*hook)(void*, int, int), void* user);   // svo_elas.hip: svo_elas_batch_dev on stream `s`
 // svo_track.hip: svo_track_batch_dev / svo_track_sharded_dev for the host-fed entries (svo_hostfeed.hip), whose images arrive on a
 // copy stream: pair i of the call is resident in HBM after pair_ready[i] (context g's own pair i: pair_ready[g][i])
+// The colour (8UC3 BGR) pairs behind a call's gray ones (svo_track_batch_bgr_dev / _host): pair b at L / R + b * H * stride.
+// convert: the call writes the gray pairs itself from these, on the stream that reads them first (after waiting for `wait`);
+// otherwise they are already there.  With depth_source 2 MSA reads the colour instead of B = G = R copies of the gray.
+struct SvoBgrSrc {
+  const uint8_t* L = nullptr;
+  const uint8_t* R = nullptr;
+  int stride = 0;
+  bool convert = false;
+  const hipEvent_t* wait = nullptr;
+  int n_wait = 0;
+};
 int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
-                        const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready);
+                        const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready,
+                        const SvoBgrSrc* bgr = nullptr);
+// svo_track.hip: svo_track_frame once both gray images are in the context's staging slots 0 / 1 (d_bgrL / d_bgrR: the colour
+// pair in HBM for depth_source 2, `bgr_pitch` bytes per row; nullptr: MSA takes B = G = R copies of the gray)
+int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
+                           const uint8_t* d_bgrR, int bgr_pitch);
+// svo_colour.hip: cv::cvtColor(COLOR_BGR2GRAY) of n images (image i at bgr + i * bgr_frame, rows `bgr_stride` bytes apart, any
+// stride >= 3 W) into gray + i * gray_frame (rows `gray_pitch` apart), enqueued on `st`
+void svo_launch_bgr2gray(hipStream_t st, const uint8_t* bgr, int bgr_stride, size_t bgr_frame, uint8_t* gray, int gray_pitch,
+                         size_t gray_frame, int W, int H, int n);
+void svo_colour_release(svo_ctx* ctx);
 int svo_track_sharded_fed(svo_ctx* const* ctxs, int G, const uint8_t* const* d_grayL, const uint8_t* const* d_grayR, int stride, int B,
                           const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* const* pair_ready);
 hipError_t svo_stream_create_masked(hipStream_t* st, int device, int percent);
@@ -334,9 +356,10 @@ struct HostTimer {
   }
 };
 
-int svo_msa_run_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitch, int W, int H, int d, float* d_disp);
+// bgr = false: dL / dR are gray (MSA gets B = G = R); true: they are 8UC3 BGR rows, `pitch` bytes apart
+int svo_msa_run_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitch, int W, int H, int d, float* d_disp, bool bgr = false);
 int svo_msa_run_many_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitch, size_t frame_stride, int W, int H, int d,
-                         int B, float* d_disp);
+                         int B, float* d_disp, bool bgr = false);
 int svo_elas_run_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitch, int W, int H,
                      const svo_elas_params* params, float** dD1, float** dD2, int* produced);
 

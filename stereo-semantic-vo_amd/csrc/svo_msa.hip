@@ -999,19 +999,26 @@ __global__ void k_msa_to_float(const uint8_t* d, int n, float* out) {
 }
 }  // namespace
 
-// frame::MB (src/frame.cc:82-91) for the tracker's dense-depth mode: gray images already on the device (a grayscale
-// file read as colour has B = G = R), disparity as CV_32F like `disp_img.convertTo(disp_32f, CV_32F, 1)`.
+// MSA's input image in its tight 8UC3 layout: B = G = R copies of a gray image on the device (what a grayscale file read as
+// colour gives), or a pitched copy of a colour image on the device (the colour entries, main.cpp:160-161)
+static hipError_t msa_load_img3(hipStream_t st, const uint8_t* src, int pitch, bool bgr, int m, int n, uint8_t* img3) {
+  if (bgr) return hipMemcpy2DAsync(img3, 3 * (size_t)m, src, pitch, 3 * (size_t)m, n, hipMemcpyDeviceToDevice, st);
+  hipLaunchKernelGGL(k_msa_gray_to_bgr, dim3((m + 255) / 256, n), dim3(256), 0, st, src, pitch, m, n, img3);
+  return hipSuccess;
+}
+
+// frame::MB (src/frame.cc:82-91) for the tracker's dense-depth mode: gray or colour images already on the device, disparity
+// as CV_32F like `disp_img.convertTo(disp_32f, CV_32F, 1)`.
 static int msa_run_on_stream(svo_ctx* ctx, hipStream_t st, int arena, const uint8_t* dL, const uint8_t* dR, int pitch, int W,
-                             int H, int d, float* d_disp) {
+                             int H, int d, float* d_disp, bool bgr) {
   if (H < 5 || W < 5 || d < 0 || d > 255) return SVO_E_INVALID;
   const size_t N = (size_t)W * H;
   DevBuf& buf = msa_arena(ctx, arena);
   uint8_t* img3[2] = {buf.get<uint8_t>(3 * N), buf.get<uint8_t>(3 * N)};
   uint8_t* d_out = buf.get<uint8_t>(N);
   if (!img3[0] || !img3[1] || !d_out) { ctx->last_error = "svo_msa_run_dev: hipMalloc"; return SVO_E_NOMEM; }
-  const dim3 px((W + 255) / 256, H);
-  hipLaunchKernelGGL(k_msa_gray_to_bgr, px, dim3(256), 0, st, dL, pitch, W, H, img3[0]);
-  hipLaunchKernelGGL(k_msa_gray_to_bgr, px, dim3(256), 0, st, dR, pitch, W, H, img3[1]);
+  SVO_HIP(ctx, msa_load_img3(st, dL, pitch, bgr, W, H, img3[0]));
+  SVO_HIP(ctx, msa_load_img3(st, dR, pitch, bgr, W, H, img3[1]));
   const int rc = msa_solve_device(ctx, st, buf, img3, H, W, d, 1, d_out);
   if (rc) return rc;
   hipLaunchKernelGGL(k_msa_to_float, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_out, (int)N, d_disp);
@@ -1019,8 +1026,8 @@ static int msa_run_on_stream(svo_ctx* ctx, hipStream_t st, int arena, const uint
   return SVO_OK;
 }
 
-int svo_msa_run_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitch, int W, int H, int d, float* d_disp) {
-  return msa_run_on_stream(ctx, ctx->stream, 0, dL, dR, pitch, W, H, d, d_disp);
+int svo_msa_run_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitch, int W, int H, int d, float* d_disp, bool bgr) {
+  return msa_run_on_stream(ctx, ctx->stream, 0, dL, dR, pitch, W, H, d, d_disp, bgr);
 }
 
 // MSA::solve for C frames together (gray frames on the device, float maps out): init per frame, all 2C trees on host
@@ -1031,7 +1038,7 @@ int svo_msa_run_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitc
 // aggregates the previous one and initialises the next.
 static int msa_many_device(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int pitch, size_t frame_stride,
                            int m, int n, int d, int C, float* d_disp_out, int lane, std::mutex* host_phase,
-                           std::mutex* gpu_phase) {
+                           std::mutex* gpu_phase, bool bgr) {
   const bool dbg = getenv("SVO_MSA_DEBUG") != nullptr;
   auto t_last = std::chrono::steady_clock::now();
   auto mark = [&](const char* what) {
@@ -1079,8 +1086,8 @@ static int msa_many_device(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const
   std::vector<std::vector<double>>& h_gra = hs.gra;
   mark("host buffers");
   for (int b = 0; b < C; ++b) {
-    hipLaunchKernelGGL(k_msa_gray_to_bgr, px, dim3(256), 0, s, dL + b * frame_stride, pitch, m, n, img3[0]);
-    hipLaunchKernelGGL(k_msa_gray_to_bgr, px, dim3(256), 0, s, dR + b * frame_stride, pitch, m, n, img3[1]);
+    SVO_HIP(ctx, msa_load_img3(s, dL + b * frame_stride, pitch, bgr, m, n, img3[0]));
+    SVO_HIP(ctx, msa_load_img3(s, dR + b * frame_stride, pitch, bgr, m, n, img3[1]));
     for (int side = 0; side < 2; ++side) {
       hipLaunchKernelGGL(k_msa_gray, dim3(nbN), dim3(256), 0, s, img3[side], (int)N, gray);
       hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 1, 127.5, g + side * N);
@@ -1209,11 +1216,11 @@ static int msa_many_device(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const
 // B frames (frame b at dL + b * frame_stride bytes, map b at d_disp + b * W * H floats), solved in chunks that share
 // their launches and build their trees side by side.
 int svo_msa_run_many_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitch, size_t frame_stride, int W, int H, int d,
-                         int B, float* d_disp) {
+                         int B, float* d_disp, bool bgr) {
   const size_t N = (size_t)W * H;
   if (B <= 1 || ctx->profiling || (int64_t)N * (d + 1) * 16 > ((int64_t)1 << 31) || getenv("SVO_MSA_FRAME_BY_FRAME")) {
     for (int b = 0; b < B; ++b) {
-      const int rc = svo_msa_run_dev(ctx, dL + b * frame_stride, dR + b * frame_stride, pitch, W, H, d, d_disp + b * N);
+      const int rc = svo_msa_run_dev(ctx, dL + b * frame_stride, dR + b * frame_stride, pitch, W, H, d, d_disp + b * N, bgr);
       if (rc) return rc;
     }
     return SVO_OK;
@@ -1221,7 +1228,7 @@ int svo_msa_run_many_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int
   // chunks of up to 16 frames: ~0.4 GB of HBM per frame at KITTI size (four cost volumes)
   const int nchunk = (B + 15) / 16;
   if (nchunk == 1)
-    return msa_many_device(ctx, ctx->stream, dL, dR, pitch, frame_stride, W, H, d, B, d_disp, 0, nullptr, nullptr);
+    return msa_many_device(ctx, ctx->stream, dL, dR, pitch, frame_stride, W, H, d, B, d_disp, 0, nullptr, nullptr, bgr);
   // two lanes (threads, streams, arenas) take the chunks alternately
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));   // whatever produced the frames
   std::mutex host_phase, gpu_phase;
@@ -1233,7 +1240,7 @@ int svo_msa_run_many_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int
     for (int c = t; c < nchunk; c += 2) {
       const int b0 = 16 * c, C = std::min(16, B - b0);
       const int rc = msa_many_device(ctx, st[t], dL + b0 * frame_stride, dR + b0 * frame_stride, pitch, frame_stride, W, H, d, C,
-                                     d_disp + b0 * N, t, &host_phase, &gpu_phase);
+                                     d_disp + b0 * N, t, &host_phase, &gpu_phase, bgr);
       if (rc) { rcs[t] = rc; return; }
     }
   };

@@ -1917,13 +1917,20 @@ extern "C" int svo_track_frame(svo_ctx* ctx, const uint8_t* grayL, int strideL,
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset first
   hipSetDevice(ctx->device);
   { const int rcq = svo_track_quiesce(ctx); if (rcq) return rcq; }
+  int rc = svo_upload_image(ctx, grayL, strideL, 0);
+  if (rc) return rc;
+  if ((rc = svo_upload_image(ctx, grayR, strideR, 1))) return rc;
+  return svo_track_frame_staged(ctx, boxes, n_boxes, res, nullptr, nullptr, 0);
+}
+
+// svo_track_frame / svo_track_frame_bgr from the point where the pair's gray images are in staging slots 0 / 1
+int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
+                           const uint8_t* d_bgrR, int bgr_pitch) {
   const SvoGeom& g = ctx->g;
   TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
   uint8_t* dL = ctx->d_stage;
   uint8_t* dR = ctx->d_stage + (size_t)g.H * ctx->stage_pitch;
-  int rc = svo_upload_image(ctx, grayL, strideL, 0);
-  if (rc) return rc;
-  if ((rc = svo_upload_image(ctx, grayR, strideR, 1))) return rc;
+  int rc;
   // the frame's boxes go to HBM with the images (pinned staging: the copies are asynchronous, the caller's array may be
   // pageable); from there on a gated frame is device work only
   int32_t* h_box = reinterpret_cast<int32_t*>(ctx->h_pinned + ctx->pinned_bytes - 4096);   // the buffer's last page: reserved for this (svo_msa.hip stays below it)
@@ -1949,7 +1956,10 @@ extern "C" int svo_track_frame(svo_ctx* ctx, const uint8_t* grayL, int strideL,
     // the reference's live configuration: frame::MB = MSA::solve(left, right, 48, 1) (src/Tracking.cc:225-228)
     if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 1))) return rc;
     if ((rc = dense_reserve(ctx, 1))) return rc;
-    if ((rc = svo_msa_run_dev(ctx, dL, dR, ctx->stage_pitch, g.W, g.H, 48, ctx->d_dense))) return rc;
+    // (colour entry: MSA gets the true colour pair, as in the reference; gray entry: B = G = R copies of the gray)
+    if ((rc = d_bgrL ? svo_msa_run_dev(ctx, d_bgrL, d_bgrR, bgr_pitch, g.W, g.H, 48, ctx->d_dense, true)
+                     : svo_msa_run_dev(ctx, dL, dR, ctx->stage_pitch, g.W, g.H, 48, ctx->d_dense)))
+      return rc;
     SvoTimer t(ctx, "k_tk_dense_depth");
     hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_kp,
                        ctx->d_nkp, ctx->d_dense, g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, (size_t)0,
@@ -2033,13 +2043,27 @@ extern "C" int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, co
 }
 
 int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
-                        const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready) {
+                        const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr) {
   if (!ctx || !d_grayL || !d_grayR || !d_results || B < 1 || stride < ctx->g.W) return SVO_E_INVALID;
   if (B > ctx->max_batch) return SVO_E_CAPACITY;
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;
   hipSetDevice(ctx->device);
   { const int rcs = svo_shard_quiesce(ctx); if (rcs) return rcs; }   // (a sharded call of this context may still be in flight: staging sets, work records)
   int rc;
+  // colour entries: the gray pairs f0 .. f0 + b - 1 are written here, on the stream that reads them first
+  const bool convert = bgr && bgr->convert;
+  const size_t gray_img = (size_t)ctx->g.H * stride, bgr_img = bgr ? (size_t)ctx->g.H * bgr->stride : 0;
+  auto bgr_wait = [&](hipStream_t s) -> int {   // the readers of the gray staging in the previous colour call
+    for (int k = 0; convert && k < bgr->n_wait; ++k) SVO_HIP(ctx, hipStreamWaitEvent(s, bgr->wait[k], 0));
+    return SVO_OK;
+  };
+  auto bgr_convert = [&](hipStream_t s, int f0, int b) {
+    if (!convert) return;
+    svo_launch_bgr2gray(s, bgr->L + f0 * bgr_img, bgr->stride, bgr_img, const_cast<uint8_t*>(d_grayL) + f0 * gray_img, stride, gray_img,
+                        ctx->g.W, ctx->g.H, b);
+    svo_launch_bgr2gray(s, bgr->R + f0 * bgr_img, bgr->stride, bgr_img, const_cast<uint8_t*>(d_grayR) + f0 * gray_img, stride, gray_img,
+                        ctx->g.W, ctx->g.H, b);
+  };
   if (ctx->opt_depth_source == 1) {
     // BASELINE configs[4] as a pipeline: the dense front end (ORB on the left images, ELAS maps, the reference's per-keypoint
     // lookups - src/Tracking.cc:225-228, src/frame.cc:122-164) runs on a stream of its own; svo_elas_batch_dev moves the call's
@@ -2110,6 +2134,8 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
       }
     } hook{ctx, boxes, d_results, dD1, d_prod, n, K, 0};
     if (pair_ready) SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_dense, pair_ready[B - 1], 0));   // host-fed: the call's uploads
+    if ((rc = bgr_wait(ctx->stream_dense))) return rc;
+    bgr_convert(ctx->stream_dense, 0, B);   // (ELAS runs on the gray, like ORB: the reference never calls libelas)
     rc = svo_launch_orb(ctx, ctx->stream_dense, svo_fe_own(ctx), d_grayL, d_grayR, stride, B, B);   // left images only
     if (rc == SVO_OK)
       rc = svo_elas_batch_dev_hooked(ctx, ctx->stream_dense, d_grayL, d_grayR, stride, ctx->g.W, ctx->g.H, B, &ep, dD1, dD2, ctx->h_prod,
@@ -2120,9 +2146,13 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
     const size_t n = (size_t)ctx->g.W * ctx->g.H;
     if ((rc = dense_reserve(ctx, B))) return rc;
     if (pair_ready) SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, pair_ready[B - 1], 0));   // host-fed: the call's uploads
+    if ((rc = bgr_wait(ctx->stream))) return rc;
+    bgr_convert(ctx->stream, 0, B);
     if ((rc = svo_launch_orb(ctx, ctx->stream, svo_fe_own(ctx), d_grayL, d_grayR, stride, B, B))) return rc;   // left images only
-    if ((rc = svo_msa_run_many_dev(ctx, d_grayL, d_grayR, stride, (size_t)ctx->g.H * stride, ctx->g.W, ctx->g.H, 48, B,
-                                   ctx->d_dense)))
+    // (colour entries: MSA gets the true colour pairs, as in the reference; gray entries: B = G = R copies of the gray)
+    if ((rc = bgr ? svo_msa_run_many_dev(ctx, bgr->L, bgr->R, bgr->stride, bgr_img, ctx->g.W, ctx->g.H, 48, B, ctx->d_dense, true)
+                  : svo_msa_run_many_dev(ctx, d_grayL, d_grayR, stride, (size_t)ctx->g.H * stride, ctx->g.W, ctx->g.H, 48, B,
+                                         ctx->d_dense)))
       return rc;
     hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256, B), dim3(256), 0, ctx->stream, ctx->d_kp, ctx->d_nkp,
                        ctx->d_dense, ctx->g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, n, (const int32_t*)nullptr);
@@ -2165,11 +2195,13 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
     const SvoFeBufs set = svo_fe_own(ctx).with_outputs(ctx->tb_out[p]);   // (set 0: tb_out[0] is empty, the context's own outputs)
     const size_t K = ctx->max_kp, img = (size_t)ctx->g.H * stride;
     hipStream_t fs = ctx->stream_fe_batch;
+    if ((rc = bgr_wait(fs))) return rc;
     for (int j = 0; j < nsub && rc == SVO_OK; ++j) {
       const int f0 = j * SUB, b = std::min(SUB, B - f0);
       const SvoFeBufs fb = set.outputs_at(K, f0, f0);
       if (pair_ready && hipStreamWaitEvent(fs, pair_ready[f0 + b - 1], 0) != hipSuccess) rc = SVO_E_HIP;   // host-fed: this sub-batch's uploads
       if (rc) break;
+      bgr_convert(fs, f0, b);   // (colour entries: this sub-batch's gray, on the front end's share of the CUs)
       rc = svo_launch_orb(ctx, fs, fb, d_grayL + f0 * img, d_grayR + f0 * img, stride, b, 2 * b);
       if (rc == SVO_OK) rc = svo_launch_stereo(ctx, fs, fb, d_grayL + f0 * img, d_grayR + f0 * img, stride, b, &ctx->cam);
       if (rc == SVO_OK && hipEventRecord(ctx->ev_sub[j], fs) != hipSuccess) rc = SVO_E_HIP;

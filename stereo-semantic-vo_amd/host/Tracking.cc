@@ -51,7 +51,7 @@ Tracking::~Tracking() {
 }
 
 void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n, const double* timestamps,
-                          const std::vector<std::vector<std::vector<int>>>& detection_box) {
+                          const std::vector<std::vector<std::vector<int>>>& detection_box, bool bgr) {
   if (n < 1) return;
   if (n > batch_capacity) throw std::runtime_error("TrackBatch: more frames than batch_capacity");
   if (!ctx_batch) {
@@ -77,8 +77,10 @@ void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n,
       for (int j = 0; j < 4; ++j) flat[((size_t)k * most + b) * 4 + j] = detection_box[k][b][j];
   }
   const svo_boxes_host bx{flat.data(), cnt.data(), std::max(most, 1)};
-  const int rc = svo_track_batch_host(ctx_batch, L, R, stride, n, most > 0 ? &bx : nullptr, batch_results.data() + first);
-  if (rc != SVO_OK) throw std::runtime_error(std::string("svo_track_batch_host: ") + svo_last_error(ctx_batch));
+  const int rc = (bgr ? svo_track_batch_bgr_host : svo_track_batch_host)(ctx_batch, L, R, stride, n, most > 0 ? &bx : nullptr,
+                                                                       batch_results.data() + first);
+  if (rc != SVO_OK)
+    throw std::runtime_error(std::string(bgr ? "svo_track_batch_bgr_host: " : "svo_track_batch_host: ") + svo_last_error(ctx_batch));
   frame_num += n;
 }
 
@@ -150,6 +152,26 @@ void Tracking::SaveTrajectoryAndDraw(std::ofstream& f, std::ofstream& f2) {
 
 void Tracking::Track(const GrayImage& imLeft, const GrayImage& imRight, double timestamp, std::ofstream& f,
                      std::ofstream& f2, const std::vector<std::vector<int>>& detection_box) {
+  TrackImages(imLeft, imRight, nullptr, nullptr, timestamp, f, f2, detection_box);
+}
+
+void Tracking::Track(const BgrImage& imLeft, const BgrImage& imRight, double timestamp, std::ofstream& f,
+                     std::ofstream& f2, const std::vector<std::vector<int>>& detection_box) {
+  // cv::ORB's own reduction (COLOR_BGR2GRAY, src/frame.cc:75-79), on the device
+  GrayImage gL, gR;
+  const BgrImage* in[2] = {&imLeft, &imRight};
+  GrayImage* out[2] = {&gL, &gR};
+  for (int s = 0; s < 2; ++s) {
+    out[s]->cols = in[s]->cols; out[s]->rows = in[s]->rows;
+    out[s]->data.resize((size_t)in[s]->cols * in[s]->rows);
+    if (svo_bgr_to_gray(ctx, in[s]->ptr(), in[s]->cols, in[s]->rows, in[s]->step(), out[s]->data.data(), in[s]->cols) != SVO_OK)
+      throw std::runtime_error(std::string("svo_bgr_to_gray: ") + svo_last_error(ctx));
+  }
+  TrackImages(gL, gR, &imLeft, &imRight, timestamp, f, f2, detection_box);
+}
+
+void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, const BgrImage* colLeft, const BgrImage* colRight,
+                           double timestamp, std::ofstream& f, std::ofstream& f2, const std::vector<std::vector<int>>& detection_box) {
   currentframe = new frame(ctx, imLeft, imRight, timestamp, K, detection_box);
   if (depth_source == 1) {                // src/Tracking.cc:225-228 literally: features, dense map, lookups
     currentframe->featuredetect(imLeft);
@@ -158,7 +180,8 @@ void Tracking::Track(const GrayImage& imLeft, const GrayImage& imRight, double t
     currentframe->disp2Depth(bf);
   } else if (depth_source == 2) {         // the same four calls with the reference's own MB body (MSA)
     currentframe->featuredetect(imLeft);
-    currentframe->MBdense(imLeft, imRight);
+    if (colLeft) currentframe->MBdense(*colLeft, *colRight);
+    else currentframe->MBdense(imLeft, imRight);
     currentframe->computekeypoint_r();
     currentframe->disp2Depth(bf);
   } else {

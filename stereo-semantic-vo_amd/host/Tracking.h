@@ -20,17 +20,27 @@ class Tracking {
   // src/Tracking.cc:180-252 (imdepth / img_detect / Pangolin matrix arguments dropped: GUI only)
   void Track(const svo_host::GrayImage& imLeft, const svo_host::GrayImage& imRight, double timestamp,
              std::ofstream& f, std::ofstream& f2, const std::vector<std::vector<int>>& detection_box);
+  // The same for the reference's own 8UC3 BGR input (main.cpp:160-161): the seams that take gray get the gray svo_bgr_to_gray
+  // makes of it on the device (cv::ORB's COLOR_BGR2GRAY), frame::MBdense (depth_source 2) gets the colour.
+  void Track(const svo_host::BgrImage& imLeft, const svo_host::BgrImage& imRight, double timestamp,
+             std::ofstream& f, std::ofstream& f2, const std::vector<std::vector<int>>& detection_box);
   // The same loop PIPELINED (svo_track_batch_host): the next n stereo pairs of the sequence at once, images in host memory
   // (n x rows x stride bytes each side, frame k at L + k * rows * stride); returns at once - uploads, front end and the ordered
   // tail run behind the caller's back while it decodes the next pairs.  detection_box[k]: frame k's offline boxes (may be
   // empty).  FinishBatches() waits for everything and writes the trajectory rows of all batched frames in order
   // (SaveTrajectoryAndDraw's two formats).  Not to be mixed with Track() on one sequence.
+  // bgr: the images are 8UC3 BGR, `stride` >= 3 * width (svo_track_batch_bgr_host).
   void TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n, const double* timestamps,
-                  const std::vector<std::vector<std::vector<int>>>& detection_box);
+                  const std::vector<std::vector<std::vector<int>>>& detection_box, bool bgr = false);
   void FinishBatches(std::ofstream& f, std::ofstream& f2);
   void GetVelocity();                                                   // :99-106
   void Tracklastframe();                                                // :107-121
   void SaveTrajectoryAndDraw(std::ofstream& f, std::ofstream& f2);      // :124-144
+
+ private:
+  void TrackImages(const svo_host::GrayImage& imLeft, const svo_host::GrayImage& imRight, const svo_host::BgrImage* colLeft,
+                   const svo_host::BgrImage* colRight, double timestamp, std::ofstream& f, std::ofstream& f2,
+                   const std::vector<std::vector<int>>& detection_box);
 
  public:
   svo_ctx* ctx = nullptr;

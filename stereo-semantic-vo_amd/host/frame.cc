@@ -116,6 +116,16 @@ int frame::MBdense(const GrayImage& left, const GrayImage& right) {
   return valid;
 }
 
+int frame::MBdense(const BgrImage& left, const BgrImage& right) {
+  const size_t n = (size_t)left.cols * left.rows;
+  std::vector<uint8_t> disp(n, 0);
+  dispimg.assign(n, -1.f);
+  if (svo_msa_solve(ctx, left.ptr(), right.ptr(), left.cols, left.rows, left.step(), 48, 1, disp.data()) != SVO_OK) return 0;
+  int valid = 0;
+  for (size_t t = 0; t < n; ++t) { dispimg[t] = (float)disp[t]; valid += disp[t] != 0; }
+  return valid;
+}
+
 // src/frame.cc:122-138.  After MB() keypoints_r already holds the sub-pixel right x; after ElasMatch() it is read
 // off the dense map at the truncated keypoint position, as `dispimg.at<float>(ly, lx)` does.
 void frame::computekeypoint_r() {

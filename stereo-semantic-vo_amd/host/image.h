@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace svo_host {
@@ -15,6 +16,14 @@ struct GrayImage {   // 8-bit gray, row-major, tight rows (what main.cpp's imrea
   std::vector<uint8_t> data;
   bool empty() const { return data.empty(); }
   const uint8_t* ptr() const { return data.data(); }
+};
+
+struct BgrImage {    // 8UC3 BGR, interleaved, tight rows (3 * cols bytes) - what main.cpp's cv::imread(..., CV_LOAD_IMAGE_UNCHANGED) yields
+  int cols = 0, rows = 0;
+  std::vector<uint8_t> data;
+  bool empty() const { return data.empty(); }
+  const uint8_t* ptr() const { return data.data(); }
+  int step() const { return 3 * cols; }
 };
 
 // binary PGM (P5) reader/writer - the only image codec the harness needs offline
@@ -37,6 +46,34 @@ inline bool read_pgm(const std::string& path, GrayImage& img) {
   img.data.resize((size_t)w * h);
   const bool ok = fread(img.data.data(), 1, img.data.size(), f) == img.data.size();
   fclose(f);
+  return ok;
+}
+
+// binary PPM (P6, RGB, maxval 255) reader: the pixels come back in BGR order, like cv::imread
+inline bool read_ppm_bgr(const std::string& path, BgrImage& img) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  char magic[3] = {0};
+  int w = 0, h = 0, mx = 0;
+  if (fscanf(f, "%2s", magic) != 1 || strcmp(magic, "P6") != 0) { fclose(f); return false; }
+  int vals[3];
+  for (int k = 0; k < 3; ++k) {   // width, height, maxval; whitespace and '#' comments in between
+    int c = fgetc(f);
+    while (c == ' ' || c == '\n' || c == '\r' || c == '\t' || c == '#') {
+      if (c == '#') while (c != '\n' && c != EOF) c = fgetc(f);
+      c = fgetc(f);
+    }
+    ungetc(c, f);
+    if (fscanf(f, "%d", &vals[k]) != 1) { fclose(f); return false; }
+  }
+  w = vals[0]; h = vals[1]; mx = vals[2];
+  if (mx != 255 || w <= 0 || h <= 0 || w > 4095 || h > 4095) { fclose(f); return false; }
+  fgetc(f);
+  img.cols = w; img.rows = h;
+  img.data.resize((size_t)w * h * 3);
+  const bool ok = fread(img.data.data(), 1, img.data.size(), f) == img.data.size();
+  fclose(f);
+  for (size_t i = 0; ok && i < img.data.size(); i += 3) std::swap(img.data[i], img.data[i + 2]);
   return ok;
 }
 

@@ -8,6 +8,10 @@
 // stereo_kitti --pipelined <vocabulary> <settings.yaml> <sequence_dir> [frames per call, default 32]: the same sequence through
 // Tracking::TrackBatch (svo_track_batch_host): this thread decodes the next frames while uploads, front end and ordered tail of
 // the earlier ones run; same trajectory files; reports frames per second over the whole loop (decoding included).
+// --colour (before the other arguments, with or without --pipelined): keep the images as 8UC3 BGR, as main.cpp:160-161 reads
+// them, and track them through the colour entries (svo_track_frame_bgr's seams / svo_track_batch_bgr_host): the gray ORB sees is
+// the same, MSA (depth_source 2) gets the colour.  Without it the files are reduced to gray on decode, as before.
+// stereo_kitti --decode-bgr in.(png|ppm|pgm) out.ppm: codec self-test of the colour decode (the PPM holds RGB, as the format says).
 #include <algorithm>
 #include <chrono>
 #include <iomanip>
@@ -33,6 +37,18 @@ int main(int argc, char** argv) {
     fclose(o);
     return 0;
   }
+  if (argc == 4 && std::string(argv[1]) == "--decode-bgr") {   // colour codec self-test: png/ppm/pgm -> ppm
+    BgrImage img;
+    if (!read_image_bgr(argv[2], img)) return 1;
+    FILE* o = fopen(argv[3], "wb");
+    if (!o) return 1;
+    fprintf(o, "P6\n%d %d\n255\n", img.cols, img.rows);
+    std::vector<uint8_t> rgb(img.data);
+    for (size_t i = 0; i < rgb.size(); i += 3) std::swap(rgb[i], rgb[i + 2]);
+    fwrite(rgb.data(), 1, rgb.size(), o);
+    fclose(o);
+    return 0;
+  }
   if (argc == 11 && std::string(argv[1]) == "--quat") {   // convert::toQuaternion self-test
     Mat33f R;
     for (int i = 0; i < 9; ++i) R.m[i] = (float)atof(argv[2 + i]);
@@ -40,6 +56,14 @@ int main(int argc, char** argv) {
     std::cout << std::fixed << std::setprecision(7) << q[0] << " " << q[1] << " " << q[2] << " " << q[3] << std::endl;
     return 0;
   }
+  bool colour = false;
+  for (int i = 1; i < argc; ++i)
+    if (std::string(argv[i]) == "--colour") {
+      colour = true;
+      for (int j = i; j + 1 < argc; ++j) argv[j] = argv[j + 1];
+      --argc;
+      break;
+    }
   bool pipelined = false;
   int per_call = 32;
   if (argc >= 5 && std::string(argv[1]) == "--pipelined") {
@@ -49,7 +73,7 @@ int main(int argc, char** argv) {
     argc = 4;
   }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--pipelined] path_to_vocabulary path_to_settings path_to_sequence [frames_per_call]" << std::endl;
+    std::cerr << "Usage: ./stereo_kitti [--colour] [--pipelined] path_to_vocabulary path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
   const std::string seq = argv[3];
@@ -96,18 +120,23 @@ int main(int argc, char** argv) {
       int cols = 0;
       for (int k = 0; k < n; ++k) {
         GrayImage imLeft, imRight;
-        if (!read_image(name(dl, n0 + k, ext), imLeft) || !read_image(name(dr, n0 + k, ext), imRight)) {
+        BgrImage cLeft, cRight;
+        const bool ok = colour ? read_image_bgr(name(dl, n0 + k, ext), cLeft) && read_image_bgr(name(dr, n0 + k, ext), cRight)
+                               : read_image(name(dl, n0 + k, ext), imLeft) && read_image(name(dr, n0 + k, ext), imRight);
+        if (!ok) {
           std::cerr << std::endl << "Failed to load image at: " << name(dl, n0 + k, ext) << std::endl;
           return 1;
         }
-        if (k == 0) { fb = imLeft.data.size(); cols = imLeft.cols; bufL.resize(fb * n); bufR.resize(fb * n); }
-        if (imLeft.data.size() != fb || imRight.data.size() != fb) { std::cerr << "image size changes within the sequence" << std::endl; return 1; }
-        memcpy(bufL.data() + fb * k, imLeft.data.data(), fb);
-        memcpy(bufR.data() + fb * k, imRight.data.data(), fb);
+        const std::vector<uint8_t>& l = colour ? cLeft.data : imLeft.data;
+        const std::vector<uint8_t>& r = colour ? cRight.data : imRight.data;
+        if (k == 0) { fb = l.size(); cols = colour ? cLeft.step() : imLeft.cols; bufL.resize(fb * n); bufR.resize(fb * n); }
+        if (l.size() != fb || r.size() != fb) { std::cerr << "image size changes within the sequence" << std::endl; return 1; }
+        memcpy(bufL.data() + fb * k, l.data(), fb);
+        memcpy(bufR.data() + fb * k, r.data(), fb);
         boxes[k] = read_boxes(n0 + k);
       }
       // (pageable buffers: the call returns when they are staged, so they are refilled at once while the GPU works)
-      mpTracker->TrackBatch(bufL.data(), bufR.data(), cols, n, &vTimestamps[n0], boxes);
+      mpTracker->TrackBatch(bufL.data(), bufR.data(), cols, n, &vTimestamps[n0], boxes, colour);
     }
     mpTracker->FinishBatches(f, f2);
     const double total = std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t0).count();
@@ -121,7 +150,10 @@ int main(int argc, char** argv) {
   }
   for (int ni = 0; ni < nImages; ++ni) {
     GrayImage imLeft, imRight;
-    if (!read_image(name(dl, ni, ext), imLeft) || !read_image(name(dr, ni, ext), imRight)) {
+    BgrImage cLeft, cRight;
+    const bool ok = colour ? read_image_bgr(name(dl, ni, ext), cLeft) && read_image_bgr(name(dr, ni, ext), cRight)
+                           : read_image(name(dl, ni, ext), imLeft) && read_image(name(dr, ni, ext), imRight);
+    if (!ok) {
       std::cerr << std::endl << "Failed to load image at: " << name(dl, ni, ext) << std::endl;
       return 1;
     }
@@ -133,7 +165,8 @@ int main(int argc, char** argv) {
       while (bf >> l >> r >> t >> b) boxes.push_back({l, r, t, b});
     }
     const auto t1 = std::chrono::steady_clock::now();
-    mpTracker->Track(imLeft, imRight, vTimestamps[ni], f, f2, boxes);
+    if (colour) mpTracker->Track(cLeft, cRight, vTimestamps[ni], f, f2, boxes);
+    else mpTracker->Track(imLeft, imRight, vTimestamps[ni], f, f2, boxes);
     const auto t2 = std::chrono::steady_clock::now();
     vTimesTrack[ni] = (float)std::chrono::duration_cast<std::chrono::duration<double>>(t2 - t1).count();
   }
