@@ -65,7 +65,8 @@ typedef enum svo_status {
   SVO_E_CAPACITY = -5,  /* batch / keypoint capacity of the ctx exceeded */
   SVO_E_TIMEOUT = -6    /* svo_sync: a bounded wait inside the tracker's pose chain ran out (sticky flag 4, svo_track_overflowed): the frame
                            concerned was tracked as a PnP failure (its record has n_pnp_inliers = -1), nothing stale was used; returned
-                           once, the context continues with the two-launch pose chain ("tail_fused" = 0) */
+                           once per svo_track_reset / svo_track_multi_reset, whatever the number of sequences (svo_last_error then
+                           names the sequences concerned); the context continues with the two-launch pose chain ("tail_fused" = 0) */
 } svo_status;
 
 typedef struct svo_ctx svo_ctx;
@@ -468,7 +469,10 @@ int svo_track_sharded_dev(svo_ctx* const* ctxs, int G, const uint8_t* const* d_g
  * valid until svo_sync or until the second following host-fed call on this context returns; pageable images are first
  * gathered into a pinned ring by up to four worker threads inside the call (the call returns when they are staged - they
  * may be reused at once).  `results` is complete after svo_sync(ctx) (pageable: copied out of a pinned buffer there), or after the
- * second following host-fed call returned.  Consecutive calls overlap exactly like svo_track_batch_dev's (two image sets
+ * second following host-fed call returned.  Both "second following call" rules hold for pinned and pageable memory alike and
+ * across kinds (svo_track_batch_host, svo_track_batch_bgr_host, svo_frontend_batch_host on one context share two image sets):
+ * a host-fed call first waits for what the call two back left on the set it reuses - its uploads and its outputs, normally
+ * long done.  Consecutive calls overlap exactly like svo_track_batch_dev's (two image sets
  * alternate): the uploads of call c + 1 run while the tail of call c is busy.  Records are byte-identical to
  * svo_track_batch_dev's on the same frames.  boxes (may be NULL): the frames' offline detection boxes, host arrays.
  * Works with every "depth_source" (the dense stages wait for the call's last upload instead of sub-batch by sub-batch).
@@ -516,7 +520,8 @@ int svo_track_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_bgrL, const uint8_t* 
 int svo_track_batch_bgr_host(svo_ctx* ctx, const uint8_t* bgrL, const uint8_t* bgrR, int stride, int B,
                              const svo_boxes_host* boxes, svo_track_result* results);
 
-/* Sticky flag of the device tracker (synchronises).  4: see SVO_E_TIMEOUT.  1: capacity - *flag != 0 once a frame needed more than the 4096 live
+/* Sticky flag of the device tracker (synchronises), a bit set OR-ed over the sequences and cleared by svo_track_reset /
+ * svo_track_multi_reset: both bits may be set.  4: see SVO_E_TIMEOUT.  1: capacity - *flag != 0 once a frame needed more than the 4096 live
  * map points the pool holds, or a map point stayed alive for more than 2^20 creations (its slot in the position table
  * was about to be reused).  Neither can happen with the reference's 500 keypoints per frame on sequences of KITTI
  * length; results after the flag is set are not the reference's. */

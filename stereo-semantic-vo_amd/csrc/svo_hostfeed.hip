@@ -2,7 +2,8 @@
 // svo_frontend_batch_host).  The reference reads one stereo pair from disk per Tracking::Track (main.cpp:159-195); SURVEY.md
 // section 8e prices the GPU path at "H2D 2 P bytes, D2H ~30 KB" per pair with pair k uploaded to GPU k mod G.  These entries are
 // that path: the caller's images start in HOST memory, are uploaded on a copy stream of their own a few pairs ahead of the front
-// end (eight pairs per event), and the records come back to host memory on the way out - no synchronisation inside a call.
+// end (eight pairs per event), and the records come back to host memory on the way out - a call waits for nothing but what the
+// call two back left on the image set it reuses (reclaim_set), which is normally long done.
 //
 //   host images --(pinned: copied where they lie | pageable: rows gathered into a pinned ring by worker threads)-->
 //   copy stream: H2D into image set p (two sets alternate between calls)  --event per 8 pairs-->
@@ -32,6 +33,7 @@ struct HostFeed {
   uint8_t* d_img[2] = {nullptr, nullptr};        // set p: cap left images, then cap right images, H x stage_pitch each
   uint8_t* h_img[2] = {nullptr, nullptr};        // pinned staging of the same layout (allocated with the first pageable source)
   std::vector<hipEvent_t> ev_up[2];              // upload events of set p, one per FEED_CHUNK pairs
+  int n_up[2] = {0, 0};                          // how many of them the set's last use recorded
   std::vector<hipEvent_t> pair_ev;               // the call being enqueued: pair i is resident after pair_ev[i]
   hipEvent_t img_free[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // the readers of set p are done with it
   int n_free[2] = {0, 0};
@@ -40,6 +42,7 @@ struct HostFeed {
   svo_track_result* d_res[2] = {nullptr, nullptr};
   svo_track_result* h_res[2] = {nullptr, nullptr};
   hipEvent_t res_done[2] = {nullptr, nullptr};
+  hipEvent_t done[2] = {nullptr, nullptr};       // behind the outputs of the set's last use: res_done[p] / fe_done[p] (nullptr: none here)
   PendingOut pending[2];
   int32_t* d_box[2] = {nullptr, nullptr};        // cap x SVO_MAX_BOXES x 4 boxes, then cap counts
   int32_t* h_box[2] = {nullptr, nullptr};
@@ -159,6 +162,7 @@ int feed_upload(svo_ctx* ctx, int p, const uint8_t* grayL, const uint8_t* grayR,
   uint8_t* dR = dL + (size_t)hf->cap * ib;
   const bool pinned = is_pinned(grayL) && is_pinned(grayR);
   hf->pair_ev.assign((size_t)n, nullptr);
+  hf->n_up[p] = nchunk;
   if (pinned) {
     // copied where they lie: one linear copy per chunk and side when the caller's frames are consecutive and pitched like the
     // set, one 2-D copy per chunk and side when only the pitch differs (rows of consecutive frames continue at `stride`),
@@ -203,10 +207,7 @@ int feed_upload(svo_ctx* ctx, int p, const uint8_t* grayL, const uint8_t* grayR,
       return SVO_E_NOMEM;
     }
     memset(ring, 0, 2 * (size_t)hf->cap * ib);
-  } else if (hf->used[p] && !hf->ev_up[p].empty()) {
-    // the uploads that last read this half of the ring (two calls back)
-    for (hipEvent_t e : hf->ev_up[p]) SVO_HIP(ctx, hipEventSynchronize(e));
-  }
+  }   // (the uploads that last read this half of the ring, two calls back, are done: reclaim_set)
   uint8_t* hL = ring;
   uint8_t* hR = ring + (size_t)hf->cap * ib;
   std::vector<std::atomic<int>> staged((size_t)nchunk);
@@ -270,7 +271,6 @@ int feed_boxes(svo_ctx* ctx, int p, const svo_boxes_host* boxes, int B, svo_boxe
     any |= boxes->n[f];
   }
   if (!any) return SVO_OK;
-  if (hf->used[p]) SVO_HIP(ctx, hipEventSynchronize(hf->res_done[p]));   // the chain that last read this set's boxes (two calls back)
   int32_t* hb = hf->h_box[p];
   int32_t* hn = hb + (size_t)hf->cap * SVO_MAX_BOXES * 4;
   for (int f = 0; f < B; ++f) {
@@ -294,6 +294,7 @@ int feed_results_out(svo_ctx* ctx, int p, int B, svo_track_result* results) {
   SVO_HIP(ctx, hipEventRecord(hf->res_done[p], ctx->stream));
   hf->pending[p].user = direct ? nullptr : results;
   hf->pending[p].n = B;
+  hf->done[p] = hf->res_done[p];
   return SVO_OK;
 }
 
@@ -317,6 +318,20 @@ int flush_set(svo_ctx* ctx, HostFeed* hf, int p) {
     fo.B = 0;
   }
   return SVO_OK;
+}
+
+// Before a host-fed call (of any kind) reuses set p: what the call two back left on it is finished - its uploads (the caller may
+// reuse pinned source images from here on), the chain that read its images and boxes, and its outputs (pinned records are
+// complete, staged ones are copied out).  include/svo.h promises all of it once the second following host-fed call has returned;
+// the work is two calls old, so the waits normally find it done.
+int reclaim_set(svo_ctx* ctx, HostFeed* hf, int p) {
+  if (hf->used[p]) {
+    for (int c = 0; c < hf->n_up[p]; ++c) SVO_HIP(ctx, hipEventSynchronize(hf->ev_up[p][c]));
+    if (hf->done[p]) SVO_HIP(ctx, hipEventSynchronize(hf->done[p]));
+  }
+  hf->n_up[p] = 0;
+  hf->done[p] = nullptr;
+  return flush_set(ctx, hf, p);
 }
 
 }  // namespace
@@ -383,7 +398,7 @@ int track_batch_host(svo_ctx* ctx, const uint8_t* grayL, const uint8_t* grayR, i
       }
   }
   const int p = hf->parity;
-  if ((rc = flush_set(ctx, hf, p))) return rc;          // what the call two back left in this set's pinned buffers
+  if ((rc = reclaim_set(ctx, hf, p))) return rc;        // what the call two back left on this set
   svo_boxes_dev bx;
   if ((rc = feed_boxes(ctx, p, boxes, B, &bx))) return rc;
   if ((rc = feed_upload(ctx, p, grayL, grayR, stride, 0, 1, B, bgr))) return rc;
@@ -444,7 +459,7 @@ extern "C" int svo_track_sharded_host(svo_ctx* const* ctxs, int G, const uint8_t
     HostFeed* hf = feed_of(c);
     const int p = hf->parity;
     par[g] = p;
-    if ((rc = flush_set(c, hf, p))) break;
+    if ((rc = reclaim_set(c, hf, p))) break;
     const int nb = (B - g + G - 1) / G;
     if (nb > 0 && (rc = feed_upload(c, p, grayL, grayR, stride, g, G, nb))) break;
     dl[g] = hf->d_img[p];
@@ -488,7 +503,7 @@ extern "C" int svo_frontend_batch_host(svo_ctx* ctx, const uint8_t* grayL, const
   if (rc) return rc;
   HostFeed* hf = feed_of(ctx);
   const int p = hf->parity;
-  if ((rc = flush_set(ctx, hf, p))) return rc;
+  if ((rc = reclaim_set(ctx, hf, p))) return rc;
   const size_t K = ctx->max_kp, cap = (size_t)hf->cap;
   const size_t o_desc = sizeof(svo_kp) * K * cap, o_n = o_desc + 32 * K * cap, o_uR = o_n + 4 * cap, o_dep = o_uR + 4 * K * cap, total = o_dep + 4 * K * cap;
   for (int q = 0; q < 2; ++q) {
@@ -516,6 +531,7 @@ extern "C" int svo_frontend_batch_host(svo_ctx* ctx, const uint8_t* grayL, const
   if (depth) SVO_HIP(ctx, hipMemcpyAsync(h + o_dep, d + o_dep, 4 * K * B, hipMemcpyDeviceToHost, ctx->stream));
   SVO_HIP(ctx, hipEventRecord(hf->fe_done[p], ctx->stream));
   hf->fe_pending[p] = HostFeed::FeOut{kpL, descL, nL, uR, depth, B};
+  hf->done[p] = hf->fe_done[p];
   hf->used[p] = true;
   hf->parity ^= 1;
   return SVO_OK;

@@ -822,7 +822,7 @@ __global__ __launch_bounds__(1024) void k_ti_resolve(TrackState* st, TrackWork* 
     st->lastN = nkp;
     st->npool = total_live;
     st->next_gid = next_gid;
-    if (overflow || lapped) st->overflow = 1;
+    if (overflow || lapped) atomicOr(&st->overflow, 1);
     st->cur ^= 1;
     st->frame_num = id + 1;
   }
@@ -1060,7 +1060,7 @@ __device__ __forceinline__ bool tp_wait_work(TrackState* st, const TrackWork* wo
       int spins = 0;
       while (ld_agent(&work->ready) != tag && spins < (1 << 22)) { __builtin_amdgcn_s_sleep(2); ++spins; }
       s_lost = spins >= (1 << 22) ? 1 : 0;
-      if (s_lost) st->overflow = 4;                  // lost hand-over: svo_track_overflowed reports it
+      if (s_lost) atomicOr(&st->overflow, 4);        // lost hand-over: svo_track_overflowed reports it
     }
     __syncthreads();
     // what the record points at (keypoints, depths: written by front-end kernels on other CUs and L2s, with plain stores, before
@@ -1329,7 +1329,7 @@ __device__ __forceinline__ void tp_frame_body(TpLds& S, TrackState* st, TrackWor
       // sticky flag becomes 4 and the next svo_sync / svo_track_overflowed reports it (SVO_E_TIMEOUT) and switches the
       // context to the two-launch pose chain ("tail_fused" = 0).
       const bool late = spins >= (1 << 22);
-      if (late) st->overflow = 4;
+      if (late) atomicOr(&st->overflow, 4);
       S.late[tid] = late ? 1 : 0;
       const int c = late ? 0 : ld_agent(&st->hyp[tid].cnt), o = late ? 0 : ld_agent(&st->hyp[tid].ok);
       S.cnt[tid] = c; S.ok[tid] = o;
@@ -1352,7 +1352,7 @@ __device__ __forceinline__ void tp_frame_body(TpLds& S, TrackState* st, TrackWor
       if (tid == 0) {
         int spins = 0;
         while (ld_agent(&work->hyp_done) < PNP_HYP && spins < (1 << 22)) { __builtin_amdgcn_s_sleep(1); ++spins; }
-        if (spins >= (1 << 22)) { st->overflow = 4; S.lost = 1; }
+        if (spins >= (1 << 22)) { atomicOr(&st->overflow, 4); S.lost = 1; }
       }
       __syncthreads();
     }
@@ -1862,6 +1862,7 @@ static int track_reset_n(svo_ctx* ctx, const svo_camera* cam, int nseq) {
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->cam = *cam;
   ctx->track_frame = 0;
+  ctx->timeout_reported = false;   // (a new sequence: its timeouts are reported again)
   return SVO_OK;
 }
 
@@ -2244,26 +2245,37 @@ extern "C" int svo_track_tail_dev(svo_ctx* ctx, const svo_kp* d_kp, const uint8_
   return SVO_OK;
 }
 
-// svo_sync's look at the sticky flag of a single-sequence tracker (the stream is idle here): code 4 = a wait inside the pose chain
+// svo_sync's look at the sticky flags of the tracker's sequences (the stream is idle here): bit 4 = a wait inside the pose chain
 // ran into its bound (k_tp_tail_ord's frame part waiting for the samples of its own launch, or a kernel polling for a hand-over
 // record with "pose_flag").  The frame concerned was treated as a PnP failure (record: n_pnp_inliers = -1) - nothing stale was
-// consumed -; the context falls back to the two-launch pose chain, whose kernels never wait for each other, and says so.
+// consumed -; the context falls back to the two-launch pose chain, whose kernels never wait for each other, and says so (once
+// per svo_track_reset / svo_track_multi_reset, naming the sequences concerned when there are several).
 int svo_track_check_timeout(svo_ctx* ctx) {
-  if (!ctx->d_track || ctx->n_seq != 1 || ctx->timeout_reported) return SVO_OK;
-  TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
-  int32_t v = 0;
-  SVO_HIP(ctx, svo_memcpy_sync(ctx, &v, &st->overflow, 4, hipMemcpyDeviceToHost));
-  if (v != 4) return SVO_OK;
+  if (!ctx->d_track || ctx->timeout_reported) return SVO_OK;
+  const TrackState* st = reinterpret_cast<const TrackState*>(ctx->d_track);
+  const int n = ctx->n_seq;
+  std::vector<int32_t> v((size_t)n, 0);
+  // (every sequence's flag in one strided copy: st[q].overflow, sizeof(TrackState) bytes apart)
+  SVO_HIP(ctx, hipMemcpy2DAsync(v.data(), sizeof(int32_t), &st->overflow, sizeof(TrackState), sizeof(int32_t), (size_t)n,
+                                hipMemcpyDeviceToHost, ctx->stream));
+  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::string seqs;
+  for (int q = 0; q < n; ++q)
+    if (v[(size_t)q] & 4) seqs += (seqs.empty() ? "" : ", ") + std::to_string(q);
+  if (seqs.empty()) return SVO_OK;
   ctx->timeout_reported = true;
   ctx->opt_tail_fused = 0;
   ctx->opt_pose_flag = 0;
-  ctx->last_error = "tracker: a wait inside the pose chain timed out (sticky flag 4): the frame was treated as a PnP failure (n_pnp_inliers = -1); "
+  ctx->last_error = std::string("tracker: a wait inside the pose chain timed out (sticky flag 4") +
+                    (n > 1 ? "; sequence(s) " + seqs + " of " + std::to_string(n) : std::string()) +
+                    "): the frame was treated as a PnP failure (n_pnp_inliers = -1); "
                     "the context now runs the two-launch pose chain (tail_fused = 0, pose_flag = 0)";
   return SVO_E_TIMEOUT;
 }
 
-// Sticky flag of the tracker (0 = fine).  1: a frame wanted more than 4096 live map points or a map point outlived the position
-// table (2^20 ids) - results after that are not the reference's.  4: a bounded wait inside the pose chain timed out (above).
+// Sticky flag of the tracker (0 = fine), a bit set (device side: atomicOr), OR-ed over the sequences.  1: a frame wanted more than
+// 4096 live map points or a map point outlived the position table (2^20 ids) - results after that are not the reference's.
+// 4: a bounded wait inside the pose chain timed out (above).
 extern "C" int svo_track_overflowed(svo_ctx* ctx, int32_t* flag) {
   if (!ctx || !flag || !ctx->d_track) return SVO_E_INVALID;
   TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
