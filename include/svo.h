@@ -693,6 +693,96 @@ int svo_msa_solve(svo_ctx* ctx, const uint8_t* bgrL, const uint8_t* bgrR, int wi
 int svo_msa_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int width, int height, int B, int d,
                       float* d_disp);
 
+/* ---- darknet YOLO detector on the device (ABI-7 additions; no existing entry changed) -------------------------------------
+ * The online half of semantic gating: Semantic::Run (src/semantic.cc) calls YOLOv3::Detect(leftimg, 0.8), which goes through
+ * the dlopen C-ABI of include/YOLOv3SE.h (YoloLoad / YoloDetectFromImage) into Thirdparty/darknet/src/yolo_v3.c.  These
+ * entries load any compatible darknet .cfg + .weights and run the network, decoding and NMS on the device.
+ *   cfg: [net] (width, height, channels) and the sections [convolutional] (filters, size, stride, pad, padding,
+ *        batch_normalize, activation leaky / linear / logistic; groups = 1, binary = 0, xnor = 0), [maxpool] (size, stride,
+ *        padding; darknet's defaults: size = stride, padding = (size-1)/2, out = (w + 2*padding)/stride), [route] (layers,
+ *        negative or absolute), [shortcut] (from, activation linear, same shape only), [upsample] (stride >= 1, scale 1),
+ *        [yolo] (mask, anchors, classes, num) and [region] (anchors, classes, coords 4, num, softmax; no tree / map /
+ *        background).  Training-only keys of [net] / [yolo] / [region] (jitter, ignore_thresh, object_scale, ...) are
+ *        accepted and ignored.  Any other section or key, or an unsupported value, fails with SVO_E_INVALID and
+ *        svo_det_last_error names the section and its line.  All output layers must share one class count.
+ *   weights: load_weights_upto's layout - int major, minor, revision, then `seen` as size_t when major*10+minor >= 2 (and
+ *        both < 1000) else as int; the transposed form (major or minor > 1000) is rejected.  Per convolutional layer, in
+ *        order: biases, then scales / rolling mean / rolling variance with batch_normalize, then [filters][c][size][size]
+ *        weights.  A file shorter or longer than the cfg implies fails (SVO_E_INVALID).
+ * Numerics: the input tensor is darknet's letterbox_image of data/255. bit for bit; convolutions are f32 products with
+ * f32 accumulation on the matrix cores (summation order differs from darknet's gemm); the epilogue is darknet's
+ * (x - mean)/(sqrt(var) + .000001f) * scale + bias, then the activation; logistic and exp are evaluated in double as
+ * darknet does.  Decoding, do_nms_sort(0.45) and YoloDetect's record loop run on the device in darknet's order, with one
+ * exception: darknet sorts with libc qsort, whose order for equal scores is unspecified - here equal scores keep the order
+ * they had before the sort (a stable sort), the one point where darknet's order is not pinned. */
+typedef struct svo_det svo_det;
+
+enum { SVO_DET_CONV = 0, SVO_DET_MAXPOOL = 1, SVO_DET_ROUTE = 2, SVO_DET_SHORTCUT = 3, SVO_DET_UPSAMPLE = 4,
+       SVO_DET_YOLO = 5, SVO_DET_REGION = 6 };
+enum { SVO_DET_ACT_LINEAR = 0, SVO_DET_ACT_LEAKY = 1, SVO_DET_ACT_LOGISTIC = 2 };
+
+/* One layer of svo_det_describe. */
+typedef struct svo_det_layer {
+  int32_t type;                      /* SVO_DET_* */
+  int32_t in_w, in_h, in_c;
+  int32_t out_w, out_h, out_c;
+  int32_t size, stride, pad;         /* convolutional / maxpool (pad = the padding in pixels); upsample: stride */
+  int32_t batch_normalize, activation;   /* convolutional: 0 / 1, SVO_DET_ACT_*; shortcut: SVO_DET_ACT_LINEAR */
+  int32_t classes, num;              /* yolo / region: classes, anchors used by the layer (yolo: the mask's length) */
+  int32_t from[4];                   /* route: up to 4 absolute source layers (-1 unused); shortcut: from[0] */
+  int64_t n_params;                  /* floats this layer reads from the .weights file */
+} svo_det_layer;
+
+/* Host only, no device: parse `cfg` (and, if `weights` is not NULL, check the weights file's header and exact size against
+ * it).  Writes up to max_layers layers, *n_layers = the network's layer count, *n_params = the floats the weights file
+ * must hold after its header.  layers may be NULL with max_layers = 0. */
+int svo_det_describe(const char* cfg, const char* weights, svo_det_layer* layers, int max_layers, int* n_layers,
+                     int64_t* n_params);
+/* Text of the last failure of `det`; with det = NULL, of the calling thread's last svo_det_describe / svo_det_create. */
+const char* svo_det_last_error(const svo_det* det);
+
+/* A detector on HIP device `device` for batches of up to max_batch images (YoloLoad + set_batch_network).  The weights live
+ * in HBM; every layer's output is kept for max_batch images (svo_det_debug_tensor). */
+int svo_det_create(int device, const char* cfg, const char* weights, int max_batch, svo_det** out);
+int svo_det_destroy(svo_det* det);
+
+/* Latency mode, YoloDetectFromImage's semantics on one 8-bit interleaved image (HOST memory, `stride` bytes per row):
+ * C = 3 - channel k is byte k as stored, as YOLOv3::Detect hands darknet the BGR cv::Mat unswapped; C = 1 - a gray image,
+ * replicated to three channels (the project's B = G = R convention for gray input to colour stages; not reference
+ * behaviour, the reference has no gray detector input).  Records [class, prob, left, top, right - left, bot - top] go to
+ * `result` in darknet's final order while result_idx * 6 + 5 < result_sz; *n = records written.  Synchronises. */
+int svo_det_detect(svo_det* det, const uint8_t* img, int W, int H, int C, int stride, float thresh, float* result,
+                   int result_sz, int* n);
+
+/* Throughput mode: B images in HBM (image f at d_img + f * H * stride), the same records per image - frame f's at
+ * d_records + 6 * max_records * f, count d_n_records[f] (<= max_records).  d_boxes_out (may be NULL; the struct is read on
+ * the host, its arrays are DEVICE pointers written here): frame f's first min(count, 64, stride) records as tracker boxes
+ * {left = x, right = x + w, top = y, bottom = y + h} at boxes + 4 * stride * f and their number at n[f] - the online path
+ * the reference left commented in src/frame.cc:209-214 / src/Tracking.cc:70-77.  Does not synchronise: the detector runs
+ * on a stream of its own.  consumer (may be NULL, same device): that context's NEXT device-resident tracking call
+ * (svo_track_batch_dev, svo_track_batch_bgr_dev, svo_track_tail_dev, ...) waits on the device for these outputs before
+ * it reads any box, so the boxes can be handed over with no host synchronisation in between; and this call first waits
+ * on the device for the consumer's last tracking call that read boxes, so a steady detect -> track loop may reuse the same
+ * box and record arrays without a host synchronisation either.  The images must stay valid until the work is done
+ * (svo_det_sync, or the consumer's svo_sync after its tracking call). */
+int svo_det_batch_dev(svo_det* det, const uint8_t* d_img, int W, int H, int C, int stride, int B, float thresh,
+                      float* d_records, int max_records, int32_t* d_n_records, const svo_boxes_dev* d_boxes_out,
+                      svo_ctx* consumer);
+/* YoloDetectFromImage itself: darknet's planar float image (HOST memory, C = 3 planes of H x W floats, used as given - no
+ * scaling, no channel swap), otherwise as svo_det_detect.  Synchronises.  (The drop-in libYOLOv3SE.so calls this.) */
+int svo_det_detect_planar(svo_det* det, const float* data, int W, int H, int C, float thresh, float* result, int result_sz,
+                          int* n);
+/* Per-layer timing: with enable != 0, each later call records HIP events around the input kernel, every layer and the
+ * decode; svo_det_layer_times then gives the last call's times in ms - ms[0] the input, ms[1 + i] layer i, ms[n - 1] the
+ * decode + NMS + records; *n = layers + 2.  Synchronises.  Profiling adds an event per launch. */
+int svo_det_profile(svo_det* det, int enable);
+int svo_det_layer_times(svo_det* det, float* ms, int max_n, int* n);
+/* Wait for the detector's work in flight. */
+int svo_det_sync(svo_det* det);
+/* Parity probe: layer `layer`'s output for image `frame` of the last call, out_c x out_h x out_w floats (layer = -1: the
+ * network input, 3 x height x width).  Synchronises. */
+int svo_det_debug_tensor(svo_det* det, int layer, int frame, float* host_out);
+
 #ifdef __cplusplus
 }
 #endif

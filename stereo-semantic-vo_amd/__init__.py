@@ -55,6 +55,8 @@ ABI_SYMBOLS = [
     "svo_ctmf", "svo_track_multi_reset", "svo_track_multi_step_dev", "svo_track_tail_dev", "svo_track_overflowed", "svo_track_epnp_fallbacks", "svo_debug_stream_probe", "svo_debug_stream_pipes", "svo_track_sharded_dev", "svo_elas_batch_dev", "svo_msa_init", "svo_msa_tree", "svo_msa_tree_dp", "svo_msa_wta", "svo_msa_lrcheck", "svo_msa_solve", "svo_msa_batch_dev",
     "svo_create_ex", "svo_stream_mode", "svo_track_batch_host", "svo_track_sharded_host", "svo_frontend_batch_host",
     "svo_bgr_to_gray", "svo_track_frame_bgr", "svo_track_batch_bgr_dev", "svo_track_batch_bgr_host",
+    "svo_det_describe", "svo_det_last_error", "svo_det_create", "svo_det_destroy", "svo_det_detect", "svo_det_batch_dev",
+    "svo_det_sync", "svo_det_debug_tensor", "svo_det_detect_planar", "svo_det_profile", "svo_det_layer_times",
 ]
 
 # svo_create_ex flags (include/svo.h)
@@ -143,6 +145,21 @@ def load_library():
         lib.svo_stream_mode.argtypes = [C.c_void_p]
         lib.svo_destroy.argtypes = [C.c_void_p]
         lib.svo_destroy.restype = None
+        lib.svo_det_last_error.restype = C.c_char_p
+        lib.svo_det_last_error.argtypes = [C.c_void_p]
+        lib.svo_det_describe.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64)]
+        lib.svo_det_create.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+        lib.svo_det_destroy.argtypes = [C.c_void_p]
+        lib.svo_det_sync.argtypes = [C.c_void_p]
+        lib.svo_det_detect.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                       C.c_int, C.POINTER(C.c_int)]
+        lib.svo_det_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.svo_det_debug_tensor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        lib.svo_det_detect_planar.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int,
+                                              C.POINTER(C.c_int)]
+        lib.svo_det_profile.argtypes = [C.c_void_p, C.c_int]
+        lib.svo_det_layer_times.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
         _lib = lib
     return _lib
 
@@ -653,3 +670,119 @@ def elas_delaunay(xy):
     if rc != 0:
         raise SvoError("svo_elas_delaunay failed (%d)" % rc)
     return tri[:n.value].copy()
+
+
+# ---- darknet YOLO detector (svo_det_*, include/svo.h) ----------------------------------------------------------------------
+DET_LAYER_DTYPE = np.dtype([("type", "<i4"), ("in_w", "<i4"), ("in_h", "<i4"), ("in_c", "<i4"), ("out_w", "<i4"),
+                            ("out_h", "<i4"), ("out_c", "<i4"), ("size", "<i4"), ("stride", "<i4"), ("pad", "<i4"),
+                            ("batch_normalize", "<i4"), ("activation", "<i4"), ("classes", "<i4"), ("num", "<i4"),
+                            ("from", "<i4", (4,)), ("n_params", "<i8")])
+DET_LAYER_TYPES = ("convolutional", "maxpool", "route", "shortcut", "upsample", "yolo", "region")
+
+
+def _det_path(p):
+    return None if p is None else os.fsencode(str(p))
+
+
+class Detector:
+    """Darknet YOLO detection on one GPU (wraps svo_det): the online counterpart of the reference's YOLOv3 class
+    (include/YOLOv3SE.h -> Thirdparty/darknet/src/yolo_v3.c)."""
+
+    @staticmethod
+    def describe(cfg, weights=None):
+        """Host only: (layers as a DET_LAYER_DTYPE array, parameter floats).  Raises SvoError naming the section and line."""
+        lib = load_library()
+        n, npar = C.c_int(0), C.c_int64(0)
+        rc = lib.svo_det_describe(_det_path(cfg), _det_path(weights), None, 0, C.byref(n), C.byref(npar))
+        if rc != 0:
+            raise SvoError("svo_det_describe: %s" % lib.svo_det_last_error(None).decode())
+        out = np.zeros(n.value, DET_LAYER_DTYPE)
+        rc = lib.svo_det_describe(_det_path(cfg), _det_path(weights), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n),
+                                  C.byref(npar))
+        if rc != 0:
+            raise SvoError("svo_det_describe: %s" % lib.svo_det_last_error(None).decode())
+        return out, int(npar.value)
+
+    def __init__(self, cfg, weights, device=0, max_batch=1):
+        self.lib = load_library()
+        self.layers, self.n_params = Detector.describe(cfg, weights)
+        h = C.c_void_p()
+        rc = self.lib.svo_det_create(int(device), _det_path(cfg), _det_path(weights), int(max_batch), C.byref(h))
+        if rc != 0:
+            raise SvoError("svo_det_create: %s: %s" % (self.lib.svo_strerror(rc).decode(),
+                                                       self.lib.svo_det_last_error(None).decode()))
+        self.h = h
+        self.max_batch = int(max_batch)
+        first = self.layers[0]
+        self.net_w, self.net_h = int(first["in_w"]), int(first["in_h"])
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.svo_det_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise SvoError("%s: %s: %s" % (what, self.lib.svo_strerror(rc).decode(),
+                                           self.lib.svo_det_last_error(self.h).decode()))
+
+    def detect(self, img, thresh=0.8, result_sz=6000):
+        """YoloDetectFromImage on an 8-bit H x W (gray) or H x W x C image (channel k = byte k, e.g. BGR as stored):
+        records [class, prob, left, top, width, height] (n x 6 float32) in darknet's order."""
+        a = np.ascontiguousarray(img, np.uint8)
+        H, W = a.shape[:2]
+        Cc = 1 if a.ndim == 2 else a.shape[2]
+        res = np.zeros(max(int(result_sz), 1), np.float32)
+        n = C.c_int(0)
+        self._chk(self.lib.svo_det_detect(self.h, a.ctypes.data_as(C.c_void_p), W, H, Cc, W * Cc, float(thresh),
+                                          res.ctypes.data_as(C.c_void_p), int(result_sz), C.byref(n)), "svo_det_detect")
+        return res[:6 * n.value].reshape(-1, 6).copy()
+
+    def batch_dev(self, d_img, W, H, C_, stride, B, thresh, d_records, max_records, d_n_records, boxes=None, consumer=None):
+        """svo_det_batch_dev with device pointers (ints, e.g. torch tensors' data_ptr()); boxes: a BoxesDev or None;
+        consumer: an Svo whose next device-resident tracking call waits for these boxes.  Does not synchronise."""
+        self._chk(self.lib.svo_det_batch_dev(self.h, C.c_void_p(int(d_img)), int(W), int(H), int(C_), int(stride), int(B),
+                                             float(thresh), C.c_void_p(int(d_records)), int(max_records),
+                                             C.c_void_p(int(d_n_records)), _bx(boxes),
+                                             None if consumer is None else consumer.h), "svo_det_batch_dev")
+
+    def detect_planar(self, planar, thresh=0.8, result_sz=6000):
+        """YoloDetectFromImage on darknet's planar float image (3 x H x W float32, used as given)."""
+        a = np.ascontiguousarray(planar, np.float32)
+        Cc, H, W = a.shape
+        res = np.zeros(max(int(result_sz), 1), np.float32)
+        n = C.c_int(0)
+        self._chk(self.lib.svo_det_detect_planar(self.h, a.ctypes.data_as(C.c_void_p), W, H, Cc, float(thresh),
+                                                 res.ctypes.data_as(C.c_void_p), int(result_sz), C.byref(n)), "svo_det_detect_planar")
+        return res[:6 * n.value].reshape(-1, 6).copy()
+
+    def profile(self, enable=True):
+        self._chk(self.lib.svo_det_profile(self.h, int(bool(enable))), "svo_det_profile")
+
+    def layer_times(self):
+        """The last profiled call's times in ms: [input, layer 0, ..., layer n-1, decode]."""
+        ms = np.zeros(len(self.layers) + 2, np.float32)
+        n = C.c_int(0)
+        self._chk(self.lib.svo_det_layer_times(self.h, ms.ctypes.data_as(C.c_void_p), len(ms), C.byref(n)), "svo_det_layer_times")
+        return ms[:n.value]
+
+    def sync(self):
+        self._chk(self.lib.svo_det_sync(self.h), "svo_det_sync")
+
+    def debug_tensor(self, layer, frame=0):
+        """Layer `layer`'s output for image `frame` of the last call (out_c x out_h x out_w); layer -1: the network input."""
+        if layer < 0:
+            shape = (3, self.net_h, self.net_w)
+        else:
+            L = self.layers[layer]
+            shape = (int(L["out_c"]), int(L["out_h"]), int(L["out_w"]))
+        out = np.zeros(shape, np.float32)
+        self._chk(self.lib.svo_det_debug_tensor(self.h, int(layer), int(frame), out.ctypes.data_as(C.c_void_p)),
+                  "svo_det_debug_tensor")
+        return out

@@ -324,6 +324,9 @@ extern "C" void svo_destroy(svo_ctx* ctx) {
                   ctx->d_scratch, ctx->d_track, ctx->d_pnp_subsets};
   for (void* p : ptrs)
     if (p) hipFree(p);
+  if (ctx->det_ready) hipEventDestroy(ctx->det_ready);
+  for (hipEvent_t e : ctx->det_read)
+    if (e) hipEventDestroy(e);
   if (ctx->h_pinned) hipHostFree(ctx->h_pinned);
   if (ctx->h_stage) hipHostFree(ctx->h_stage);
   if (ctx->prof_impl) {

@@ -148,6 +148,10 @@ struct svo_ctx {
   hipStream_t stream_elas_a = nullptr;   // svo_elas_batch_dev: phase A (descriptors, support candidates) of the next chunks, beside phase B of the earlier ones
   int stream_elas_a_pct = -1;            //   the share of the CUs it was made for (0: all; as the stream phase B runs on)
   hipEvent_t ev_elas_setup = nullptr;
+  hipEvent_t det_ready = nullptr;   // svo_det_batch_dev(consumer = this ctx): recorded on the detector's stream behind its boxes
+  bool det_pending = false;         // the next tail_enqueue waits for det_ready on both tail streams, then clears this
+  hipEvent_t det_read[2] = {nullptr, nullptr};   // recorded on both tail streams behind a call that read boxes while det_ready exists;
+  bool det_read_valid = false;                    // the next svo_det_batch_dev(consumer = this ctx) waits for them before it writes
   hipEvent_t shard_wait = nullptr;   // borrowed: the gather event of the sharded tracker call that last read this context's result arrays
   void* d_gate_pre = nullptr;   // GatePre records (brute-force matches + F solved ahead of the index chain), like d_work
   int idx_probe_attempts = -1;  // how many candidate streams the index chain's stream was chosen from (-1: not chosen yet, 0: probe off)

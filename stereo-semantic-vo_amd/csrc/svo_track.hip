@@ -1660,6 +1660,11 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
   if (bx && (!bx->boxes || !bx->n || bx->stride < 1)) bx = nullptr;
   int rc = track_resources(ctx, frames, nseq);
   if (rc) return rc;
+  if (ctx->det_pending) {   // boxes written by svo_det_batch_dev(consumer = ctx) on the detector's own stream
+    SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->det_ready, 0));
+    SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_idx, ctx->det_ready, 0));
+    ctx->det_pending = false;
+  }
   TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
   TrackWork* work = reinterpret_cast<TrackWork*>(ctx->d_work) + (size_t)work_half * ctx->work_cap;
   ctx->work_last_half = work_half;
@@ -1826,6 +1831,13 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
     prev0 = cur0; prev1 = cur1;
   }
   ctx->profiling = prof;
+  if (bx && ctx->det_ready) {   // a detector feeds this context: its next call may overwrite these boxes once both chains read them
+    for (int k = 0; k < 2; ++k)
+      if (!ctx->det_read[k]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->det_read[k], hipEventDisableTiming));
+    SVO_HIP(ctx, hipEventRecord(ctx->det_read[0], s0));
+    SVO_HIP(ctx, hipEventRecord(ctx->det_read[1], s1));
+    ctx->det_read_valid = true;
+  }
   SVO_HIP(ctx, hipGetLastError());
   return SVO_OK;
 }

@@ -21,6 +21,7 @@
 #include "Tracking.h"
 #include "convert.h"
 #include "png_reader.h"
+#include "yolov3.h"
 
 using namespace svo_host;
 
@@ -56,6 +57,40 @@ int main(int argc, char** argv) {
     std::cout << std::fixed << std::setprecision(7) << q[0] << " " << q[1] << " " << q[2] << " " << q[3] << std::endl;
     return 0;
   }
+  // --detect <cfg> <weights> [threshold] / --write-boxes <dir> (before the other arguments): take each frame's boxes from the
+  // detector on the left image (the online mode of src/semantic.cc, YOLOv3::Detect(leftimg, 0.8)) instead of boxes/<n>.txt,
+  // and / or write the boxes each frame used in the offline format (main.cpp:59-97: `left right top bottom` per line)
+  std::string det_cfg, det_weights, write_dir;
+  float det_thresh = 0.8f;
+  for (int i = 1; i < argc;) {
+    const std::string a = argv[i];
+    int take = 0;
+    if (a == "--detect" && i + 2 < argc) {
+      det_cfg = argv[i + 1];
+      det_weights = argv[i + 2];
+      take = 3;
+      char* end = nullptr;
+      if (i + 3 < argc) {
+        const float t = strtof(argv[i + 3], &end);
+        if (end && *end == 0 && end != argv[i + 3]) { det_thresh = t; take = 4; }
+      }
+    } else if (a == "--write-boxes" && i + 1 < argc) {
+      write_dir = argv[i + 1];
+      take = 2;
+    }
+    if (!take) { ++i; continue; }
+    for (int j = i; j + take < argc; ++j) argv[j] = argv[j + take];
+    argc -= take;
+  }
+  YOLOv3 detector;
+  if (!det_cfg.empty()) {
+    try {
+      detector.Create(det_weights, det_cfg, "");
+    } catch (const std::exception& e) {
+      std::cerr << e.what() << std::endl;
+      return 1;
+    }
+  }
   bool colour = false;
   for (int i = 1; i < argc; ++i)
     if (std::string(argv[i]) == "--colour") {
@@ -73,7 +108,8 @@ int main(int argc, char** argv) {
     argc = 4;
   }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--colour] [--pipelined] path_to_vocabulary path_to_settings path_to_sequence [frames_per_call]" << std::endl;
+    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--pipelined] path_to_vocabulary"
+                 " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
   const std::string seq = argv[3];
@@ -101,12 +137,22 @@ int main(int argc, char** argv) {
   std::vector<float> vTimesTrack(nImages);
   std::cout << std::endl << "-------" << std::endl << "Start processing sequence ..." << std::endl
             << "Images in the sequence: " << nImages << std::endl << std::endl;
-  auto read_boxes = [&](int ni) {
+  // frame ni's boxes: from the detector on its left image, or from <sequence>/boxes/<ni+1>.txt; with --write-boxes also to
+  // <dir>/<ni+1>.txt
+  auto frame_boxes = [&](int ni, const GrayImage& gL, const BgrImage& cL) {
     std::vector<std::vector<int>> boxes;
-    std::stringstream bp; bp << seq << "/boxes/" << (ni + 1) << ".txt";
-    std::ifstream bf(bp.str());
-    int l, r, t, b;
-    while (bf >> l >> r >> t >> b) boxes.push_back({l, r, t, b});
+    if (!det_cfg.empty()) {
+      boxes = YOLOv3::TrackerBoxes(colour ? detector.Detect(cL, det_thresh) : detector.Detect(gL, det_thresh));
+    } else {
+      std::stringstream bp; bp << seq << "/boxes/" << (ni + 1) << ".txt";
+      std::ifstream bf(bp.str());
+      int l, r, t, b;
+      while (bf >> l >> r >> t >> b) boxes.push_back({l, r, t, b});
+    }
+    if (!write_dir.empty()) {
+      std::ofstream o(write_dir + "/" + std::to_string(ni + 1) + ".txt");
+      for (const auto& b : boxes) o << b[0] << " " << b[1] << " " << b[2] << " " << b[3] << "\n";
+    }
     return boxes;
   };
   if (pipelined) {
@@ -133,7 +179,7 @@ int main(int argc, char** argv) {
         if (l.size() != fb || r.size() != fb) { std::cerr << "image size changes within the sequence" << std::endl; return 1; }
         memcpy(bufL.data() + fb * k, l.data(), fb);
         memcpy(bufR.data() + fb * k, r.data(), fb);
-        boxes[k] = read_boxes(n0 + k);
+        boxes[k] = frame_boxes(n0 + k, imLeft, cLeft);
       }
       // (pageable buffers: the call returns when they are staged, so they are refilled at once while the GPU works)
       mpTracker->TrackBatch(bufL.data(), bufR.data(), cols, n, &vTimestamps[n0], boxes, colour);
@@ -157,13 +203,7 @@ int main(int argc, char** argv) {
       std::cerr << std::endl << "Failed to load image at: " << name(dl, ni, ext) << std::endl;
       return 1;
     }
-    std::vector<std::vector<int>> boxes;
-    {
-      std::stringstream bp; bp << seq << "/boxes/" << (ni + 1) << ".txt";
-      std::ifstream bf(bp.str());
-      int l, r, t, b;
-      while (bf >> l >> r >> t >> b) boxes.push_back({l, r, t, b});
-    }
+    const std::vector<std::vector<int>> boxes = frame_boxes(ni, imLeft, cLeft);
     const auto t1 = std::chrono::steady_clock::now();
     if (colour) mpTracker->Track(cLeft, cRight, vTimestamps[ni], f, f2, boxes);
     else mpTracker->Track(imLeft, imRight, vTimestamps[ni], f, f2, boxes);
