@@ -6,6 +6,7 @@ bench.py's cpu_baseline leg - never by the product package.
 import ctypes as C
 import os
 import subprocess
+import sys
 
 import numpy as np
 
@@ -506,3 +507,137 @@ def msa_solve(bgrL, bgrR, d=48, scale=1):
     rc = lib().orc_msa_solve(_p(a), _p(b), n, m, int(d), int(scale), _p(out))
     assert rc == 0, rc
     return out
+
+
+# --- the reference's darknet on the CPU (oracle/Makefile.ref -> oracle/_ref/libref_darknet.so, ref_darknet_wrap.c) ---------
+_REF_DARKNET = None
+REF_DN_TYPES = ("convolutional", "maxpool", "route", "shortcut", "upsample", "yolo", "region")
+
+
+def ref_darknet_lib():
+    """The reference's real darknet (Thirdparty/darknet/src), CPU build.  None when oracle/_ref/ has not been built."""
+    global _REF_DARKNET
+    so = os.path.join(_HERE, "_ref", "libref_darknet.so")
+    if _REF_DARKNET is None and os.path.exists(so):
+        L = C.CDLL(so)
+        L.YoloLoad.restype = C.c_void_p
+        L.YoloLoad.argtypes = [C.c_char_p, C.c_char_p]
+        L.YoloDetectFromImage.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_int]
+        L.ref_dn_net_size.argtypes = [C.c_void_p, C.c_void_p]
+        L.ref_dn_layer_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.ref_dn_layer_type_ids.argtypes = [C.c_void_p]
+        L.ref_dn_forward.argtypes = [C.c_void_p, C.c_void_p]
+        L.ref_dn_forward.restype = None
+        L.ref_dn_layer_output.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(C.c_float))]
+        L.ref_dn_letterbox.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.ref_dn_letterbox.restype = None
+        L.ref_dn_free.argtypes = [C.c_void_p]
+        L.ref_dn_free.restype = None
+        L.ref_dn_flush.restype = None
+        _REF_DARKNET = L
+    return _REF_DARKNET
+
+
+def ref_dn_letterbox(planar, nw, nh):
+    """darknet's letterbox_image on a planar float image (c x H x W float32) -> c x nh x nw float32."""
+    a = np.ascontiguousarray(planar, np.float32)
+    c, H, W = a.shape
+    out = np.zeros((c, nh, nw), np.float32)
+    ref_darknet_lib().ref_dn_letterbox(_p(a), W, H, c, nw, nh, _p(out))
+    return out
+
+
+def ref_qsort_is_stable(n=12000, size=48, keys=7):
+    """Whether this process's libc qsort - the one do_nms_sort calls - keeps equal elements in their order, probed on an array
+    shaped like darknet's detections (n structs of `size` bytes, a comparator that returns 0 on equal keys).  do_nms_sort sorts
+    ALL detections of a class, those with score 0 included; these compare equal, and their order after the last class's sort
+    is the order of the records.  C leaves that order open; glibc's merge sort (used while the temporary array fits in memory)
+    keeps it, as the device and the restatement do.  The probe is meant to be at least as large as the largest `total` the tests
+    let darknet sort (darknet53 at 416: 10,647 detections): glibc leaves its merge sort when the temporary array does not fit,
+    so a smaller probe would not speak for the larger sort."""
+    libc = C.CDLL(None)
+    CMP = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
+    a = np.zeros((n, size // 4), np.int32)
+    a[:, 0] = np.random.default_rng(0).integers(0, keys, n)
+    a[:, 1] = np.arange(n)
+
+    def cmp(pa, pb):
+        ka, kb = C.c_int32.from_address(pa).value, C.c_int32.from_address(pb).value
+        return (ka > kb) - (ka < kb)
+    libc.qsort.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, CMP]
+    libc.qsort.restype = None
+    libc.qsort(_p(a), n, size, CMP(cmp))
+    same_key = a[1:, 0] == a[:-1, 0]
+    return bool((np.diff(a[:, 0]) >= 0).all() and (a[1:, 1][same_key] > a[:-1, 1][same_key]).all())
+
+
+class RefDarknet:
+    """A network loaded by the reference's YoloLoad (parse_network_cfg + load_weights + set_batch_network(1))."""
+
+    def __init__(self, cfg, weights):
+        self.lib = ref_darknet_lib()
+        if self.lib is None:
+            raise RuntimeError("oracle/_ref/libref_darknet.so not built (make -C oracle -f Makefile.ref)")
+        # darknet prints its layer table (hundreds of lines for darknet53) with printf / fprintf: both descriptors go to
+        # /dev/null for the length of the load
+        sys.stdout.flush()
+        sys.stderr.flush()
+        saved = [os.dup(1), os.dup(2)]
+        null = os.open(os.devnull, os.O_WRONLY)
+        try:
+            os.dup2(null, 1)
+            os.dup2(null, 2)
+            self.net = self.lib.YoloLoad(os.fsencode(str(cfg)), os.fsencode(str(weights)))
+            self.lib.ref_dn_flush()
+        finally:
+            os.dup2(saved[0], 1)
+            os.dup2(saved[1], 2)
+            for fd in saved + [null]:
+                os.close(fd)
+        whc = np.zeros(3, np.int32)
+        self.n = self.lib.ref_dn_net_size(self.net, _p(whc))
+        self.w, self.h, self.c = (int(v) for v in whc)
+        ids = np.zeros(7, np.int32)
+        self.lib.ref_dn_layer_type_ids(_p(ids))
+        names = {int(v): i for i, v in enumerate(ids)}
+        self.layers = []
+        for i in range(self.n):
+            info = np.zeros(9, np.int32)
+            self.lib.ref_dn_layer_info(self.net, i, _p(info))
+            t = names.get(int(info[0]), -1)
+            self.layers.append(dict(type=t, in_w=int(info[1]), in_h=int(info[2]), in_c=int(info[3]), out_w=int(info[4]),
+                                    out_h=int(info[5]), out_c=int(info[6]), outputs=int(info[7]), n_params=int(info[8])))
+
+    def forward(self, x):
+        """network_predict on one ready input (c x h x w float32): every layer's output, out_c x out_h x out_w."""
+        a = np.ascontiguousarray(x, np.float32)
+        assert a.shape == (self.c, self.h, self.w)
+        self.lib.ref_dn_forward(self.net, _p(a))
+        return self.outputs()
+
+    def outputs(self, only=None):
+        """Every layer's `output` as the last forward left it (network_predict, or the one inside YoloDetectFromImage);
+        only: the layer indices wanted (None elsewhere)."""
+        outs = []
+        for i, L in enumerate(self.layers):
+            if only is not None and i not in only:
+                outs.append(None)
+                continue
+            ptr = C.POINTER(C.c_float)()
+            n = self.lib.ref_dn_layer_output(self.net, i, C.byref(ptr))
+            o = np.ctypeslib.as_array(ptr, shape=(n,)).copy()
+            outs.append(o.reshape(L["out_c"], L["out_h"], L["out_w"]) if L["out_c"] * L["out_h"] * L["out_w"] == n else o)
+        return outs
+
+    def detect(self, planar, thresh, result_sz=6000):
+        """YoloDetectFromImage on a planar float image (3 x H x W float32): records n x 6 float32."""
+        a = np.ascontiguousarray(planar, np.float32)
+        c, H, W = a.shape
+        res = np.zeros(max(int(result_sz), 1), np.float32)
+        n = self.lib.YoloDetectFromImage(_p(a), W, H, c, self.net, float(thresh), _p(res), int(result_sz))
+        return res[:6 * n].reshape(-1, 6).copy()
+
+    def close(self):
+        if self.net:
+            self.lib.ref_dn_free(self.net)
+            self.net = None

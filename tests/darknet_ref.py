@@ -149,11 +149,22 @@ def letterbox_geom(W, H, nw, nh):
     return new_w, new_h
 
 
+def planar(img):
+    """ipl_to_image: H x W (gray, replicated to three channels) or H x W x C uint8, channel k = byte k -> C x H x W float32."""
+    a = img if img.ndim == 3 else np.repeat(img[:, :, None], 3, axis=2)
+    return np.ascontiguousarray((a.astype(np.float64) / 255.).astype(np.float32).transpose(2, 0, 1))
+
+
 def letterbox(img, nw, nh):
     """img: H x W (gray, replicated to three channels) or H x W x C uint8, channel k = byte k.  -> 3 x nh x nw float32."""
-    a = img if img.ndim == 3 else np.repeat(img[:, :, None], 3, axis=2)
-    H, W = a.shape[:2]
-    im = (a.astype(np.float64) / 255.).astype(np.float32).transpose(2, 0, 1)     # 3 x H x W
+    return letterbox_planar(planar(img), nw, nh)
+
+
+def letterbox_planar(im, nw, nh):
+    """letterbox_image of darknet's planar float image (C x H x W float32) -> C x nh x nw float32.  darknet's resize_image
+    reads column (int)sx + 1, which its get_pixel asserts to be inside the row; here it is clamped (the device does the same)."""
+    im = np.asarray(im, np.float32)
+    H, W = im.shape[1:]
     new_w, new_h = letterbox_geom(W, H, nw, nh)
     w_scale = np.float32(W - 1) / np.float32(new_w - 1)
     h_scale = np.float32(H - 1) / np.float32(new_h - 1)
@@ -176,7 +187,7 @@ def letterbox(img, nw, nh):
     add = dy * part[:, np.minimum(iy + 1, H - 1), :]
     keep = ~((r == new_h - 1) | (H == 1))
     res[:, keep, :] = res[:, keep, :] + add[:, keep, :]
-    out = np.full((3, nh, nw), np.float32(.5), np.float32)
+    out = np.full((im.shape[0], nh, nw), np.float32(.5), np.float32)
     dx0, dy0 = (nw - new_w) // 2, (nh - new_h) // 2
     out[:, dy0:dy0 + new_h, dx0:dx0 + new_w] = res
     return out
@@ -187,84 +198,91 @@ def _logistic(x, dt):
     return (1. / (1. + np.exp(-x.astype(np.float64)))).astype(dt)
 
 
+def apply_layer(net, P, i, cur, outs, dtype):
+    """Layer i of the network applied to `cur` (B x C x H x W, its input) in `dtype`; `outs`: the earlier layers' outputs
+    (route and shortcut read them).  P: split_params(net, params)."""
+    dt = np.dtype(dtype)
+    L = net["layers"][i]
+    cur = cur.astype(dt)
+    t = L["type"]
+    if t == CONV:
+        bias, sc, mu, var, wt = P[i]
+        y = torch.nn.functional.conv2d(torch.from_numpy(np.ascontiguousarray(cur)), torch.from_numpy(wt.astype(dt)),
+                                       stride=L["stride"], padding=L["pad"]).numpy()
+        f = lambda a: a.astype(dt)[None, :, None, None]
+        if L["bn"]:
+            if dt == np.float64:
+                y = (y - f(mu)) / (np.sqrt(f(var)) + np.float64(np.float32(.000001))) * f(sc) + f(bias)
+            else:
+                den = np.sqrt(var.astype(np.float64)) + np.float64(np.float32(.000001))
+                y = ((y - f(mu)).astype(np.float64) / den[None, :, None, None]).astype(dt)
+                y = y * f(sc)
+                y = y + f(bias)
+        else:
+            y = y + f(bias)
+        if L["act"] == "leaky":
+            y = np.where(y > 0, y, (.1 * y.astype(np.float64)).astype(dt))
+        elif L["act"] == "logistic":
+            y = _logistic(y, dt)
+    elif t == MAXPOOL:
+        p, s, k = L["pad"], L["stride"], L["size"]
+        B, C, H, W = cur.shape
+        oh, ow = L["out_h"], L["out_w"]
+        padded = np.full((B, C, H + 2 * p + k, W + 2 * p + k), np.finfo(np.float32).min, dt)
+        padded[:, :, p:p + H, p:p + W] = cur
+        y = np.full((B, C, oh, ow), np.finfo(np.float32).min, dt)
+        for n in range(k):
+            for m in range(k):
+                y = np.maximum(y, padded[:, :, n:n + oh * s:s, m:m + ow * s:s][:, :, :oh, :ow])
+    elif t == ROUTE:
+        y = np.concatenate([outs[j].astype(dt) for j in L["route"]], axis=1)
+    elif t == SHORTCUT:
+        y = cur + outs[L["frm"]].astype(dt)
+    elif t == UPSAMPLE:
+        s = L["stride"]
+        y = cur.repeat(s, axis=2).repeat(s, axis=3)
+    elif t == YOLO:
+        B, C, H, W = cur.shape
+        E = L["classes"] + 5
+        y = cur.reshape(B, L["n"], E, H, W).copy()
+        for e in [0, 1] + list(range(4, E)):
+            y[:, :, e] = _logistic(y[:, :, e], dt)
+        y = y.reshape(B, C, H, W)
+    elif t == REGION:
+        B, C, H, W = cur.shape
+        E = L["classes"] + 5
+        y = cur.reshape(B, L["n"], E, H, W).copy()
+        for e in (0, 1, 4):
+            y[:, :, e] = _logistic(y[:, :, e], dt)
+        cl = y[:, :, 5:]
+        if L["softmax"]:
+            if dt == np.float32:     # blas.c softmax: float largest, e = (float)exp(x - largest), float sum in class order
+                largest = cl.max(axis=2, keepdims=True)
+                e = np.exp((cl - largest).astype(np.float64)).astype(np.float32)
+                ssum = np.zeros_like(e[:, :, 0:1])
+                for j in range(L["classes"]):
+                    ssum = ssum + e[:, :, j:j + 1]
+                y[:, :, 5:] = e / ssum
+            else:
+                e = np.exp(cl - cl.max(axis=2, keepdims=True))
+                y[:, :, 5:] = e / e.sum(axis=2, keepdims=True)
+        else:
+            y[:, :, 5:] = _logistic(cl, dt)
+        y = y.reshape(B, C, H, W)
+    else:
+        raise ValueError(t)
+    return y
+
+
 def forward(net, params, x, dtype):
     """x: B x 3 x h x w.  Every layer's output (B x C x H x W) in `dtype`: float64 (exact reference) or float32 (darknet's
     roundings, a different summation order)."""
     P = split_params(net, params)
-    dt = np.dtype(dtype)
-    tdt = torch.float64 if dt == np.float64 else torch.float32
     outs = []
-    cur = x.astype(dt)
-    for i, L in enumerate(net["layers"]):
-        t = L["type"]
-        if t == CONV:
-            bias, sc, mu, var, wt = P[i]
-            y = torch.nn.functional.conv2d(torch.from_numpy(np.ascontiguousarray(cur)), torch.from_numpy(wt.astype(dt)),
-                                           stride=L["stride"], padding=L["pad"]).numpy()
-            f = lambda a: a.astype(dt)[None, :, None, None]
-            if L["bn"]:
-                if dt == np.float64:
-                    y = (y - f(mu)) / (np.sqrt(f(var)) + 1e-6) * f(sc) + f(bias)
-                else:
-                    den = np.sqrt(var.astype(np.float64)) + np.float64(np.float32(.000001))
-                    y = ((y - f(mu)).astype(np.float64) / den[None, :, None, None]).astype(dt)
-                    y = y * f(sc)
-                    y = y + f(bias)
-            else:
-                y = y + f(bias)
-            if L["act"] == "leaky":
-                y = np.where(y > 0, y, (.1 * y.astype(np.float64)).astype(dt))
-            elif L["act"] == "logistic":
-                y = _logistic(y, dt)
-        elif t == MAXPOOL:
-            p, s, k = L["pad"], L["stride"], L["size"]
-            B, C, H, W = cur.shape
-            oh, ow = L["out_h"], L["out_w"]
-            padded = np.full((B, C, H + 2 * p + k, W + 2 * p + k), np.finfo(np.float32).min, dt)
-            padded[:, :, p:p + H, p:p + W] = cur
-            y = np.full((B, C, oh, ow), np.finfo(np.float32).min, dt)
-            for n in range(k):
-                for m in range(k):
-                    y = np.maximum(y, padded[:, :, n:n + oh * s:s, m:m + ow * s:s][:, :, :oh, :ow])
-        elif t == ROUTE:
-            y = np.concatenate([outs[j] for j in L["route"]], axis=1)
-        elif t == SHORTCUT:
-            y = cur + outs[L["frm"]]
-        elif t == UPSAMPLE:
-            s = L["stride"]
-            y = cur.repeat(s, axis=2).repeat(s, axis=3)
-        elif t == YOLO:
-            B, C, H, W = cur.shape
-            E = L["classes"] + 5
-            y = cur.reshape(B, L["n"], E, H, W).copy()
-            for e in [0, 1] + list(range(4, E)):
-                y[:, :, e] = _logistic(y[:, :, e], dt)
-            y = y.reshape(B, C, H, W)
-        elif t == REGION:
-            B, C, H, W = cur.shape
-            E = L["classes"] + 5
-            y = cur.reshape(B, L["n"], E, H, W).copy()
-            for e in (0, 1, 4):
-                y[:, :, e] = _logistic(y[:, :, e], dt)
-            cl = y[:, :, 5:]
-            if L["softmax"]:
-                if dt == np.float32:     # blas.c softmax: float largest, e = (float)exp(x - largest), float sum in class order
-                    largest = cl.max(axis=2, keepdims=True)
-                    e = np.exp((cl - largest).astype(np.float64)).astype(np.float32)
-                    ssum = np.zeros_like(e[:, :, 0:1])
-                    for j in range(L["classes"]):
-                        ssum = ssum + e[:, :, j:j + 1]
-                    y[:, :, 5:] = e / ssum
-                else:
-                    e = np.exp(cl - cl.max(axis=2, keepdims=True))
-                    y[:, :, 5:] = e / e.sum(axis=2, keepdims=True)
-            else:
-                y[:, :, 5:] = _logistic(cl, dt)
-            y = y.reshape(B, C, H, W)
-        else:
-            raise ValueError(t)
-        outs.append(y)
-        cur = y
+    cur = x
+    for i in range(len(net["layers"])):
+        cur = apply_layer(net, P, i, cur, outs, dtype)
+        outs.append(cur)
     return outs
 
 
@@ -368,6 +386,53 @@ def nms_sort(boxes, objs, probs, thresh=.45):
     return head + tail, probs
 
 
+def _overlap_v(x1, w1, x2, w2):
+    l1, l2 = x1 - w1 / _f(2), x2 - w2 / _f(2)
+    left = np.where(l1 > l2, l1, l2)
+    r1, r2 = x1 + w1 / _f(2), x2 + w2 / _f(2)
+    right = np.where(r1 < r2, r1, r2)
+    return right - left
+
+
+def box_iou_v(a, b):
+    """box_iou of one box against n (n x 4 float32): float32 elementwise, the operations and their order as in box_iou."""
+    w = _overlap_v(a[0], a[2], b[:, 0], b[:, 2])
+    h = _overlap_v(a[1], a[3], b[:, 1], b[:, 3])
+    i = np.where((w < 0) | (h < 0), _f(0), w * h)
+    u = a[2] * a[3] + b[:, 2] * b[:, 3] - i
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return i / u
+
+
+def nms_sort_fast(boxes, objs, probs, thresh=.45):
+    """nms_sort with the inner loop as float32 numpy elementwise operations (for thousands of candidates per class)."""
+    probs = probs.copy()
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
+    T = len(objs)
+    perm = list(range(T))
+    k = T - 1
+    i = 0
+    while i <= k:
+        if objs[perm[i]] == 0:
+            perm[i], perm[k] = perm[k], perm[i]
+            k -= 1
+            i -= 1
+        i += 1
+    total = k + 1
+    head, tail = np.array(perm[:total], np.int64), perm[total:]
+    th = _f(thresh)
+    for c in range(probs.shape[1]):
+        head = head[np.argsort(-probs[head, c], kind="stable")]
+        m = int((probs[head, c] != 0).sum())
+        for a in range(m):
+            if probs[head[a], c] == 0:
+                continue
+            rest = head[a + 1:m]
+            hit = box_iou_v(boxes[head[a]], boxes[rest]) > th
+            probs[rest[hit], c] = 0
+    return [int(d) for d in head] + tail, probs
+
+
 def records(boxes, probs, order, imw, imh, thresh, max_records):
     """YoloDetect's loop: -> n x 6 float32 [class, prob, left, top, right - left, bot - top]."""
     out = []
@@ -393,9 +458,9 @@ def records(boxes, probs, order, imw, imh, thresh, max_records):
     return np.array(out, np.float32).reshape(-1, 6)
 
 
-def detect_from_outputs(net, outs_img, imw, imh, thresh, max_records=1000):
+def detect_from_outputs(net, outs_img, imw, imh, thresh, max_records=1000, fast=False):
     boxes, objs, probs = network_boxes(net, outs_img, imw, imh, thresh)
-    order, probs = nms_sort(boxes, objs, probs)
+    order, probs = (nms_sort_fast if fast else nms_sort)(boxes, objs, probs)
     return records(boxes, probs, order, imw, imh, thresh, max_records)
 
 
