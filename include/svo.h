@@ -207,7 +207,9 @@ void svo_destroy(svo_ctx* ctx);
  * step (its own stream, two alternating private output sets) - same records.  Contract while it is on: between consecutive
  * steps nothing else is enqueued on the context (svo_sync and reading results are fine); svo_track_multi_reset restarts it.
  * "depth_source" (default 0): where svo_track_frame / svo_track_batch_dev take keypoint depth from - 0 the sparse
- * epipolar matcher (north star), 1 a dense ELAS map (svo_elas_*), 2 a dense MSA map (svo_msa_solve with d = 48: the
+ * epipolar matcher (north star), 1 a dense ELAS map (svo_elas_*), 3 a dense SGBM map (svo_sgbm_* with svo_sgbm_default_params of the
+ * image height: the body of the reference's frame::ElasMatch; on the gray, also in the _bgr entries; invalid pixels are -1, so
+ * their keypoints get depth -bf and fail every z > 0 test, as in the reference), 2 a dense MSA map (svo_msa_solve with d = 48: the
  * reference's live configuration, src/Tracking.cc:225-228 + src/frame.cc:82-91 - on the reference's colour input through the _bgr
  * entries; the gray entries hand MSA B = G = R copies of the gray), both read per keypoint as frame::computekeypoint_r /
  * disp2Depth do.
@@ -692,6 +694,49 @@ int svo_msa_solve(svo_ctx* ctx, const uint8_t* bgrL, const uint8_t* bgrR, int wi
  * calls of svo_msa_solve with scale 1.  Synchronises before it returns. */
 int svo_msa_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int width, int height, int B, int d,
                       float* d_disp);
+
+/* ---- semi-global block matching (ABI-7 additions; no existing entry changed) -----------------------------------------------
+ * The reference's third dense solver: the body of frame::ElasMatch (src/frame.cc:94-120) is cv::StereoSGBM::create(0, 16, 3)
+ * with a fixed parameter set, compute, convertTo(CV_32F, 1/16).  The algorithm here is OpenCV 3.2's MODE_SGBM (one pass, five
+ * directions) on one 8-bit gray pair, then the disp12MaxDiff check and filterSpeckles, restated as a written contract
+ * (DESIGN.md section 8 "SGBM": parity is unpinned in the sense of SURVEY section 8(c), like ORB) - all integer; the device
+ * equals the numpy restatement tests/sgbm_ref.py bit for bit.  Colour callers hand it the gray they already make. */
+typedef struct svo_sgbm_params {
+  int32_t minDisparity;       /* 0 */
+  int32_t numDisparities;     /* D: 16, 32, 48 or 64 */
+  int32_t blockSize;          /* 9 */
+  int32_t P1, P2;             /* 8 * 81, 32 * 81 */
+  int32_t disp12MaxDiff;      /* 1 */
+  int32_t preFilterCap;       /* 63 */
+  int32_t uniquenessRatio;    /* 10 */
+  int32_t speckleWindowSize;  /* 100 */
+  int32_t speckleRange;       /* 32 */
+} svo_sgbm_params;
+
+/* ElasMatch's values for an image of `height` rows: numDisparities = ((height / 8) + 15) & -16.  Host only. */
+int svo_sgbm_default_params(int height, svo_sgbm_params* params);
+
+/* One pair, host buffers (rows `stride` bytes apart) -> the int16 map `sgbm->compute` returns (disparity * 16, -16 = invalid;
+ * columns x < D are always invalid) and / or the float map disp16 / 16 (invalid = -1.0f exactly); either may be NULL.
+ * Accepts numDisparities in {16, 32, 48, 64}, width > D + 8, height >= 2, every other field at its default - anything else is
+ * SVO_E_INVALID; width > 3072 or height > 4096 is SVO_E_CAPACITY.  Parameters and sizes are checked first, on the host, before
+ * the context or a device is touched (so a NULL ctx with an oversized image still answers SVO_E_CAPACITY).  Synchronises. */
+int svo_sgbm_process(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int width, int height,
+                     const svo_sgbm_params* params, int16_t* disp16, float* disp);
+
+/* B pairs resident in HBM (pair b at d_L / d_R + b * height * stride) -> B float maps in HBM (map b at d_disp + b * width *
+ * height), four pairs at a time through the context's volumes.  Identical to B calls of svo_sgbm_process.  Synchronises. */
+int svo_sgbm_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int width, int height, int B,
+                       const svo_sgbm_params* params, float* d_disp);
+
+/* The last stage on its own, on a host map in place: cv::filterSpeckles(disp16, -16, 100, 16 * 32) - valid pixels are
+ * 4-connected where they differ by at most 512, every component of at most 100 pixels becomes -16.  Synchronises. */
+int svo_sgbm_filter_speckles(svo_ctx* ctx, int16_t* disp16, int width, int height);
+
+/* Parity probe of the last svo_sgbm_process call: which = 0 the block cost C, 1 S4 (the first four directions, saturated),
+ * 2 S (all five) - height x width x D int16, zero where undefined (x < D); 3 the right-image map disp2 (height x width, -1 = no
+ * bid), 4 disp1 after the left-right check, before the speckle filter (height x width).  Synchronises. */
+int svo_sgbm_debug_volume(svo_ctx* ctx, int which, int16_t* host);
 
 /* ---- darknet YOLO detector on the device (ABI-7 additions; no existing entry changed) -------------------------------------
  * The online half of semantic gating: Semantic::Run (src/semantic.cc) calls YOLOv3::Detect(leftimg, 0.8), which goes through

@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "svo_bgr_to_gray", "svo_track_frame_bgr", "svo_track_batch_bgr_dev", "svo_track_batch_bgr_host",
     "svo_det_describe", "svo_det_last_error", "svo_det_create", "svo_det_destroy", "svo_det_detect", "svo_det_batch_dev",
     "svo_det_sync", "svo_det_debug_tensor", "svo_det_detect_planar", "svo_det_profile", "svo_det_layer_times",
+    "svo_sgbm_default_params", "svo_sgbm_process", "svo_sgbm_batch_dev", "svo_sgbm_debug_volume", "svo_sgbm_filter_speckles",
 ]
 
 # svo_create_ex flags (include/svo.h)
@@ -599,6 +600,36 @@ class Svo:
         self._chk(self.lib.svo_msa_solve(self.h, _p(a), _p(b), W, H, 3 * W, int(d), int(scale), _p(out)))
         return out
 
+    # ---- semi-global block matching (include/svo.h: svo_sgbm_*; the body of the reference's frame::ElasMatch) ----
+    def sgbm_process(self, grayL, grayR, params=None):
+        """One gray pair -> (disp16 int16 H x W, -16 = invalid; disp float32 = disp16 / 16, -1 = invalid)."""
+        gl, gr = _u8(grayL), _u8(grayR)
+        H, W = gl.shape
+        params = params or sgbm_default_params(H)
+        d16 = np.zeros((H, W), np.int16); d = np.zeros((H, W), np.float32)
+        self._chk(self.lib.svo_sgbm_process(self.h, _p(gl), _p(gr), W, W, H, C.byref(params), _p(d16), _p(d)))
+        self._sgbm_shape = (H, W, params.numDisparities)
+        return d16, d
+
+    def sgbm_batch_dev(self, d_L, d_R, stride, W, H, B, d_disp, params=None):
+        """B device-resident gray pairs -> B device-resident float disparity maps (disp16 / 16, -1 = invalid)."""
+        params = params or sgbm_default_params(H)
+        self._chk(self.lib.svo_sgbm_batch_dev(self.h, C.c_void_p(d_L), C.c_void_p(d_R), int(stride), int(W), int(H), int(B),
+                                              C.byref(params), C.c_void_p(d_disp)))
+
+    def sgbm_filter_speckles(self, disp16):
+        """cv::filterSpeckles(disp16, -16, 100, 512) on an int16 H x W map; returns the filtered copy."""
+        d = np.ascontiguousarray(disp16, np.int16).copy()
+        self._chk(self.lib.svo_sgbm_filter_speckles(self.h, _p(d), d.shape[1], d.shape[0]))
+        return d
+
+    def sgbm_debug_volume(self, which):
+        """Stage `which` of the last sgbm_process call: 0 C, 1 S4, 2 S (H x W x D int16), 3 disp2, 4 disp1 before the speckle filter (H x W)."""
+        H, W, D = self._sgbm_shape
+        out = np.zeros((H, W, D) if which < 3 else (H, W), np.int16)
+        self._chk(self.lib.svo_sgbm_debug_volume(self.h, int(which), _p(out)))
+        return out
+
     def ctmf(self, img, r):
         """Median filter of Thirdparty/MB/ctmf.c on an H x W or H x W x C uint8 image."""
         a = _u8(img)
@@ -642,6 +673,22 @@ def elas_default_params(setting=0):
     rc = load_library().svo_elas_default_params(int(setting), C.byref(p))
     if rc != 0:
         raise SvoError("svo_elas_default_params failed")
+    return p
+
+
+class SgbmParams(C.Structure):
+    """svo_sgbm_params: cv::StereoSGBM's fields as frame::ElasMatch sets them (src/frame.cc:94-120)."""
+    _fields_ = [("minDisparity", C.c_int32), ("numDisparities", C.c_int32), ("blockSize", C.c_int32),
+                ("P1", C.c_int32), ("P2", C.c_int32), ("disp12MaxDiff", C.c_int32), ("preFilterCap", C.c_int32),
+                ("uniquenessRatio", C.c_int32), ("speckleWindowSize", C.c_int32), ("speckleRange", C.c_int32)]
+
+
+def sgbm_default_params(height):
+    """ElasMatch's parameter set for an image of `height` rows (needs no GPU)."""
+    p = SgbmParams()
+    rc = load_library().svo_sgbm_default_params(int(height), C.byref(p))
+    if rc != 0:
+        raise SvoError("svo_sgbm_default_params failed")
     return p
 
 

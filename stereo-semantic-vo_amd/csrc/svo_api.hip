@@ -317,6 +317,7 @@ extern "C" void svo_destroy(svo_ctx* ctx) {
   svo_track_release(ctx);
   svo_elas_release(ctx);
   svo_msa_release(ctx);
+  svo_sgbm_release(ctx);
   if (ctx->d_dense) hipFree(ctx->d_dense);
   void* ptrs[] = {ctx->d_xofs, ctx->d_xalpha, ctx->d_yofs, ctx->d_ybeta, ctx->d_stage, ctx->d_pyr,
                   ctx->d_corners, ctx->d_counters, ctx->d_hist, ctx->d_sel, ctx->d_selcnt,
@@ -422,7 +423,7 @@ extern "C" int svo_set_option(svo_ctx* ctx, const char* key, int value) {
     return SVO_OK;
   }
   if (!strcmp(key, "depth_source")) {
-    if (value < 0 || value > 2) return SVO_E_INVALID;   // 0 sparse matcher, 1 ELAS map, 2 MSA map
+    if (value < 0 || value > 3) return SVO_E_INVALID;   // 0 sparse matcher, 1 ELAS map, 2 MSA map, 3 SGBM map
     ctx->opt_depth_source = value;
     return SVO_OK;
   }
@@ -1131,7 +1132,7 @@ hipError_t svo_stream_create_masked(hipStream_t* st, int device, int percent) {
 //   stream           pose chain, and everything the host-buffer entries run      every CU but the first mask word's
 //   stream_idx       index chain                                                 the same
 //   stream_fe_batch  the batched tracker's front end                             "fe_cu_percent" of the CUs (first mask words)
-//   stream_dense     dense stage in front of the tracker (depth_source 1, 2)     "dense_cu_percent" of the CUs
+//   stream_dense     dense stage in front of the tracker (depth_source 1, 2, 3)  "dense_cu_percent" of the CUs
 // An option that changes a mask destroys that one stream and makes a new one through svo_pick_stream (measured against the
 // others, rejected candidates parked).  Per context (svo_create_ex flags; svo_stream_mode reports what is in effect):
 // SVO_CREATE_POOLED_STREAMS - the runtime's pooled NON-BLOCKING streams as up to round 5 (main stream only; the others on demand

@@ -188,12 +188,13 @@ struct svo_ctx {
   void* elas_batch = nullptr;   // ElasBatch: per-pair states of svo_elas_batch_dev
   int elas_strip_state = 0;     // k_cc_strip's > 64 KB dynamic-LDS opt-in on this ctx's device: 0 untried, 1 granted, -1 refused
   void* msa_arenas = nullptr;   // MsaArenas: device buffers of svo_msa_solve and of the tracker's MSA mode
+  void* sgbm = nullptr;         // SgbmArena (svo_sgbm.hip): cost / path volumes of svo_sgbm_* and of the tracker's SGBM mode
   float* d_dense = nullptr;     // dense maps of svo_track_batch_dev with depth_source 1: 2 x dense_cap x W*H
   int dense_cap = 0;
   svo_camera cam{};
   int track_frame = 0;
 
-  int opt_depth_source = 0; // svo_set_option("depth_source"): 0 sparse epipolar stereo, 1 dense ELAS map (svo_track_frame)
+  int opt_depth_source = 0; // svo_set_option("depth_source"): 0 sparse epipolar stereo, 1 dense ELAS map, 2 dense MSA map, 3 dense SGBM map
   int opt_fast_cand_cap = 2048;   // svo_set_option("fast_cand_cap"): entries of k_fast's candidate list (<= 2048)
   int opt_pose_mfma = 1;   // svo_set_option("pose_mfma"): the LM's sums over the edges - 1 on f64 MFMA (default), 2 one lane per quantity, 0 one lane for everything (svo_pose_dev.h)
   int opt_fe_cu_percent = 12;   // svo_set_option("fe_cu_percent"): share of the CUs the batched tracker's front-end stream may use
@@ -343,6 +344,12 @@ int svo_launch_unproject(svo_ctx* ctx, const float* uvz, int n, const svo_camera
 
 extern "C" void svo_elas_release(svo_ctx* ctx);
 void svo_msa_release(svo_ctx* ctx);
+void svo_sgbm_release(svo_ctx* ctx);
+// svo_sgbm.hip: B resident gray pairs (pair b at dL / dR + b * frame) -> B float maps at d_disp, enqueued on `s` in chunks of
+// svo_sgbm_chunk() pairs; no synchronisation
+int svo_sgbm_run_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,
+                     const svo_sgbm_params* p, float* d_disp);
+int svo_sgbm_chunk();
 void svo_track_release(svo_ctx* ctx);   // tracker states, work records, second stream, events
 int svo_upload_image(svo_ctx* ctx, const uint8_t* gray, int stride, int slot);
 // dense ELAS stereo on images already in HBM; the two maps stay in HBM (valid until the next call)

@@ -1977,6 +1977,18 @@ int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_
     hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_kp,
                        ctx->d_nkp, ctx->d_dense, g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, (size_t)0,
                        (const int32_t*)nullptr);
+  } else if (ctx->opt_depth_source == 3) {
+    // the body of the reference's frame::ElasMatch (src/frame.cc:94-120): SGBM on the gray pair; invalid pixels are -1
+    if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 1))) return rc;
+    if ((rc = dense_reserve(ctx, 1))) return rc;
+    svo_sgbm_params sp;
+    svo_sgbm_default_params(g.H, &sp);
+    if ((rc = svo_sgbm_run_dev(ctx, ctx->stream, dL, dR, ctx->stage_pitch, (size_t)g.H * ctx->stage_pitch, g.W, g.H, 1, &sp, ctx->d_dense)))
+      return rc;
+    SvoTimer t(ctx, "k_tk_dense_depth");
+    hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_kp,
+                       ctx->d_nkp, ctx->d_dense, g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, (size_t)0,
+                       (const int32_t*)nullptr);
   } else {
     if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 2))) return rc;
     if ((rc = svo_launch_stereo(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, &ctx->cam))) return rc;
@@ -2077,7 +2089,9 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
     svo_launch_bgr2gray(s, bgr->R + f0 * bgr_img, bgr->stride, bgr_img, const_cast<uint8_t*>(d_grayR) + f0 * gray_img, stride, gray_img,
                         ctx->g.W, ctx->g.H, b);
   };
-  if (ctx->opt_depth_source == 1) {
+  if (ctx->opt_depth_source == 1 || ctx->opt_depth_source == 3) {
+    // (depth_source 3: the same pipeline with SGBM maps, which have no host phase - chunks of svo_sgbm_chunk() pairs, every pair
+    // produces a map)
     // BASELINE configs[4] as a pipeline: the dense front end (ORB on the left images, ELAS maps, the reference's per-keypoint
     // lookups - src/Tracking.cc:225-228, src/frame.cc:122-164) runs on a stream of its own; svo_elas_batch_dev moves the call's
     // pairs through its GPU -> host -> GPU stages in chunks, and as soon as a chunk's last GPU phase is enqueued the hook
@@ -2150,6 +2164,18 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
     if ((rc = bgr_wait(ctx->stream_dense))) return rc;
     bgr_convert(ctx->stream_dense, 0, B);   // (ELAS runs on the gray, like ORB: the reference never calls libelas)
     rc = svo_launch_orb(ctx, ctx->stream_dense, svo_fe_own(ctx), d_grayL, d_grayR, stride, B, B);   // left images only
+    if (rc == SVO_OK && ctx->opt_depth_source == 3) {
+      svo_sgbm_params sp;
+      svo_sgbm_default_params(ctx->g.H, &sp);
+      for (int f0 = 0, step = svo_sgbm_chunk(); f0 < B && rc == SVO_OK; f0 += step) {
+        const int b = std::min(step, B - f0);
+        for (int k = 0; k < b; ++k) ctx->h_prod[f0 + k] = 1;
+        rc = svo_sgbm_run_dev(ctx, ctx->stream_dense, d_grayL + f0 * gray_img, d_grayR + f0 * gray_img, stride, gray_img, ctx->g.W,
+                              ctx->g.H, b, &sp, dD1 + n * f0);
+        if (rc == SVO_OK) rc = Hook::run(&hook, f0, b);
+      }
+      return rc;
+    }
     if (rc == SVO_OK)
       rc = svo_elas_batch_dev_hooked(ctx, ctx->stream_dense, d_grayL, d_grayR, stride, ctx->g.W, ctx->g.H, B, &ep, dD1, dD2, ctx->h_prod,
                                      &Hook::run, &hook);

@@ -184,6 +184,11 @@ void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, co
     else currentframe->MBdense(imLeft, imRight);
     currentframe->computekeypoint_r();
     currentframe->disp2Depth(bf);
+  } else if (depth_source == 3) {         // the same four calls with the body of the reference's ElasMatch (SGBM)
+    currentframe->featuredetect(imLeft);
+    currentframe->SGBMMatch(imLeft, imRight);
+    currentframe->computekeypoint_r();
+    currentframe->disp2Depth(bf);
   } else {
     currentframe->MB(imLeft, imRight);    // featuredetect + stereo association in one device pass
     currentframe->computekeypoint_r();

@@ -13,7 +13,7 @@ class Tracking {
   Tracking(const std::string& strSettingPath, int device = 0);
   // 0: sparse epipolar stereo (default); 1: the reference's live flow, a dense disparity map (libelas here,
   // MSA there) -> disp2Depth -> per-keypoint lookups (src/Tracking.cc:226-228)
-  int depth_source = 0;
+  int depth_source = 0;   // 0 sparse matcher, 1 ELAS map, 2 MSA map, 3 SGBM map (svo_set_option "depth_source")
   Tracking(const svo_camera& cam, int width, int height, int device = 0);
   ~Tracking();
   void init();                                                          // src/Tracking.cc:42-97

@@ -100,6 +100,16 @@ int frame::ElasMatch(const GrayImage& left, const GrayImage& right) {
   return valid;
 }
 
+int frame::SGBMMatch(const GrayImage& left, const GrayImage& right) {
+  svo_sgbm_params sp;
+  svo_sgbm_default_params(left.rows, &sp);   // numDisparities = ((rows / 8) + 15) & -16, src/frame.cc:100
+  dispimg.assign((size_t)left.cols * left.rows, -1.f);
+  if (svo_sgbm_process(ctx, left.ptr(), right.ptr(), left.cols, left.cols, left.rows, &sp, nullptr, dispimg.data()) != SVO_OK) return 0;
+  int valid = 0;
+  for (float d : dispimg) valid += d != -1.f;
+  return valid;
+}
+
 int frame::MBdense(const GrayImage& left, const GrayImage& right) {
   const size_t n = (size_t)left.cols * left.rows;
   std::vector<uint8_t> l3(3 * n), r3(3 * n), disp(n, 0);

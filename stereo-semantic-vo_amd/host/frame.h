@@ -10,6 +10,7 @@
 // With colour input featuredetect / MB / ElasMatch take the gray svo_bgr_to_gray made of it (cv::ORB's own COLOR_BGR2GRAY).
 //   ElasMatch          -> svo_elas_process         (src/frame.cc:93-120 dense disparity; the reference's body is
 //                         OpenCV SGBM under that name, the vendored solver it names is libelas: include/frame.h:15)
+//   SGBMMatch          -> svo_sgbm_process         (src/frame.cc:94-120 as the reference has it: the body of its ElasMatch)
 #pragma once
 #include <set>
 #include <vector>
@@ -31,6 +32,9 @@ class frame {
   // dense left-reference disparity map (float, width x height, negative = invalid) into `dispimg`;
   // returns the number of valid pixels
   int ElasMatch(const svo_host::GrayImage& left, const svo_host::GrayImage& right);
+  // the reference's ElasMatch body: semi-global block matching with its fixed parameter set, compute, convertTo(CV_32F, 1/16)
+  // into `dispimg` (-1 = invalid); returns the number of valid pixels
+  int SGBMMatch(const svo_host::GrayImage& left, const svo_host::GrayImage& right);
   // the reference's own MB body: MSA dense disparity (0 = none) of the two images as B = G = R colour images
   int MBdense(const svo_host::GrayImage& left, const svo_host::GrayImage& right);
   // the same with the true colour pair (the reference's 8UC3 input, main.cpp:160-161): MSA's colour cost and tree weights

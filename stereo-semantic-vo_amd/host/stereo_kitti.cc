@@ -99,6 +99,15 @@ int main(int argc, char** argv) {
       --argc;
       break;
     }
+  int depth_source = 0;   // --depth-source N: 0 sparse matcher (default), 1 ELAS map, 2 MSA map, 3 SGBM map
+  for (int i = 1; i + 1 < argc; ++i)
+    if (std::string(argv[i]) == "--depth-source") {
+      depth_source = atoi(argv[i + 1]);
+      if (depth_source < 0 || depth_source > 3) { std::cerr << "--depth-source: 0 .. 3" << std::endl; return 1; }
+      for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+      argc -= 2;
+      break;
+    }
   bool pipelined = false;
   int per_call = 32;
   if (argc >= 5 && std::string(argv[1]) == "--pipelined") {
@@ -108,7 +117,7 @@ int main(int argc, char** argv) {
     argc = 4;
   }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--pipelined] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--pipelined] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -132,6 +141,7 @@ int main(int argc, char** argv) {
   if (!exists(name(dl, 0, ext))) { ext = ".pgm"; }
   if (!exists(name(dl, 0, ext))) { dl = "image_2"; dr = "image_3"; }
   Tracking* mpTracker = new Tracking(argv[2]);
+  mpTracker->depth_source = depth_source;
   std::ofstream f("cameratrajectory_kitti.txt"); f << std::fixed;
   std::ofstream f2("cameratrajectory_tum.txt"); f2 << std::fixed;
   std::vector<float> vTimesTrack(nImages);
