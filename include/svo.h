@@ -738,6 +738,53 @@ int svo_sgbm_filter_speckles(svo_ctx* ctx, int16_t* disp16, int width, int heigh
  * bid), 4 disp1 after the left-right check, before the speckle filter (height x width).  Synchronises. */
 int svo_sgbm_debug_volume(svo_ctx* ctx, int which, int16_t* host);
 
+/* ---- sparse pyramidal Lucas-Kanade (ABI-7 additions; no existing entry changed) --------------------------------------------
+ * The dynamic-keypoint loop of the reference's Tracking::Track (src/Tracking.cc:189-223, commented out there): points inside
+ * detection boxes followed from the last left image into the current one with cv::calcOpticalFlowPyrLK and its default
+ * arguments.  The algorithm is OpenCV 3.2's on 8-bit single-channel images, restated as a written contract (DESIGN.md section
+ * 8 "LK": parity is unpinned in the sense of SURVEY section 8(c), like ORB and SGBM); the device equals the numpy restatement
+ * tests/lk_ref.py bit for bit.  Points are (x, y) float pairs and must be finite. */
+typedef struct svo_lk_params {
+  int32_t winSize;            /* 21 (square) */
+  int32_t maxLevel;           /* 0 .. 3; the level rule may stop lower (a level of width or height <= 21 is not built) */
+  int32_t maxCount;           /* 30 */
+  double epsilon;             /* 0.01 */
+  double minEigThreshold;     /* 1e-4 */
+} svo_lk_params;
+
+/* calcOpticalFlowPyrLK's defaults: 21, 3, 30, 0.01, 1e-4.  Host only. */
+int svo_lk_default_params(svo_lk_params* params);
+
+/* One pair, host buffers (rows `stride` bytes apart), n points -> next_pts (n x 2), status (n bytes, 1 = tracked), err (n floats,
+ * 0 where status is 0; may be NULL).  Accepts the defaults with maxLevel 0 .. 3 and width, height >= 22 - anything else is
+ * SVO_E_INVALID; width or height > 4096 or n > 4096 is SVO_E_CAPACITY.  Parameters, sizes and n are checked first, on the host,
+ * before the context or a device is touched.  n = 0 is SVO_OK and does nothing.  Working memory is the context's own LK arena,
+ * grown on demand and independent of svo_create's size.  Synchronises. */
+int svo_lk_track(svo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int stride, int width, int height,
+                 const svo_lk_params* params, const float* pts, int n, float* next_pts, uint8_t* status, float* err);
+
+/* B frames resident in HBM (frame b at d_frames + b * height * stride), the B - 1 consecutive pairs (b, b + 1), each with its own
+ * point list: d_counts[b] <= max_pts points at d_pts + b * 2 * max_pts; results at the same places of d_next, d_status, d_err
+ * (d_err may be NULL; entries past a list's count are not written).  Every frame's pyramid and derivatives are built once.
+ * 2 <= B <= 4096 (more is SVO_E_CAPACITY, checked on the host like the sizes).
+ * Identical to B - 1 calls of svo_lk_track.  Synchronises. */
+int svo_lk_batch_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int width, int height, int B, const svo_lk_params* params,
+                     const float* d_pts, const int32_t* d_counts, int max_pts, float* d_next, uint8_t* d_status, float* d_err);
+
+/* The reference's loop over B resident frames: frame 0's list is its seeds; for every later frame the previous frame's list is
+ * tracked into it, the status-0 points are erased in order, then the frame's own seeds (d_seed_counts[f] <= max_seeds points at
+ * d_seeds + f * 2 * max_seeds) are appended.  A list holds max_pts points: seeds that do not fit are dropped from the end and
+ * counted in d_dropped[f].  Lists at d_lists + f * 2 * max_pts, counts in d_list_counts[f].  Everything is enqueued at once, the
+ * counts never come to the host between frames; synchronises at the end.  1 <= B <= 4096 (more is SVO_E_CAPACITY). */
+int svo_lk_chain_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int width, int height, int B, const svo_lk_params* params,
+                     const float* d_seeds, const int32_t* d_seed_counts, int max_seeds, int max_pts, float* d_lists,
+                     int32_t* d_list_counts, int32_t* d_dropped);
+
+/* Parity probe of the last svo_lk_track call: which = 0 the image (uint8), 1 the derivatives (int16 pairs dx, dy) of level
+ * `level` of frame 0 (prev) or 1 (next); *w, *h the level's size, *top the effective top level (each may be NULL; host == NULL
+ * only reports them).  A level above the top is SVO_E_INVALID.  Synchronises. */
+int svo_lk_debug_level(svo_ctx* ctx, int which, int frame, int level, void* host, int* w, int* h, int* top);
+
 /* ---- darknet YOLO detector on the device (ABI-7 additions; no existing entry changed) -------------------------------------
  * The online half of semantic gating: Semantic::Run (src/semantic.cc) calls YOLOv3::Detect(leftimg, 0.8), which goes through
  * the dlopen C-ABI of include/YOLOv3SE.h (YoloLoad / YoloDetectFromImage) into Thirdparty/darknet/src/yolo_v3.c.  These

@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "svo_det_describe", "svo_det_last_error", "svo_det_create", "svo_det_destroy", "svo_det_detect", "svo_det_batch_dev",
     "svo_det_sync", "svo_det_debug_tensor", "svo_det_detect_planar", "svo_det_profile", "svo_det_layer_times",
     "svo_sgbm_default_params", "svo_sgbm_process", "svo_sgbm_batch_dev", "svo_sgbm_debug_volume", "svo_sgbm_filter_speckles",
+    "svo_lk_default_params", "svo_lk_track", "svo_lk_batch_dev", "svo_lk_chain_dev", "svo_lk_debug_level",
 ]
 
 # svo_create_ex flags (include/svo.h)
@@ -630,6 +631,43 @@ class Svo:
         self._chk(self.lib.svo_sgbm_debug_volume(self.h, int(which), _p(out)))
         return out
 
+    # ---- sparse pyramidal Lucas-Kanade (include/svo.h: svo_lk_*; the dynamic-keypoint loop of Tracking::Track) ----
+    def lk_track(self, prev, nxt, pts, params=None):
+        """One gray pair and n points (n x 2 float32) -> (next_pts n x 2 float32, status n uint8, err n float32)."""
+        a, b = _u8(prev), _u8(nxt)
+        H, W = a.shape
+        assert b.shape == (H, W)
+        params = params or lk_default_params()
+        p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = len(p)
+        out = np.zeros((n, 2), np.float32); st = np.zeros(n, np.uint8); err = np.zeros(n, np.float32)
+        self._chk(self.lib.svo_lk_track(self.h, _p(a), _p(b), W, W, H, C.byref(params), _p(p), n, _p(out), _p(st), _p(err)))
+        return out, st, err
+
+    def lk_batch_dev(self, d_frames, stride, W, H, B, d_pts, d_counts, max_pts, d_next, d_status, d_err=None, params=None):
+        """B device-resident frames, the B - 1 consecutive pairs, one point list per pair (device pointers throughout)."""
+        params = params or lk_default_params()
+        self._chk(self.lib.svo_lk_batch_dev(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params),
+                                            C.c_void_p(d_pts), C.c_void_p(d_counts), int(max_pts), C.c_void_p(d_next),
+                                            C.c_void_p(d_status), C.c_void_p(d_err) if d_err else None))
+
+    def lk_chain_dev(self, d_frames, stride, W, H, B, d_seeds, d_seed_counts, max_seeds, max_pts, d_lists, d_list_counts,
+                     d_dropped, params=None):
+        """The reference's track / erase / append loop over B device-resident frames (device pointers throughout)."""
+        params = params or lk_default_params()
+        self._chk(self.lib.svo_lk_chain_dev(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params),
+                                            C.c_void_p(d_seeds), C.c_void_p(d_seed_counts), int(max_seeds), int(max_pts),
+                                            C.c_void_p(d_lists), C.c_void_p(d_list_counts), C.c_void_p(d_dropped)))
+
+    def lk_debug_level(self, which, frame, level):
+        """Level `level` of frame 0 (prev) / 1 (next) of the last lk_track call: which 0 the image (h x w uint8), 1 the
+        derivatives (h x w x 2 int16: dx, dy).  Returns (array, effective top level)."""
+        w, h, top = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.lib.svo_lk_debug_level(self.h, int(which), int(frame), int(level), None, C.byref(w), C.byref(h), C.byref(top)))
+        out = np.zeros((h.value, w.value, 2), np.int16) if which else np.zeros((h.value, w.value), np.uint8)
+        self._chk(self.lib.svo_lk_debug_level(self.h, int(which), int(frame), int(level), _p(out), None, None, None))
+        return out, top.value
+
     def ctmf(self, img, r):
         """Median filter of Thirdparty/MB/ctmf.c on an H x W or H x W x C uint8 image."""
         a = _u8(img)
@@ -689,6 +727,21 @@ def sgbm_default_params(height):
     rc = load_library().svo_sgbm_default_params(int(height), C.byref(p))
     if rc != 0:
         raise SvoError("svo_sgbm_default_params failed")
+    return p
+
+
+class LkParams(C.Structure):
+    """svo_lk_params: cv::calcOpticalFlowPyrLK's arguments (winSize square, criteria COUNT+EPS)."""
+    _fields_ = [("winSize", C.c_int32), ("maxLevel", C.c_int32), ("maxCount", C.c_int32), ("epsilon", C.c_double),
+                ("minEigThreshold", C.c_double)]
+
+
+def lk_default_params():
+    """calcOpticalFlowPyrLK's defaults: 21 x 21, maxLevel 3, 30 iterations, epsilon 0.01, minEigThreshold 1e-4 (needs no GPU)."""
+    p = LkParams()
+    rc = load_library().svo_lk_default_params(C.byref(p))
+    if rc != 0:
+        raise SvoError("svo_lk_default_params failed")
     return p
 
 

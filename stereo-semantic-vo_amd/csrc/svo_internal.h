@@ -189,6 +189,7 @@ struct svo_ctx {
   int elas_strip_state = 0;     // k_cc_strip's > 64 KB dynamic-LDS opt-in on this ctx's device: 0 untried, 1 granted, -1 refused
   void* msa_arenas = nullptr;   // MsaArenas: device buffers of svo_msa_solve and of the tracker's MSA mode
   void* sgbm = nullptr;         // SgbmArena (svo_sgbm.hip): cost / path volumes of svo_sgbm_* and of the tracker's SGBM mode
+  void* lk = nullptr;           // LkArena (svo_lk.hip): pyramids, derivatives and point buffers of svo_lk_*
   float* d_dense = nullptr;     // dense maps of svo_track_batch_dev with depth_source 1: 2 x dense_cap x W*H
   int dense_cap = 0;
   svo_camera cam{};
@@ -345,6 +346,7 @@ int svo_launch_unproject(svo_ctx* ctx, const float* uvz, int n, const svo_camera
 extern "C" void svo_elas_release(svo_ctx* ctx);
 void svo_msa_release(svo_ctx* ctx);
 void svo_sgbm_release(svo_ctx* ctx);
+void svo_lk_release(svo_ctx* ctx);
 // svo_sgbm.hip: B resident gray pairs (pair b at dL / dR + b * frame) -> B float maps at d_disp, enqueued on `s` in chunks of
 // svo_sgbm_chunk() pairs; no synchronisation
 int svo_sgbm_run_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,

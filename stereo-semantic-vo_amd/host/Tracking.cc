@@ -109,6 +109,9 @@ void Tracking::init() {
     const float z = currentframe->kp_depth[i];
     for (const auto& b : currentframe->offline_box)
       if (u > b[0] - 5 && u < b[1] + 5 && v > b[2] - 5 && v < b[3] + 5) { dynamic = true; break; }
+    if (currentframe->dynamic_lk)           // src/Tracking.cc:70-85 with offline_box for `boxes`: strictly inside seeds
+      for (const auto& b : currentframe->offline_box)
+        if (u > b[0] && u < b[1] && v > b[2] && v < b[3]) { currentframe->DY_keypoints.push_back(Point2f{u, v}); dynamic = true; break; }
     Vec3f x3D;
     if (z > 0 && !dynamic && currentframe->UnprojectStereo(u, v, z, x3D)) {
       mappoint* newmp = new mappoint(x3D, currentframe, i);
@@ -173,6 +176,10 @@ void Tracking::Track(const BgrImage& imLeft, const BgrImage& imRight, double tim
 void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, const BgrImage* colLeft, const BgrImage* colRight,
                            double timestamp, std::ofstream& f, std::ofstream& f2, const std::vector<std::vector<int>>& detection_box) {
   currentframe = new frame(ctx, imLeft, imRight, timestamp, K, detection_box);
+  if (dynamic_lk) {                       // src/Tracking.cc:189-223: LK on the last list, erase by status, survivors -> DY_keypoints
+    currentframe->dynamic_lk = true;      // (status and error live in the current frame here, in lastframe there)
+    if (currentframe->LKTrack(lastframe) < 0) throw std::runtime_error(std::string("svo_lk_track: ") + svo_last_error(ctx));
+  }
   if (depth_source == 1) {                // src/Tracking.cc:225-228 literally: features, dense map, lookups
     currentframe->featuredetect(imLeft);
     currentframe->ElasMatch(imLeft, imRight);
@@ -219,6 +226,8 @@ void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, co
   std::vector<mappoint*>().swap(prev->MapPoints);
   std::vector<float>().swap(prev->match_score);
   std::vector<bool>().swap(prev->inlier);
+  std::vector<Point2f>().swap(prev->DY_keypoints);
+  std::vector<Point2f>().swap(prev->LK_keypoints);
   currentframe = nullptr;
   frame_num++;
 }

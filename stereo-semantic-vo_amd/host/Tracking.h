@@ -14,6 +14,12 @@ class Tracking {
   // 0: sparse epipolar stereo (default); 1: the reference's live flow, a dense disparity map (libelas here,
   // MSA there) -> disp2Depth -> per-keypoint lookups (src/Tracking.cc:226-228)
   int depth_source = 0;   // 0 sparse matcher, 1 ELAS map, 2 MSA map, 3 SGBM map (svo_set_option "depth_source")
+  // The dynamic-keypoint loop of src/Tracking.cc:189-223 (commented out there): before featuredetect, the last frame's
+  // DY_keypoints are followed into the current left image (frame::LKTrack), the status-0 points erased, the survivors become
+  // the current frame's DY_keypoints.  Seeds - keypoints strictly inside a box, offline_box in place of the reference's online
+  // `boxes` - are collected where the commented lines have them: init() (src/Tracking.cc:70-85) and frame::createmappoint
+  // while id <= 1 (src/frame.cc:209-222).  After Track() the frame's list is lastframe.DY_keypoints.  Track() only.
+  bool dynamic_lk = false;
   Tracking(const svo_camera& cam, int width, int height, int device = 0);
   ~Tracking();
   void init();                                                          // src/Tracking.cc:42-97

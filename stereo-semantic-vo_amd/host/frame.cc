@@ -25,7 +25,7 @@ frame::frame(frame* o)
       rightimg(o->rightimg), keypoints_l(o->keypoints_l), keypoints_r(o->keypoints_r),
       kp_disp(o->kp_disp), kp_depth(o->kp_depth), f_descriptor(o->f_descriptor),
       MapPoints(o->MapPoints), match_score(o->match_score), inlier(o->inlier),
-      offline_box(o->offline_box), width(o->width), height(o->height), fx(o->fx), fy(o->fy),
+      offline_box(o->offline_box), DY_keypoints(o->DY_keypoints), dynamic_lk(o->dynamic_lk), width(o->width), height(o->height), fx(o->fx), fy(o->fy),
       cx(o->cx), cy(o->cy), bf(o->bf) {
   SetPose(o->Tcw);
 }
@@ -110,6 +110,28 @@ int frame::SGBMMatch(const GrayImage& left, const GrayImage& right) {
   return valid;
 }
 
+// src/Tracking.cc:189-223 (commented out there): calcOpticalFlowPyrLK(last left, current left, last DY_keypoints, ...) with its
+// default arguments, then the erase loop over status
+int frame::LKTrack(const frame& last) {
+  const int n = (int)last.DY_keypoints.size();
+  LK_keypoints.assign(n, Point2f{0.f, 0.f});
+  status.assign(n, 0);
+  error.assign(n, 0.f);
+  DY_keypoints.clear();
+  if (n == 0) return 0;
+  if (leftimg.data.empty() || last.leftimg.cols != leftimg.cols || last.leftimg.rows != leftimg.rows ||
+      last.leftimg.data.size() != leftimg.data.size() || leftimg.data.size() < (size_t)leftimg.cols * leftimg.rows)
+    return -1;                              // the two images must be there and of one size
+  svo_lk_params lp;
+  svo_lk_default_params(&lp);
+  if (svo_lk_track(ctx, last.leftimg.ptr(), leftimg.ptr(), leftimg.cols, leftimg.cols, leftimg.rows, &lp, &last.DY_keypoints[0].x, n,
+                   &LK_keypoints[0].x, status.data(), error.data()) != SVO_OK)
+    return -1;
+  for (int i = 0; i < n; ++i)
+    if (status[i]) DY_keypoints.push_back(LK_keypoints[i]);
+  return (int)DY_keypoints.size();
+}
+
 int frame::MBdense(const GrayImage& left, const GrayImage& right) {
   const size_t n = (size_t)left.cols * left.rows;
   std::vector<uint8_t> l3(3 * n), r3(3 * n), disp(n, 0);
@@ -181,6 +203,9 @@ void frame::createmappoint(std::set<mappoint*, mappoint_by_creation>& localmap) 
     const float z = kp_depth[i];
     for (const auto& b : offline_box)
       if (u > b[0] - 5 && u < b[1] + 5 && v > b[2] - 5 && v < b[3] + 5) { dynamic = true; break; }
+    if (dynamic_lk && id <= 1)              // src/frame.cc:209-222 with offline_box for `boxes`: strictly inside seeds
+      for (const auto& b : offline_box)
+        if (u > b[0] && u < b[1] && v > b[2] && v < b[3]) { DY_keypoints.push_back(Point2f{u, v}); dynamic = true; break; }
     if (dynamic) continue;
     Vec3f x3D;
     if (UnprojectStereo(u, v, z, x3D)) {

@@ -11,6 +11,8 @@
 //   ElasMatch          -> svo_elas_process         (src/frame.cc:93-120 dense disparity; the reference's body is
 //                         OpenCV SGBM under that name, the vendored solver it names is libelas: include/frame.h:15)
 //   SGBMMatch          -> svo_sgbm_process         (src/frame.cc:94-120 as the reference has it: the body of its ElasMatch)
+//   LKTrack            -> svo_lk_track             (src/Tracking.cc:189-223, commented out there: calcOpticalFlowPyrLK on the
+//                         last frame's DY_keypoints, the status-0 points erased)
 #pragma once
 #include <set>
 #include <vector>
@@ -39,6 +41,10 @@ class frame {
   int MBdense(const svo_host::GrayImage& left, const svo_host::GrayImage& right);
   // the same with the true colour pair (the reference's 8UC3 input, main.cpp:160-161): MSA's colour cost and tree weights
   int MBdense(const svo_host::BgrImage& left, const svo_host::BgrImage& right);
+  // the dynamic keypoints of `last` (its DY_keypoints) followed from its left image into this frame's: LK_keypoints, status
+  // and error hold calcOpticalFlowPyrLK's three outputs for all of them, DY_keypoints the survivors (status != 0) in order;
+  // returns their number, or -1 when the call failed
+  int LKTrack(const frame& last);
   void disp2Depth(float bf);
   bool UnprojectStereo(float u, float v, float z, svo_host::Vec3f& x3D) const;
   void createmappoint(std::set<mappoint*, mappoint_by_creation>& localmap);
@@ -59,6 +65,10 @@ class frame {
   std::vector<float> match_score;
   std::vector<bool> inlier;
   std::vector<std::vector<int>> offline_box;
+  std::vector<svo_host::Point2f> DY_keypoints, LK_keypoints;   // include/frame.h: the dynamic keypoints and their tracked positions
+  std::vector<uint8_t> status;                                // calcOpticalFlowPyrLK's status ...
+  std::vector<float> error;                                   // ... and err
+  bool dynamic_lk = false;                                    // Tracking::dynamic_lk: createmappoint collects seeds while id <= 1
   float width = 0, height = 0;
   float fx = 0, fy = 0, cx = 0, cy = 0, bf = 0;
   svo_host::Mat44f Tcw;

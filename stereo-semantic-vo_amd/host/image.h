@@ -78,6 +78,7 @@ inline bool read_ppm_bgr(const std::string& path, BgrImage& img) {
 }
 
 // 4x4 / 3x3 / 3x1 float matrices (CV_32F in the reference), row-major
+struct Point2f { float x, y; };   // cv::Point2f's layout: n of them are the n x 2 floats svo_lk_track takes
 struct Mat44f { float m[16]; float& at(int r, int c) { return m[4 * r + c]; } float at(int r, int c) const { return m[4 * r + c]; } };
 struct Mat33f { float m[9]; float& at(int r, int c) { return m[3 * r + c]; } float at(int r, int c) const { return m[3 * r + c]; } };
 struct Vec3f { float v[3]; float& at(int i) { return v[i]; } float at(int i) const { return v[i]; } };

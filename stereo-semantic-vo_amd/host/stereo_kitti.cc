@@ -11,6 +11,8 @@
 // --colour (before the other arguments, with or without --pipelined): keep the images as 8UC3 BGR, as main.cpp:160-161 reads
 // them, and track them through the colour entries (svo_track_frame_bgr's seams / svo_track_batch_bgr_host): the gray ORB sees is
 // the same, MSA (depth_source 2) gets the colour.  Without it the files are reduced to gray on decode, as before.
+// --dynamic-lk [--write-dynamic <dir>] (frame by frame only): Tracking::dynamic_lk, the reference's LK loop over the keypoints
+// inside boxes (src/Tracking.cc:189-223); each frame's dynamic keypoints go to <dir>/NNNNNN.txt, one "x y" per line.
 // stereo_kitti --decode-bgr in.(png|ppm|pgm) out.ppm: codec self-test of the colour decode (the PPM holds RGB, as the format says).
 #include <algorithm>
 #include <chrono>
@@ -108,6 +110,19 @@ int main(int argc, char** argv) {
       argc -= 2;
       break;
     }
+  // --dynamic-lk: Tracking::dynamic_lk (the reference's LK loop over the points inside boxes); --write-dynamic <dir>: each
+  // frame's dynamic keypoints to <dir>/NNNNNN.txt, one "x y" per line (%.9g: the floats read back exactly)
+  bool dynamic_lk = false;
+  std::string dynamic_dir;
+  for (int i = 1; i < argc;) {
+    const std::string a = argv[i];
+    int take = 0;
+    if (a == "--dynamic-lk") { dynamic_lk = true; take = 1; }
+    else if (a == "--write-dynamic" && i + 1 < argc) { dynamic_dir = argv[i + 1]; take = 2; }
+    if (!take) { ++i; continue; }
+    for (int j = i; j + take < argc; ++j) argv[j] = argv[j + take];
+    argc -= take;
+  }
   bool pipelined = false;
   int per_call = 32;
   if (argc >= 5 && std::string(argv[1]) == "--pipelined") {
@@ -116,8 +131,13 @@ int main(int argc, char** argv) {
     for (int i = 1; i < 4; ++i) argv[i] = argv[i + 1];
     argc = 4;
   }
+  if (pipelined && (dynamic_lk || !dynamic_dir.empty())) {
+    std::cerr << "--dynamic-lk / --write-dynamic: frame by frame only (not with --pipelined)" << std::endl;
+    return 1;
+  }
+  if (!dynamic_dir.empty() && !dynamic_lk) { std::cerr << "--write-dynamic needs --dynamic-lk" << std::endl; return 1; }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--pipelined] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--dynamic-lk] [--write-dynamic dir] [--pipelined] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -142,6 +162,7 @@ int main(int argc, char** argv) {
   if (!exists(name(dl, 0, ext))) { dl = "image_2"; dr = "image_3"; }
   Tracking* mpTracker = new Tracking(argv[2]);
   mpTracker->depth_source = depth_source;
+  mpTracker->dynamic_lk = dynamic_lk;
   std::ofstream f("cameratrajectory_kitti.txt"); f << std::fixed;
   std::ofstream f2("cameratrajectory_tum.txt"); f2 << std::fixed;
   std::vector<float> vTimesTrack(nImages);
@@ -219,6 +240,12 @@ int main(int argc, char** argv) {
     else mpTracker->Track(imLeft, imRight, vTimestamps[ni], f, f2, boxes);
     const auto t2 = std::chrono::steady_clock::now();
     vTimesTrack[ni] = (float)std::chrono::duration_cast<std::chrono::duration<double>>(t2 - t1).count();
+    if (!dynamic_dir.empty()) {
+      FILE* o = fopen((dynamic_dir + "/" + name("", ni, ".txt").substr(seq.size() + 2)).c_str(), "w");
+      if (!o) { std::cerr << "cannot write into " << dynamic_dir << std::endl; return 1; }
+      for (const Point2f& p : mpTracker->lastframe.DY_keypoints) fprintf(o, "%.9g %.9g\n", p.x, p.y);
+      fclose(o);
+    }
   }
   f.close(); f2.close();
   std::cout << std::endl << "trajectory saved!" << std::endl;
