@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 7   /* 7, backward-compatible additions: svo_bgr_to_gray, svo_track_frame_bgr, svo_track_batch_bgr_dev,
+#define SVO_ABI_VERSION 7   /* 7, backward-compatible additions: svo_lk_track_bgr, svo_lk_batch_bgr_dev, svo_lk_chain_bgr_dev,
+                              svo_lk_debug_level_bgr (Lucas-Kanade on 8UC3 BGR frames, see "sparse pyramidal Lucas-Kanade" below); no
+                              existing entry changed.
+                              7, backward-compatible additions: svo_bgr_to_gray, svo_track_frame_bgr, svo_track_batch_bgr_dev,
                               svo_track_batch_bgr_host (8UC3 BGR input, see "colour input" below); no existing entry changed.
                               7 (round 6): + svo_track_batch_host, svo_track_sharded_host, svo_frontend_batch_host (pipelined host-fed entries:
                               images start in host memory, uploads run on a copy stream ahead of the front end, records come back to
@@ -741,9 +744,11 @@ int svo_sgbm_debug_volume(svo_ctx* ctx, int which, int16_t* host);
 /* ---- sparse pyramidal Lucas-Kanade (ABI-7 additions; no existing entry changed) --------------------------------------------
  * The dynamic-keypoint loop of the reference's Tracking::Track (src/Tracking.cc:189-223, commented out there): points inside
  * detection boxes followed from the last left image into the current one with cv::calcOpticalFlowPyrLK and its default
- * arguments.  The algorithm is OpenCV 3.2's on 8-bit single-channel images, restated as a written contract (DESIGN.md section
- * 8 "LK": parity is unpinned in the sense of SURVEY section 8(c), like ORB and SGBM); the device equals the numpy restatement
- * tests/lk_ref.py bit for bit.  Points are (x, y) float pairs and must be finite. */
+ * arguments.  The algorithm is OpenCV 3.2's, restated as a written contract (DESIGN.md section 8 "LK": parity is unpinned in
+ * the sense of SURVEY section 8(c), like ORB and SGBM): on 8-bit single-channel images (svo_lk_track, svo_lk_batch_dev,
+ * svo_lk_chain_dev; the device equals the numpy restatement tests/lk_ref.py bit for bit) and on 8UC3 BGR images, which is what
+ * the reference's call is made on (the _bgr entries, cn = 3; tests/lk_bgr_ref.py).  Points are (x, y) float pairs and must be
+ * finite. */
 typedef struct svo_lk_params {
   int32_t winSize;            /* 21 (square) */
   int32_t maxLevel;           /* 0 .. 3; the level rule may stop lower (a level of width or height <= 21 is not built) */
@@ -782,8 +787,33 @@ int svo_lk_chain_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int widt
 
 /* Parity probe of the last svo_lk_track call: which = 0 the image (uint8), 1 the derivatives (int16 pairs dx, dy) of level
  * `level` of frame 0 (prev) or 1 (next); *w, *h the level's size, *top the effective top level (each may be NULL; host == NULL
- * only reports them).  A level above the top is SVO_E_INVALID.  Synchronises. */
+ * only reports them).  A level above the top is SVO_E_INVALID.  It answers only while the context's last LK call is an
+ * svo_lk_track: after any other LK call, a colour one included, it is SVO_E_INVALID and svo_last_error says why.
+ * Synchronises. */
 int svo_lk_debug_level(svo_ctx* ctx, int which, int frame, int level, void* host, int* w, int* h, int* top);
+
+/* The same tracker on 8UC3 frames: interleaved B, G, R, rows `stride` >= 3 * width bytes apart, channel k is byte k as stored (no
+ * swap, no conversion).  This is calcOpticalFlowPyrLK with cn = 3 (DESIGN.md section 8 "LK", "colour"): the pyramid and the
+ * derivatives are built per channel, every window sum runs over 21 x 21 x 3 samples, the minimum-eigenvalue divisor stays
+ * 2 * 21 * 21 and err is divided by 32 * 21 * 3 * 21.  Parameters, defaults, checks (with stride >= 3 * width), capacities, the
+ * order of the checks and the results' layout are those of svo_lk_track.  A context may alternate gray and colour calls. */
+int svo_lk_track_bgr(svo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int stride, int width, int height,
+                     const svo_lk_params* params, const float* pts, int n, float* next_pts, uint8_t* status, float* err);
+
+/* svo_lk_batch_dev on B resident 8UC3 frames (frame b at d_frames + b * height * stride, stride >= 3 * width).  Identical to
+ * B - 1 calls of svo_lk_track_bgr.  Synchronises. */
+int svo_lk_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int width, int height, int B, const svo_lk_params* params,
+                         const float* d_pts, const int32_t* d_counts, int max_pts, float* d_next, uint8_t* d_status, float* d_err);
+
+/* svo_lk_chain_dev on B resident 8UC3 frames: the same track / erase / append loop, nothing comes to the host between frames. */
+int svo_lk_chain_bgr_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int width, int height, int B, const svo_lk_params* params,
+                         const float* d_seeds, const int32_t* d_seed_counts, int max_seeds, int max_pts, float* d_lists,
+                         int32_t* d_list_counts, int32_t* d_dropped);
+
+/* Parity probe of the last svo_lk_track_bgr call: which = 0 the level as height x width x 3 uint8, 1 its derivatives as
+ * height x width x 6 int16 (for channel c, entry 2 c is dx and entry 2 c + 1 is dy).  Otherwise as svo_lk_debug_level; it answers
+ * only while the context's last LK call is an svo_lk_track_bgr, after a gray one it is SVO_E_INVALID. */
+int svo_lk_debug_level_bgr(svo_ctx* ctx, int which, int frame, int level, void* host, int* w, int* h, int* top);
 
 /* ---- darknet YOLO detector on the device (ABI-7 additions; no existing entry changed) -------------------------------------
  * The online half of semantic gating: Semantic::Run (src/semantic.cc) calls YOLOv3::Detect(leftimg, 0.8), which goes through

@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "svo_det_sync", "svo_det_debug_tensor", "svo_det_detect_planar", "svo_det_profile", "svo_det_layer_times",
     "svo_sgbm_default_params", "svo_sgbm_process", "svo_sgbm_batch_dev", "svo_sgbm_debug_volume", "svo_sgbm_filter_speckles",
     "svo_lk_default_params", "svo_lk_track", "svo_lk_batch_dev", "svo_lk_chain_dev", "svo_lk_debug_level",
+    "svo_lk_track_bgr", "svo_lk_batch_bgr_dev", "svo_lk_chain_bgr_dev", "svo_lk_debug_level_bgr",
 ]
 
 # svo_create_ex flags (include/svo.h)
@@ -666,6 +667,43 @@ class Svo:
         self._chk(self.lib.svo_lk_debug_level(self.h, int(which), int(frame), int(level), None, C.byref(w), C.byref(h), C.byref(top)))
         out = np.zeros((h.value, w.value, 2), np.int16) if which else np.zeros((h.value, w.value), np.uint8)
         self._chk(self.lib.svo_lk_debug_level(self.h, int(which), int(frame), int(level), _p(out), None, None, None))
+        return out, top.value
+
+    # ---- the same on 8UC3 BGR frames (svo_lk_*_bgr: calcOpticalFlowPyrLK with cn = 3, the reference's own input) ----
+    def lk_track_bgr(self, prev, nxt, pts, params=None):
+        """One (H, W, 3) BGR pair and n points -> (next_pts n x 2 float32, status n uint8, err n float32)."""
+        a, b = _u8(prev), _u8(nxt)
+        H, W = a.shape[:2]
+        assert a.shape == (H, W, 3) and b.shape == (H, W, 3)
+        params = params or lk_default_params()
+        p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = len(p)
+        out = np.zeros((n, 2), np.float32); st = np.zeros(n, np.uint8); err = np.zeros(n, np.float32)
+        self._chk(self.lib.svo_lk_track_bgr(self.h, _p(a), _p(b), 3 * W, W, H, C.byref(params), _p(p), n, _p(out), _p(st), _p(err)))
+        return out, st, err
+
+    def lk_batch_bgr_dev(self, d_frames, stride, W, H, B, d_pts, d_counts, max_pts, d_next, d_status, d_err=None, params=None):
+        """lk_batch_dev on B device-resident BGR frames, rows `stride` >= 3 W bytes apart."""
+        params = params or lk_default_params()
+        self._chk(self.lib.svo_lk_batch_bgr_dev(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params),
+                                                C.c_void_p(d_pts), C.c_void_p(d_counts), int(max_pts), C.c_void_p(d_next),
+                                                C.c_void_p(d_status), C.c_void_p(d_err) if d_err else None))
+
+    def lk_chain_bgr_dev(self, d_frames, stride, W, H, B, d_seeds, d_seed_counts, max_seeds, max_pts, d_lists, d_list_counts,
+                         d_dropped, params=None):
+        """lk_chain_dev on B device-resident BGR frames."""
+        params = params or lk_default_params()
+        self._chk(self.lib.svo_lk_chain_bgr_dev(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params),
+                                                C.c_void_p(d_seeds), C.c_void_p(d_seed_counts), int(max_seeds), int(max_pts),
+                                                C.c_void_p(d_lists), C.c_void_p(d_list_counts), C.c_void_p(d_dropped)))
+
+    def lk_debug_level_bgr(self, which, frame, level):
+        """Level `level` of frame 0 (prev) / 1 (next) of the last lk_track_bgr call: which 0 the image (h x w x 3 uint8), 1 the
+        derivatives (h x w x 6 int16: dx, dy of B, of G, of R).  Returns (array, effective top level)."""
+        w, h, top = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.lib.svo_lk_debug_level_bgr(self.h, int(which), int(frame), int(level), None, C.byref(w), C.byref(h), C.byref(top)))
+        out = np.zeros((h.value, w.value, 6), np.int16) if which else np.zeros((h.value, w.value, 3), np.uint8)
+        self._chk(self.lib.svo_lk_debug_level_bgr(self.h, int(which), int(frame), int(level), _p(out), None, None, None))
         return out, top.value
 
     def ctmf(self, img, r):

@@ -1,10 +1,13 @@
 // svo_lk.hip - sparse pyramidal Lucas-Kanade (svo_lk_*): cv::calcOpticalFlowPyrLK as the reference's Tracking::Track names it
-// (src/Tracking.cc:189-223) with its default arguments, after the written contract of DESIGN.md section 8 "LK".
-//   k_lk_pyrdown   one pyramid level of every frame of a batch: [1 4 6 4 1]^2, reflect-101, tile + halo in LDS, separable
-//   k_lk_scharr    one level's (dx, dy) int16 pairs of every frame that is some pair's previous image
+// (src/Tracking.cc:189-223) with its default arguments, after the written contract of DESIGN.md section 8 "LK": on 8-bit
+// single-channel images, and (the _bgr entries) on the 8UC3 BGR images the reference's call is made on.
+//   k_lk_pyrdown   one pyramid level of every frame of a batch: [1 4 6 4 1]^2, reflect-101, tile + halo in LDS, separable;
+//                  CN interleaved channels, each on its own (one channel of one frame per blockIdx.z)
+//   k_lk_scharr    one level's (dx, dy) int16 pairs of every frame that is some pair's previous image, per channel
 //   k_lk_track     one wavefront per point, all levels in one launch: the 441 window pixels are 7 per lane, the I patch and both
 //                  derivative patches stay in registers over the iterations, the window sums are exact integers reduced on DPP,
 //                  the float tail is computed by every lane alike
+//   k_lk_track_bgr the same on three channels: a lane's 7 pixels are 21 samples, two I values to a register, the same sums
 //   k_lk_compact   order-preserving erase of the status-0 points, then a frame's seeds appended (svo_lk_chain_dev)
 // Compiled with -ffp-contract=off like the rest of the library: every float operation of the tail rounds once.
 #include <algorithm>
@@ -39,11 +42,13 @@ __device__ __forceinline__ int lk_reflect(int i, int n) {
   return i >= n ? 2 * (n - 1) - i : i;
 }
 
+template <int CN>
 __global__ __launch_bounds__(256) void k_lk_pyrdown(const uint8_t* __restrict__ src, int spitch, size_t sframe, int sw, int sh,
                                                     uint8_t* __restrict__ dst, size_t dframe, int dw, int dh) {
   __shared__ uint8_t tile[LK_PD_SH][LK_PD_SW + 1];
   __shared__ uint16_t hsum[LK_PD_SH][LK_PD_TX];
-  src += blockIdx.z * sframe; dst += blockIdx.z * dframe;
+  const int fr = blockIdx.z / CN, ch = blockIdx.z - fr * CN;
+  src += fr * sframe + ch; dst += fr * dframe + ch;
   const int tid = threadIdx.y * LK_PD_TX + threadIdx.x;
   const int x0 = 2 * blockIdx.x * LK_PD_TX - 2, y0 = 2 * blockIdx.y * LK_PD_TY - 2;
   // (a tile that hangs over the right or lower edge reaches past what one reflection covers: those source pixels feed no stored
@@ -51,7 +56,7 @@ __global__ __launch_bounds__(256) void k_lk_pyrdown(const uint8_t* __restrict__ 
   for (int i = tid; i < LK_PD_SH * LK_PD_SW; i += 256) {
     const int ty = i / LK_PD_SW, tx = i - ty * LK_PD_SW;
     const int sx = min(max(lk_reflect(x0 + tx, sw), 0), sw - 1), sy = min(max(lk_reflect(y0 + ty, sh), 0), sh - 1);
-    tile[ty][tx] = src[(size_t)sy * spitch + sx];
+    tile[ty][tx] = src[(size_t)sy * spitch + sx * CN];
   }
   __syncthreads();
   for (int i = tid; i < LK_PD_SH * LK_PD_TX; i += 256) {
@@ -64,21 +69,24 @@ __global__ __launch_bounds__(256) void k_lk_pyrdown(const uint8_t* __restrict__ 
   if (ox >= dw || oy >= dh) return;
   const int ty = 2 * threadIdx.y, tx = threadIdx.x;
   const int v = hsum[ty][tx] + 4 * hsum[ty + 1][tx] + 6 * hsum[ty + 2][tx] + 4 * hsum[ty + 3][tx] + hsum[ty + 4][tx];
-  dst[(size_t)oy * dw + ox] = (uint8_t)((v + 128) >> 8);
+  dst[((size_t)oy * dw + ox) * CN] = (uint8_t)((v + 128) >> 8);
 }
 
-// dx = [3 10 3]^T x [-1 0 1], dy = [-1 0 1]^T x [3 10 3], neighbours reflect-101 inside the level; dx in the low half-word
+// dx = [3 10 3]^T x [-1 0 1], dy = [-1 0 1]^T x [3 10 3], neighbours reflect-101 inside the level; dx in the low half-word.
+// One thread per sample of the w * CN a row holds: channel c of pixel x has entry x * CN + c, its neighbours are channel c too.
+template <int CN>
 __global__ __launch_bounds__(256) void k_lk_scharr(const uint8_t* __restrict__ img, int pitch, size_t iframe, int w, int h,
                                                    uint32_t* __restrict__ der, size_t dframe) {
-  const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-  if (x >= w || y >= h) return;
+  const int xs = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+  if (xs >= w * CN || y >= h) return;
+  const int px = xs / CN, ch = xs - px * CN;
   img += blockIdx.z * iframe; der += blockIdx.z * dframe;
-  const int xm = lk_reflect(x - 1, w), xp = lk_reflect(x + 1, w), ym = lk_reflect(y - 1, h), yp = lk_reflect(y + 1, h);
+  const int x = xs, xm = lk_reflect(px - 1, w) * CN + ch, xp = lk_reflect(px + 1, w) * CN + ch, ym = lk_reflect(y - 1, h), yp = lk_reflect(y + 1, h);
   const uint8_t *r0 = img + (size_t)ym * pitch, *r1 = img + (size_t)y * pitch, *r2 = img + (size_t)yp * pitch;
   const int a = r0[xm], b = r0[x], c = r0[xp], d = r1[xm], f = r1[xp], g = r2[xm], k = r2[x], l = r2[xp];
   const int dx = 3 * (c - a) + 10 * (f - d) + 3 * (l - g);
   const int dy = 3 * (g - a) + 10 * (k - b) + 3 * (l - c);
-  der[(size_t)y * w + x] = (uint32_t)(dx & 0xffff) | ((uint32_t)dy << 16);
+  der[(size_t)y * w * CN + x] = (uint32_t)(dx & 0xffff) | ((uint32_t)dy << 16);
 }
 
 struct LkW { int w00, w01, w10, w11; };
@@ -214,6 +222,148 @@ __global__ __launch_bounds__(256) void k_lk_track(const uint8_t* __restrict__ im
   }
 }
 
+// ---- three channels (8UC3, interleaved): the window is 21 rows of 63 samples ---------------------------------------------------
+// the four weighted taps of the three channels of pixel (x, y): one address per tap, the channels are its three bytes
+__device__ __forceinline__ void lk_tap_img3(const uint8_t* __restrict__ img, int pitch, int w, int h, int x, int y, const LkW& q,
+                                            int out[3]) {
+  const int x0 = 3 * lk_reflect(x, w), x1 = 3 * lk_reflect(x + 1, w);
+  const uint8_t *r0 = img + (size_t)lk_reflect(y, h) * pitch, *r1 = img + (size_t)lk_reflect(y + 1, h) * pitch;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[c] = r0[x0 + c] * q.w00 + r0[x1 + c] * q.w01 + r1[x0 + c] * q.w10 + r1[x1 + c] * q.w11;
+}
+
+__device__ __forceinline__ void lk_der_at3(const uint32_t* __restrict__ der, int w, int h, int x, int y, uint32_t d[3]) {
+  const bool in = (unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h;   // BORDER_CONSTANT 0
+  const uint32_t* e = der + ((size_t)y * w + x) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) d[c] = in ? e[c] : 0u;
+}
+
+// k_lk_track on 8UC3 frames: the same pixel-to-lane map, every lane holds its 7 pixels' three channels (21 samples).  I is at
+// most 8160, so two I values share a register; (gx, gy) are packed as in the gray kernel.  pyr_bytes and der_entries are a
+// frame's slot sizes (three channels), a level's offsets are three times the gray ones.
+__global__ __launch_bounds__(256) void k_lk_track_bgr(const uint8_t* __restrict__ img0, int stride0, size_t frame0,
+                                                      const uint8_t* __restrict__ pyr, size_t pyr_bytes,
+                                                      const uint32_t* __restrict__ der, size_t der_entries, int w0, int h0, int top,
+                                                      int fprev0, const float* __restrict__ pts, const int32_t* __restrict__ counts,
+                                                      int n_fixed, int max_pts, float* __restrict__ next,
+                                                      uint8_t* __restrict__ status, float* __restrict__ err) {
+  const int lane = threadIdx.x & 63;
+  const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int n = min(counts ? counts[blockIdx.y] : n_fixed, max_pts);
+  if (idx >= n) return;                                     // (whole wavefronts leave: the DPP sums below see all 64 lanes)
+  const size_t slot = (size_t)blockIdx.y * max_pts + idx;
+  const int fprev = fprev0 + blockIdx.y, fnext = fprev + 1;
+  const float ptx = pts[2 * slot], pty = pts[2 * slot + 1];
+
+  int wx[7], wy[7];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    const int p = lane + 64 * k;
+    wy[k] = p < LK_NPIX ? p / LK_WIN : 0;                   // (lanes 57..63 have no seventh pixel: they redo pixel 0 with weight 0)
+    wx[k] = p < LK_NPIX ? p - wy[k] * LK_WIN : 0;
+  }
+  const bool seventh = lane + 64 * 6 < LK_NPIX;
+
+  uint32_t Ipk[11];                                         // the I patch, sample s = 3 k + c in half-word s & 1 of Ipk[s >> 1]
+  int gxy[21];                                              // the packed (gx, gy) patch
+  float ox = 0.f, oy = 0.f, e = 0.f;
+  int st = 1;
+  for (int level = top; level >= 0; --level) {
+    const LkLevel L = lk_level(w0, h0, level);
+    const int pitch = level ? 3 * L.w : stride0;
+    const uint8_t* I = level ? pyr + fprev * pyr_bytes + 3 * L.ioff : img0 + fprev * frame0;
+    const uint8_t* J = level ? pyr + fnext * pyr_bytes + 3 * L.ioff : img0 + fnext * frame0;
+    const uint32_t* G = der + fprev * der_entries + 3 * L.doff;
+    const float sc = 1.f / (float)(1 << level);
+    float px = ptx * sc, py = pty * sc;
+    if (level == top) { ox = px; oy = py; } else { ox = ox * 2.f; oy = oy * 2.f; }
+    px -= 10.f; py -= 10.f;
+    const int ipx = (int)floorf(px), ipy = (int)floorf(py);
+    if (lk_outside(ipx, ipy, L.w, L.h)) { if (level == 0) st = 0; continue; }
+    const LkW q = lk_weights(px - (float)ipx, py - (float)ipy);
+    int s11 = 0, s12 = 0, s22 = 0;                          // 21 products a lane: 21 * 4080^2 < 2^31
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      const int x = ipx + wx[k], y = ipy + wy[k];
+      int iv[3];
+      lk_tap_img3(I, pitch, L.w, L.h, x, y, q, iv);
+      uint32_t d00[3], d01[3], d10[3], d11[3];
+      lk_der_at3(G, L.w, L.h, x, y, d00); lk_der_at3(G, L.w, L.h, x + 1, y, d01);
+      lk_der_at3(G, L.w, L.h, x, y + 1, d10); lk_der_at3(G, L.w, L.h, x + 1, y + 1, d11);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int s = 3 * k + c;
+        const uint32_t v = (uint32_t)((iv[c] + 256) >> 9);
+        if (s & 1) Ipk[s >> 1] |= v << 16; else Ipk[s >> 1] = v;
+        int gx = (int16_t)d00[c] * q.w00 + (int16_t)d01[c] * q.w01 + (int16_t)d10[c] * q.w10 + (int16_t)d11[c] * q.w11;
+        int gy = ((int)d00[c] >> 16) * q.w00 + ((int)d01[c] >> 16) * q.w01 + ((int)d10[c] >> 16) * q.w10 + ((int)d11[c] >> 16) * q.w11;
+        gx = (gx + 8192) >> 14; gy = (gy + 8192) >> 14;
+        if (k == 6 && !seventh) gx = gy = 0;
+        gxy[s] = (int)((uint32_t)(gx & 0xffff) | ((uint32_t)gy << 16));
+        s11 += gx * gx; s12 += gx * gy; s22 += gy * gy;
+      }
+    }
+    const float A11 = lk_scaled(lk_wave_sum64(s11)), A12 = lk_scaled(lk_wave_sum64(s12)), A22 = lk_scaled(lk_wave_sum64(s22));
+    float D = A11 * A22 - A12 * A12;
+    const float t = A11 - A22;
+    const float min_eig = ((A22 + A11) - sqrtf(t * t + (4.f * A12) * A12)) / 882.f;   // 2 * 21 * 21: without the channel count
+    if ((double)min_eig < 1e-4 || D < 1.1920928955078125e-7f) { if (level == 0) st = 0; continue; }
+    D = 1.f / D;
+    float nx = ox - 10.f, ny = oy - 10.f, pdx = 0.f, pdy = 0.f;
+    for (int j = 0; j < LK_MAX_COUNT; ++j) {
+      const int inx = (int)floorf(nx), iny = (int)floorf(ny);
+      if (lk_outside(inx, iny, L.w, L.h)) { if (level == 0) st = 0; break; }
+      const LkW r = lk_weights(nx - (float)inx, ny - (float)iny);
+      int s1 = 0, s2 = 0;                                   // 21 * 8160 * 4080 < 2^31
+#pragma unroll
+      for (int k = 0; k < 7; ++k) {
+        int jv[3];
+        lk_tap_img3(J, pitch, L.w, L.h, inx + wx[k], iny + wy[k], r, jv);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int s = 3 * k + c;
+          const int diff = ((jv[c] + 256) >> 9) - (int)((Ipk[s >> 1] >> (16 * (s & 1))) & 0xffffu);
+          s1 += diff * (int16_t)gxy[s]; s2 += diff * (gxy[s] >> 16);
+        }
+      }
+      const float b1 = lk_scaled(lk_wave_sum64(s1)), b2 = lk_scaled(lk_wave_sum64(s2));
+      const float dx = (A12 * b2 - A22 * b1) * D, dy = (A12 * b1 - A11 * b2) * D;
+      nx += dx; ny += dy;
+      ox = nx + 10.f; oy = ny + 10.f;
+      if ((double)dx * dx + (double)dy * dy <= 1e-4) break;
+      if (j > 0 && (double)fabsf(dx + pdx) < 0.01 && (double)fabsf(dy + pdy) < 0.01) { ox -= dx * 0.5f; oy -= dy * 0.5f; break; }
+      pdx = dx; pdy = dy;
+    }
+    if (level == 0 && st) {
+      const float fx = ox - 10.f, fy = oy - 10.f;
+      const int ifx = (int)floorf(fx), ify = (int)floorf(fy);
+      if (lk_outside(ifx, ify, L.w, L.h)) st = 0;
+      else {
+        const LkW r = lk_weights(fx - (float)ifx, fy - (float)ify);
+        int s = 0;
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+          int jv[3];
+          lk_tap_img3(J, pitch, L.w, L.h, ifx + wx[k], ify + wy[k], r, jv);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int i = 3 * k + c;
+            const int diff = ((jv[c] + 256) >> 9) - (int)((Ipk[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+            s += (k == 6 && !seventh) ? 0 : abs(diff);
+          }
+        }
+        e = (float)wave_sum_i32_dpp(s) / 42336.f;           // 32 * 21 * 3 * 21; at most 1323 * 8160 < 2^24: exact in an int32 and in a float
+      }
+    }
+  }
+  if (lane == 0) {
+    next[2 * slot] = ox; next[2 * slot + 1] = oy;
+    status[slot] = (uint8_t)st;
+    if (err) err[slot] = e;
+  }
+}
+
 // One workgroup: the tracked points with status != 0 in order, then the frame's seeds while the list has room
 __global__ __launch_bounds__(256) void k_lk_compact(const float* __restrict__ trk, const uint8_t* __restrict__ st,
                                                     const int32_t* __restrict__ n_prev, const float* __restrict__ seeds,
@@ -244,14 +394,14 @@ __global__ __launch_bounds__(256) void k_lk_compact(const float* __restrict__ tr
 }
 
 struct LkArena {
-  uint8_t* img = nullptr;       // svo_lk_track: the two level-0 images, rows W bytes apart
-  uint8_t* pyr = nullptr;       // levels 1.. of every frame
-  uint32_t* der = nullptr;      // (dx, dy) of every level of every frame
+  uint8_t* img = nullptr;       // svo_lk_track / svo_lk_track_bgr: the two level-0 images, rows cn W bytes apart
+  uint8_t* pyr = nullptr;       // levels 1.. of every frame (cn bytes a pixel)
+  uint32_t* der = nullptr;      // (dx, dy) of every level of every frame (cn entries a pixel)
   float *pts = nullptr, *next = nullptr, *err = nullptr;
   uint8_t* status = nullptr;
-  size_t cap_img = 0, cap_pyr = 0, cap_der = 0, cap_pts = 0;
+  size_t cap_img = 0, cap_pyr = 0, cap_der = 0, cap_pts = 0;   // (in elements: a gray and a colour call share them, the larger need stays)
   hipStream_t last = nullptr;
-  bool dbg_valid = false;
+  int dbg_cn = 0;               // channels of the last single-pair call, 0: none to report
   bool dbg_next_der = false;    // svo_lk_track builds the previous frame's derivatives only; svo_lk_debug_level adds the next frame's when asked
   int W = 0, H = 0, top = 0;
 };
@@ -279,9 +429,9 @@ int lk_check(const svo_lk_params* p, int W, int H, int n, int frames) {
   return SVO_OK;
 }
 
-int lk_args(svo_ctx* ctx, const char* who, bool pointers, const svo_lk_params* p, int W, int H, int stride, int n, int frames) {
+int lk_args(svo_ctx* ctx, const char* who, bool pointers, const svo_lk_params* p, int W, int H, int stride, int cn, int n, int frames) {
   int rc = lk_check(p, W, H, n, frames);
-  if (rc == SVO_OK && (!ctx || !pointers || stride < W)) rc = SVO_E_INVALID;
+  if (rc == SVO_OK && (!ctx || !pointers || stride < cn * W)) rc = SVO_E_INVALID;
   if (rc && ctx)
     ctx->last_error = std::string(who) + (rc == SVO_E_CAPACITY ? ": image larger than 4096 x 4096, more than 4096 points or more than 4096 frames"
                                                                : ": invalid argument or unsupported parameters");
@@ -304,19 +454,19 @@ int lk_grow(svo_ctx* ctx, LkArena* A, T** p, size_t* cap, size_t count) {
   return SVO_OK;
 }
 
-// the context's arena: pyramids and derivatives of `frames` images, point buffers for `pts` points (0: untouched)
-int lk_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int top, int frames, size_t pts, bool host_images, LkArena** out) {
+// the context's arena: pyramids and derivatives of `frames` images of cn channels, point buffers for `pts` points (0: untouched)
+int lk_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int cn, int top, int frames, size_t pts, bool host_images, LkArena** out) {
   if (!ctx->lk) ctx->lk = new LkArena();
   LkArena* A = static_cast<LkArena*>(ctx->lk);
   *out = A;
   if (A->last && A->last != s) SVO_HIP(ctx, hipStreamSynchronize(A->last));   // one user at a time
-  A->dbg_valid = false;
+  A->dbg_cn = 0;
   const LkLevel end = lk_level(W, H, top + 1);
   int rc;
-  if ((rc = lk_grow(ctx, A, &A->pyr, &A->cap_pyr, std::max<size_t>(end.ioff, 1) * frames)) ||
-      (rc = lk_grow(ctx, A, &A->der, &A->cap_der, end.doff * frames)))
+  if ((rc = lk_grow(ctx, A, &A->pyr, &A->cap_pyr, std::max<size_t>(end.ioff, 1) * cn * frames)) ||
+      (rc = lk_grow(ctx, A, &A->der, &A->cap_der, end.doff * cn * frames)))
     return rc;
-  if (host_images && (rc = lk_grow(ctx, A, &A->img, &A->cap_img, (size_t)W * H * 2))) return rc;
+  if (host_images && (rc = lk_grow(ctx, A, &A->img, &A->cap_img, (size_t)W * H * cn * 2))) return rc;
   if (pts && A->cap_pts < pts) {
     size_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
     A->cap_pts = 0;
@@ -331,32 +481,144 @@ int lk_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int top, int frames, s
 
 // pyramid levels 1 .. top of `frames` resident images, and the derivatives of levels 0 .. top of frames der_first ..
 // der_first + der_frames - 1 (a frame that is no pair's previous image needs none: the tracker reads the previous frame's only)
-void lk_build(hipStream_t s, LkArena* A, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top, int frames,
-              int der_first, int der_frames) {
+template <int CN>
+void lk_build_cn(hipStream_t s, LkArena* A, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top, int frames,
+                 int der_first, int der_frames) {
   const LkLevel end = lk_level(W, H, top + 1);
   for (int l = 0; l <= top; ++l) {
     const LkLevel L = lk_level(W, H, l);
-    const uint8_t* src = l ? A->pyr + L.ioff : img0;
-    const int pitch = l ? L.w : stride0;
-    const size_t frame = l ? end.ioff : frame0;
+    const uint8_t* src = l ? A->pyr + CN * L.ioff : img0;
+    const int pitch = l ? CN * L.w : stride0;
+    const size_t frame = l ? CN * end.ioff : frame0;
     if (der_frames > 0)
-      hipLaunchKernelGGL(k_lk_scharr, dim3((L.w + 63) / 64, (L.h + 3) / 4, der_frames), dim3(64, 4), 0, s, src + der_first * frame,
-                         pitch, frame, L.w, L.h, A->der + der_first * end.doff + L.doff, end.doff);
+      hipLaunchKernelGGL(k_lk_scharr<CN>, dim3((CN * L.w + 63) / 64, (L.h + 3) / 4, der_frames), dim3(64, 4), 0, s,
+                         src + der_first * frame, pitch, frame, L.w, L.h, A->der + CN * (der_first * end.doff + L.doff), CN * end.doff);
     if (l < top && frames > 0) {
       const LkLevel N = lk_level(W, H, l + 1);
-      hipLaunchKernelGGL(k_lk_pyrdown, dim3((N.w + LK_PD_TX - 1) / LK_PD_TX, (N.h + LK_PD_TY - 1) / LK_PD_TY, frames),
-                         dim3(LK_PD_TX, LK_PD_TY), 0, s, src, pitch, frame, L.w, L.h, A->pyr + N.ioff, end.ioff, N.w, N.h);
+      hipLaunchKernelGGL(k_lk_pyrdown<CN>, dim3((N.w + LK_PD_TX - 1) / LK_PD_TX, (N.h + LK_PD_TY - 1) / LK_PD_TY, CN * frames),
+                         dim3(LK_PD_TX, LK_PD_TY), 0, s, src, pitch, frame, L.w, L.h, A->pyr + CN * N.ioff, CN * end.ioff, N.w, N.h);
     }
   }
 }
 
-void lk_launch_track(hipStream_t s, LkArena* A, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top, int fprev0,
-                     int pairs, const float* pts, const int32_t* counts, int n_fixed, int max_pts, float* next, uint8_t* status,
-                     float* err) {
+void lk_build(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top, int frames,
+              int der_first, int der_frames) {
+  if (cn == 3) lk_build_cn<3>(s, A, img0, stride0, frame0, W, H, top, frames, der_first, der_frames);
+  else lk_build_cn<1>(s, A, img0, stride0, frame0, W, H, top, frames, der_first, der_frames);
+}
+
+void lk_launch_track(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top,
+                     int fprev0, int pairs, const float* pts, const int32_t* counts, int n_fixed, int max_pts, float* next,
+                     uint8_t* status, float* err) {
   const LkLevel end = lk_level(W, H, top + 1);
   const int waves = counts ? max_pts : n_fixed;
-  hipLaunchKernelGGL(k_lk_track, dim3((waves + 3) / 4, pairs), dim3(256), 0, s, img0, stride0, frame0, A->pyr, end.ioff, A->der,
-                     end.doff, W, H, top, fprev0, pts, counts, n_fixed, max_pts, next, status, err);
+  hipLaunchKernelGGL(cn == 3 ? k_lk_track_bgr : k_lk_track, dim3((waves + 3) / 4, pairs), dim3(256), 0, s, img0, stride0, frame0,
+                     A->pyr, cn * end.ioff, A->der, cn * end.doff, W, H, top, fprev0, pts, counts, n_fixed, max_pts, next, status,
+                     err);
+}
+
+int lk_track_pair(svo_ctx* ctx, const char* who, int cn, const uint8_t* prev, const uint8_t* next, int stride, int W, int H,
+                  const svo_lk_params* p, const float* pts, int n, float* next_pts, uint8_t* status, float* err) {
+  int rc = lk_args(ctx, who, prev && next && (n == 0 || (pts && next_pts && status)), p, W, H, stride, cn, n, 2);
+  if (rc || n == 0) return rc;
+  SVO_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int top = lk_top_level(W, H, p->maxLevel);
+  LkArena* A = nullptr;
+  if ((rc = lk_reserve(ctx, s, W, H, cn, top, 2, n, true, &A))) return rc;
+  const size_t row = (size_t)cn * W, img = row * H;
+  SVO_HIP(ctx, hipMemcpy2DAsync(A->img, row, prev, stride, row, H, hipMemcpyHostToDevice, s));
+  SVO_HIP(ctx, hipMemcpy2DAsync(A->img + img, row, next, stride, row, H, hipMemcpyHostToDevice, s));
+  SVO_HIP(ctx, hipMemcpyAsync(A->pts, pts, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
+  lk_build(s, A, cn, A->img, (int)row, img, W, H, top, 2, 0, 1);
+  lk_launch_track(s, A, cn, A->img, (int)row, img, W, H, top, 0, 1, A->pts, nullptr, n, n, A->next, A->status, A->err);
+  SVO_HIP(ctx, hipGetLastError());
+  SVO_HIP(ctx, hipMemcpyAsync(next_pts, A->next, 2 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+  SVO_HIP(ctx, hipMemcpyAsync(status, A->status, n, hipMemcpyDeviceToHost, s));
+  if (err) SVO_HIP(ctx, hipMemcpyAsync(err, A->err, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+  SVO_HIP(ctx, hipStreamSynchronize(s));
+  A->W = W; A->H = H; A->top = top; A->dbg_cn = cn; A->dbg_next_der = false;
+  return SVO_OK;
+}
+
+int lk_batch(svo_ctx* ctx, const char* who, int cn, const uint8_t* d_frames, int stride, int W, int H, int B, const svo_lk_params* p,
+             const float* d_pts, const int32_t* d_counts, int max_pts, float* d_next, uint8_t* d_status, float* d_err) {
+  int rc = lk_args(ctx, who, d_frames && B >= 2 && (max_pts == 0 || (d_pts && d_counts && d_next && d_status)), p, W, H, stride, cn,
+                   max_pts, B);
+  if (rc || max_pts == 0) return rc;
+  SVO_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int top = lk_top_level(W, H, p->maxLevel);
+  LkArena* A = nullptr;
+  if ((rc = lk_reserve(ctx, s, W, H, cn, top, B, 0, false, &A))) return rc;
+  const size_t frame = (size_t)H * stride;
+  lk_build(s, A, cn, d_frames, stride, frame, W, H, top, B, 0, B - 1);
+  lk_launch_track(s, A, cn, d_frames, stride, frame, W, H, top, 0, B - 1, d_pts, d_counts, 0, max_pts, d_next, d_status, d_err);
+  SVO_HIP(ctx, hipGetLastError());
+  SVO_HIP(ctx, hipStreamSynchronize(s));
+  return SVO_OK;
+}
+
+int lk_chain(svo_ctx* ctx, const char* who, int cn, const uint8_t* d_frames, int stride, int W, int H, int B, const svo_lk_params* p,
+             const float* d_seeds, const int32_t* d_seed_counts, int max_seeds, int max_pts, float* d_lists, int32_t* d_list_counts,
+             int32_t* d_dropped) {
+  int rc = lk_args(ctx, who,
+                   d_frames && B >= 1 && max_seeds >= 0 && max_pts >= 1 && d_seeds && d_seed_counts && d_lists && d_list_counts && d_dropped,
+                   p, W, H, stride, cn, std::max(max_pts, max_seeds), B);
+  if (rc) return rc;
+  SVO_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int top = lk_top_level(W, H, p->maxLevel);
+  LkArena* A = nullptr;
+  if ((rc = lk_reserve(ctx, s, W, H, cn, top, B, max_pts, false, &A))) return rc;
+  const size_t frame = (size_t)H * stride;
+  lk_build(s, A, cn, d_frames, stride, frame, W, H, top, B, 0, B - 1);
+  for (int f = 0; f < B; ++f) {                             // enqueued back to back: the counts never come to the host
+    float* list = d_lists + (size_t)f * 2 * max_pts;
+    if (f)
+      lk_launch_track(s, A, cn, d_frames, stride, frame, W, H, top, f - 1, 1, list - 2 * (size_t)max_pts, d_list_counts + f - 1, 0,
+                      max_pts, A->next, A->status, nullptr);
+    hipLaunchKernelGGL(k_lk_compact, dim3(1), dim3(256), 0, s, A->next, A->status, f ? d_list_counts + f - 1 : nullptr,
+                       d_seeds + (size_t)f * 2 * max_seeds, d_seed_counts + f, max_seeds, max_pts, list, d_list_counts + f,
+                       d_dropped + f);
+  }
+  SVO_HIP(ctx, hipGetLastError());
+  SVO_HIP(ctx, hipStreamSynchronize(s));
+  return SVO_OK;
+}
+
+// the probe of the last single-pair call of `cn` channels: a level as h x w x cn bytes, its derivatives as h x w x cn entries
+int lk_debug(svo_ctx* ctx, const char* who, int cn, int which, int frame, int level, void* host, int* w, int* h, int* top) {
+  if (!ctx || which < 0 || which > 1 || frame < 0 || frame > 1 || level < 0) return SVO_E_INVALID;
+  LkArena* A = static_cast<LkArena*>(ctx->lk);
+  if (!A || !A->dbg_cn) {
+    ctx->last_error = std::string(who) + (cn == 3 ? ": no svo_lk_track_bgr call to report" : ": no svo_lk_track call to report");
+    return SVO_E_INVALID;
+  }
+  if (A->dbg_cn != cn) {
+    ctx->last_error = std::string(who) + (cn == 3 ? ": the last LK call was a gray one (svo_lk_debug_level reports it)"
+                                                  : ": the last LK call was a colour one (svo_lk_debug_level_bgr reports it)");
+    return SVO_E_INVALID;
+  }
+  if (top) *top = A->top;
+  if (level > A->top) { ctx->last_error = std::string(who) + ": level above the effective top level"; return SVO_E_INVALID; }
+  const LkLevel L = lk_level(A->W, A->H, level), end = lk_level(A->W, A->H, A->top + 1);
+  if (w) *w = L.w;
+  if (h) *h = L.h;
+  if (!host) return SVO_OK;
+  SVO_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t px = (size_t)L.w * L.h * cn, img = (size_t)A->W * A->H * cn;
+  if (which == 1 && frame == 1 && !A->dbg_next_der) {       // the tracker had no use for them: built here, on demand
+    lk_build(ctx->stream, A, cn, A->img, cn * A->W, img, A->W, A->H, A->top, 0, 1, 1);
+    SVO_HIP(ctx, hipGetLastError());
+    A->dbg_next_der = true;
+  }
+  if (which == 1)
+    SVO_HIP(ctx, svo_memcpy_sync(ctx, host, A->der + cn * (frame * end.doff + L.doff), px * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  else
+    SVO_HIP(ctx, svo_memcpy_sync(ctx, host, level ? A->pyr + cn * (frame * end.ioff + L.ioff) : A->img + frame * img, px,
+                                 hipMemcpyDeviceToHost));
+  return SVO_OK;
 }
 
 }  // namespace
@@ -373,98 +635,42 @@ extern "C" int svo_lk_default_params(svo_lk_params* p) {
 
 extern "C" int svo_lk_track(svo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int stride, int W, int H, const svo_lk_params* p,
                             const float* pts, int n, float* next_pts, uint8_t* status, float* err) {
-  int rc = lk_args(ctx, "svo_lk_track", prev && next && (n == 0 || (pts && next_pts && status)), p, W, H, stride, n, 2);
-  if (rc || n == 0) return rc;
-  SVO_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  const int top = lk_top_level(W, H, p->maxLevel);
-  LkArena* A = nullptr;
-  if ((rc = lk_reserve(ctx, s, W, H, top, 2, n, true, &A))) return rc;
-  const size_t pix = (size_t)W * H;
-  SVO_HIP(ctx, hipMemcpy2DAsync(A->img, W, prev, stride, W, H, hipMemcpyHostToDevice, s));
-  SVO_HIP(ctx, hipMemcpy2DAsync(A->img + pix, W, next, stride, W, H, hipMemcpyHostToDevice, s));
-  SVO_HIP(ctx, hipMemcpyAsync(A->pts, pts, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, s));
-  lk_build(s, A, A->img, W, pix, W, H, top, 2, 0, 1);
-  lk_launch_track(s, A, A->img, W, pix, W, H, top, 0, 1, A->pts, nullptr, n, n, A->next, A->status, A->err);
-  SVO_HIP(ctx, hipGetLastError());
-  SVO_HIP(ctx, hipMemcpyAsync(next_pts, A->next, 2 * (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-  SVO_HIP(ctx, hipMemcpyAsync(status, A->status, n, hipMemcpyDeviceToHost, s));
-  if (err) SVO_HIP(ctx, hipMemcpyAsync(err, A->err, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
-  SVO_HIP(ctx, hipStreamSynchronize(s));
-  A->W = W; A->H = H; A->top = top; A->dbg_valid = true; A->dbg_next_der = false;
-  return SVO_OK;
+  return lk_track_pair(ctx, "svo_lk_track", 1, prev, next, stride, W, H, p, pts, n, next_pts, status, err);
+}
+extern "C" int svo_lk_track_bgr(svo_ctx* ctx, const uint8_t* prev, const uint8_t* next, int stride, int W, int H,
+                                const svo_lk_params* p, const float* pts, int n, float* next_pts, uint8_t* status, float* err) {
+  return lk_track_pair(ctx, "svo_lk_track_bgr", 3, prev, next, stride, W, H, p, pts, n, next_pts, status, err);
 }
 
 extern "C" int svo_lk_batch_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int W, int H, int B, const svo_lk_params* p,
                                 const float* d_pts, const int32_t* d_counts, int max_pts, float* d_next, uint8_t* d_status,
                                 float* d_err) {
-  int rc = lk_args(ctx, "svo_lk_batch_dev", d_frames && B >= 2 && (max_pts == 0 || (d_pts && d_counts && d_next && d_status)), p, W, H,
-                   stride, max_pts, B);
-  if (rc || max_pts == 0) return rc;
-  SVO_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  const int top = lk_top_level(W, H, p->maxLevel);
-  LkArena* A = nullptr;
-  if ((rc = lk_reserve(ctx, s, W, H, top, B, 0, false, &A))) return rc;
-  const size_t frame = (size_t)H * stride;
-  lk_build(s, A, d_frames, stride, frame, W, H, top, B, 0, B - 1);
-  lk_launch_track(s, A, d_frames, stride, frame, W, H, top, 0, B - 1, d_pts, d_counts, 0, max_pts, d_next, d_status, d_err);
-  SVO_HIP(ctx, hipGetLastError());
-  SVO_HIP(ctx, hipStreamSynchronize(s));
-  return SVO_OK;
+  return lk_batch(ctx, "svo_lk_batch_dev", 1, d_frames, stride, W, H, B, p, d_pts, d_counts, max_pts, d_next, d_status, d_err);
+}
+extern "C" int svo_lk_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int W, int H, int B, const svo_lk_params* p,
+                                    const float* d_pts, const int32_t* d_counts, int max_pts, float* d_next, uint8_t* d_status,
+                                    float* d_err) {
+  return lk_batch(ctx, "svo_lk_batch_bgr_dev", 3, d_frames, stride, W, H, B, p, d_pts, d_counts, max_pts, d_next, d_status, d_err);
 }
 
 extern "C" int svo_lk_chain_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int W, int H, int B, const svo_lk_params* p,
                                 const float* d_seeds, const int32_t* d_seed_counts, int max_seeds, int max_pts, float* d_lists,
                                 int32_t* d_list_counts, int32_t* d_dropped) {
-  int rc = lk_args(ctx, "svo_lk_chain_dev",
-                   d_frames && B >= 1 && max_seeds >= 0 && max_pts >= 1 && d_seeds && d_seed_counts && d_lists && d_list_counts && d_dropped,
-                   p, W, H, stride, std::max(max_pts, max_seeds), B);
-  if (rc) return rc;
-  SVO_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  const int top = lk_top_level(W, H, p->maxLevel);
-  LkArena* A = nullptr;
-  if ((rc = lk_reserve(ctx, s, W, H, top, B, max_pts, false, &A))) return rc;
-  const size_t frame = (size_t)H * stride;
-  lk_build(s, A, d_frames, stride, frame, W, H, top, B, 0, B - 1);
-  for (int f = 0; f < B; ++f) {                             // enqueued back to back: the counts never come to the host
-    float* list = d_lists + (size_t)f * 2 * max_pts;
-    if (f)
-      lk_launch_track(s, A, d_frames, stride, frame, W, H, top, f - 1, 1, list - 2 * (size_t)max_pts, d_list_counts + f - 1, 0,
-                      max_pts, A->next, A->status, nullptr);
-    hipLaunchKernelGGL(k_lk_compact, dim3(1), dim3(256), 0, s, A->next, A->status, f ? d_list_counts + f - 1 : nullptr,
-                       d_seeds + (size_t)f * 2 * max_seeds, d_seed_counts + f, max_seeds, max_pts, list, d_list_counts + f,
-                       d_dropped + f);
-  }
-  SVO_HIP(ctx, hipGetLastError());
-  SVO_HIP(ctx, hipStreamSynchronize(s));
-  return SVO_OK;
+  return lk_chain(ctx, "svo_lk_chain_dev", 1, d_frames, stride, W, H, B, p, d_seeds, d_seed_counts, max_seeds, max_pts, d_lists,
+                  d_list_counts, d_dropped);
+}
+extern "C" int svo_lk_chain_bgr_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int W, int H, int B, const svo_lk_params* p,
+                                    const float* d_seeds, const int32_t* d_seed_counts, int max_seeds, int max_pts, float* d_lists,
+                                    int32_t* d_list_counts, int32_t* d_dropped) {
+  return lk_chain(ctx, "svo_lk_chain_bgr_dev", 3, d_frames, stride, W, H, B, p, d_seeds, d_seed_counts, max_seeds, max_pts, d_lists,
+                  d_list_counts, d_dropped);
 }
 
 extern "C" int svo_lk_debug_level(svo_ctx* ctx, int which, int frame, int level, void* host, int* w, int* h, int* top) {
-  if (!ctx || which < 0 || which > 1 || frame < 0 || frame > 1 || level < 0) return SVO_E_INVALID;
-  LkArena* A = static_cast<LkArena*>(ctx->lk);
-  if (!A || !A->dbg_valid) { ctx->last_error = "svo_lk_debug_level: no svo_lk_track call to report"; return SVO_E_INVALID; }
-  if (top) *top = A->top;
-  if (level > A->top) { ctx->last_error = "svo_lk_debug_level: level above the effective top level"; return SVO_E_INVALID; }
-  const LkLevel L = lk_level(A->W, A->H, level), end = lk_level(A->W, A->H, A->top + 1);
-  if (w) *w = L.w;
-  if (h) *h = L.h;
-  if (!host) return SVO_OK;
-  SVO_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t px = (size_t)L.w * L.h;
-  if (which == 1 && frame == 1 && !A->dbg_next_der) {       // the tracker had no use for them: built here, on demand
-    lk_build(ctx->stream, A, A->img, A->W, (size_t)A->W * A->H, A->W, A->H, A->top, 0, 1, 1);
-    SVO_HIP(ctx, hipGetLastError());
-    A->dbg_next_der = true;
-  }
-  if (which == 1)
-    SVO_HIP(ctx, svo_memcpy_sync(ctx, host, A->der + frame * end.doff + L.doff, px * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  else
-    SVO_HIP(ctx, svo_memcpy_sync(ctx, host, level ? A->pyr + frame * end.ioff + L.ioff : A->img + frame * (size_t)A->W * A->H, px,
-                                 hipMemcpyDeviceToHost));
-  return SVO_OK;
+  return lk_debug(ctx, "svo_lk_debug_level", 1, which, frame, level, host, w, h, top);
+}
+extern "C" int svo_lk_debug_level_bgr(svo_ctx* ctx, int which, int frame, int level, void* host, int* w, int* h, int* top) {
+  return lk_debug(ctx, "svo_lk_debug_level_bgr", 3, which, frame, level, host, w, h, top);
 }
 
 void svo_lk_release(svo_ctx* ctx) {

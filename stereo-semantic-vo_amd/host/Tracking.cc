@@ -178,7 +178,11 @@ void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, co
   currentframe = new frame(ctx, imLeft, imRight, timestamp, K, detection_box);
   if (dynamic_lk) {                       // src/Tracking.cc:189-223: LK on the last list, erase by status, survivors -> DY_keypoints
     currentframe->dynamic_lk = true;      // (status and error live in the current frame here, in lastframe there)
-    if (currentframe->LKTrack(lastframe) < 0) throw std::runtime_error(std::string("svo_lk_track: ") + svo_last_error(ctx));
+    if (dynamic_lk_bgr) {
+      if (!colLeft) throw std::runtime_error("Tracking::dynamic_lk_bgr needs the colour Track()");
+      currentframe->leftimg_bgr = *colLeft;
+      if (currentframe->LKTrackBgr(lastframe) < 0) throw std::runtime_error(std::string("svo_lk_track_bgr: ") + svo_last_error(ctx));
+    } else if (currentframe->LKTrack(lastframe) < 0) throw std::runtime_error(std::string("svo_lk_track: ") + svo_last_error(ctx));
   }
   if (depth_source == 1) {                // src/Tracking.cc:225-228 literally: features, dense map, lookups
     currentframe->featuredetect(imLeft);
@@ -217,7 +221,7 @@ void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, co
   // The reference leaks every frame (`new frame`, never deleted).  Map points key their
   // observations by the frame's ADDRESS, so the object must stay allocated for addresses to
   // remain unique; its payload (images, keypoints, descriptors) is released instead.
-  prev->leftimg = GrayImage(); prev->rightimg = GrayImage();
+  prev->leftimg = GrayImage(); prev->rightimg = GrayImage(); prev->leftimg_bgr = BgrImage();
   std::vector<svo_kp>().swap(prev->keypoints_l);
   std::vector<uint8_t>().swap(prev->f_descriptor);
   std::vector<float>().swap(prev->keypoints_r);

@@ -20,6 +20,9 @@ class Tracking {
   // `boxes` - are collected where the commented lines have them: init() (src/Tracking.cc:70-85) and frame::createmappoint
   // while id <= 1 (src/frame.cc:209-222).  After Track() the frame's list is lastframe.DY_keypoints.  Track() only.
   bool dynamic_lk = false;
+  // With dynamic_lk: run that loop on the colour left images (frame::LKTrackBgr), as the reference's call would - its leftimg
+  // is the 8UC3 image.  Needs the colour Track(); the seeds and everything else are unchanged.
+  bool dynamic_lk_bgr = false;
   Tracking(const svo_camera& cam, int width, int height, int device = 0);
   ~Tracking();
   void init();                                                          // src/Tracking.cc:42-97

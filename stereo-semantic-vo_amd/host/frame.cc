@@ -22,7 +22,7 @@ frame::frame() { Tcw = eye4(); }
 
 frame::frame(frame* o)
     : ctx(o->ctx), N(o->N), timestamp(o->timestamp), id(o->id), leftimg(o->leftimg),
-      rightimg(o->rightimg), keypoints_l(o->keypoints_l), keypoints_r(o->keypoints_r),
+      rightimg(o->rightimg), leftimg_bgr(o->leftimg_bgr), keypoints_l(o->keypoints_l), keypoints_r(o->keypoints_r),
       kp_disp(o->kp_disp), kp_depth(o->kp_depth), f_descriptor(o->f_descriptor),
       MapPoints(o->MapPoints), match_score(o->match_score), inlier(o->inlier),
       offline_box(o->offline_box), DY_keypoints(o->DY_keypoints), dynamic_lk(o->dynamic_lk), width(o->width), height(o->height), fx(o->fx), fy(o->fy),
@@ -126,6 +126,28 @@ int frame::LKTrack(const frame& last) {
   svo_lk_default_params(&lp);
   if (svo_lk_track(ctx, last.leftimg.ptr(), leftimg.ptr(), leftimg.cols, leftimg.cols, leftimg.rows, &lp, &last.DY_keypoints[0].x, n,
                    &LK_keypoints[0].x, status.data(), error.data()) != SVO_OK)
+    return -1;
+  for (int i = 0; i < n; ++i)
+    if (status[i]) DY_keypoints.push_back(LK_keypoints[i]);
+  return (int)DY_keypoints.size();
+}
+
+// the same call on the reference's own input: `leftimg` there is the 8UC3 image (cn = 3)
+int frame::LKTrackBgr(const frame& last) {
+  const int n = (int)last.DY_keypoints.size();
+  LK_keypoints.assign(n, Point2f{0.f, 0.f});
+  status.assign(n, 0);
+  error.assign(n, 0.f);
+  DY_keypoints.clear();
+  if (n == 0) return 0;
+  const BgrImage &a = last.leftimg_bgr, &b = leftimg_bgr;
+  if (b.data.empty() || a.cols != b.cols || a.rows != b.rows || a.data.size() != b.data.size() ||
+      b.data.size() < (size_t)b.step() * b.rows)
+    return -1;                              // the two colour images must be there and of one size
+  svo_lk_params lp;
+  svo_lk_default_params(&lp);
+  if (svo_lk_track_bgr(ctx, a.ptr(), b.ptr(), b.step(), b.cols, b.rows, &lp, &last.DY_keypoints[0].x, n, &LK_keypoints[0].x,
+                       status.data(), error.data()) != SVO_OK)
     return -1;
   for (int i = 0; i < n; ++i)
     if (status[i]) DY_keypoints.push_back(LK_keypoints[i]);

@@ -13,6 +13,8 @@
 //   SGBMMatch          -> svo_sgbm_process         (src/frame.cc:94-120 as the reference has it: the body of its ElasMatch)
 //   LKTrack            -> svo_lk_track             (src/Tracking.cc:189-223, commented out there: calcOpticalFlowPyrLK on the
 //                         last frame's DY_keypoints, the status-0 points erased)
+//   LKTrackBgr         -> svo_lk_track_bgr         (the same call on the 8UC3 left images, which is what `leftimg` is in the
+//                         reference: the clone of main.cpp:160-161's colour image)
 #pragma once
 #include <set>
 #include <vector>
@@ -45,6 +47,8 @@ class frame {
   // and error hold calcOpticalFlowPyrLK's three outputs for all of them, DY_keypoints the survivors (status != 0) in order;
   // returns their number, or -1 when the call failed
   int LKTrack(const frame& last);
+  // the same on the colour left images (leftimg_bgr of both frames): calcOpticalFlowPyrLK with three channels
+  int LKTrackBgr(const frame& last);
   void disp2Depth(float bf);
   bool UnprojectStereo(float u, float v, float z, svo_host::Vec3f& x3D) const;
   void createmappoint(std::set<mappoint*, mappoint_by_creation>& localmap);
@@ -56,6 +60,7 @@ class frame {
   double timestamp = 0;
   long id = 0;
   svo_host::GrayImage leftimg, rightimg;
+  svo_host::BgrImage leftimg_bgr;         // the colour left image beside leftimg (Tracking::dynamic_lk_bgr only; else empty)
   std::vector<svo_kp> keypoints_l;        // cv::KeyPoint layout
   std::vector<float> keypoints_r;         // right-image x per keypoint (-1: none)
   std::vector<float> kp_disp, kp_depth;   // per-keypoint stand-ins for dispimg / depthimg

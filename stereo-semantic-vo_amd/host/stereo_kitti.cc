@@ -13,6 +13,7 @@
 // the same, MSA (depth_source 2) gets the colour.  Without it the files are reduced to gray on decode, as before.
 // --dynamic-lk [--write-dynamic <dir>] (frame by frame only): Tracking::dynamic_lk, the reference's LK loop over the keypoints
 // inside boxes (src/Tracking.cc:189-223); each frame's dynamic keypoints go to <dir>/NNNNNN.txt, one "x y" per line.
+// --dynamic-lk-bgr (implies --dynamic-lk; needs --colour): the same loop on the colour left images, svo_lk_track_bgr.
 // stereo_kitti --decode-bgr in.(png|ppm|pgm) out.ppm: codec self-test of the colour decode (the PPM holds RGB, as the format says).
 #include <algorithm>
 #include <chrono>
@@ -112,12 +113,13 @@ int main(int argc, char** argv) {
     }
   // --dynamic-lk: Tracking::dynamic_lk (the reference's LK loop over the points inside boxes); --write-dynamic <dir>: each
   // frame's dynamic keypoints to <dir>/NNNNNN.txt, one "x y" per line (%.9g: the floats read back exactly)
-  bool dynamic_lk = false;
+  bool dynamic_lk = false, dynamic_lk_bgr = false;
   std::string dynamic_dir;
   for (int i = 1; i < argc;) {
     const std::string a = argv[i];
     int take = 0;
     if (a == "--dynamic-lk") { dynamic_lk = true; take = 1; }
+    else if (a == "--dynamic-lk-bgr") { dynamic_lk = dynamic_lk_bgr = true; take = 1; }
     else if (a == "--write-dynamic" && i + 1 < argc) { dynamic_dir = argv[i + 1]; take = 2; }
     if (!take) { ++i; continue; }
     for (int j = i; j + take < argc; ++j) argv[j] = argv[j + take];
@@ -132,12 +134,13 @@ int main(int argc, char** argv) {
     argc = 4;
   }
   if (pipelined && (dynamic_lk || !dynamic_dir.empty())) {
-    std::cerr << "--dynamic-lk / --write-dynamic: frame by frame only (not with --pipelined)" << std::endl;
+    std::cerr << "--dynamic-lk / --dynamic-lk-bgr / --write-dynamic: frame by frame only (not with --pipelined)" << std::endl;
     return 1;
   }
+  if (dynamic_lk_bgr && !colour) { std::cerr << "--dynamic-lk-bgr needs --colour" << std::endl; return 1; }
   if (!dynamic_dir.empty() && !dynamic_lk) { std::cerr << "--write-dynamic needs --dynamic-lk" << std::endl; return 1; }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--dynamic-lk] [--write-dynamic dir] [--pipelined] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--dynamic-lk | --dynamic-lk-bgr] [--write-dynamic dir] [--pipelined] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -163,6 +166,7 @@ int main(int argc, char** argv) {
   Tracking* mpTracker = new Tracking(argv[2]);
   mpTracker->depth_source = depth_source;
   mpTracker->dynamic_lk = dynamic_lk;
+  mpTracker->dynamic_lk_bgr = dynamic_lk_bgr;
   std::ofstream f("cameratrajectory_kitti.txt"); f << std::fixed;
   std::ofstream f2("cameratrajectory_tum.txt"); f2 << std::fixed;
   std::vector<float> vTimesTrack(nImages);
