@@ -747,7 +747,7 @@ int svo_sgbm_debug_volume(svo_ctx* ctx, int which, int16_t* host);
  * arguments.  The algorithm is OpenCV 3.2's, restated as a written contract (DESIGN.md section 8 "LK": parity is unpinned in
  * the sense of SURVEY section 8(c), like ORB and SGBM): on 8-bit single-channel images (svo_lk_track, svo_lk_batch_dev,
  * svo_lk_chain_dev; the device equals the numpy restatement tests/lk_ref.py bit for bit) and on 8UC3 BGR images, which is what
- * the reference's call is made on (the _bgr entries, cn = 3; tests/lk_bgr_ref.py).  Points are (x, y) float pairs and must be
+ * the reference's call is made on (the _bgr entries, cn = 3; tests/lk_ref.py).  Points are (x, y) float pairs and must be
  * finite. */
 typedef struct svo_lk_params {
   int32_t winSize;            /* 21 (square) */

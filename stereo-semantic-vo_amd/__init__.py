@@ -632,79 +632,78 @@ class Svo:
         self._chk(self.lib.svo_sgbm_debug_volume(self.h, int(which), _p(out)))
         return out
 
-    # ---- sparse pyramidal Lucas-Kanade (include/svo.h: svo_lk_*; the dynamic-keypoint loop of Tracking::Track) ----
-    def lk_track(self, prev, nxt, pts, params=None):
-        """One gray pair and n points (n x 2 float32) -> (next_pts n x 2 float32, status n uint8, err n float32)."""
+    # ---- sparse pyramidal Lucas-Kanade (include/svo.h: svo_lk_*; the dynamic-keypoint loop of Tracking::Track), on gray frames
+    # and (svo_lk_*_bgr: calcOpticalFlowPyrLK with cn = 3, the reference's own input) on 8UC3 BGR frames ----
+    def _lk_track(self, entry, cn, prev, nxt, pts, params):
         a, b = _u8(prev), _u8(nxt)
-        H, W = a.shape
-        assert b.shape == (H, W)
+        H, W = a.shape if cn == 1 else a.shape[:2]
+        shape = (H, W) if cn == 1 else (H, W, cn)
+        assert a.shape == shape and b.shape == shape
         params = params or lk_default_params()
         p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
         n = len(p)
         out = np.zeros((n, 2), np.float32); st = np.zeros(n, np.uint8); err = np.zeros(n, np.float32)
-        self._chk(self.lib.svo_lk_track(self.h, _p(a), _p(b), W, W, H, C.byref(params), _p(p), n, _p(out), _p(st), _p(err)))
+        self._chk(entry(self.h, _p(a), _p(b), cn * W, W, H, C.byref(params), _p(p), n, _p(out), _p(st), _p(err)))
         return out, st, err
+
+    def _lk_batch(self, entry, d_frames, stride, W, H, B, d_pts, d_counts, max_pts, d_next, d_status, d_err, params):
+        params = params or lk_default_params()
+        self._chk(entry(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params), C.c_void_p(d_pts),
+                        C.c_void_p(d_counts), int(max_pts), C.c_void_p(d_next), C.c_void_p(d_status),
+                        C.c_void_p(d_err) if d_err else None))
+
+    def _lk_chain(self, entry, d_frames, stride, W, H, B, d_seeds, d_seed_counts, max_seeds, max_pts, d_lists, d_list_counts,
+                  d_dropped, params):
+        params = params or lk_default_params()
+        self._chk(entry(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params), C.c_void_p(d_seeds),
+                        C.c_void_p(d_seed_counts), int(max_seeds), int(max_pts), C.c_void_p(d_lists), C.c_void_p(d_list_counts),
+                        C.c_void_p(d_dropped)))
+
+    def _lk_debug(self, entry, cn, which, frame, level):
+        w, h, top = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(entry(self.h, int(which), int(frame), int(level), None, C.byref(w), C.byref(h), C.byref(top)))
+        out = np.zeros((h.value, w.value, 2 * cn), np.int16) if which else np.zeros((h.value, w.value) + (cn,) * (cn > 1), np.uint8)
+        self._chk(entry(self.h, int(which), int(frame), int(level), _p(out), None, None, None))
+        return out, top.value
+
+    def lk_track(self, prev, nxt, pts, params=None):
+        """One gray pair and n points (n x 2 float32) -> (next_pts n x 2 float32, status n uint8, err n float32)."""
+        return self._lk_track(self.lib.svo_lk_track, 1, prev, nxt, pts, params)
+
+    def lk_track_bgr(self, prev, nxt, pts, params=None):
+        """One (H, W, 3) BGR pair and n points -> (next_pts n x 2 float32, status n uint8, err n float32)."""
+        return self._lk_track(self.lib.svo_lk_track_bgr, 3, prev, nxt, pts, params)
 
     def lk_batch_dev(self, d_frames, stride, W, H, B, d_pts, d_counts, max_pts, d_next, d_status, d_err=None, params=None):
         """B device-resident frames, the B - 1 consecutive pairs, one point list per pair (device pointers throughout)."""
-        params = params or lk_default_params()
-        self._chk(self.lib.svo_lk_batch_dev(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params),
-                                            C.c_void_p(d_pts), C.c_void_p(d_counts), int(max_pts), C.c_void_p(d_next),
-                                            C.c_void_p(d_status), C.c_void_p(d_err) if d_err else None))
+        self._lk_batch(self.lib.svo_lk_batch_dev, d_frames, stride, W, H, B, d_pts, d_counts, max_pts, d_next, d_status, d_err, params)
+
+    def lk_batch_bgr_dev(self, d_frames, stride, W, H, B, d_pts, d_counts, max_pts, d_next, d_status, d_err=None, params=None):
+        """lk_batch_dev on B device-resident BGR frames, rows `stride` >= 3 W bytes apart."""
+        self._lk_batch(self.lib.svo_lk_batch_bgr_dev, d_frames, stride, W, H, B, d_pts, d_counts, max_pts, d_next, d_status, d_err,
+                       params)
 
     def lk_chain_dev(self, d_frames, stride, W, H, B, d_seeds, d_seed_counts, max_seeds, max_pts, d_lists, d_list_counts,
                      d_dropped, params=None):
         """The reference's track / erase / append loop over B device-resident frames (device pointers throughout)."""
-        params = params or lk_default_params()
-        self._chk(self.lib.svo_lk_chain_dev(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params),
-                                            C.c_void_p(d_seeds), C.c_void_p(d_seed_counts), int(max_seeds), int(max_pts),
-                                            C.c_void_p(d_lists), C.c_void_p(d_list_counts), C.c_void_p(d_dropped)))
-
-    def lk_debug_level(self, which, frame, level):
-        """Level `level` of frame 0 (prev) / 1 (next) of the last lk_track call: which 0 the image (h x w uint8), 1 the
-        derivatives (h x w x 2 int16: dx, dy).  Returns (array, effective top level)."""
-        w, h, top = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._chk(self.lib.svo_lk_debug_level(self.h, int(which), int(frame), int(level), None, C.byref(w), C.byref(h), C.byref(top)))
-        out = np.zeros((h.value, w.value, 2), np.int16) if which else np.zeros((h.value, w.value), np.uint8)
-        self._chk(self.lib.svo_lk_debug_level(self.h, int(which), int(frame), int(level), _p(out), None, None, None))
-        return out, top.value
-
-    # ---- the same on 8UC3 BGR frames (svo_lk_*_bgr: calcOpticalFlowPyrLK with cn = 3, the reference's own input) ----
-    def lk_track_bgr(self, prev, nxt, pts, params=None):
-        """One (H, W, 3) BGR pair and n points -> (next_pts n x 2 float32, status n uint8, err n float32)."""
-        a, b = _u8(prev), _u8(nxt)
-        H, W = a.shape[:2]
-        assert a.shape == (H, W, 3) and b.shape == (H, W, 3)
-        params = params or lk_default_params()
-        p = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
-        n = len(p)
-        out = np.zeros((n, 2), np.float32); st = np.zeros(n, np.uint8); err = np.zeros(n, np.float32)
-        self._chk(self.lib.svo_lk_track_bgr(self.h, _p(a), _p(b), 3 * W, W, H, C.byref(params), _p(p), n, _p(out), _p(st), _p(err)))
-        return out, st, err
-
-    def lk_batch_bgr_dev(self, d_frames, stride, W, H, B, d_pts, d_counts, max_pts, d_next, d_status, d_err=None, params=None):
-        """lk_batch_dev on B device-resident BGR frames, rows `stride` >= 3 W bytes apart."""
-        params = params or lk_default_params()
-        self._chk(self.lib.svo_lk_batch_bgr_dev(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params),
-                                                C.c_void_p(d_pts), C.c_void_p(d_counts), int(max_pts), C.c_void_p(d_next),
-                                                C.c_void_p(d_status), C.c_void_p(d_err) if d_err else None))
+        self._lk_chain(self.lib.svo_lk_chain_dev, d_frames, stride, W, H, B, d_seeds, d_seed_counts, max_seeds, max_pts, d_lists,
+                       d_list_counts, d_dropped, params)
 
     def lk_chain_bgr_dev(self, d_frames, stride, W, H, B, d_seeds, d_seed_counts, max_seeds, max_pts, d_lists, d_list_counts,
                          d_dropped, params=None):
         """lk_chain_dev on B device-resident BGR frames."""
-        params = params or lk_default_params()
-        self._chk(self.lib.svo_lk_chain_bgr_dev(self.h, C.c_void_p(d_frames), int(stride), int(W), int(H), int(B), C.byref(params),
-                                                C.c_void_p(d_seeds), C.c_void_p(d_seed_counts), int(max_seeds), int(max_pts),
-                                                C.c_void_p(d_lists), C.c_void_p(d_list_counts), C.c_void_p(d_dropped)))
+        self._lk_chain(self.lib.svo_lk_chain_bgr_dev, d_frames, stride, W, H, B, d_seeds, d_seed_counts, max_seeds, max_pts, d_lists,
+                       d_list_counts, d_dropped, params)
+
+    def lk_debug_level(self, which, frame, level):
+        """Level `level` of frame 0 (prev) / 1 (next) of the last lk_track call: which 0 the image (h x w uint8), 1 the
+        derivatives (h x w x 2 int16: dx, dy).  Returns (array, effective top level)."""
+        return self._lk_debug(self.lib.svo_lk_debug_level, 1, which, frame, level)
 
     def lk_debug_level_bgr(self, which, frame, level):
         """Level `level` of frame 0 (prev) / 1 (next) of the last lk_track_bgr call: which 0 the image (h x w x 3 uint8), 1 the
         derivatives (h x w x 6 int16: dx, dy of B, of G, of R).  Returns (array, effective top level)."""
-        w, h, top = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._chk(self.lib.svo_lk_debug_level_bgr(self.h, int(which), int(frame), int(level), None, C.byref(w), C.byref(h), C.byref(top)))
-        out = np.zeros((h.value, w.value, 6), np.int16) if which else np.zeros((h.value, w.value, 3), np.uint8)
-        self._chk(self.lib.svo_lk_debug_level_bgr(self.h, int(which), int(frame), int(level), _p(out), None, None, None))
-        return out, top.value
+        return self._lk_debug(self.lib.svo_lk_debug_level_bgr, 3, which, frame, level)
 
     def ctmf(self, img, r):
         """Median filter of Thirdparty/MB/ctmf.c on an H x W or H x W x C uint8 image."""

@@ -6,8 +6,8 @@
 //   k_lk_scharr    one level's (dx, dy) int16 pairs of every frame that is some pair's previous image, per channel
 //   k_lk_track     one wavefront per point, all levels in one launch: the 441 window pixels are 7 per lane, the I patch and both
 //                  derivative patches stay in registers over the iterations, the window sums are exact integers reduced on DPP,
-//                  the float tail is computed by every lane alike
-//   k_lk_track_bgr the same on three channels: a lane's 7 pixels are 21 samples, two I values to a register, the same sums
+//                  the float tail is computed by every lane alike.  One template on the channel count, two instantiations:
+//                  <1> keeps an I value per register, <3> holds a lane's 21 samples with two I values to a register
 //   k_lk_compact   order-preserving erase of the status-0 points, then a frame's seeds appended (svo_lk_chain_dev)
 // Compiled with -ffp-contract=off like the rest of the library: every float operation of the tail rounds once.
 #include <algorithm>
@@ -100,15 +100,23 @@ __device__ __forceinline__ LkW lk_weights(float a, float b) {
   return q;
 }
 
-// the four weighted taps of the image at (x, y), pixels outside the level read reflect-101 (x, y in [-21, size + 19])
-__device__ __forceinline__ int lk_tap_img(const uint8_t* __restrict__ img, int pitch, int w, int h, int x, int y, const LkW& q) {
-  const int x0 = lk_reflect(x, w), x1 = lk_reflect(x + 1, w);
+// the four weighted taps of the CN channels of pixel (x, y), pixels outside the level read reflect-101 (x, y in [-21, size + 19]):
+// one address per tap, the channels are its CN bytes
+template <int CN>
+__device__ __forceinline__ void lk_tap_img(const uint8_t* __restrict__ img, int pitch, int w, int h, int x, int y, const LkW& q,
+                                           int out[CN]) {
+  const int x0 = CN * lk_reflect(x, w), x1 = CN * lk_reflect(x + 1, w);
   const uint8_t *r0 = img + (size_t)lk_reflect(y, h) * pitch, *r1 = img + (size_t)lk_reflect(y + 1, h) * pitch;
-  return r0[x0] * q.w00 + r0[x1] * q.w01 + r1[x0] * q.w10 + r1[x1] * q.w11;
+#pragma unroll
+  for (int c = 0; c < CN; ++c) out[c] = r0[x0 + c] * q.w00 + r0[x1 + c] * q.w01 + r1[x0 + c] * q.w10 + r1[x1 + c] * q.w11;
 }
 
-__device__ __forceinline__ uint32_t lk_der_at(const uint32_t* __restrict__ der, int w, int h, int x, int y) {
-  return ((unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h) ? der[(size_t)y * w + x] : 0u;   // BORDER_CONSTANT 0
+template <int CN>
+__device__ __forceinline__ void lk_der_at(const uint32_t* __restrict__ der, int w, int h, int x, int y, uint32_t d[CN]) {
+  const bool in = (unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h;   // BORDER_CONSTANT 0
+  const uint32_t* e = der + ((size_t)y * w + x) * CN;
+#pragma unroll
+  for (int c = 0; c < CN; ++c) d[c] = in ? e[c] : 0u;
 }
 
 __device__ __forceinline__ bool lk_outside(int ix, int iy, int w, int h) { return ix < -LK_WIN || ix >= w || iy < -LK_WIN || iy >= h; }
@@ -119,14 +127,36 @@ __device__ __forceinline__ long long lk_wave_sum64(int v) {
 }
 __device__ __forceinline__ float lk_scaled(long long sum) { return (float)(double)sum * (1.f / 1048576.f); }   // one rounding, then 2^-20
 
-// Pairs (fprev0 + blockIdx.y, fprev0 + blockIdx.y + 1) of the resident frames; point list blockIdx.y at pts + blockIdx.y * 2 max_pts
-// with counts[blockIdx.y] entries (counts == nullptr: n_fixed); one wavefront per point.
+// A lane's I patch: sample s = CN k + c is channel c of its pixel k.  One channel: a value per register.  More: I is at most
+// 8160, so two values share a register, sample s in half-word s & 1 of v[s >> 1] (set() is called with s ascending).
+template <int CN>
+struct LkPatch {
+  uint32_t v[(7 * CN + 1) / 2];
+  __device__ __forceinline__ void set(int s, int val) { if (s & 1) v[s >> 1] |= (uint32_t)val << 16; else v[s >> 1] = (uint32_t)val; }
+  __device__ __forceinline__ int get(int s) const { return (int)((v[s >> 1] >> (16 * (s & 1))) & 0xffffu); }
+};
+template <>
+struct LkPatch<1> {
+  int v[7];
+  __device__ __forceinline__ void set(int s, int val) { v[s] = val; }
+  __device__ __forceinline__ int get(int s) const { return v[s]; }
+};
+
+// Pairs (fprev0 + blockIdx.y, fprev0 + blockIdx.y + 1) of the resident frames of CN interleaved channels; point list blockIdx.y
+// at pts + blockIdx.y * 2 max_pts with counts[blockIdx.y] entries (counts == nullptr: n_fixed); one wavefront per point, every
+// lane holds the CN channels of its 7 pixels (7 CN samples).  pyr_bytes and der_entries are a frame's slot sizes (all channels),
+// a level's offsets are CN times the one-channel ones.
+template <int CN>
 __global__ __launch_bounds__(256) void k_lk_track(const uint8_t* __restrict__ img0, int stride0, size_t frame0,
                                                   const uint8_t* __restrict__ pyr, size_t pyr_bytes, const uint32_t* __restrict__ der,
                                                   size_t der_entries, int w0, int h0, int top, int fprev0,
                                                   const float* __restrict__ pts, const int32_t* __restrict__ counts, int n_fixed,
                                                   int max_pts, float* __restrict__ next, uint8_t* __restrict__ status,
                                                   float* __restrict__ err) {
+  // I <= 8160 and |gx|, |gy| <= 4080 (16 * 255).  A lane's int32 partial sums of 7 CN products, and the wave's error sum:
+  static_assert(7LL * CN * 4080 * 4080 < (1LL << 31), "s11, s12, s22");                  // three channels: 21 * 4080^2
+  static_assert(7LL * CN * 8160 * 4080 < (1LL << 31), "s1, s2");                         // 21 * 8160 * 4080
+  static_assert((long long)LK_NPIX * CN * 8160 < (1LL << 24), "err: exact in an int32 and in a float");   // 1323 * 8160
   const int lane = threadIdx.x & 63;
   const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int n = min(counts ? counts[blockIdx.y] : n_fixed, max_pts);
@@ -144,15 +174,16 @@ __global__ __launch_bounds__(256) void k_lk_track(const uint8_t* __restrict__ im
   }
   const bool seventh = lane + 64 * 6 < LK_NPIX;
 
-  int Iv[7], gxy[7];                                        // the I patch and the packed (gx, gy) patch
+  LkPatch<CN> Iv;                                           // the I patch
+  int gxy[7 * CN];                                          // the packed (gx, gy) patch
   float ox = 0.f, oy = 0.f, e = 0.f;
   int st = 1;
   for (int level = top; level >= 0; --level) {
     const LkLevel L = lk_level(w0, h0, level);
-    const int pitch = level ? L.w : stride0;
-    const uint8_t* I = level ? pyr + fprev * pyr_bytes + L.ioff : img0 + fprev * frame0;
-    const uint8_t* J = level ? pyr + fnext * pyr_bytes + L.ioff : img0 + fnext * frame0;
-    const uint32_t* G = der + fprev * der_entries + L.doff;
+    const int pitch = level ? CN * L.w : stride0;
+    const uint8_t* I = level ? pyr + fprev * pyr_bytes + CN * L.ioff : img0 + fprev * frame0;
+    const uint8_t* J = level ? pyr + fnext * pyr_bytes + CN * L.ioff : img0 + fnext * frame0;
+    const uint32_t* G = der + fprev * der_entries + CN * L.doff;
     const float sc = 1.f / (float)(1 << level);
     float px = ptx * sc, py = pty * sc;
     if (level == top) { ox = px; oy = py; } else { ox = ox * 2.f; oy = oy * 2.f; }
@@ -164,138 +195,15 @@ __global__ __launch_bounds__(256) void k_lk_track(const uint8_t* __restrict__ im
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
       const int x = ipx + wx[k], y = ipy + wy[k];
-      Iv[k] = (lk_tap_img(I, pitch, L.w, L.h, x, y, q) + 256) >> 9;
-      const uint32_t d00 = lk_der_at(G, L.w, L.h, x, y), d01 = lk_der_at(G, L.w, L.h, x + 1, y);
-      const uint32_t d10 = lk_der_at(G, L.w, L.h, x, y + 1), d11 = lk_der_at(G, L.w, L.h, x + 1, y + 1);
-      int gx = (int16_t)d00 * q.w00 + (int16_t)d01 * q.w01 + (int16_t)d10 * q.w10 + (int16_t)d11 * q.w11;
-      int gy = ((int)d00 >> 16) * q.w00 + ((int)d01 >> 16) * q.w01 + ((int)d10 >> 16) * q.w10 + ((int)d11 >> 16) * q.w11;
-      gx = (gx + 8192) >> 14; gy = (gy + 8192) >> 14;
-      if (k == 6 && !seventh) gx = gy = 0;
-      gxy[k] = (int)((uint32_t)(gx & 0xffff) | ((uint32_t)gy << 16));
-      s11 += gx * gx; s12 += gx * gy; s22 += gy * gy;
-    }
-    const float A11 = lk_scaled(lk_wave_sum64(s11)), A12 = lk_scaled(lk_wave_sum64(s12)), A22 = lk_scaled(lk_wave_sum64(s22));
-    float D = A11 * A22 - A12 * A12;
-    const float t = A11 - A22;
-    const float min_eig = ((A22 + A11) - sqrtf(t * t + (4.f * A12) * A12)) / 882.f;
-    if ((double)min_eig < 1e-4 || D < 1.1920928955078125e-7f) { if (level == 0) st = 0; continue; }
-    D = 1.f / D;
-    float nx = ox - 10.f, ny = oy - 10.f, pdx = 0.f, pdy = 0.f;
-    for (int j = 0; j < LK_MAX_COUNT; ++j) {
-      const int inx = (int)floorf(nx), iny = (int)floorf(ny);
-      if (lk_outside(inx, iny, L.w, L.h)) { if (level == 0) st = 0; break; }
-      const LkW r = lk_weights(nx - (float)inx, ny - (float)iny);
-      int s1 = 0, s2 = 0;
+      int iv[CN];
+      lk_tap_img<CN>(I, pitch, L.w, L.h, x, y, q, iv);
+      uint32_t d00[CN], d01[CN], d10[CN], d11[CN];
+      lk_der_at<CN>(G, L.w, L.h, x, y, d00); lk_der_at<CN>(G, L.w, L.h, x + 1, y, d01);
+      lk_der_at<CN>(G, L.w, L.h, x, y + 1, d10); lk_der_at<CN>(G, L.w, L.h, x + 1, y + 1, d11);
 #pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        const int diff = ((lk_tap_img(J, pitch, L.w, L.h, inx + wx[k], iny + wy[k], r) + 256) >> 9) - Iv[k];
-        s1 += diff * (int16_t)gxy[k]; s2 += diff * (gxy[k] >> 16);
-      }
-      const float b1 = lk_scaled(lk_wave_sum64(s1)), b2 = lk_scaled(lk_wave_sum64(s2));
-      const float dx = (A12 * b2 - A22 * b1) * D, dy = (A12 * b1 - A11 * b2) * D;
-      nx += dx; ny += dy;
-      ox = nx + 10.f; oy = ny + 10.f;
-      if ((double)dx * dx + (double)dy * dy <= 1e-4) break;
-      if (j > 0 && (double)fabsf(dx + pdx) < 0.01 && (double)fabsf(dy + pdy) < 0.01) { ox -= dx * 0.5f; oy -= dy * 0.5f; break; }
-      pdx = dx; pdy = dy;
-    }
-    if (level == 0 && st) {
-      const float fx = ox - 10.f, fy = oy - 10.f;
-      const int ifx = (int)floorf(fx), ify = (int)floorf(fy);
-      if (lk_outside(ifx, ify, L.w, L.h)) st = 0;
-      else {
-        const LkW r = lk_weights(fx - (float)ifx, fy - (float)ify);
-        int s = 0;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) {
-          const int diff = ((lk_tap_img(J, pitch, L.w, L.h, ifx + wx[k], ify + wy[k], r) + 256) >> 9) - Iv[k];
-          s += (k == 6 && !seventh) ? 0 : abs(diff);
-        }
-        e = (float)wave_sum_i32_dpp(s) / 14112.f;           // at most 441 * 8160: exact in an int32 and in a float
-      }
-    }
-  }
-  if (lane == 0) {
-    next[2 * slot] = ox; next[2 * slot + 1] = oy;
-    status[slot] = (uint8_t)st;
-    if (err) err[slot] = e;
-  }
-}
-
-// ---- three channels (8UC3, interleaved): the window is 21 rows of 63 samples ---------------------------------------------------
-// the four weighted taps of the three channels of pixel (x, y): one address per tap, the channels are its three bytes
-__device__ __forceinline__ void lk_tap_img3(const uint8_t* __restrict__ img, int pitch, int w, int h, int x, int y, const LkW& q,
-                                            int out[3]) {
-  const int x0 = 3 * lk_reflect(x, w), x1 = 3 * lk_reflect(x + 1, w);
-  const uint8_t *r0 = img + (size_t)lk_reflect(y, h) * pitch, *r1 = img + (size_t)lk_reflect(y + 1, h) * pitch;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) out[c] = r0[x0 + c] * q.w00 + r0[x1 + c] * q.w01 + r1[x0 + c] * q.w10 + r1[x1 + c] * q.w11;
-}
-
-__device__ __forceinline__ void lk_der_at3(const uint32_t* __restrict__ der, int w, int h, int x, int y, uint32_t d[3]) {
-  const bool in = (unsigned)x < (unsigned)w && (unsigned)y < (unsigned)h;   // BORDER_CONSTANT 0
-  const uint32_t* e = der + ((size_t)y * w + x) * 3;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) d[c] = in ? e[c] : 0u;
-}
-
-// k_lk_track on 8UC3 frames: the same pixel-to-lane map, every lane holds its 7 pixels' three channels (21 samples).  I is at
-// most 8160, so two I values share a register; (gx, gy) are packed as in the gray kernel.  pyr_bytes and der_entries are a
-// frame's slot sizes (three channels), a level's offsets are three times the gray ones.
-__global__ __launch_bounds__(256) void k_lk_track_bgr(const uint8_t* __restrict__ img0, int stride0, size_t frame0,
-                                                      const uint8_t* __restrict__ pyr, size_t pyr_bytes,
-                                                      const uint32_t* __restrict__ der, size_t der_entries, int w0, int h0, int top,
-                                                      int fprev0, const float* __restrict__ pts, const int32_t* __restrict__ counts,
-                                                      int n_fixed, int max_pts, float* __restrict__ next,
-                                                      uint8_t* __restrict__ status, float* __restrict__ err) {
-  const int lane = threadIdx.x & 63;
-  const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int n = min(counts ? counts[blockIdx.y] : n_fixed, max_pts);
-  if (idx >= n) return;                                     // (whole wavefronts leave: the DPP sums below see all 64 lanes)
-  const size_t slot = (size_t)blockIdx.y * max_pts + idx;
-  const int fprev = fprev0 + blockIdx.y, fnext = fprev + 1;
-  const float ptx = pts[2 * slot], pty = pts[2 * slot + 1];
-
-  int wx[7], wy[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const int p = lane + 64 * k;
-    wy[k] = p < LK_NPIX ? p / LK_WIN : 0;                   // (lanes 57..63 have no seventh pixel: they redo pixel 0 with weight 0)
-    wx[k] = p < LK_NPIX ? p - wy[k] * LK_WIN : 0;
-  }
-  const bool seventh = lane + 64 * 6 < LK_NPIX;
-
-  uint32_t Ipk[11];                                         // the I patch, sample s = 3 k + c in half-word s & 1 of Ipk[s >> 1]
-  int gxy[21];                                              // the packed (gx, gy) patch
-  float ox = 0.f, oy = 0.f, e = 0.f;
-  int st = 1;
-  for (int level = top; level >= 0; --level) {
-    const LkLevel L = lk_level(w0, h0, level);
-    const int pitch = level ? 3 * L.w : stride0;
-    const uint8_t* I = level ? pyr + fprev * pyr_bytes + 3 * L.ioff : img0 + fprev * frame0;
-    const uint8_t* J = level ? pyr + fnext * pyr_bytes + 3 * L.ioff : img0 + fnext * frame0;
-    const uint32_t* G = der + fprev * der_entries + 3 * L.doff;
-    const float sc = 1.f / (float)(1 << level);
-    float px = ptx * sc, py = pty * sc;
-    if (level == top) { ox = px; oy = py; } else { ox = ox * 2.f; oy = oy * 2.f; }
-    px -= 10.f; py -= 10.f;
-    const int ipx = (int)floorf(px), ipy = (int)floorf(py);
-    if (lk_outside(ipx, ipy, L.w, L.h)) { if (level == 0) st = 0; continue; }
-    const LkW q = lk_weights(px - (float)ipx, py - (float)ipy);
-    int s11 = 0, s12 = 0, s22 = 0;                          // 21 products a lane: 21 * 4080^2 < 2^31
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      const int x = ipx + wx[k], y = ipy + wy[k];
-      int iv[3];
-      lk_tap_img3(I, pitch, L.w, L.h, x, y, q, iv);
-      uint32_t d00[3], d01[3], d10[3], d11[3];
-      lk_der_at3(G, L.w, L.h, x, y, d00); lk_der_at3(G, L.w, L.h, x + 1, y, d01);
-      lk_der_at3(G, L.w, L.h, x, y + 1, d10); lk_der_at3(G, L.w, L.h, x + 1, y + 1, d11);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int s = 3 * k + c;
-        const uint32_t v = (uint32_t)((iv[c] + 256) >> 9);
-        if (s & 1) Ipk[s >> 1] |= v << 16; else Ipk[s >> 1] = v;
+      for (int c = 0; c < CN; ++c) {
+        const int s = CN * k + c;
+        Iv.set(s, (iv[c] + 256) >> 9);
         int gx = (int16_t)d00[c] * q.w00 + (int16_t)d01[c] * q.w01 + (int16_t)d10[c] * q.w10 + (int16_t)d11[c] * q.w11;
         int gy = ((int)d00[c] >> 16) * q.w00 + ((int)d01[c] >> 16) * q.w01 + ((int)d10[c] >> 16) * q.w10 + ((int)d11[c] >> 16) * q.w11;
         gx = (gx + 8192) >> 14; gy = (gy + 8192) >> 14;
@@ -315,15 +223,15 @@ __global__ __launch_bounds__(256) void k_lk_track_bgr(const uint8_t* __restrict_
       const int inx = (int)floorf(nx), iny = (int)floorf(ny);
       if (lk_outside(inx, iny, L.w, L.h)) { if (level == 0) st = 0; break; }
       const LkW r = lk_weights(nx - (float)inx, ny - (float)iny);
-      int s1 = 0, s2 = 0;                                   // 21 * 8160 * 4080 < 2^31
+      int s1 = 0, s2 = 0;
 #pragma unroll
       for (int k = 0; k < 7; ++k) {
-        int jv[3];
-        lk_tap_img3(J, pitch, L.w, L.h, inx + wx[k], iny + wy[k], r, jv);
+        int jv[CN];
+        lk_tap_img<CN>(J, pitch, L.w, L.h, inx + wx[k], iny + wy[k], r, jv);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const int s = 3 * k + c;
-          const int diff = ((jv[c] + 256) >> 9) - (int)((Ipk[s >> 1] >> (16 * (s & 1))) & 0xffffu);
+        for (int c = 0; c < CN; ++c) {
+          const int s = CN * k + c;
+          const int diff = ((jv[c] + 256) >> 9) - Iv.get(s);
           s1 += diff * (int16_t)gxy[s]; s2 += diff * (gxy[s] >> 16);
         }
       }
@@ -344,16 +252,15 @@ __global__ __launch_bounds__(256) void k_lk_track_bgr(const uint8_t* __restrict_
         int s = 0;
 #pragma unroll
         for (int k = 0; k < 7; ++k) {
-          int jv[3];
-          lk_tap_img3(J, pitch, L.w, L.h, ifx + wx[k], ify + wy[k], r, jv);
+          int jv[CN];
+          lk_tap_img<CN>(J, pitch, L.w, L.h, ifx + wx[k], ify + wy[k], r, jv);
 #pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const int i = 3 * k + c;
-            const int diff = ((jv[c] + 256) >> 9) - (int)((Ipk[i >> 1] >> (16 * (i & 1))) & 0xffffu);
+          for (int c = 0; c < CN; ++c) {
+            const int diff = ((jv[c] + 256) >> 9) - Iv.get(CN * k + c);
             s += (k == 6 && !seventh) ? 0 : abs(diff);
           }
         }
-        e = (float)wave_sum_i32_dpp(s) / 42336.f;           // 32 * 21 * 3 * 21; at most 1323 * 8160 < 2^24: exact in an int32 and in a float
+        e = (float)wave_sum_i32_dpp(s) / (float)(32 * LK_NPIX * CN);   // 32 * 21 * cn * 21: 14112 or 42336
       }
     }
   }
@@ -512,7 +419,7 @@ void lk_launch_track(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int
                      uint8_t* status, float* err) {
   const LkLevel end = lk_level(W, H, top + 1);
   const int waves = counts ? max_pts : n_fixed;
-  hipLaunchKernelGGL(cn == 3 ? k_lk_track_bgr : k_lk_track, dim3((waves + 3) / 4, pairs), dim3(256), 0, s, img0, stride0, frame0,
+  hipLaunchKernelGGL(cn == 3 ? k_lk_track<3> : k_lk_track<1>, dim3((waves + 3) / 4, pairs), dim3(256), 0, s, img0, stride0, frame0,
                      A->pyr, cn * end.ioff, A->der, cn * end.doff, W, H, top, fprev0, pts, counts, n_fixed, max_pts, next, status,
                      err);
 }

@@ -111,47 +111,37 @@ int frame::SGBMMatch(const GrayImage& left, const GrayImage& right) {
 }
 
 // src/Tracking.cc:189-223 (commented out there): calcOpticalFlowPyrLK(last left, current left, last DY_keypoints, ...) with its
-// default arguments, then the erase loop over status
-int frame::LKTrack(const frame& last) {
+// default arguments, then the erase loop over status.  `prev` and `next` are the two left images' bytes, rows `stride` apart;
+// `entry` is svo_lk_track or svo_lk_track_bgr.
+static int lk_track_into(frame& cur, const frame& last, const std::vector<uint8_t>& prev, const std::vector<uint8_t>& next,
+                         bool same_dims, int stride, int cols, int rows, decltype(&svo_lk_track) entry) {
   const int n = (int)last.DY_keypoints.size();
-  LK_keypoints.assign(n, Point2f{0.f, 0.f});
-  status.assign(n, 0);
-  error.assign(n, 0.f);
-  DY_keypoints.clear();
+  cur.LK_keypoints.assign(n, Point2f{0.f, 0.f});
+  cur.status.assign(n, 0);
+  cur.error.assign(n, 0.f);
+  cur.DY_keypoints.clear();
   if (n == 0) return 0;
-  if (leftimg.data.empty() || last.leftimg.cols != leftimg.cols || last.leftimg.rows != leftimg.rows ||
-      last.leftimg.data.size() != leftimg.data.size() || leftimg.data.size() < (size_t)leftimg.cols * leftimg.rows)
+  if (next.empty() || !same_dims || prev.size() != next.size() || next.size() < (size_t)stride * rows)
     return -1;                              // the two images must be there and of one size
   svo_lk_params lp;
   svo_lk_default_params(&lp);
-  if (svo_lk_track(ctx, last.leftimg.ptr(), leftimg.ptr(), leftimg.cols, leftimg.cols, leftimg.rows, &lp, &last.DY_keypoints[0].x, n,
-                   &LK_keypoints[0].x, status.data(), error.data()) != SVO_OK)
+  if (entry(cur.ctx, prev.data(), next.data(), stride, cols, rows, &lp, &last.DY_keypoints[0].x, n, &cur.LK_keypoints[0].x,
+            cur.status.data(), cur.error.data()) != SVO_OK)
     return -1;
   for (int i = 0; i < n; ++i)
-    if (status[i]) DY_keypoints.push_back(LK_keypoints[i]);
-  return (int)DY_keypoints.size();
+    if (cur.status[i]) cur.DY_keypoints.push_back(cur.LK_keypoints[i]);
+  return (int)cur.DY_keypoints.size();
+}
+
+int frame::LKTrack(const frame& last) {
+  const GrayImage &a = last.leftimg, &b = leftimg;
+  return lk_track_into(*this, last, a.data, b.data, a.cols == b.cols && a.rows == b.rows, b.cols, b.cols, b.rows, svo_lk_track);
 }
 
 // the same call on the reference's own input: `leftimg` there is the 8UC3 image (cn = 3)
 int frame::LKTrackBgr(const frame& last) {
-  const int n = (int)last.DY_keypoints.size();
-  LK_keypoints.assign(n, Point2f{0.f, 0.f});
-  status.assign(n, 0);
-  error.assign(n, 0.f);
-  DY_keypoints.clear();
-  if (n == 0) return 0;
   const BgrImage &a = last.leftimg_bgr, &b = leftimg_bgr;
-  if (b.data.empty() || a.cols != b.cols || a.rows != b.rows || a.data.size() != b.data.size() ||
-      b.data.size() < (size_t)b.step() * b.rows)
-    return -1;                              // the two colour images must be there and of one size
-  svo_lk_params lp;
-  svo_lk_default_params(&lp);
-  if (svo_lk_track_bgr(ctx, a.ptr(), b.ptr(), b.step(), b.cols, b.rows, &lp, &last.DY_keypoints[0].x, n, &LK_keypoints[0].x,
-                       status.data(), error.data()) != SVO_OK)
-    return -1;
-  for (int i = 0; i < n; ++i)
-    if (status[i]) DY_keypoints.push_back(LK_keypoints[i]);
-  return (int)DY_keypoints.size();
+  return lk_track_into(*this, last, a.data, b.data, a.cols == b.cols && a.rows == b.rows, b.step(), b.cols, b.rows, svo_lk_track_bgr);
 }
 
 int frame::MBdense(const GrayImage& left, const GrayImage& right) {

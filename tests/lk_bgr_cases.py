@@ -1,7 +1,7 @@
 """Inputs of the colour Lucas-Kanade tests (tests/test_lk_bgr_cpu.py, tests/test_lk_bgr_gpu.py): 8UC3 images (H, W, 3), B, G, R
 interleaved.  Colour textures are three smooth canvases of tests/lk_cases.py with different seeds - uncorrelated channels -
 moved by one planted shift.  The positions of the oscillation, the 30-iteration and the gray-against-colour points were found
-by running the restatements (tests/lk_ref.py, tests/lk_bgr_ref.py) on the CPU over candidate points, then fixed here."""
+by running the restatement (tests/lk_ref.py) on the CPU over candidate points, then fixed here."""
 import struct
 import zlib
 

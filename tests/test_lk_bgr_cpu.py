@@ -1,5 +1,5 @@
 """CPU suite of the colour Lucas-Kanade work: the four _bgr entries are declared and bound and answer their arguments on the
-host; the colour restatement (tests/lk_bgr_ref.py) against the gray one on B = G = R input, on planted translations and on
+host; the colour restatement (tests/lk_ref.py) against the gray one on B = G = R input, on planted translations and on
 the isoluminant pair, which a gray tracker cannot follow at all."""
 import ctypes as C
 
@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 
 import lk_bgr_cases
-import lk_bgr_ref
 import lk_cases
 import lk_ref
 import test_abi
@@ -43,7 +42,7 @@ def replicated():
     """The gray planted pair of tests/test_lk_cpu.py and its B = G = R copy through both restatements."""
     prev, nxt = lk_cases.planted_pair(11, 200, 180, lk_cases.SHIFTS[2])
     pts = np.concatenate([lk_cases.inner_grid(200, 180, 40, 40), lk_cases.edge_points(200, 180, 6)]).astype(np.float32)
-    return prev, nxt, pts, lk_ref.track(prev, nxt, pts), lk_bgr_ref.track(lk_bgr_cases.replicate(prev), lk_bgr_cases.replicate(nxt), pts)
+    return prev, nxt, pts, lk_ref.track(prev, nxt, pts), lk_ref.track(lk_bgr_cases.replicate(prev), lk_bgr_cases.replicate(nxt), pts)
 
 
 def test_replicated_gray_every_level_and_plane_equals_the_gray_restatement(replicated):
@@ -89,7 +88,7 @@ def test_planted_translations_are_recovered_in_colour():
         prev, nxt = lk_bgr_cases.colour_pair((11, 12, 13), 200, 180, shift)
         pts = lk_cases.inner_grid(200, 180)
         assert len(pts) >= 40 and pts.min() >= 40 and np.all(pts[:, 0] <= 160) and np.all(pts[:, 1] <= 140)
-        r = lk_bgr_ref.track(prev, nxt, pts)
+        r = lk_ref.track(prev, nxt, pts)
         assert r["top"] == 3 and np.all(r["status"] == 1)
         e = float(np.abs(r["next_pts"] - pts - np.float32(shift)).max())
         print("shift %s: largest error %.4f px" % (shift, e))
@@ -111,7 +110,7 @@ def test_the_isoluminant_pair_is_invisible_in_gray_and_tracked_in_colour():
     assert len(pts) >= 40
     g = lk_ref.track(lk_bgr_cases.gray_of(prev), lk_bgr_cases.gray_of(nxt), pts)
     assert not g["status"].any() and (g["exits"][:, 0] == lk_ref.EXIT_MIN_EIG).all()
-    c = lk_bgr_ref.track(prev, nxt, pts)
+    c = lk_ref.track(prev, nxt, pts)
     assert np.all(c["status"] == 1)
     e = float(np.abs(c["next_pts"] - pts - np.float32(lk_bgr_cases.ISO_SHIFT)).max())
     print("isoluminant pair: largest error %.4f px" % e)
@@ -122,14 +121,14 @@ def test_the_colour_cases_reach_every_exit():
     prev, nxt = lk_bgr_cases.exits_pair()
     pts = lk_bgr_cases.exits_points()
     assert pts.shape == (lk_bgr_cases.EXITS_N, 2) and pts.dtype == np.float32
-    r = lk_bgr_ref.track(prev, nxt, pts)
+    r = lk_ref.track(prev, nxt, pts)
     for code in range(1, 7):
         assert (r["exits"] == code).any(), code
     assert r["exits"][:3, 0].tolist() == [lk_ref.EXIT_RANGE_PREV, lk_ref.EXIT_MIN_EIG, lk_ref.EXIT_RANGE_NEXT]
     assert r["iterations"][2, 0] >= 1 and not r["status"][:3].any() and 0 < r["status"].sum() < len(pts)
-    r = lk_bgr_ref.track(*lk_bgr_cases.low_contrast_pair(), [lk_bgr_cases.OSCILLATION_POINT])
+    r = lk_ref.track(*lk_bgr_cases.low_contrast_pair(), [lk_bgr_cases.OSCILLATION_POINT])
     assert r["exits"][0, 0] == lk_ref.EXIT_OSCILLATION and r["status"][0] == 1 and 2 <= r["iterations"][0, 0] < 30
-    r = lk_bgr_ref.track(*lk_bgr_cases.wander_pair(), [lk_bgr_cases.MAX_COUNT_POINT])
+    r = lk_ref.track(*lk_bgr_cases.wander_pair(), [lk_bgr_cases.MAX_COUNT_POINT])
     assert r["top"] == 0 and r["exits"][0, 0] == lk_ref.EXIT_MAX_COUNT and r["iterations"][0, 0] == 30 and r["status"][0] == 1
 
 
@@ -138,7 +137,7 @@ def test_one_point_two_statuses():
     point fails the minimum-eigenvalue test as gray and passes it as colour."""
     prev, nxt = lk_bgr_cases.faint_pair()
     g = lk_ref.track(prev, nxt, [lk_bgr_cases.SPLIT_POINT])
-    c = lk_bgr_ref.track(lk_bgr_cases.replicate(prev), lk_bgr_cases.replicate(nxt), [lk_bgr_cases.SPLIT_POINT])
+    c = lk_ref.track(lk_bgr_cases.replicate(prev), lk_bgr_cases.replicate(nxt), [lk_bgr_cases.SPLIT_POINT])
     assert g["status"][0] == 0 and g["exits"][0, 0] == lk_ref.EXIT_MIN_EIG and g["err"][0] == 0
     assert c["status"][0] == 1 and c["exits"][0, 0] in (lk_ref.EXIT_EPSILON, lk_ref.EXIT_OSCILLATION, lk_ref.EXIT_MAX_COUNT)
 

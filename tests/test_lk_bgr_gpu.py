@@ -1,4 +1,4 @@
-"""GPU suite of the colour Lucas-Kanade entries (svo_lk_*_bgr): the device against the numpy restatement tests/lk_bgr_ref.py, bit
+"""GPU suite of the colour Lucas-Kanade entries (svo_lk_*_bgr): the device against the numpy restatement tests/lk_ref.py, bit
 for bit - every pyramid and derivative level through svo_lk_debug_level_bgr, then next points, status and err; a point whose
 status differs between gray and colour; the batch and the chain entries against single calls; gray and colour calls
 alternating on one context; the host class seams frame::LKTrackBgr (host/lk_check --bgr) and Tracking::dynamic_lk_bgr
@@ -12,7 +12,6 @@ import numpy as np
 import pytest
 
 import lk_bgr_cases
-import lk_bgr_ref
 import lk_cases
 import lk_ref
 
@@ -68,8 +67,8 @@ STAGE_TOP = {"185x177": 3, "120x50": 1, "1241x48": 1, "83x37": 0}
 def test_every_level_equals_the_restatement(pkg, svo, name):
     prev, nxt = _stage_case(name)
     H, W = prev.shape[:2]
-    levels_p, derivs_p = lk_bgr_ref.build_pyramid(prev)
-    levels_n, derivs_n = lk_bgr_ref.build_pyramid(nxt)
+    levels_p, derivs_p = lk_ref.build_pyramid(prev)
+    levels_n, derivs_n = lk_ref.build_pyramid(nxt)
     top = len(levels_p) - 1
     assert top == STAGE_TOP[name.split("_")[1]]
     _track_padded(pkg, svo, prev, nxt, np.float32([[W / 2, H / 2]]), 13)      # rows 3 W + 13 bytes apart
@@ -116,7 +115,7 @@ def _ref(name):
     """The restatement of a result case, computed once per session and never modified."""
     if name not in _refs:
         prev, nxt, pts = _result_case(name)
-        _refs[name] = (prev, nxt, pts, lk_bgr_ref.track(prev, nxt, pts))
+        _refs[name] = (prev, nxt, pts, lk_ref.track(prev, nxt, pts))
     return _refs[name]
 
 
@@ -164,7 +163,7 @@ def test_one_point_fails_as_gray_and_is_tracked_as_colour(svo):
     prev, nxt = lk_bgr_cases.faint_pair()
     pts = np.concatenate([[lk_bgr_cases.SPLIT_POINT], lk_cases.inner_grid(64, 64, 12, 8)]).astype(np.float32)
     g_ref = lk_ref.track(prev, nxt, pts)
-    c_ref = lk_bgr_ref.track(lk_bgr_cases.replicate(prev), lk_bgr_cases.replicate(nxt), pts)
+    c_ref = lk_ref.track(lk_bgr_cases.replicate(prev), lk_bgr_cases.replicate(nxt), pts)
     assert g_ref["status"][0] == 0 and g_ref["exits"][0, 0] == lk_ref.EXIT_MIN_EIG and c_ref["status"][0] == 1
     g = svo.lk_track(prev, nxt, pts)
     c = svo.lk_track_bgr(lk_bgr_cases.replicate(prev), lk_bgr_cases.replicate(nxt), pts)
@@ -178,11 +177,11 @@ def test_max_level_is_honoured(pkg, svo):
     prev, nxt, pts, _ = _ref("planted120x50")
     p = pkg.lk_default_params()
     p.maxLevel = 0
-    ref = lk_bgr_ref.track(prev, nxt, pts[:16], max_level=0)
+    ref = lk_ref.track(prev, nxt, pts[:16], max_level=0)
     got = svo.lk_track_bgr(prev, nxt, pts[:16], p)
     assert svo.lk_debug_level_bgr(0, 0, 0)[1] == 0
     _assert_equals_ref(got, ref)
-    full = lk_bgr_ref.track(prev, nxt, pts[:16])
+    full = lk_ref.track(prev, nxt, pts[:16])
     assert not _same_bits(full["next_pts"], ref["next_pts"]), "the case must tell one level from two"
 
 
