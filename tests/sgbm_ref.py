@@ -181,7 +181,7 @@ def speckles(disp, max_size=SPECKLE_WIN, max_diff=16 * SPECKLE_RANGE):
 
 
 def sgbm(L, R, D=None):
-    """Every stage of one pair: dict with C, S4, S (H x W x D int16), sum4 (the unsaturated int32 sum behind S4), disp2, disp1_raw, disp1_lr, disp16 (int16), disp (float32)."""
+    """Every stage of one pair: dict with C, S4, S (H x W x D int16), sum4 and sum5 (the unsaturated int32 sums behind S4 and S: L0 + .. + L3, and S4 + L4), disp2, disp1_raw, disp1_lr, disp16 (int16), disp (float32)."""
     L = np.ascontiguousarray(L, np.uint8); R = np.ascontiguousarray(R, np.uint8)
     H, W = L.shape
     D = default_D(H) if D is None else D
@@ -189,11 +189,12 @@ def sgbm(L, R, D=None):
     C = block_cost(L, R, D)
     Ls = [path_cost(C, D, k) for k in range(5)]
     S4 = sat16(Ls[0] + Ls[1] + Ls[2] + Ls[3])
-    S = sat16(S4 + Ls[4])
+    sum5 = S4 + Ls[4]
+    S = sat16(sum5)
     S4[:, :D] = 0; S[:, :D] = 0
     raw, disp2 = winner(S, D)
     lr = lr_check(raw, disp2)
     fin = speckles(lr)
-    return dict(D=D, sum4=Ls[0] + Ls[1] + Ls[2] + Ls[3], C=C.astype(np.int16), S4=S4.astype(np.int16), S=S.astype(np.int16), disp2=disp2.astype(np.int16),
+    return dict(D=D, sum4=Ls[0] + Ls[1] + Ls[2] + Ls[3], sum5=sum5, C=C.astype(np.int16), S4=S4.astype(np.int16), S=S.astype(np.int16), disp2=disp2.astype(np.int16),
                 disp1_raw=raw.astype(np.int16), disp1_lr=lr.astype(np.int16), disp16=fin.astype(np.int16),
                 disp=(fin.astype(np.float32) / np.float32(16.0)))

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import sgbm_cases
 import sgbm_ref
 import test_abi
 
@@ -128,3 +129,93 @@ def test_restatement_speckle_sizes():
     assert np.all(out[2:11, 2:13] == -16) and np.all(out[2:12, 20:30] == -16)
     assert np.all(out[15, 2:52] == 2000) and np.all(out[16, 2:53] == 2000)
     assert (out == 160).sum() == d.size - 300
+
+
+# ---- what the device's stage cases exercise ----------------------------------------------------------------------------------
+def _census_case(out, **planted):
+    """census() on a hand-made S volume (x < D empty); disp1_raw comes from the restatement's own winner loop."""
+    raw, disp2 = sgbm_ref.winner(out["S"].astype(np.int32), out["D"])
+    full = dict(out, disp1_raw=raw, disp1_lr=planted.get("disp1_lr", raw), sum4=out["S"].astype(np.int32), sum5=out["S"].astype(np.int32))
+    return sgbm_cases.census(full), disp2
+
+
+def test_census_counts_planted_rules():
+    """One row, D = 16, W = 40, S = 1000 everywhere but for planted minima.  Pixels 30 (best 5) and 27 (best 2) both bid 77 for
+    column 25: one tie, and the larger x keeps the column.  Pixel 20 wins at d = 15, pixel 22 at d = 0; pixel 35 has the
+    numerator (10 - 14) * 16 + 24 = -40, no multiple of 48; pixel 33 has a rival at d = 9 within 10 % and is rejected, as
+    is every untouched pixel."""
+    D, W = 16, 40
+    S = np.full((1, W, D), 1000, np.int16)
+    S[0, :D] = 0
+    S[0, 30, 5] = 77; S[0, 27, 2] = 77
+    S[0, 20, 15] = 500; S[0, 22, 0] = 500
+    S[0, 35, 4:7] = (510, 500, 514)
+    S[0, 33, 3] = 600; S[0, 33, 9] = 660
+    c, disp2 = _census_case(dict(D=D, S=S))
+    assert disp2[0, 25] == 5, "the restatement keeps the bid of the largest x"
+    assert c["bid_ties"] == 1 and c["best_first"] == 1 and c["best_last"] == 1 and c["negative_numerator_with_remainder"] == 1
+    flat = (W - D) - 6                       # the untouched pixels: all S equal and positive, 1000 * 90 < 1000 * 100 rejects them
+    assert c["uniqueness_rejections"] == flat + 1
+    assert c["left_right_invalidated"] == 0 and c["sum4_saturated"] == 0 and c["sum5_saturated"] == 0
+    S[0, 27, 2] = 78                         # no tie any more: the lower bid wins whatever the order
+    c, disp2 = _census_case(dict(D=D, S=S))
+    assert c["bid_ties"] == 0 and disp2[0, 25] == 5
+
+
+def test_every_written_rule_is_live_in_the_union_of_the_stage_cases():
+    """The device is compared with the restatement on sgbm_cases.STAGE_CASES.  A rule that never decides anything there is a
+    rule the device could have wrong unnoticed, so each count of the census must be at least 1 over the union of the cases, and
+    tied right-image bids at least 8: one lucky ordering of the device's atomics must not be enough."""
+    total = dict.fromkeys(sgbm_cases.CENSUS_KEYS, 0)
+    for name in sgbm_cases.STAGE_CASES:
+        c = sgbm_cases.census(sgbm_cases.ref(name)[3])
+        assert tuple(c) == sgbm_cases.CENSUS_KEYS
+        print("%-20s valid %.2f / %.2f  %s" % ((name,) + sgbm_cases.valid_fractions(sgbm_cases.ref(name)[3]) + (list(c.values()),)))
+        for k, v in c.items():
+            total[k] += v
+    print("union", total)
+    for k, v in total.items():
+        assert v >= (8 if k == "bid_ties" else 1), (k, v)
+    tie_total = sum(sgbm_cases.census(sgbm_cases.ref(n)[3])["bid_ties"] for n in sgbm_cases.TIE_CASES)
+    assert tie_total >= 8, "the pairs the search found carry the ties"
+
+
+def test_two_guards_of_the_contract_can_never_fire():
+    """The denominator clamp and the left-right probe's x - a < 0 (see sgbm_cases.census for why): 0 on every stage case."""
+    for name in sgbm_cases.STAGE_CASES:
+        assert sgbm_cases.impossible(sgbm_cases.ref(name)[3]) == dict(denominator_clamped=0, probe_left_of_image=0), name
+
+
+def test_stage_cases_are_the_shapes_they_claim():
+    for name in sgbm_cases.PORTRAIT_CASES:
+        L, _, D = sgbm_cases.case(name)
+        assert L.shape[0] > L.shape[1] - D, name
+    assert sgbm_cases.case("tall30x300d16")[0].shape == (300, 30)
+    assert sgbm_cases.case("portrait75x100d48")[2] == 48
+    assert sgbm_cases.case("wide3072x2d16")[0].shape == (2, 3072)
+    for name in sgbm_cases.MINIMAL_CASES:
+        L, _, D = sgbm_cases.case(name)
+        out = sgbm_cases.ref(name)[3]
+        assert L.shape == (2, D + 9)
+        assert (out["disp1_lr"] != -16).any() and np.all(out["disp16"] == -16)
+    for name in sgbm_cases.STAGE_CASES:
+        if name not in sgbm_cases.MINIMAL_CASES:
+            assert sgbm_cases.valid_fractions(sgbm_cases.ref(name)[3])[1] > 0.2, name
+
+
+def test_speckle_maps_are_what_the_device_tests_need():
+    d = sgbm_cases.serpentine()
+    assert d.shape == (64, 600) and (d != -16).sum() == 19232
+    assert np.array_equal(sgbm_ref.speckles(d.astype(np.int32)), d), "one component, far above 100 pixels"
+    cut = d.copy(); cut[31, :] = -16         # (row 31 holds the one pixel that joins the upper and the lower half)
+    assert (sgbm_ref.speckles(cut.astype(np.int32)) != -16).sum() == 19231
+    d, go, stay = sgbm_cases.comb()
+    out = sgbm_ref.speckles(d.astype(np.int32))
+    assert all(d[s].size == 100 and np.all(d[s] != -16) and np.all(out[s] == -16) for s in go)
+    assert all(d[s].size == 101 and np.array_equal(out[s], d[s]) for s in stay)
+    assert any(s[1].start <= 255 and s[1].stop > 256 for s in go + stay) and any(s[1].start <= 511 and s[1].stop > 512 for s in go + stay)
+    d = sgbm_cases.seeded_speckle_map()
+    assert d.shape == (129, 333) and 0.08 < (d == -16).mean() < 0.12 and np.all(d[d != -16] % 171 == 0)
+    both = (d[:, 1:] != -16) & (d[:, :-1] != -16)
+    dif = np.abs(np.diff(d.astype(np.int32), axis=1))[both]
+    assert (dif == 342).sum() > 100 and (dif == 513).sum() > 100

@@ -1,6 +1,9 @@
 """GPU suite of the semi-global block matcher (svo_sgbm_*): the device against the numpy restatement tests/sgbm_ref.py, bit
-for bit, stage by stage through svo_sgbm_debug_volume and then the final maps; the batch entry; the speckle filter on planted
-components; depth_source = 3 in the tracker's entries; the host class seam frame::SGBMMatch."""
+for bit, stage by stage through svo_sgbm_debug_volume and then the final maps (the cases are tests/sgbm_cases.py's: landscape,
+portrait, the smallest and the widest legal sizes, pairs with tied right-image bids); strided input; the arena across calls of
+different sizes; the batch entry; the speckle filter on planted components and on maps wider than one block row;
+depth_source = 3 in the tracker's entries; the host class seam frame::SGBMMatch."""
+import ctypes as C
 import importlib
 import os
 import subprocess
@@ -8,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import sgbm_cases
 import sgbm_ref
 import util
 
@@ -15,52 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STAGES = ("C", "S4", "S", "disp2", "disp1_lr")   # svo_sgbm_debug_volume's `which` 0 .. 4
 
 
-def _noise_pair(seed, W, H):
-    rng = np.random.default_rng(seed)
-    L = rng.integers(0, 256, (H, W), dtype=np.uint8)
-    R = np.roll(L, -5, axis=1)
-    R[::3] = rng.integers(0, 256, R[::3].shape, dtype=np.uint8)     # two rows in three carry a true match, the others none
-    return L, R
-
-
-def _saturating_pair(W=120, H=30):
-    """No iid-noise pair of seeds 0..63 at 120 x 30 saturates S4 (the largest four-direction sum seen there is about 21 000;
-    checked with the restatement), and two constant images with an offset cannot either: their gradient planes are equal, so the
-    pixel cost stops at 255 >> 2 and C at 81 * 63 = 5103.  C > 8191 needs the gradient term: saw-tooth ramps of opposite slope
-    (prefiltered gradients 0 against 126 nearly everywhere) under a little noise."""
-    x = np.arange(W)
-    rng = np.random.default_rng(7)
-    L = np.tile(255 - 10 * (x % 24), (H, 1)) - rng.integers(0, 8, (H, W))
-    R = np.tile(10 * (x % 24), (H, 1)) + rng.integers(0, 8, (H, W))
-    return np.clip(L, 0, 255).astype(np.uint8), np.clip(R, 0, 255).astype(np.uint8)
-
-
-def _case(name):
-    if name == "noise83x37":          # odd width and height, every border rule live
-        return _noise_pair(1, 83, 37) + (16,)
-    if name == "urban200x26":         # real texture
-        return util.urban_pair(200, 26, 400, 80) + (48,)
-    if name == "rows1241x12":         # full-width rows, diagonals that enter from both side columns
-        return util.shifted_pair(9, 1241, 12, disparity=17) + (48,)
-    if name == "saturated120x30":
-        return _saturating_pair() + (16,)
-    if name == "noise150x20d64":      # the widest disparity range, all 64 lanes of a group in use
-        return _noise_pair(4, 150, 20) + (64,)
-    if name == "noise120x30d32":
-        return _noise_pair(2, 120, 30) + (32,)
-    raise KeyError(name)
-
-
-CASES = ("noise83x37", "urban200x26", "rows1241x12", "saturated120x30", "noise150x20d64", "noise120x30d32")
-_refs = {}
-
-
-def _ref(name):
-    """The restatement of a case, computed once per session and never modified."""
-    if name not in _refs:
-        L, R, D = _case(name)
-        _refs[name] = (L, R, D, sgbm_ref.sgbm(L, R, D))
-    return _refs[name]
+CASES = sgbm_cases.OLD_CASES
+_ref = sgbm_cases.ref        # (L, R, D, restatement) of a case, computed once per session and never modified
 
 
 @pytest.fixture(scope="module")
@@ -76,23 +36,112 @@ def _params(pkg, H, D):
     return p
 
 
+def _assert_stages(stages, maps, ref, name):
+    """Every stage and both final maps against the restatement (or against another call's), bit for bit."""
+    D = ref["D"]
+    for key, got in zip(STAGES, stages):
+        bad = np.argwhere(got != ref[key])
+        assert len(bad) == 0, "%s: stage %s differs at %d places, first (y, x[, d]) %s" % (name, key, len(bad), bad[:4].tolist())
+    d16, d = maps
+    assert np.array_equal(d16, ref["disp16"])
+    assert d.dtype == np.float32 and np.array_equal(d.view(np.uint32), ref["disp"].view(np.uint32))
+    assert np.all(d[d16 == -16] == -1.0) and np.all(d16[:, :D] == -16)
+
+
+def _run(pkg, svo, L, R, D):
+    """svo_sgbm_process and its five debug stages."""
+    maps = svo.sgbm_process(L, R, _params(pkg, L.shape[0], D))
+    return [svo.sgbm_debug_volume(which) for which in range(len(STAGES))], maps
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", CASES)
 def test_every_stage_equals_the_restatement(pkg, svo, name):
     L, R, D, ref = _ref(name)
-    H, W = L.shape
     if name == "saturated120x30":
         assert (ref["sum4"][:, D:] > 32767).any(), "the restatement alone must show a saturated S4 entry"
         assert (ref["S4"] == 32767).any()
-    d16, d = svo.sgbm_process(L, R, _params(pkg, H, D))
-    for which, key in enumerate(STAGES):
-        got = svo.sgbm_debug_volume(which)
-        bad = np.argwhere(got != ref[key])
-        assert len(bad) == 0, "%s: stage %s differs at %d places, first (y, x[, d]) %s" % (name, key, len(bad), bad[:4].tolist())
-    assert np.array_equal(d16, ref["disp16"])
-    assert d.dtype == np.float32 and np.array_equal(d.view(np.uint32), ref["disp"].view(np.uint32))
-    assert np.all(d[d16 == -16] == -1.0) and np.all(d16[:, :D] == -16)
+    stages, (d16, d) = _run(pkg, svo, L, R, D)
+    _assert_stages(stages, (d16, d), ref, name)
     assert (d16 != -16).mean() > 0.2       # not an all-invalid map
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sgbm_cases.NEW_CASES)
+def test_every_stage_equals_the_restatement_at_the_shapes_and_ties_beyond_landscape(pkg, svo, name):
+    """H > W - D (whole lane groups without a direction-2 path, diagonals clipped by the width), the smallest and the widest
+    legal images, and the pairs whose right-image columns receive equal bids (sgbm_cases.census counts them)."""
+    L, R, D, ref = _ref(name)
+    stages, (d16, d) = _run(pkg, svo, L, R, D)
+    _assert_stages(stages, (d16, d), ref, name)
+    if name in sgbm_cases.MINIMAL_CASES:   # 9 columns x 2 rows of disparities: at most 18 <= 100 pixels, all of them speckles
+        assert (ref["disp1_lr"] != -16).mean() > 0 and (stages[4] != -16).any()
+        assert np.all(d16 == -16) and np.all(d == -1.0)
+    else:
+        assert (d16 != -16).mean() > 0.2
+
+
+def _process_strided(pkg, svo, L, R, D, stride, fill=0xA5):
+    """svo_sgbm_process on rows `stride` bytes apart (the wrapper passes stride = W only), the padding filled with `fill`."""
+    H, W = L.shape
+    bufs = []
+    for img in (L, R):
+        b = np.full((H, stride), fill, np.uint8)
+        b[:, :W] = img
+        bufs.append(b)
+    d16 = np.full((H, W), 77, np.int16); d = np.full((H, W), 77, np.float32)
+    p = _params(pkg, H, D)
+    rc = svo.lib.svo_sgbm_process(svo.h, bufs[0].ctypes.data_as(C.c_void_p), bufs[1].ctypes.data_as(C.c_void_p), stride, W, H,
+                                  C.byref(p), d16.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p))
+    assert rc == 0, svo.lib.svo_last_error(svo.h)
+    stages = []
+    for which in range(len(STAGES)):
+        out = np.zeros((H, W, D) if which < 3 else (H, W), np.int16)
+        assert svo.lib.svo_sgbm_debug_volume(svo.h, which, out.ctypes.data_as(C.c_void_p)) == 0
+        stages.append(out)
+    return stages, (d16, d)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["noise83x37", "portrait41x90d16"])
+def test_strided_rows_give_the_contiguous_calls_bytes(pkg, svo, name):
+    """stride = W + 13 (odd, so that no row but the first is aligned), the 13 bytes between the rows 0xA5: a kernel or a copy
+    that read them would change the cost of the border columns."""
+    L, R, D, ref = _ref(name)
+    W = L.shape[1]
+    want_stages, want_maps = _run(pkg, svo, L, R, D)
+    svo.sgbm_process(R, L, _params(pkg, L.shape[0], D))       # something else in the arena in between
+    stages, maps = _process_strided(pkg, svo, L, R, D, W + 13)
+    for key, a, b in zip(STAGES, stages, want_stages):
+        assert a.tobytes() == b.tobytes(), (name, key)
+    assert maps[0].tobytes() == want_maps[0].tobytes() and maps[1].tobytes() == want_maps[1].tobytes()
+    _assert_stages(stages, maps, ref, name)
+
+
+def _debug_rc(svo, which=0):
+    sink = np.zeros(1 << 20, np.int16)       # larger than any volume of these tests, should the call answer after all
+    return svo.lib.svo_sgbm_debug_volume(svo.h, which, sink.ctypes.data_as(C.c_void_p))
+
+
+@pytest.mark.gpu
+def test_one_arena_serves_calls_of_different_sizes_in_turn(pkg):
+    """The arena is sized by the first, largest call; the smaller ones then run in buffers whose capacity is not their volume.
+    Nothing of a smaller call may remain in the larger one's result, and the smaller ones are right themselves."""
+    ctx = pkg.Svo(640, 240, max_batch=1)
+    try:
+        L, R, D, ref = _ref("urban200x26")
+        first = _run(pkg, ctx, L, R, D)
+        _assert_stages(first[0], first[1], ref, "urban200x26")
+        for name in ("minimal25x2d16", "portrait57x75d32"):
+            l, r, dd, want = _ref(name)
+            stages, maps = _run(pkg, ctx, l, r, dd)
+            _assert_stages(stages, maps, want, name + " after urban200x26")
+        last = _run(pkg, ctx, L, R, D)
+        for key, a, b in zip(STAGES, first[0], last[0]):
+            assert a.tobytes() == b.tobytes(), key
+        assert first[1][0].tobytes() == last[1][0].tobytes() and first[1][1].tobytes() == last[1][1].tobytes()
+    finally:
+        ctx.close()
 
 
 @pytest.mark.gpu
@@ -156,6 +205,120 @@ def test_batch_of_five_equals_five_single_calls(pkg, svo):
         want = d16.astype(np.float32) / np.float32(16)
         assert np.array_equal(got[b], want) and np.all(got[b][d16 == -16] == -1.0), b
     assert len({s[0].tobytes() for s in single}) == B
+
+
+def _batch(pkg, ctx, pairs, D, pitch, sentinel=7.0):
+    """svo_sgbm_batch_dev on resident pairs whose rows are `pitch` bytes apart; the output is prefilled with `sentinel`."""
+    import torch
+    B = len(pairs)
+    H, W = pairs[0][0].shape
+    dev = torch.device("cuda", 0)
+    dL = torch.full((B, H, pitch), 0xA5, dtype=torch.uint8, device=dev); dR = torch.full_like(dL, 0xA5)
+    dL[:, :, :W] = torch.from_numpy(np.stack([a for a, _ in pairs])).to(dev)
+    dR[:, :, :W] = torch.from_numpy(np.stack([b for _, b in pairs])).to(dev)
+    out = torch.full((B, H, W), sentinel, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    ctx.sgbm_batch_dev(dL.data_ptr(), dR.data_ptr(), pitch, W, H, B, out.data_ptr(), _params(pkg, H, D))
+    return out.cpu().numpy()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H,D,pitch", [(83, 37, 16, 128), (150, 20, 64, 192)])
+def test_batch_of_nine_in_a_larger_arena_equals_nine_single_calls(pkg, svo, W, H, D, pitch):
+    """B = 9 is chunks of 4, 4 and 1 pairs; D = 16 and 64 take k_sgbm_paths<16> and <64> to gridDim.z = 4.  The context's
+    arena was sized by a 200 x 26 x 48 call before, so the pairs of a chunk lie W * H * D apart in volumes made for more."""
+    B = 9
+    pairs = [sgbm_cases.noise_pair(40 + b, W, H) for b in range(B)]
+    single = [svo.sgbm_process(L, R, _params(pkg, H, D)) for L, R in pairs]
+    assert len({s[0].tobytes() for s in single}) == B and all((s[0] != -16).mean() > 0.2 for s in single)
+    ctx = pkg.Svo(640, 240, max_batch=1)
+    try:
+        L, R, Du, ref = _ref("urban200x26")
+        assert 200 * 26 * Du > W * H * D
+        d16, _ = ctx.sgbm_process(L, R, _params(pkg, 26, Du))
+        assert np.array_equal(d16, ref["disp16"])
+        assert _debug_rc(ctx) == 0
+        got = _batch(pkg, ctx, pairs, D, pitch)
+        assert _debug_rc(ctx) == -1             # SVO_E_INVALID: the batch entry leaves no volume to report
+    finally:
+        ctx.close()
+    for b in range(B):
+        d16, d = single[b]
+        assert np.array_equal(got[b].view(np.uint32), d.view(np.uint32)), b
+        assert np.all(got[b][d16 == -16] == -1.0), b
+
+
+@pytest.mark.gpu
+def test_debug_volume_reports_no_stale_volume(pkg):
+    """svo_sgbm_debug_volume describes the last svo_sgbm_process call only: after the batch entry or the speckle filter have
+    used the arena it answers SVO_E_INVALID for every stage."""
+    ctx = pkg.Svo(640, 240, max_batch=1)
+    try:
+        assert _debug_rc(ctx) == -1                            # nothing has run yet
+        L, R, D, _ = _ref("noise83x37")
+        ctx.sgbm_process(L, R, _params(pkg, L.shape[0], D))
+        assert all(_debug_rc(ctx, w) == 0 for w in range(5))
+        ctx.sgbm_filter_speckles(np.full((5, 9), 160, np.int16))
+        assert all(_debug_rc(ctx, w) == -1 for w in range(5))
+        ctx.sgbm_process(L, R, _params(pkg, L.shape[0], D))
+        assert _debug_rc(ctx) == 0
+        _batch(pkg, ctx, [(L, R)], D, 96)
+        assert all(_debug_rc(ctx, w) == -1 for w in range(5))
+        with pytest.raises(pkg.SvoError, match="invalid"):
+            ctx.sgbm_debug_volume(2)
+    finally:
+        ctx.close()
+
+
+# ---- the speckle filter beyond one 256-thread block row ----------------------------------------------------------------------
+@pytest.mark.gpu
+def test_speckle_filter_keeps_a_component_that_winds_through_every_block(pkg, svo):
+    """600 x 64, one component of 19 232 pixels: full even rows joined at alternating ends, so that the union-find meets
+    parent chains across block columns and rows (cc_find compresses no path).  The device time is printed (pytest -s)."""
+    import time
+    d = sgbm_cases.serpentine()
+    assert (d != -16).sum() == 19232
+    want = sgbm_ref.speckles(d.astype(np.int32)).astype(np.int16)
+    assert np.array_equal(want, d), "the restatement keeps all of it"
+    svo.sgbm_filter_speckles(np.full((4, 4), 160, np.int16))           # (the arena's first use is not what is timed)
+    t0 = time.perf_counter()
+    got = svo.sgbm_filter_speckles(d)
+    dt = time.perf_counter() - t0
+    print("serpentine 600 x 64: svo_sgbm_filter_speckles took %.1f ms (upload, four kernels, download)" % (1e3 * dt))
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.gpu
+def test_speckle_filter_sizes_bars_across_block_boundaries(pkg, svo):
+    """Bars of exactly 100 and 101 pixels beside and across x = 255 | 256 and x = 511 | 512: the 100s go, the 101s stay."""
+    d, go, stay = sgbm_cases.comb()
+    want = sgbm_ref.speckles(d.astype(np.int32)).astype(np.int16)
+    got = svo.sgbm_filter_speckles(d)
+    assert np.array_equal(got, want)
+    assert len(go) == 6 and len(stay) == 6
+    for s in go:
+        assert d[s].size == 100 and np.all(got[s] == -16)
+    for s in stay:
+        assert d[s].size == 101 and np.array_equal(got[s], d[s])
+    assert (got != -16).sum() == 6 * 101
+
+
+@pytest.mark.gpu
+def test_speckle_filter_on_a_seeded_map_and_on_single_rows_and_columns(pkg, svo):
+    d = sgbm_cases.seeded_speckle_map()
+    want = sgbm_ref.speckles(d.astype(np.int32)).astype(np.int16)
+    removed = ((d != -16) & (want == -16)).sum()
+    assert removed > 1000 and (want != -16).sum() > 1000, "both outcomes must be common on this map"
+    assert np.array_equal(svo.sgbm_filter_speckles(d), want)
+    # one column and one row (W = 1, H = 1 pass the argument check): runs of 100 and 101 between invalid pixels
+    line = np.full(300, -16, np.int16)
+    line[3:103] = 400; line[110:211] = 400 + 512; line[211:230] = 400 + 1025; line[250:300] = 90
+    for shape in ((300, 1), (1, 300)):
+        m = line.reshape(shape)
+        want = sgbm_ref.speckles(m.astype(np.int32)).astype(np.int16)
+        got = svo.sgbm_filter_speckles(m)
+        assert got.shape == shape and np.array_equal(got, want), shape
+        assert np.all(got.ravel()[3:103] == -16) and np.all(got.ravel()[110:211] == 912) and np.all(got.ravel()[211:] == -16)
 
 
 # ---- the tracker with depth_source = 3 -------------------------------------------------------------------------------------
