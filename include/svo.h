@@ -415,6 +415,12 @@ int svo_debug_track_gate(svo_ctx* ctx, double F[9], int32_t* n_vetoed);
  * sequences first ..; svo_track_frame: first = 0, n = 1).  Synchronises. */
 int svo_debug_track_frames(svo_ctx* ctx, int first, int n, svo_track_debug* out);
 
+/* Parity probe (ABI-7 addition): the keypoints of frame `frame` of the LAST call of a tracker entry with depth_source 1, 2 or
+ * 3 (svo_track_frame[_bgr]: frame 0; svo_track_batch_[bgr_]dev / _host: frames 0 .. B - 1) and the depth the dense map gave
+ * each of them: bf / disp at the truncated keypoint position, -1 where disp is 0 (src/frame.cc:122-164; an invalid SGBM pixel
+ * is disp = -1, so -bf).  kp, depth: max_kp entries each, *n the frame's keypoint count.  Synchronises the device. */
+int svo_debug_track_depths(svo_ctx* ctx, int frame, svo_kp* kp, float* depth, int32_t* n);
+
 /* Parity probe: cv::solvePnPRansac's outcome for the frame just tracked, and the pose (row-major 4x4, before the CV_32F
  * rounding of SetPose) it handed to PoseOptimization.  Either pointer may be NULL. */
 int svo_debug_track_pnp(svo_ctx* ctx, svo_pnp_stats* stats, double T_pnp[16]);
@@ -703,7 +709,8 @@ int svo_msa_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int 
  * with a fixed parameter set, compute, convertTo(CV_32F, 1/16).  The algorithm here is OpenCV 3.2's MODE_SGBM (one pass, five
  * directions) on one 8-bit gray pair, then the disp12MaxDiff check and filterSpeckles, restated as a written contract
  * (DESIGN.md section 8 "SGBM": parity is unpinned in the sense of SURVEY section 8(c), like ORB) - all integer; the device
- * equals the numpy restatement tests/sgbm_ref.py bit for bit.  Colour callers hand it the gray they already make. */
+ * equals the numpy restatement tests/sgbm_ref.py bit for bit.  Colour callers hand these entries the gray they already make;
+ * the _bgr entries below run the three-channel function the reference itself calls. */
 typedef struct svo_sgbm_params {
   int32_t minDisparity;       /* 0 */
   int32_t numDisparities;     /* D: 16, 32, 48 or 64 */
@@ -738,8 +745,35 @@ int svo_sgbm_filter_speckles(svo_ctx* ctx, int16_t* disp16, int width, int heigh
 
 /* Parity probe of the last svo_sgbm_process call: which = 0 the block cost C, 1 S4 (the first four directions, saturated),
  * 2 S (all five) - height x width x D int16, zero where undefined (x < D); 3 the right-image map disp2 (height x width, -1 = no
- * bid), 4 disp1 after the left-right check, before the speckle filter (height x width).  Synchronises. */
+ * bid), 4 disp1 after the left-right check, before the speckle filter (height x width).  Synchronises.
+ * (Also after svo_sgbm_process_bgr, whose C is the low 16 bits of the true block sum; after a batch entry: SVO_E_INVALID.) */
 int svo_sgbm_debug_volume(svo_ctx* ctx, int which, int16_t* host);
+
+/* ---- semi-global block matching on 8UC3 pairs (ABI-7 additions; no existing entry changed) ----------------------------------
+ * frame::ElasMatch takes cn = leftImage.channels() and is called on the 8UC3 images main.cpp reads: P1 = 8 cn 81 = 1944,
+ * P2 = 32 cn 81 = 7776, and the pixel cost is the sum over the three channels of BT(prefiltered channel) + (BT(channel) >> 2)
+ * (0 .. 567).  The 9 x 9 block sum reaches 45 927 and is kept in a short as OpenCV keeps it: C is the low 16 bits of the true
+ * sum, sign-extended.  Along a path the predecessor's values are read as the shorts they were stored as and its minimum as
+ * the short of the unwrapped minimum; the step itself is int32 and goes unwrapped into the saturated sums S4 and S.  The
+ * written contract is DESIGN.md section 8 "f-4 SGBM: colour", its executable form the numpy restatement tests/sgbm_bgr_ref.py,
+ * which the device equals bit for bit; everything else (directions, winner, uniqueness, left-right check, speckles, the maps,
+ * D in {16, 32, 48, 64}) is the gray contract.  Images are interleaved, rows `stride` >= 3 * width bytes apart; the channel
+ * order does not matter to the result.  Width cap: 3072, as for gray (the cost stage makes one pass per channel over the
+ * same 20 bytes of LDS per column); height cap 4096.  One context's arena serves gray and colour calls in turn. */
+
+/* svo_sgbm_default_params with P1 = 1944 and P2 = 7776.  Host only. */
+int svo_sgbm_default_params_bgr(int height, svo_sgbm_params* params);
+
+/* svo_sgbm_process on two 8UC3 host images.  Accepts exactly the set svo_sgbm_default_params_bgr gives (numDisparities in
+ * {16, 32, 48, 64}): gray's P1 / P2 are SVO_E_INVALID here, as this set is in the gray entries; stride < 3 * width is
+ * SVO_E_INVALID; width > 3072 or height > 4096 is SVO_E_CAPACITY, answered before the context or a device is touched. */
+int svo_sgbm_process_bgr(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int width, int height,
+                         const svo_sgbm_params* params, int16_t* disp16, float* disp);
+
+/* svo_sgbm_batch_dev on B resident 8UC3 pairs (pair b at d_L / d_R + b * height * stride), two pairs at a time through the
+ * context's volumes (the path sums are int32 here).  Identical to B calls of svo_sgbm_process_bgr.  Synchronises. */
+int svo_sgbm_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int width, int height, int B,
+                           const svo_sgbm_params* params, float* d_disp);
 
 /* ---- sparse pyramidal Lucas-Kanade (ABI-7 additions; no existing entry changed) --------------------------------------------
  * The dynamic-keypoint loop of the reference's Tracking::Track (src/Tracking.cc:189-223, commented out there): points inside

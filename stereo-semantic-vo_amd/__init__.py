@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "svo_det_describe", "svo_det_last_error", "svo_det_create", "svo_det_destroy", "svo_det_detect", "svo_det_batch_dev",
     "svo_det_sync", "svo_det_debug_tensor", "svo_det_detect_planar", "svo_det_profile", "svo_det_layer_times",
     "svo_sgbm_default_params", "svo_sgbm_process", "svo_sgbm_batch_dev", "svo_sgbm_debug_volume", "svo_sgbm_filter_speckles",
+    "svo_sgbm_default_params_bgr", "svo_sgbm_process_bgr", "svo_sgbm_batch_bgr_dev", "svo_debug_track_depths",
     "svo_lk_default_params", "svo_lk_track", "svo_lk_batch_dev", "svo_lk_chain_dev", "svo_lk_debug_level",
     "svo_lk_track_bgr", "svo_lk_batch_bgr_dev", "svo_lk_chain_bgr_dev", "svo_lk_debug_level_bgr",
 ]
@@ -405,6 +406,12 @@ class Svo:
         self._chk(self.lib.svo_debug_track_frames(self.h, int(first), int(n), _p(out)))
         return out
 
+    def debug_track_depths(self, frame=0):
+        """svo_debug_track_depths: (keypoints KP_DTYPE, depths float32) of frame `frame` of the last dense-depth tracker call."""
+        kp = np.zeros(self.max_kp, KP_DTYPE); z = np.zeros(self.max_kp, np.float32); n = C.c_int32(0)
+        self._chk(self.lib.svo_debug_track_depths(self.h, int(frame), _p(kp), _p(z), C.byref(n)))
+        return kp[:n.value], z[:n.value]
+
     def debug_track_matches(self):
         out = np.zeros(self.max_kp, np.int32)
         self._chk(self.lib.svo_debug_track_matches(self.h, _p(out)))
@@ -619,6 +626,24 @@ class Svo:
         self._chk(self.lib.svo_sgbm_batch_dev(self.h, C.c_void_p(d_L), C.c_void_p(d_R), int(stride), int(W), int(H), int(B),
                                               C.byref(params), C.c_void_p(d_disp)))
 
+    def sgbm_process_bgr(self, bgrL, bgrR, params=None):
+        """One 8UC3 pair (H x W x 3) through the cn = 3 solver -> (disp16, disp) as sgbm_process; sgbm_debug_volume describes it."""
+        a, b = _u8(bgrL), _u8(bgrR)
+        H, W = a.shape[:2]
+        if a.shape != (H, W, 3) or b.shape != a.shape:
+            raise SvoError("sgbm_process_bgr: two H x W x 3 uint8 images expected")
+        params = params or sgbm_default_params_bgr(H)
+        d16 = np.zeros((H, W), np.int16); d = np.zeros((H, W), np.float32)
+        self._chk(self.lib.svo_sgbm_process_bgr(self.h, _p(a), _p(b), 3 * W, W, H, C.byref(params), _p(d16), _p(d)))
+        self._sgbm_shape = (H, W, params.numDisparities)
+        return d16, d
+
+    def sgbm_batch_bgr_dev(self, d_L, d_R, stride, W, H, B, d_disp, params=None):
+        """B device-resident 8UC3 pairs (rows `stride` >= 3 W bytes apart) -> B device-resident float disparity maps."""
+        params = params or sgbm_default_params_bgr(H)
+        self._chk(self.lib.svo_sgbm_batch_bgr_dev(self.h, C.c_void_p(d_L), C.c_void_p(d_R), int(stride), int(W), int(H), int(B),
+                                                  C.byref(params), C.c_void_p(d_disp)))
+
     def sgbm_filter_speckles(self, disp16):
         """cv::filterSpeckles(disp16, -16, 100, 512) on an int16 H x W map; returns the filtered copy."""
         d = np.ascontiguousarray(disp16, np.int16).copy()
@@ -764,6 +789,15 @@ def sgbm_default_params(height):
     rc = load_library().svo_sgbm_default_params(int(height), C.byref(p))
     if rc != 0:
         raise SvoError("svo_sgbm_default_params failed")
+    return p
+
+
+def sgbm_default_params_bgr(height):
+    """ElasMatch's parameter set with cn = 3 (P1 = 1944, P2 = 7776) for an image of `height` rows (needs no GPU)."""
+    p = SgbmParams()
+    rc = load_library().svo_sgbm_default_params_bgr(int(height), C.byref(p))
+    if rc != 0:
+        raise SvoError("svo_sgbm_default_params_bgr failed")
     return p
 
 

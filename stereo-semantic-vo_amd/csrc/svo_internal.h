@@ -195,6 +195,7 @@ struct svo_ctx {
   svo_camera cam{};
   int track_frame = 0;
 
+  bool opt_sgbm_colour = false;   // svo_set_option("sgbm_colour"): with depth_source 3 the _bgr tracker entries run the cn = 3 solver on their BGR frames
   int opt_depth_source = 0; // svo_set_option("depth_source"): 0 sparse epipolar stereo, 1 dense ELAS map, 2 dense MSA map, 3 dense SGBM map
   int opt_fast_cand_cap = 2048;   // svo_set_option("fast_cand_cap"): entries of k_fast's candidate list (<= 2048)
   int opt_pose_mfma = 1;   // svo_set_option("pose_mfma"): the LM's sums over the edges - 1 on f64 MFMA (default), 2 one lane per quantity, 0 one lane for everything (svo_pose_dev.h)
@@ -352,6 +353,10 @@ void svo_lk_release(svo_ctx* ctx);
 int svo_sgbm_run_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,
                      const svo_sgbm_params* p, float* d_disp);
 int svo_sgbm_chunk();
+// the same on 8UC3 pairs (stride >= 3 W, the cn = 3 parameter set), in chunks of svo_sgbm_chunk_bgr() pairs
+int svo_sgbm_run_bgr_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H,
+                         int B, const svo_sgbm_params* p, float* d_disp);
+int svo_sgbm_chunk_bgr();
 void svo_track_release(svo_ctx* ctx);   // tracker states, work records, second stream, events
 int svo_upload_image(svo_ctx* ctx, const uint8_t* gray, int stride, int slot);
 // dense ELAS stereo on images already in HBM; the two maps stay in HBM (valid until the next call)

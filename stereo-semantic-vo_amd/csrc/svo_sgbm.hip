@@ -13,6 +13,12 @@
 //   k_sgbm_lr       left-right check
 //   k_sgbm_cc_*     speckles: union-find over the pixels' right / lower edges, sizes, removal, float map
 // Paths are independent: no hand-over between workgroups, no fence inside a kernel.
+//
+// The cost and path stages are templates on the channel count CN (DESIGN.md section 8 "f-4 SGBM: colour").  CN = 1 is the gray
+// solver above, unchanged.  CN = 3 takes interleaved 8UC3 rows: k_sgbm_hsum makes one pass per channel over the same four LDS
+// planes and accumulates into T; P1 and P2 are three times gray's; C is the low 16 bits of the true block sum; the carried
+// Lp and m are wrapped to int16 while the unwrapped int32 step goes into A and B, which are int32 volumes there (so a chunk
+// of the arena holds half as many colour pairs).
 #include "svo_internal.h"
 
 #include <limits.h>
@@ -23,12 +29,13 @@ namespace {
 
 constexpr int SGBM_P1 = 648, SGBM_P2 = 2592, SGBM_CAP = 63, SGBM_R = 4;
 constexpr int SGBM_CHUNK = 4;          // pairs of a batch that share the arena's volumes
+constexpr int SGBM_CHUNK_BGR = 2;      // colour: A and B are int32, so the same bytes hold half as many pairs
 constexpr int SGBM_MAX_W = 3072;       // k_sgbm_hsum keeps 20 bytes per column in LDS
 constexpr int SGBM_MAX_H = 4096;
 constexpr int16_t SGBM_INVALID = -16;
 
 struct SgbmArena {
-  int16_t *C = nullptr, *A = nullptr, *B = nullptr;       // cap_img volumes each
+  int16_t *C = nullptr, *A = nullptr, *B = nullptr;       // cap_n volumes each (colour calls use A and B as int32 volumes of half as many pairs)
   int16_t *dbgS4 = nullptr, *dbgS = nullptr;              // svo_sgbm_process only (one volume each)
   int16_t *disp1 = nullptr, *dbg_disp2 = nullptr, *dbg_lr = nullptr;
   uint32_t* bid = nullptr;
@@ -44,6 +51,10 @@ struct SgbmArena {
 };
 
 __device__ __forceinline__ int sat16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+__device__ __forceinline__ int wrap16(int v) { return (int16_t)v; }   // the low 16 bits, sign-extended
+
+template <int CN> struct SgbmAcc { typedef int16_t type; };
+template <> struct SgbmAcc<3> { typedef int32_t type; };               // L0 + L1 and L2 + L3 leave int16 with three channels
 
 // Birchfield-Tomasi on two packed (u | u0 << 8 | u1 << 16) entries
 __device__ __forceinline__ int bt_cost(uint32_t a, uint32_t b) {
@@ -54,52 +65,64 @@ __device__ __forceinline__ int bt_cost(uint32_t a, uint32_t b) {
   return min(c0, c1);
 }
 
+// (I points at channel c of pixel (0, 0); pixels are CN bytes apart)
+template <int CN>
 __device__ __forceinline__ int prefilter_px(const uint8_t* I, int stride, int W, int H, int x, int y) {
   if (x == 0 || x == W - 1) return SGBM_CAP;
   const uint8_t* r = I + (size_t)y * stride;
   const uint8_t* rm = I + (size_t)max(y - 1, 0) * stride;
   const uint8_t* rp = I + (size_t)min(y + 1, H - 1) * stride;
-  const int v = 2 * ((int)r[x + 1] - (int)r[x - 1]) + ((int)rm[x + 1] - (int)rm[x - 1]) + ((int)rp[x + 1] - (int)rp[x - 1]);
+  const int a = (x + 1) * CN, b = (x - 1) * CN;
+  const int v = 2 * ((int)r[a] - (int)r[b]) + ((int)rm[a] - (int)rm[b]) + ((int)rp[a] - (int)rp[b]);
   return min(max(v, -SGBM_CAP), SGBM_CAP) + SGBM_CAP;
 }
 
 // T(x, y, d) = sum over dx of the pixel cost at (clamp(x + dx, D, W - 1), y, d).  Grid (H, pairs), blockDim = D * (256 / D):
 // thread -> (column offset, d), so that a wave's stores are contiguous.  LDS: 4 byte planes, then 4 packed planes.
+template <int CN>
 __global__ void k_sgbm_hsum(const uint8_t* L, const uint8_t* R, int stride, size_t frame, int W, int H, int D, int16_t* T, size_t vol) {
   extern __shared__ uint32_t lds[];
   uint32_t* pk = lds;                                        // [4][W]: gradient L, gray L, gradient R, gray R
   uint8_t* raw = reinterpret_cast<uint8_t*>(lds + 4 * (size_t)W);   // [4][W]
   const int y = blockIdx.x;
   L += blockIdx.y * frame; R += blockIdx.y * frame; T += blockIdx.y * vol;
-  for (int x = threadIdx.x; x < W; x += blockDim.x) {
-    raw[x] = (uint8_t)prefilter_px(L, stride, W, H, x, y);
-    raw[W + x] = L[(size_t)y * stride + x];
-    raw[2 * W + x] = (uint8_t)prefilter_px(R, stride, W, H, x, y);
-    raw[3 * W + x] = R[(size_t)y * stride + x];
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 4 * W; i += blockDim.x) {
-    const int x = i % W;
-    const uint8_t* p = raw + (i - x);
-    const int u = p[x];
-    const int ul = x > 0 ? (u + p[x - 1]) / 2 : u;
-    const int ur = x < W - 1 ? (u + p[x + 1]) / 2 : u;
-    pk[i] = (uint32_t)u | ((uint32_t)min(u, min(ul, ur)) << 8) | ((uint32_t)max(u, max(ul, ur)) << 16);
-  }
-  __syncthreads();
   const int d = threadIdx.x % D, cols = blockDim.x / D;
-  for (int x = D + threadIdx.x / D; x < W; x += cols) {
-    int sum = 0;
+  // CN = 3: one pass per channel over the same planes; a thread adds to the T entries it wrote itself in the pass before
+  // (the row's sum is at most 9 * 567 = 5103)
 #pragma unroll
-    for (int dx = -SGBM_R; dx <= SGBM_R; ++dx) {
-      const int xx = min(max(x + dx, D), W - 1), xr = xx - d;
-      sum += bt_cost(pk[xx], pk[2 * W + xr]) + (bt_cost(pk[W + xx], pk[3 * W + xr]) >> 2);
+  for (int c = 0; c < CN; ++c) {
+    if (c) __syncthreads();                                  // the pass before has read the planes
+    for (int x = threadIdx.x; x < W; x += blockDim.x) {
+      raw[x] = (uint8_t)prefilter_px<CN>(L + c, stride, W, H, x, y);
+      raw[W + x] = L[(size_t)y * stride + x * CN + c];
+      raw[2 * W + x] = (uint8_t)prefilter_px<CN>(R + c, stride, W, H, x, y);
+      raw[3 * W + x] = R[(size_t)y * stride + x * CN + c];
     }
-    T[((size_t)y * W + x) * D + d] = (int16_t)sum;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * W; i += blockDim.x) {
+      const int x = i % W;
+      const uint8_t* p = raw + (i - x);
+      const int u = p[x];
+      const int ul = x > 0 ? (u + p[x - 1]) / 2 : u;
+      const int ur = x < W - 1 ? (u + p[x + 1]) / 2 : u;
+      pk[i] = (uint32_t)u | ((uint32_t)min(u, min(ul, ur)) << 8) | ((uint32_t)max(u, max(ul, ur)) << 16);
+    }
+    __syncthreads();
+    for (int x = D + threadIdx.x / D; x < W; x += cols) {
+      int sum = 0;
+#pragma unroll
+      for (int dx = -SGBM_R; dx <= SGBM_R; ++dx) {
+        const int xx = min(max(x + dx, D), W - 1), xr = xx - d;
+        sum += bt_cost(pk[xx], pk[2 * W + xr]) + (bt_cost(pk[W + xx], pk[3 * W + xr]) >> 2);
+      }
+      int16_t* t = &T[((size_t)y * W + x) * D + d];
+      *t = (int16_t)(c ? *t + sum : sum);
+    }
   }
 }
 
 // C(x, y, d) = sum over dy of T(x, clamp(y + dy, 0, H - 1), d).  Grid (ceil((W - D) * D / 256), H, pairs).
+// The conversion keeps the low 16 bits: the value itself in gray (at most 15 309), wrap16 of the true sum with three channels.
 __global__ void k_sgbm_vsum(const int16_t* T, int16_t* C, int W, int H, int D, size_t vol) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (e >= (W - D) * D) return;
@@ -138,21 +161,33 @@ __device__ __forceinline__ int group_min(int v) {
 }
 
 // One step of L(p, d) = C + min(Lp[d], Lp[d-1] + P1, Lp[d+1] + P1, m + P2) - (m + P2) on a lane group (lane = d; lanes >= D idle)
-template <int G>
+// (P1, P2 = CN times gray's.  With CN = 3 the caller carries Lp and m wrapped to int16; the result is the unwrapped int32.)
+template <int G, int CN>
 __device__ __forceinline__ int sgbm_step(int c, int Lp, int m, int d, int D) {
+  constexpr int P1 = SGBM_P1 * CN, P2 = SGBM_P2 * CN;
   const int lo = __shfl_up(Lp, 1, G), hi = __shfl_down(Lp, 1, G);
-  int a = min(Lp, m + SGBM_P2);
-  if (d > 0) a = min(a, lo + SGBM_P1);
-  if (d < D - 1) a = min(a, hi + SGBM_P1);
-  return c + a - (m + SGBM_P2);
+  int a = min(Lp, m + P2);
+  if (d > 0) a = min(a, lo + P1);
+  if (d < D - 1) a = min(a, hi + P1);
+  return c + a - (m + P2);
+}
+
+// what the next pixel of a path sees of this one's step: the value as stored in a short, and the short of the unwrapped minimum
+template <int G, int CN>
+__device__ __forceinline__ void sgbm_carry(int v, bool lane, int& Lp, int& m) {
+  Lp = CN == 1 ? v : wrap16(v);
+  m = group_min<G>(lane ? v : INT_MAX);
+  if (CN != 1) m = wrap16(m);
 }
 
 // Directions dir0 (blockIdx.y = 0, into out0) and dir1 (blockIdx.y = 1, into out1): written (add = 0) or added to what is there.
 // blockDim 256 = 256 / G paths; a wave runs to its longest path, lanes of shorter ones idle (no workgroup barrier in here).
-template <int G>
-__global__ void k_sgbm_paths(const int16_t* C, int16_t* out0, int16_t* out1, int dir0, int dir1, int add, int W, int H, int D, size_t vol) {
+template <int G, int CN>
+__global__ void k_sgbm_paths(const int16_t* C, typename SgbmAcc<CN>::type* out0, typename SgbmAcc<CN>::type* out1, int dir0, int dir1,
+                             int add, int W, int H, int D, size_t vol) {
+  typedef typename SgbmAcc<CN>::type acc_t;
   const int dir = blockIdx.y ? dir1 : dir0;
-  int16_t* out = (blockIdx.y ? out1 : out0) + blockIdx.z * vol;
+  acc_t* out = (blockIdx.y ? out1 : out0) + blockIdx.z * vol;
   C += blockIdx.z * vol;
   const int d = threadIdx.x % G, p = blockIdx.x * (blockDim.x / G) + threadIdx.x / G;
   int x, y, sx, sy, len;
@@ -175,17 +210,16 @@ __global__ void k_sgbm_paths(const int16_t* C, int16_t* out0, int16_t* out1, int
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int v = sgbm_step<G>(c[u], Lp, m, d, D);
-      if (lane && k0 + u < len) out[idx[u]] = (int16_t)(prev[u] + v);
-      Lp = v;
-      m = group_min<G>(lane ? v : INT_MAX);
+      const int v = sgbm_step<G, CN>(c[u], Lp, m, d, D);
+      if (lane && k0 + u < len) out[idx[u]] = (acc_t)(prev[u] + v);
+      sgbm_carry<G, CN>(v, lane, Lp, m);
     }
   }
 }
 
 // Direction 4 along row p (right to left), the sums, and the winner of every pixel.  bid: H x W, 0xffffffff = no bid.
-template <int G>
-__global__ void k_sgbm_winner(const int16_t* C, const int16_t* A, const int16_t* B, int16_t* dbgS4, int16_t* dbgS, int16_t* disp1,
+template <int G, int CN>
+__global__ void k_sgbm_winner(const int16_t* C, const typename SgbmAcc<CN>::type* A, const typename SgbmAcc<CN>::type* B, int16_t* dbgS4, int16_t* dbgS, int16_t* disp1,
                               uint32_t* bid, int W, int H, int D, size_t vol, size_t pix) {
   C += blockIdx.z * vol; A += blockIdx.z * vol; B += blockIdx.z * vol;
   disp1 += blockIdx.z * pix; bid += blockIdx.z * pix;
@@ -211,9 +245,8 @@ __global__ void k_sgbm_winner(const int16_t* C, const int16_t* A, const int16_t*
     for (int u = 0; u < U; ++u) {
       const bool on = lane && k0 + u < len;      // (uniform over the group's lanes below D)
       const int x = W - 1 - k0 - u;
-      const int v = sgbm_step<G>(c[u], Lp, m, d, D);
-      Lp = v;
-      m = group_min<G>(lane ? v : INT_MAX);
+      const int v = sgbm_step<G, CN>(c[u], Lp, m, d, D);
+      sgbm_carry<G, CN>(v, lane, Lp, m);
       const int s = sat16(s4[u] + v);
       if (on && dbgS) { dbgS4[idx[u]] = (int16_t)s4[u]; dbgS[idx[u]] = (int16_t)s; }
       // first minimum over d ascending: smallest (S, d)
@@ -323,10 +356,10 @@ __global__ void k_sgbm_cc_apply(int16_t* disp, const int32_t* root, const int32_
   if (out) out[o] = (float)v / 16.0f;
 }
 
-int sgbm_check(const svo_sgbm_params* p, int W, int H) {
+int sgbm_check(const svo_sgbm_params* p, int W, int H, int cn = 1) {
   if (!p) return SVO_E_INVALID;
   svo_sgbm_params d;
-  svo_sgbm_default_params(H, &d);
+  if (cn == 3) svo_sgbm_default_params_bgr(H, &d); else svo_sgbm_default_params(H, &d);
   const int D = p->numDisparities;
   if (D != 16 && D != 32 && D != 48 && D != 64) return SVO_E_INVALID;
   if (p->minDisparity != d.minDisparity || p->blockSize != d.blockSize || p->P1 != d.P1 || p->P2 != d.P2 ||
@@ -340,9 +373,9 @@ int sgbm_check(const svo_sgbm_params* p, int W, int H) {
 
 // The parameters and sizes first (host arithmetic only, so that they are answered the same with or without a context or a
 // device), then the pointers; the reason goes to the context's last_error when there is one.
-int sgbm_args(svo_ctx* ctx, const char* who, bool pointers, const svo_sgbm_params* p, int W, int H, int stride) {
-  int rc = sgbm_check(p, W, H);
-  if (rc == SVO_OK && (!ctx || !pointers || stride < W)) rc = SVO_E_INVALID;
+int sgbm_args(svo_ctx* ctx, const char* who, bool pointers, const svo_sgbm_params* p, int W, int H, int stride, int cn = 1) {
+  int rc = sgbm_check(p, W, H, cn);
+  if (rc == SVO_OK && (!ctx || !pointers || stride < cn * W)) rc = SVO_E_INVALID;
   if (rc && ctx) ctx->last_error = std::string(who) + (rc == SVO_E_CAPACITY ? ": image larger than 3072 x 4096" : ": invalid argument or unsupported parameters");
   return rc;
 }
@@ -359,8 +392,9 @@ int sgbm_alloc(svo_ctx* ctx, T** p, size_t count) {
   return SVO_OK;
 }
 
-// the context's arena: volumes for n pairs of W x H x D (the debug copies and the host path's staging with dbg)
-int sgbm_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int D, int n, bool dbg, SgbmArena** out) {
+// the context's arena: volumes for n gray pairs of W x H x D (the debug copies and the host path's staging with dbg; img_bytes:
+// the uploaded pair).  A colour call of k pairs asks for n = 2 k: its A and B are int32.
+int sgbm_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int D, int n, bool dbg, SgbmArena** out, size_t img_bytes = 0) {
   if (!ctx->sgbm) ctx->sgbm = new SgbmArena();
   SgbmArena* A = static_cast<SgbmArena*>(ctx->sgbm);
   *out = A;
@@ -371,7 +405,7 @@ int sgbm_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int D, int n, bool d
     if (A->last) SVO_HIP(ctx, hipStreamSynchronize(A->last));
     const size_t v = std::max(vol, A->cap_vol), q = std::max(pix, A->cap_pix);
     const size_t m = (size_t)std::max(n, A->cap_n);
-    A->cap_vol = A->cap_pix = 0; A->cap_n = 0; A->has_dbg = false; A->dbg_valid = false;
+    A->cap_vol = A->cap_pix = 0; A->cap_n = 0; A->has_dbg = false; A->dbg_valid = false; A->cap_img_bytes = 0;
     if ((rc = sgbm_alloc(ctx, &A->C, v * m)) || (rc = sgbm_alloc(ctx, &A->A, v * m)) || (rc = sgbm_alloc(ctx, &A->B, v * m)) ||
         (rc = sgbm_alloc(ctx, &A->disp1, q * m)) || (rc = sgbm_alloc(ctx, &A->bid, q * m)) || (rc = sgbm_alloc(ctx, &A->label, q * m)) ||
         (rc = sgbm_alloc(ctx, &A->root, q * m)) || (rc = sgbm_alloc(ctx, &A->cnt, q * m)))
@@ -385,18 +419,27 @@ int sgbm_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int D, int n, bool d
         (rc = sgbm_alloc(ctx, &A->img, 2 * A->cap_pix)) || (rc = sgbm_alloc(ctx, &A->dispf, A->cap_pix)))
       return rc;
     A->has_dbg = true;
+    A->cap_img_bytes = 2 * A->cap_pix;
+  }
+  if (dbg && A->cap_img_bytes < img_bytes) {   // a colour pair: three bytes per pixel
+    if (A->last) SVO_HIP(ctx, hipStreamSynchronize(A->last));
+    A->cap_img_bytes = 0; A->dbg_valid = false;
+    if ((rc = sgbm_alloc(ctx, &A->img, img_bytes))) return rc;
+    A->cap_img_bytes = img_bytes;
   }
   A->last = s;
   return SVO_OK;
 }
 
-template <int G>
+template <int G, int CN>
 void sgbm_launch_paths(hipStream_t s, SgbmArena* A, int W, int H, int D, int n, size_t vol, size_t pix, bool dbg) {
+  typedef typename SgbmAcc<CN>::type acc_t;
   const int gpb = 256 / G, nx = W - D;
   const int n02 = std::max(H, nx), n13 = nx + H - 1;
-  hipLaunchKernelGGL(k_sgbm_paths<G>, dim3((n02 + gpb - 1) / gpb, 2, n), dim3(256), 0, s, A->C, A->A, A->B, 0, 2, 0, W, H, D, vol);
-  hipLaunchKernelGGL(k_sgbm_paths<G>, dim3((n13 + gpb - 1) / gpb, 2, n), dim3(256), 0, s, A->C, A->A, A->B, 1, 3, 1, W, H, D, vol);
-  hipLaunchKernelGGL(k_sgbm_winner<G>, dim3((H + gpb - 1) / gpb, 1, n), dim3(256), 0, s, A->C, A->A, A->B, dbg ? A->dbgS4 : nullptr,
+  acc_t *a = reinterpret_cast<acc_t*>(A->A), *b = reinterpret_cast<acc_t*>(A->B);
+  hipLaunchKernelGGL((k_sgbm_paths<G, CN>), dim3((n02 + gpb - 1) / gpb, 2, n), dim3(256), 0, s, A->C, a, b, 0, 2, 0, W, H, D, vol);
+  hipLaunchKernelGGL((k_sgbm_paths<G, CN>), dim3((n13 + gpb - 1) / gpb, 2, n), dim3(256), 0, s, A->C, a, b, 1, 3, 1, W, H, D, vol);
+  hipLaunchKernelGGL((k_sgbm_winner<G, CN>), dim3((H + gpb - 1) / gpb, 1, n), dim3(256), 0, s, A->C, a, b, dbg ? A->dbgS4 : nullptr,
                      dbg ? A->dbgS : nullptr, A->disp1, A->bid, W, H, D, vol, pix);
 }
 
@@ -411,6 +454,8 @@ void sgbm_speckles(hipStream_t s, SgbmArena* A, int W, int H, int n, float* d_di
 }
 
 // n <= cap_n resident pairs (pair b at dL / dR + b * frame) -> d_disp (+ b * W * H floats; may be null), int16 maps in A->disp1
+// (CN = 3: n <= cap_n / 2 pairs of interleaved three-channel rows)
+template <int CN>
 int sgbm_enqueue(svo_ctx* ctx, hipStream_t s, SgbmArena* A, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W,
                  int H, int D, int n, float* d_disp, bool dbg) {
   const size_t pix = (size_t)W * H, vol = pix * D;
@@ -420,11 +465,12 @@ int sgbm_enqueue(svo_ctx* ctx, hipStream_t s, SgbmArena* A, const uint8_t* dL, c
     SVO_HIP(ctx, hipMemsetAsync(A->dbgS, 0, vol * sizeof(int16_t), s));
   }
   SVO_HIP(ctx, hipMemsetAsync(A->bid, 0xff, pix * n * sizeof(uint32_t), s));
-  hipLaunchKernelGGL(k_sgbm_hsum, dim3(H, n), dim3(D * (256 / D)), 20 * (size_t)W, s, dL, dR, stride, frame, W, H, D, A->A, vol);
+  // (T goes through the front of A->A as int16; the paths overwrite it)
+  hipLaunchKernelGGL(k_sgbm_hsum<CN>, dim3(H, n), dim3(D * (256 / D)), 20 * (size_t)W, s, dL, dR, stride, frame, W, H, D, A->A, vol);
   hipLaunchKernelGGL(k_sgbm_vsum, dim3(((W - D) * D + 255) / 256, H, n), dim3(256), 0, s, A->A, A->C, W, H, D, vol);
-  if (D == 16) sgbm_launch_paths<16>(s, A, W, H, D, n, vol, pix, dbg);
-  else if (D == 32) sgbm_launch_paths<32>(s, A, W, H, D, n, vol, pix, dbg);
-  else sgbm_launch_paths<64>(s, A, W, H, D, n, vol, pix, dbg);
+  if (D == 16) sgbm_launch_paths<16, CN>(s, A, W, H, D, n, vol, pix, dbg);
+  else if (D == 32) sgbm_launch_paths<32, CN>(s, A, W, H, D, n, vol, pix, dbg);
+  else sgbm_launch_paths<64, CN>(s, A, W, H, D, n, vol, pix, dbg);
   hipLaunchKernelGGL(k_sgbm_lr, dim3((W + 255) / 256, H, n), dim3(256), 0, s, A->disp1, A->bid, dbg ? A->dbg_disp2 : nullptr,
                      dbg ? A->dbg_lr : nullptr, W, H, pix);
   sgbm_speckles(s, A, W, H, n, d_disp);
@@ -449,43 +495,80 @@ extern "C" int svo_sgbm_default_params(int height, svo_sgbm_params* p) {
   return SVO_OK;
 }
 
-// B resident pairs -> B float maps, SGBM_CHUNK pairs at a time, enqueued on `s` (no synchronisation)
-int svo_sgbm_run_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,
-                     const svo_sgbm_params* p, float* d_disp) {
-  int rc = sgbm_check(p, W, H);
+// ElasMatch's set for a three-channel image: P1 = 8 cn 81, P2 = 32 cn 81 (src/frame.cc:103-104)
+extern "C" int svo_sgbm_default_params_bgr(int height, svo_sgbm_params* p) {
+  const int rc = svo_sgbm_default_params(height, p);
+  if (rc) return rc;
+  p->P1 *= 3;
+  p->P2 *= 3;
+  return SVO_OK;
+}
+
+namespace {
+
+// B resident pairs -> B float maps, a chunk of pairs at a time, enqueued on `s` (no synchronisation)
+template <int CN>
+int sgbm_run(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,
+             const svo_sgbm_params* p, float* d_disp) {
+  constexpr int chunk = CN == 3 ? SGBM_CHUNK_BGR : SGBM_CHUNK, unit = SGBM_CHUNK / chunk;
+  int rc = sgbm_check(p, W, H, CN);
   if (rc) { ctx->last_error = "svo_sgbm: unsupported parameters or image size"; return rc; }
   SgbmArena* A = nullptr;
-  if ((rc = sgbm_reserve(ctx, s, W, H, p->numDisparities, std::min(B, SGBM_CHUNK), false, &A))) return rc;
+  if ((rc = sgbm_reserve(ctx, s, W, H, p->numDisparities, std::min(B, chunk) * unit, false, &A))) return rc;
   A->dbg_valid = false;
-  for (int f0 = 0; f0 < B; f0 += SGBM_CHUNK) {
-    const int n = std::min(SGBM_CHUNK, B - f0);
-    if ((rc = sgbm_enqueue(ctx, s, A, dL + f0 * frame, dR + f0 * frame, stride, frame, W, H, p->numDisparities, n,
-                           d_disp + (size_t)f0 * W * H, false)))
+  for (int f0 = 0; f0 < B; f0 += chunk) {
+    const int n = std::min(chunk, B - f0);
+    if ((rc = sgbm_enqueue<CN>(ctx, s, A, dL + f0 * frame, dR + f0 * frame, stride, frame, W, H, p->numDisparities, n,
+                               d_disp + (size_t)f0 * W * H, false)))
       return rc;
   }
   return SVO_OK;
 }
 
-int svo_sgbm_chunk() { return SGBM_CHUNK; }
-
-extern "C" int svo_sgbm_process(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int W, int H, const svo_sgbm_params* p,
-                                int16_t* disp16, float* disp) {
-  int rc = sgbm_args(ctx, "svo_sgbm_process", L && R, p, W, H, stride);
+template <int CN>
+int sgbm_process(svo_ctx* ctx, const char* who, const uint8_t* L, const uint8_t* R, int stride, int W, int H, const svo_sgbm_params* p,
+                 int16_t* disp16, float* disp) {
+  int rc = sgbm_args(ctx, who, L && R, p, W, H, stride, CN);
   if (rc) return rc;
   SVO_HIP(ctx, hipSetDevice(ctx->device));
   SgbmArena* A = nullptr;
   hipStream_t s = ctx->stream;
-  if ((rc = sgbm_reserve(ctx, s, W, H, p->numDisparities, 1, true, &A))) return rc;
-  const size_t pix = (size_t)W * H;
+  const size_t pix = (size_t)W * H, row = (size_t)W * CN, img = pix * CN;
+  if ((rc = sgbm_reserve(ctx, s, W, H, p->numDisparities, SGBM_CHUNK / (CN == 3 ? SGBM_CHUNK_BGR : SGBM_CHUNK), true, &A, 2 * img))) return rc;
   A->dbg_valid = false;
-  SVO_HIP(ctx, hipMemcpy2DAsync(A->img, W, L, stride, W, H, hipMemcpyHostToDevice, s));
-  SVO_HIP(ctx, hipMemcpy2DAsync(A->img + pix, W, R, stride, W, H, hipMemcpyHostToDevice, s));
-  if ((rc = sgbm_enqueue(ctx, s, A, A->img, A->img + pix, W, pix, W, H, p->numDisparities, 1, A->dispf, true))) return rc;
+  SVO_HIP(ctx, hipMemcpy2DAsync(A->img, row, L, stride, row, H, hipMemcpyHostToDevice, s));
+  SVO_HIP(ctx, hipMemcpy2DAsync(A->img + img, row, R, stride, row, H, hipMemcpyHostToDevice, s));
+  if ((rc = sgbm_enqueue<CN>(ctx, s, A, A->img, A->img + img, (int)row, img, W, H, p->numDisparities, 1, A->dispf, true))) return rc;
   if (disp16) SVO_HIP(ctx, hipMemcpyAsync(disp16, A->disp1, pix * sizeof(int16_t), hipMemcpyDeviceToHost, s));
   if (disp) SVO_HIP(ctx, hipMemcpyAsync(disp, A->dispf, pix * sizeof(float), hipMemcpyDeviceToHost, s));
   SVO_HIP(ctx, hipStreamSynchronize(s));
   A->W = W; A->H = H; A->D = p->numDisparities; A->dbg_valid = true;
   return SVO_OK;
+}
+
+}  // namespace
+
+int svo_sgbm_run_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,
+                     const svo_sgbm_params* p, float* d_disp) {
+  return sgbm_run<1>(ctx, s, dL, dR, stride, frame, W, H, B, p, d_disp);
+}
+
+int svo_sgbm_run_bgr_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H,
+                         int B, const svo_sgbm_params* p, float* d_disp) {
+  return sgbm_run<3>(ctx, s, dL, dR, stride, frame, W, H, B, p, d_disp);
+}
+
+int svo_sgbm_chunk() { return SGBM_CHUNK; }
+int svo_sgbm_chunk_bgr() { return SGBM_CHUNK_BGR; }
+
+extern "C" int svo_sgbm_process(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int W, int H, const svo_sgbm_params* p,
+                                int16_t* disp16, float* disp) {
+  return sgbm_process<1>(ctx, "svo_sgbm_process", L, R, stride, W, H, p, disp16, disp);
+}
+
+extern "C" int svo_sgbm_process_bgr(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int W, int H, const svo_sgbm_params* p,
+                                    int16_t* disp16, float* disp) {
+  return sgbm_process<3>(ctx, "svo_sgbm_process_bgr", L, R, stride, W, H, p, disp16, disp);
 }
 
 extern "C" int svo_sgbm_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
@@ -494,6 +577,16 @@ extern "C" int svo_sgbm_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_
   if (rc) return rc;
   SVO_HIP(ctx, hipSetDevice(ctx->device));
   if ((rc = svo_sgbm_run_dev(ctx, ctx->stream, d_L, d_R, stride, (size_t)H * stride, W, H, B, p, d_disp))) return rc;
+  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SVO_OK;
+}
+
+extern "C" int svo_sgbm_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
+                                      const svo_sgbm_params* p, float* d_disp) {
+  int rc = sgbm_args(ctx, "svo_sgbm_batch_bgr_dev", d_L && d_R && d_disp && B >= 1, p, W, H, stride, 3);
+  if (rc) return rc;
+  SVO_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = svo_sgbm_run_bgr_dev(ctx, ctx->stream, d_L, d_R, stride, (size_t)H * stride, W, H, B, p, d_disp))) return rc;
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SVO_OK;
 }

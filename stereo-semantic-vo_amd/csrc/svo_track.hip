@@ -1981,10 +1981,16 @@ int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_
     // the body of the reference's frame::ElasMatch (src/frame.cc:94-120): SGBM on the gray pair; invalid pixels are -1
     if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 1))) return rc;
     if ((rc = dense_reserve(ctx, 1))) return rc;
+    // (colour entry with "sgbm_colour": the cn = 3 solver on the BGR pair, as the reference calls it)
     svo_sgbm_params sp;
-    svo_sgbm_default_params(g.H, &sp);
-    if ((rc = svo_sgbm_run_dev(ctx, ctx->stream, dL, dR, ctx->stage_pitch, (size_t)g.H * ctx->stage_pitch, g.W, g.H, 1, &sp, ctx->d_dense)))
-      return rc;
+    if (d_bgrL && ctx->opt_sgbm_colour) {
+      svo_sgbm_default_params_bgr(g.H, &sp);
+      rc = svo_sgbm_run_bgr_dev(ctx, ctx->stream, d_bgrL, d_bgrR, bgr_pitch, (size_t)g.H * bgr_pitch, g.W, g.H, 1, &sp, ctx->d_dense);
+    } else {
+      svo_sgbm_default_params(g.H, &sp);
+      rc = svo_sgbm_run_dev(ctx, ctx->stream, dL, dR, ctx->stage_pitch, (size_t)g.H * ctx->stage_pitch, g.W, g.H, 1, &sp, ctx->d_dense);
+    }
+    if (rc) return rc;
     SvoTimer t(ctx, "k_tk_dense_depth");
     hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_kp,
                        ctx->d_nkp, ctx->d_dense, g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, (size_t)0,
@@ -2000,6 +2006,19 @@ int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->track_frame++;
   if (res->n_pnp_inliers == -1) return svo_track_check_timeout(ctx);   // (the record is valid: the frame was tracked as a PnP failure)
+  return SVO_OK;
+}
+
+// Parity probe: what the dense depth sources handed the tail for frame `frame` of the last call (the context's own arrays)
+extern "C" int svo_debug_track_depths(svo_ctx* ctx, int frame, svo_kp* kp, float* depth, int32_t* n) {
+  if (!ctx || !kp || !depth || !n || frame < 0 || frame >= ctx->max_batch) return SVO_E_INVALID;
+  if (ctx->opt_depth_source == 0) { ctx->last_error = "svo_debug_track_depths: depth_source must be 1, 2 or 3"; return SVO_E_INVALID; }
+  hipSetDevice(ctx->device);
+  SVO_HIP(ctx, hipDeviceSynchronize());
+  const size_t K = ctx->max_kp;
+  SVO_HIP(ctx, hipMemcpy(n, ctx->d_nkp + frame, sizeof(int32_t), hipMemcpyDeviceToHost));
+  SVO_HIP(ctx, hipMemcpy(kp, ctx->d_kp + frame * K, K * sizeof(svo_kp), hipMemcpyDeviceToHost));
+  SVO_HIP(ctx, hipMemcpy(depth, ctx->d_depth + frame * K, K * sizeof(float), hipMemcpyDeviceToHost));
   return SVO_OK;
 }
 
@@ -2165,12 +2184,16 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
     bgr_convert(ctx->stream_dense, 0, B);   // (ELAS runs on the gray, like ORB: the reference never calls libelas)
     rc = svo_launch_orb(ctx, ctx->stream_dense, svo_fe_own(ctx), d_grayL, d_grayR, stride, B, B);   // left images only
     if (rc == SVO_OK && ctx->opt_depth_source == 3) {
+      // (colour entries with "sgbm_colour": the cn = 3 solver on the BGR pairs, in its own, smaller chunks)
+      const bool colour = bgr && ctx->opt_sgbm_colour;
       svo_sgbm_params sp;
-      svo_sgbm_default_params(ctx->g.H, &sp);
-      for (int f0 = 0, step = svo_sgbm_chunk(); f0 < B && rc == SVO_OK; f0 += step) {
+      if (colour) svo_sgbm_default_params_bgr(ctx->g.H, &sp); else svo_sgbm_default_params(ctx->g.H, &sp);
+      for (int f0 = 0, step = colour ? svo_sgbm_chunk_bgr() : svo_sgbm_chunk(); f0 < B && rc == SVO_OK; f0 += step) {
         const int b = std::min(step, B - f0);
         for (int k = 0; k < b; ++k) ctx->h_prod[f0 + k] = 1;
-        rc = svo_sgbm_run_dev(ctx, ctx->stream_dense, d_grayL + f0 * gray_img, d_grayR + f0 * gray_img, stride, gray_img, ctx->g.W,
+        rc = colour ? svo_sgbm_run_bgr_dev(ctx, ctx->stream_dense, bgr->L + f0 * bgr_img, bgr->R + f0 * bgr_img, bgr->stride, bgr_img,
+                                           ctx->g.W, ctx->g.H, b, &sp, dD1 + n * f0)
+                    : svo_sgbm_run_dev(ctx, ctx->stream_dense, d_grayL + f0 * gray_img, d_grayR + f0 * gray_img, stride, gray_img, ctx->g.W,
                               ctx->g.H, b, &sp, dD1 + n * f0);
         if (rc == SVO_OK) rc = Hook::run(&hook, f0, b);
       }

@@ -14,6 +14,9 @@ class Tracking {
   // 0: sparse epipolar stereo (default); 1: the reference's live flow, a dense disparity map (libelas here,
   // MSA there) -> disp2Depth -> per-keypoint lookups (src/Tracking.cc:226-228)
   int depth_source = 0;   // 0 sparse matcher, 1 ELAS map, 2 MSA map, 3 SGBM map (svo_set_option "depth_source")
+  // With depth_source 3 and the colour Track() / TrackBatch(bgr): SGBM on the colour pair (frame::ElasMatchBgr, svo_set_option
+  // "sgbm_colour"), as the reference calls it; otherwise on the gray
+  bool sgbm_colour = false;
   // The dynamic-keypoint loop of src/Tracking.cc:189-223 (commented out there): before featuredetect, the last frame's
   // DY_keypoints are followed into the current left image (frame::LKTrack), the status-0 points erased, the survivors become
   // the current frame's DY_keypoints.  Seeds - keypoints strictly inside a box, offline_box in place of the reference's online

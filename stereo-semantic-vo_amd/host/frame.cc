@@ -110,6 +110,17 @@ int frame::SGBMMatch(const GrayImage& left, const GrayImage& right) {
   return valid;
 }
 
+int frame::ElasMatchBgr(const BgrImage& left, const BgrImage& right) {
+  svo_sgbm_params sp;
+  svo_sgbm_default_params_bgr(left.rows, &sp);   // P1 = 8 * cn * 81, P2 = 32 * cn * 81 with cn = 3, src/frame.cc:96-104
+  dispimg.assign((size_t)left.cols * left.rows, -1.f);
+  if (left.cols != right.cols || left.rows != right.rows) return 0;
+  if (svo_sgbm_process_bgr(ctx, left.ptr(), right.ptr(), left.step(), left.cols, left.rows, &sp, nullptr, dispimg.data()) != SVO_OK) return 0;
+  int valid = 0;
+  for (float d : dispimg) valid += d != -1.f;
+  return valid;
+}
+
 // src/Tracking.cc:189-223 (commented out there): calcOpticalFlowPyrLK(last left, current left, last DY_keypoints, ...) with its
 // default arguments, then the erase loop over status.  `prev` and `next` are the two left images' bytes, rows `stride` apart;
 // `entry` is svo_lk_track or svo_lk_track_bgr.

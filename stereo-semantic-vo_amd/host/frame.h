@@ -11,6 +11,7 @@
 //   ElasMatch          -> svo_elas_process         (src/frame.cc:93-120 dense disparity; the reference's body is
 //                         OpenCV SGBM under that name, the vendored solver it names is libelas: include/frame.h:15)
 //   SGBMMatch          -> svo_sgbm_process         (src/frame.cc:94-120 as the reference has it: the body of its ElasMatch)
+//   ElasMatchBgr       -> svo_sgbm_process_bgr     (the same body on the 8UC3 pair it is called with: cn = 3, P1 = 1944, P2 = 7776)
 //   LKTrack            -> svo_lk_track             (src/Tracking.cc:189-223, commented out there: calcOpticalFlowPyrLK on the
 //                         last frame's DY_keypoints, the status-0 points erased)
 //   LKTrackBgr         -> svo_lk_track_bgr         (the same call on the 8UC3 left images, which is what `leftimg` is in the
@@ -39,6 +40,8 @@ class frame {
   // the reference's ElasMatch body: semi-global block matching with its fixed parameter set, compute, convertTo(CV_32F, 1/16)
   // into `dispimg` (-1 = invalid); returns the number of valid pixels
   int SGBMMatch(const svo_host::GrayImage& left, const svo_host::GrayImage& right);
+  // the same on the colour pair, which is what the reference hands its ElasMatch: cn = leftImage.channels() = 3
+  int ElasMatchBgr(const svo_host::BgrImage& left, const svo_host::BgrImage& right);
   // the reference's own MB body: MSA dense disparity (0 = none) of the two images as B = G = R colour images
   int MBdense(const svo_host::GrayImage& left, const svo_host::GrayImage& right);
   // the same with the true colour pair (the reference's 8UC3 input, main.cpp:160-161): MSA's colour cost and tree weights

@@ -1,7 +1,10 @@
 """Semi-global block matching on one MI355X: latency of one pair host to host (svo_sgbm_process), pairs/s of
 svo_sgbm_batch_dev over 64 resident pairs, frames/s of svo_track_batch_dev at depth_source 3 over 256 frames.  Every figure is
 the median of --repeats timed runs after a warm-up, with the spread (min .. max) beside it.  Prints one JSON line.
-Usage: python tools/sgbm_bench.py [--repeats N] [--only latency|batch|track]"""
+--bgr: the same three figures for the cn = 3 solver on 8UC3 pairs (svo_sgbm_process_bgr, svo_sgbm_batch_bgr_dev,
+svo_track_batch_bgr_dev with "sgbm_colour" 1).  --both: gray and colour in one session, and the colour / gray ratios of the
+medians (time per pair or frame: above 1 means colour is slower).
+Usage: python tools/sgbm_bench.py [--repeats N] [--only latency|batch|track] [--bgr | --both]"""
 import argparse
 import importlib
 import json
@@ -23,10 +26,11 @@ ap.add_argument("--repeats", type=int, default=7)
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--frames", type=int, default=256)
 ap.add_argument("--only", choices=["latency", "batch", "track"], default=None)
+ap.add_argument("--bgr", action="store_true", help="the cn = 3 solver on 8UC3 pairs")
+ap.add_argument("--both", action="store_true", help="gray and colour in one session, and their ratios")
 a = ap.parse_args()
 svo = svo_loader.load()
 dev = torch.device("cuda", 0)
-stride = 1280
 
 
 def timed(fn, repeats):
@@ -43,48 +47,85 @@ def spread(vals, digits):
     return {"median": round(statistics.median(vals), digits), "min": round(min(vals), digits), "max": round(max(vals), digits)}
 
 
-out = {"workload": "semi-global block matching, 1241x376, D = 48", "repeats": a.repeats}
-L, R = util.urban_pair()
-H, W = L.shape
-if a.only in (None, "latency"):
-    ctx = svo.Svo(W, H)
-    ts = timed(lambda: ctx.sgbm_process(L, R), a.repeats)
-    out["one_pair_host_to_host_ms"] = spread([1e3 * t for t in ts], 3)
-    ctx.close()
-if a.only in (None, "batch"):
-    B = a.batch
-    ctx = svo.Svo(W, H)
-    dL = torch.zeros((B, H, stride), dtype=torch.uint8, device=dev); dR = torch.zeros_like(dL)
-    dL[:, :, :W] = torch.from_numpy(L).to(dev); dR[:, :, :W] = torch.from_numpy(R).to(dev)
-    D = torch.zeros((B, H, W), dtype=torch.float32, device=dev)
-    torch.cuda.synchronize()
-    ts = timed(lambda: ctx.sgbm_batch_dev(dL.data_ptr(), dR.data_ptr(), stride, W, H, B, D.data_ptr()), a.repeats)
-    out["batch_%d_pairs_per_s" % B] = spread([B / t for t in ts], 1)
-    assert np.array_equal(D[B - 1].cpu().numpy(), ctx.sgbm_process(L, R)[1])
-    ctx.close()
-if a.only in (None, "track"):
-    N = a.frames
-    synth = importlib.import_module("stereo_semantic_vo_amd.synth")
-    dL = torch.zeros((N, H, stride), dtype=torch.uint8, device=dev); dR = torch.zeros_like(dL)
-    for c0 in range(0, N, 64):
-        c = min(64, N - c0)
-        Ls, Rs, _ = synth.render_sequence(c, device=dev, start=c0)
-        dL[c0:c0 + c, :, :W] = Ls; dR[c0:c0 + c, :, :W] = Rs
-    res = torch.zeros((N, svo.TRACK_DTYPE.itemsize), dtype=torch.uint8, device=dev)
-    ctx = svo.Svo(W, H, max_batch=N)
-    ctx.set_option("depth_source", 3)
-    cam = svo.Camera(**svo.KITTI_00_02)
-    torch.cuda.synchronize()
+def colourise(g):
+    """(..., H, W) gray -> (..., H, W, 3): three channels that are no copies of each other (torch or numpy).  The complement
+    goes into B, which BGR2GRAY weighs least: the gray the tracker makes keeps 0.75 of the texture (in G it would cancel it)."""
+    if isinstance(g, np.ndarray):
+        g = g.astype(np.int32)
+        return np.stack([128 + (128 - g) // 2, g, np.clip(3 * g // 4 + 32, 0, 255)], -1).astype(np.uint8)
+    g = g.to(torch.int32)
+    return torch.stack([128 + torch.div(128 - g, 2, rounding_mode="floor"), g, torch.clamp(torch.div(3 * g, 4, rounding_mode="floor") + 32, 0, 255)], -1).to(torch.uint8)
 
-    def run():
-        ctx.track_reset(cam)
-        ctx.track_batch_dev(dL.data_ptr(), dR.data_ptr(), stride, N, res.data_ptr())
-        ctx.sync()
 
-    ts = timed(run, a.repeats)
-    out["track_%d_frames_per_s" % N] = spread([N / t for t in ts], 1)
-    rec = res.cpu().numpy().view(svo.TRACK_DTYPE).reshape(-1)
-    out["track_last_frame"] = {"n_stereo": int(rec[-1]["n_stereo"]), "n_lm_edges": int(rec[-1]["n_lm_edges"])}
-    assert ctx.track_overflowed() == 0
-    ctx.close()
+def measure(colour):
+    cn = 3 if colour else 1
+    out = {}
+    L, R = util.urban_pair()
+    H, W = L.shape
+    stride = 3840 if colour else 1280
+    if colour:
+        L, R = colourise(L), colourise(R)
+    process = (lambda c: c.sgbm_process_bgr(L, R)) if colour else (lambda c: c.sgbm_process(L, R))
+    if a.only in (None, "latency"):
+        ctx = svo.Svo(W, H)
+        ts = timed(lambda: process(ctx), a.repeats)
+        out["one_pair_host_to_host_ms"] = spread([1e3 * t for t in ts], 3)
+        ctx.close()
+    if a.only in (None, "batch"):
+        B = a.batch
+        ctx = svo.Svo(W, H)
+        dL = torch.zeros((B, H, stride), dtype=torch.uint8, device=dev); dR = torch.zeros_like(dL)
+        dL[:, :, :cn * W] = torch.from_numpy(L.reshape(H, cn * W)).to(dev); dR[:, :, :cn * W] = torch.from_numpy(R.reshape(H, cn * W)).to(dev)
+        D = torch.zeros((B, H, W), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        entry = ctx.sgbm_batch_bgr_dev if colour else ctx.sgbm_batch_dev
+        ts = timed(lambda: entry(dL.data_ptr(), dR.data_ptr(), stride, W, H, B, D.data_ptr()), a.repeats)
+        out["batch_%d_pairs_per_s" % B] = spread([B / t for t in ts], 1)
+        assert np.array_equal(D[B - 1].cpu().numpy(), process(ctx)[1])
+        ctx.close()
+    if a.only in (None, "track"):
+        N = a.frames
+        synth = importlib.import_module("stereo_semantic_vo_amd.synth")
+        dL = torch.zeros((N, H, stride), dtype=torch.uint8, device=dev); dR = torch.zeros_like(dL)
+        for c0 in range(0, N, 64):
+            c = min(64, N - c0)
+            Ls, Rs, _ = synth.render_sequence(c, device=dev, start=c0)
+            if colour:
+                Ls, Rs = colourise(Ls).reshape(c, H, 3 * W), colourise(Rs).reshape(c, H, 3 * W)
+            dL[c0:c0 + c, :, :cn * W] = Ls; dR[c0:c0 + c, :, :cn * W] = Rs
+        res = torch.zeros((N, svo.TRACK_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        ctx = svo.Svo(W, H, max_batch=N)
+        ctx.set_option("depth_source", 3)
+        ctx.set_option("sgbm_colour", 1 if colour else 0)
+        cam = svo.Camera(**svo.KITTI_00_02)
+        torch.cuda.synchronize()
+        entry = ctx.track_batch_bgr_dev if colour else ctx.track_batch_dev
+
+        def run():
+            ctx.track_reset(cam)
+            entry(dL.data_ptr(), dR.data_ptr(), stride, N, res.data_ptr())
+            ctx.sync()
+
+        ts = timed(run, a.repeats)
+        out["track_%d_frames_per_s" % N] = spread([N / t for t in ts], 1)
+        rec = res.cpu().numpy().view(svo.TRACK_DTYPE).reshape(-1)
+        out["track_last_frame"] = {"n_stereo": int(rec[-1]["n_stereo"]), "n_lm_edges": int(rec[-1]["n_lm_edges"])}
+        assert ctx.track_overflowed() == 0
+        ctx.close()
+    return out
+
+
+if a.both:
+    out = {"workload": "semi-global block matching, 1241x376, D = 48, gray (cn = 1) and 8UC3 (cn = 3)", "repeats": a.repeats,
+           "gray": measure(False), "bgr": measure(True)}
+    ratios = {}
+    for k, g in out["gray"].items():
+        if k == "track_last_frame":
+            continue
+        b = out["bgr"][k]["median"]
+        ratios[k.replace("_ms", "").replace("_per_s", "") + "_time"] = round(b / g["median"] if k.endswith("_ms") else g["median"] / b, 3)
+    out["bgr_over_gray"] = ratios
+else:
+    out = {"workload": "semi-global block matching, 1241x376, D = 48" + (", 8UC3 (cn = 3)" if a.bgr else ""), "repeats": a.repeats}
+    out.update(measure(a.bgr))
 print(json.dumps(out))
