@@ -322,7 +322,13 @@ EO_FN unsigned long long jacobi_rows(Lds& S, int n, int base, int lane) {
     [base] "v"(base), [act] "v"(act), [pm] "v"(pm), [mk] "v"(mk), [eps] "v"(eps), [eps2hi] "v"(eps2hi), [eps2lo] "v"(eps2lo),   \
     [amine] "v"(amine), [axch] "v"(axch)                                                                                          \
   : EO_JACOBI_ASM_CLOBBERS
-  if (M == 12) asm volatile(EO_JACOBI_ASM_12 EO_JACOBI_OPERANDS);
+  // M = 12 (one problem on rows 0..11): the schedule is unrolled in the block, which only reads the lane's table entries of the period
+  if (M == 12)
+    asm volatile(EO_JACOBI_ASM_12
+                 : [x0] "+v"(x0), [x1] "+v"(x1), [x2] "+v"(x2), [chg] "+v"(chg), [flag] "+v"(flag)
+                 : [tper] "v"(twrap), [lane] "v"(lane), [base] "v"(base), [act] "v"(act), [pm] "v"(pm), [eps] "v"(eps),
+                   [eps2hi] "v"(eps2hi), [eps2lo] "v"(eps2lo), [amine] "v"(amine), [axch] "v"(axch)
+                 : EO_JACOBI_ASM_CLOBBERS);
   else if (M == 6) asm volatile(EO_JACOBI_ASM_6 EO_JACOBI_OPERANDS);
   else asm volatile(EO_JACOBI_ASM_3 EO_JACOBI_OPERANDS);
 #undef EO_JACOBI_OPERANDS

@@ -9,7 +9,28 @@ result is read, 2 between a VALU write of an SGPR / VCC and a VALU read of it as
 and a DMFMA read of it, 4 between dependent 4x4x4 DMFMAs (SrcC), 6 before a VALU read and 9 before an LDS read of a DMFMA
 result.
 
-Registers: the block owns v140..v253 and s60..s71 (clobbers); the row (x0, x1, x2) lives in v150..v155 while the loop runs.
+Two layouts:
+  M = 6, M = 3 (program): ONE copy of the step body that walks the schedule table in LDS - the entry of step t + 2 is read while
+    step t computes (TT / TP / SB, wrap to the prologue's end), decode() turns an entry into the partner's address, the lane mask
+    VALID, the sign and the sweep bit, and every step tests the entry's closing bit.  Three problems of different sizes share
+    one schedule there, with per-problem closing bits.
+  M = 12 (program12, class Unrolled): one problem, so everything decode() derives depends on the lane and the step only.  The
+    schedule (tools/gen_jacobi_schedule.py: PRO prologue steps, then PER steps that repeat with the sweep base one higher) is
+    unrolled: one copy of the step body per step - the PRO prologue copies, then, behind .p2align, the PER copies of the period
+    with ONE backward branch.  Before the first step the block reads the lane's PER table entries of the period from LDS and
+    turns them into two registers per slot (partner row's address; sign | relative sweep); VALID of a copy is a 16-bit constant
+    of that copy & ACT; the sweep bookkeeping and the exit test are emitted only in the copy that closes a sweep (the period's
+    last), where the base bit U_BB is doubled.  No table read, no walk, no decode and no closing test per step.  pair_test,
+    decide, the rotation, the commit and the write-back are the same instruction sequences as in the table-driven layout.
+
+Registers: the block owns v140..v255 and s60..s71 (clobbers); the row (x0, x1, x2) lives in v150..v155 while the loop runs.
+  v140..v149, v174..v175  U0..U2, V0..V2 (squares for the DMFMA chains)       v150..v157  X0..X2, WW
+  v160..v173  division / square-root temporaries, QQ, TA..TC                  v180..v199  ONE, T0..T2, AB, Y, G, H, RR, D
+  v200..v233  P, THR, PLO (partner row, 4 + 2 registers with P2), WP, BETA, HI, LO, GAM, R1, R2, CC, SS, N0..N2
+  table-driven: v234..v253  E, E1, E2, TT, TP, SB, SBE, SBE1, SGN, SWBIT, AP, AW, TMP, TMP2, ROW, QI, ONEI, STEPS, PRO, TSTEP
+  unrolled:     v234..v245  U_AP[0..11] partner addresses per slot; v158, v159, v176..v179, v246..v251  U_K[0..11] sign | sweep
+                v252 U_SGN, v253 U_TMP, v254 U_BB (1 << sweep base), v255 U_TMP2; N0 / N1 hold the row and its index during set-up
+  s[60:61] ACT, s[62:63] VALID, s[64:65] ROT, s[66:67] SAVE (exec), s[68:69] CL, s[70:71] ST
 """
 
 import os
@@ -74,7 +95,7 @@ def mfma(dst, b, c):
     return "v_mfma_f64_4x4x4_4b_f64 %s, %s, %s, %s" % (dst, pair(ONE), b, c)
 
 
-def pair_test(M):
+def pair_test(M, wait=1):
     """P = sum_k mine[k] theirs[k], WW = sum_k mine[k]^2 (= W of my row), WP = sum_k theirs[k]^2 (= W of the partner row) over the A
     columns: three interleaved DMFMA chains (dependent DMFMAs end up 4 wait states apart)."""
     p, wa, wb = pair(P), pair(WW), pair(WP)
@@ -84,7 +105,8 @@ def pair_test(M):
     for q in range(nq):      # the squares of my own row need no partner: they go in front of the wait for its arrival
         t, u, w, x, y = regs[q]
         out.append("v_mul_f64 %s, %s, %s" % (pair(u), pair(x), pair(x)))
-    out.append("s_waitcnt lgkmcnt(1)")             # the partner's row (requested at the end of the previous step)
+    out.append("s_waitcnt lgkmcnt(%d)" % wait)     # the partner's row (requested at the end of the previous step; table-driven loop:
+                                                   # the table read issued after it may still be on its way)
     for q in range(nq):
         t, u, w, x, y = regs[q]
         out += ["v_mul_f64 %s, %s, %s" % (pair(t), pair(x), pair(y)), "v_mul_f64 %s, %s, %s" % (pair(w), pair(y), pair(y))]
@@ -103,7 +125,7 @@ def pair_test(M):
     return out
 
 
-def decide():
+def decide(tag=""):
     """ROT = VALID & !(|p| <= eps sqrt(W[i] W[j])).  Decided on the squares with a margin of 2^-40 (the roundings of either side are
     of the order 2^-52); a pair inside the margin - or with a NaN - takes the exact expression for the whole wave."""
     return [
@@ -115,12 +137,74 @@ def decide():
         "v_cmp_lt_f64 %s, %s, %s" % (ST, pair(G), pair(RR)),        # well below: does not
         "s_or_b64 %s, vcc, %s" % (ST, ST),
         "s_andn2_b64 %s, %s, %s" % (ST, VALID, ST),                 # undecided (valid pairs only)
-        "s_cbranch_scc0 L_decided_%=",
+        "s_cbranch_scc0 L_decided_%s%%=" % tag,
     ] + nsqrt(pair(THR), pair(AB)) + [
         "v_mul_f64 %s, %s, %%[eps]" % (pair(THR), pair(THR)),
         "v_cmp_nle_f64 vcc, |%s|, %s" % (pair(P), pair(THR)),
-        "L_decided_%=:",
+        "L_decided_%s%%=:" % tag,
         "s_and_b64 %s, vcc, %s" % (ROT, VALID),
+    ]
+
+
+def rotation(sgn):
+    """(c, s) of the pair by OpenCV's formulas and the rotated row N0..N2 = c mine + (+-s) theirs; `sgn`: the register that holds
+    0x80000000 in the lanes of the pair's second (j) row."""
+    o = []
+    a = o.append
+    a("v_add_f64 %s, %s, %s" % (pair(P), pair(P), pair(P)))
+    a("v_add_f64 %s, %s, -%s" % (pair(BETA), pair(WW), pair(WP)))
+    a("v_xor_b32 %s, %s, %s" % (v(BETA + 1), v(BETA + 1), v(sgn)))
+    a("v_cmp_gt_f64 vcc, |%s|, |%s|" % (pair(P), pair(BETA)))
+    a("s_nop 1")
+    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(HI), v(BETA), v(P)))
+    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(HI + 1), v(BETA + 1), v(P + 1)))
+    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(LO), v(P), v(BETA)))
+    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(LO + 1), v(P + 1), v(BETA + 1)))
+    o += ndiv(pair(QQ), "|%s|" % pair(LO), "|%s|" % pair(HI))
+    a("v_mul_f64 %s, %s, %s" % (pair(TA), pair(QQ), pair(QQ)))
+    a("v_add_f64 %s, %s, 1.0" % (pair(TA), pair(TA)))
+    o += nsqrt(pair(TB), pair(TA))
+    a("v_mul_f64 %s, |%s|, %s" % (pair(GAM), pair(HI), pair(TB)))
+    a("v_add_f64 %s, %s, |%s|" % (pair(TA), pair(GAM), pair(BETA)))
+    a("v_add_f64 %s, %s, %s" % (pair(TC), pair(GAM), pair(GAM)))
+    o += ndiv(pair(QQ), pair(TA), pair(TC))
+    o += nsqrt(pair(R1), pair(QQ))
+    a("v_mul_f64 %s, %s, %s" % (pair(TA), pair(GAM), pair(R1)))
+    a("v_add_f64 %s, %s, %s" % (pair(TA), pair(TA), pair(TA)))
+    o += ndiv(pair(R2), pair(P), pair(TA))
+    a("v_cmp_gt_f64 vcc, 0, %s" % pair(BETA))
+    a("s_nop 1")
+    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(SS), v(R2), v(R1)))
+    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(SS + 1), v(R2 + 1), v(R1 + 1)))
+    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(CC), v(R1), v(R2)))
+    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(CC + 1), v(R1 + 1), v(R2 + 1)))
+    a("v_xor_b32 %s, %s, %s" % (v(SS + 1), v(SS + 1), v(sgn)))
+    for n_, x_, q_, t_ in ((N0, X0, Q0, T0), (N1, X1, Q1, T1), (N2, X2, P2, T2)):
+        a("v_mul_f64 %s, %s, %s" % (pair(n_), pair(CC), pair(x_)))
+        a("v_mul_f64 %s, %s, %s" % (pair(t_), pair(SS), pair(q_)))
+    for n_, t_ in ((N0, T0), (N1, T1), (N2, T2)):
+        a("v_add_f64 %s, %s, %s" % (pair(n_), pair(n_), pair(t_)))
+    return o
+
+
+def commit():
+    """The rows that rotate take the rotated row."""
+    o = []
+    a = o.append
+    for x_, n_ in ((X0, N0), (X1, N1), (X2, N2)):
+        a("v_cndmask_b32_e64 %s, %s, %s, %s" % (v(x_), v(x_), v(n_), ROT))
+        a("v_cndmask_b32_e64 %s, %s, %s, %s" % (v(x_ + 1), v(x_ + 1), v(n_ + 1), ROT))
+    return o
+
+
+def write_back():
+    """The rotated rows go back to the exchange (lanes of ROT only)."""
+    return [
+        "s_mov_b64 %s, exec" % SAVE,
+        "s_mov_b64 exec, %s" % ROT,
+        "ds_write2_b64 %%[amine], %s, %s offset1:1" % (pair(X0), pair(X1)),
+        "ds_write_b64 %%[amine], %s offset:16" % pair(X2),
+        "s_mov_b64 exec, %s" % SAVE,
     ]
 
 
@@ -187,51 +271,11 @@ def program(M):
     o += pair_test(M)
     o += decide()
     a("s_cbranch_scc0 L_skip_%=")
-    # rotation
-    a("v_add_f64 %s, %s, %s" % (pair(P), pair(P), pair(P)))
-    a("v_add_f64 %s, %s, -%s" % (pair(BETA), pair(WW), pair(WP)))
-    a("v_xor_b32 %s, %s, %s" % (v(BETA + 1), v(BETA + 1), v(SGN)))
-    a("v_cmp_gt_f64 vcc, |%s|, |%s|" % (pair(P), pair(BETA)))
-    a("s_nop 1")
-    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(HI), v(BETA), v(P)))
-    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(HI + 1), v(BETA + 1), v(P + 1)))
-    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(LO), v(P), v(BETA)))
-    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(LO + 1), v(P + 1), v(BETA + 1)))
-    o += ndiv(pair(QQ), "|%s|" % pair(LO), "|%s|" % pair(HI))
-    a("v_mul_f64 %s, %s, %s" % (pair(TA), pair(QQ), pair(QQ)))
-    a("v_add_f64 %s, %s, 1.0" % (pair(TA), pair(TA)))
-    o += nsqrt(pair(TB), pair(TA))
-    a("v_mul_f64 %s, |%s|, %s" % (pair(GAM), pair(HI), pair(TB)))
-    a("v_add_f64 %s, %s, |%s|" % (pair(TA), pair(GAM), pair(BETA)))
-    a("v_add_f64 %s, %s, %s" % (pair(TC), pair(GAM), pair(GAM)))
-    o += ndiv(pair(QQ), pair(TA), pair(TC))
-    o += nsqrt(pair(R1), pair(QQ))
-    a("v_mul_f64 %s, %s, %s" % (pair(TA), pair(GAM), pair(R1)))
-    a("v_add_f64 %s, %s, %s" % (pair(TA), pair(TA), pair(TA)))
-    o += ndiv(pair(R2), pair(P), pair(TA))
-    a("v_cmp_gt_f64 vcc, 0, %s" % pair(BETA))
-    a("s_nop 1")
-    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(SS), v(R2), v(R1)))
-    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(SS + 1), v(R2 + 1), v(R1 + 1)))
-    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(CC), v(R1), v(R2)))
-    a("v_cndmask_b32 %s, %s, %s, vcc" % (v(CC + 1), v(R1 + 1), v(R2 + 1)))
-    a("v_xor_b32 %s, %s, %s" % (v(SS + 1), v(SS + 1), v(SGN)))
-    for n_, x_, q_, t_ in ((N0, X0, Q0, T0), (N1, X1, Q1, T1), (N2, X2, P2, T2)):
-        a("v_mul_f64 %s, %s, %s" % (pair(n_), pair(CC), pair(x_)))
-        a("v_mul_f64 %s, %s, %s" % (pair(t_), pair(SS), pair(q_)))
-    for n_, t_ in ((N0, T0), (N1, T1), (N2, T2)):
-        a("v_add_f64 %s, %s, %s" % (pair(n_), pair(n_), pair(t_)))
-    # commit for the rows that rotate
-    for x_, n_ in ((X0, N0), (X1, N1), (X2, N2)):
-        a("v_cndmask_b32_e64 %s, %s, %s, %s" % (v(x_), v(x_), v(n_), ROT))
-        a("v_cndmask_b32_e64 %s, %s, %s, %s" % (v(x_ + 1), v(x_ + 1), v(n_ + 1), ROT))
+    o += rotation(SGN)
+    o += commit()
     a("v_cndmask_b32_e64 %s, 0, %s, %s" % (v(TMP), v(SWBIT), ROT))
     a("v_or_b32 %%[chg], %%[chg], %s" % v(TMP))
-    a("s_mov_b64 %s, exec" % SAVE)
-    a("s_mov_b64 exec, %s" % ROT)
-    a("ds_write2_b64 %%[amine], %s, %s offset1:1" % (pair(X0), pair(X1)))
-    a("ds_write_b64 %%[amine], %s offset:16" % pair(X2))
-    a("s_mov_b64 exec, %s" % SAVE)
+    o += write_back()
     a("L_skip_%=:")
     # the next step's pair (requested before the bookkeeping: more instructions between the request and the use)
     o += decode(E1, SBE1)
@@ -270,17 +314,203 @@ def program(M):
     return [l.replace('%%[', '%[') for l in o]
 
 
+# ---- M = 12: the schedule unrolled ------------------------------------------------------------------------------------
+# The 12-row schedule (tools/gen_jacobi_schedule.py) is PRO prologue steps followed by PER steps that repeat with the sweep base
+# one higher each time.  What a step's table entry says depends on the lane and the step only, so the loop is emitted as one copy
+# of the step body per step: the prologue copies, then - aligned, L_loop - the copies of the period.
+#   slot j = the j-th step of the period.  Per lane and slot two registers are filled ONCE per solve, before the first step, from
+#   the table in LDS: U_AP[j] the address of the partner's row in the exchange (the lane's own row where it idles or its row belongs
+#   to no problem) and U_K[j] = bit 31: the lane's row is the pair's second row | bits 0-1: the pair's sweep relative to the base.
+#   A prologue step is the slot PER - PRO steps further on with fewer pairs: its valid lanes have the same partner and sign there and
+#   belong to sweep 0 (checked below), so prologue copies use that slot's registers and the constant sweep bit 1.
+#   VALID of a step = its lanes with a partner (a 16-bit constant per step, the same in every lane group) & ACT.
+#   U_BB = 1 << sweep base, doubled where a copy closes a sweep; only those copies carry the sweep bookkeeping and the exit test.
+U_AP = list(range(234, 246))
+U_K = [158, 159, 176, 177, 178, 179, 246, 247, 248, 249, 250, 251]
+U_SGN, U_TMP, U_BB, U_TMP2 = 252, 253, 254, 255
+U_ROW, U_QI = N0, N1                 # set-up only
+
+
+class Unrolled:
+    """The constants of the unrolled M = 12 program, from the schedule alone (tests/test_jacobi_unrolled.py walks them)."""
+
+    def __init__(self):
+        import gen_jacobi_schedule
+        self.n = 12
+        self.tab, self.pro, self.per = gen_jacobi_schedule.table(12, 12)
+        self.steps = self.pro + self.per
+        assert self.per == len(U_AP) == len(U_K)
+        assert self.pro <= self.per
+
+    # what the table says about (step, row)
+    def partner(self, t, r):
+        return self.tab[t][r] & 15
+
+    def has_pair(self, t, r):
+        return self.partner(t, r) != r
+
+    def second(self, t, r):
+        return (self.tab[t][r] >> 4) & 1
+
+    def srel(self, t, r):
+        return (self.tab[t][r] >> 5) & 3
+
+    def closes(self, t):
+        """None, or the sweep (relative to the base) that is complete after step t."""
+        e = self.tab[t][0]
+        return ((e >> 8) & 3) if e & 0x80 else None
+
+    # what the unrolled program uses
+    def copies(self):
+        """Execution order: every step once, then the period again and again."""
+        return list(range(self.steps))
+
+    def next_copy(self, t):
+        return t + 1 if t + 1 < self.steps else self.pro
+
+    def slot(self, t):
+        """The slot whose registers the copy of step t reads."""
+        return t - self.pro if t >= self.pro else t + self.per - self.pro
+
+    def slot_step(self, j):
+        """The step whose table entries fill slot j."""
+        return self.pro + j
+
+    def valid16(self, t):
+        """Bit r: row r has a partner in step t."""
+        return sum(1 << r for r in range(self.n) if self.has_pair(t, r))
+
+    def lane_constants(self, t, lane):
+        """(partner row, valid, second row of the pair, sweep relative to the base of the copy's period, closing sweep or None) the
+        copy of step t uses in `lane`; the base of the prologue's copies is that of the first period."""
+        r = lane & 15
+        if r >= self.n:
+            return r, False, 0, 0, self.closes(t)
+        ts = self.slot_step(self.slot(t))
+        valid = bool(self.valid16(t) >> r & 1)
+        srel = self.srel(ts, r) if t >= self.pro else 0
+        return (self.partner(ts, r) if valid else r), valid, self.second(ts, r), srel, self.closes(t)
+
+    def check(self):
+        for t in range(self.pro):          # a prologue step = its slot with fewer pairs, all of sweep 0
+            ts = self.slot_step(self.slot(t))
+            assert self.closes(t) is None
+            for r in range(self.n):
+                if self.has_pair(t, r):
+                    assert self.partner(t, r) == self.partner(ts, r) and self.second(t, r) == self.second(ts, r)
+                    assert self.srel(t, r) == 0 and self.srel(ts, r) == 1
+        for t in range(self.steps):
+            assert self.closes(t) in (None, 0)     # U_BB is the bit of the sweep a closing copy completes
+        assert self.closes(self.steps - 1) == 0    # the loop's backward branch sits behind a closing copy
+
+
+def decode12(u, t):
+    """VALID of step t; its partner rows are requested."""
+    m = u.valid16(t)
+    lit = "0x%08x" % (m | m << 16)
+    ap = U_AP[u.slot(t)]
+    return [
+        "s_and_b32 s62, s60, %s" % lit,
+        "s_and_b32 s63, s61, %s" % lit,
+        "ds_read_b128 v[%d:%d], %s" % (PLO, PLO + 3, v(ap)),
+        "ds_read_b64 %s, %s offset:16" % (pair(P2), v(ap)),
+    ]
+
+
+def program12():
+    u = Unrolled()
+    u.check()
+    o = []
+    a = o.append
+    # ---- set-up
+    for dst, src in ((X0, "%[x0]"), (X1, "%[x1]"), (X2, "%[x2]")):
+        a("v_mov_b64 %s, %s" % (pair(dst), src))
+    a("v_mov_b64 %s, 1.0" % pair(ONE))
+    a("v_mov_b32 %s, 1" % v(U_BB))
+    for j in range(u.per):                         # the lane's entries of the period's steps
+        a("ds_read_b32 %s, %%[tper] offset:%d" % (v(U_K[j]), 4 * u.n * j))
+    a("v_and_b32 %s, 15, %%[lane]" % v(U_ROW))
+    a("v_sub_u32 %s, %s, %%[base]" % (v(U_QI), v(U_ROW)))
+    a("v_cmp_ne_u32 %s, 0, %%[act]" % ACT)
+    a("s_waitcnt lgkmcnt(0)")
+    for j in range(u.per):
+        e, ap = U_K[j], U_AP[j]
+        a("v_and_b32 %s, 15, %s" % (v(U_TMP), v(e)))
+        a("v_cmp_ne_u32 vcc, %s, %s" % (v(U_TMP), v(U_QI)))
+        a("s_and_b64 %s, vcc, %s" % (VALID, ACT))
+        a("v_add_u32 %s, %s, %%[base]" % (v(U_TMP), v(U_TMP)))
+        a("v_cndmask_b32_e64 %s, %s, %s, %s" % (v(U_TMP), v(U_ROW), v(U_TMP), VALID))
+        a("v_lshl_add_u32 %s, %s, 7, %%[axch]" % (v(ap), v(U_TMP)))
+        a("v_bfe_u32 %s, %s, 5, 2" % (v(U_TMP), v(e)))
+        a("v_and_b32 %s, 0x80000000, %s" % (v(e), v(e)))
+        a("v_or_b32 %s, %s, %s" % (v(e), v(e), v(U_TMP)))
+    o += decode12(u, 0)
+    a("s_cmp_lg_u64 %s, 0" % ACT)
+    a("s_cbranch_scc0 L_done_%=")
+    # ---- the steps
+    for t in u.copies():
+        k = U_K[u.slot(t)]
+        if t == u.pro:
+            a(".p2align %d" % LOOP_ALIGN)            # the loop's address relative to the fetch lines must not depend on the code in front of it
+            for _ in range(LOOP_NOPS):
+                a("s_nop 0")
+            a("L_loop_%=:")
+        o += pair_test(12, wait=0)
+        o += decide("%d_" % t)
+        a("s_cbranch_scc0 L_skip_%d_%%=" % t)
+        a("v_and_b32 %s, 0x80000000, %s" % (v(U_SGN), v(k)))
+        o += rotation(U_SGN)
+        o += commit()
+        if t >= u.pro:
+            a("v_lshlrev_b32 %s, %s, %s" % (v(U_TMP), v(k), v(U_BB)))      # 1 << (base + the pair's relative sweep)
+            a("v_cndmask_b32_e64 %s, 0, %s, %s" % (v(U_TMP), v(U_TMP), ROT))
+        else:
+            a("v_cndmask_b32_e64 %s, 0, 1, %s" % (v(U_TMP), ROT))           # sweep 0
+        a("v_or_b32 %%[chg], %%[chg], %s" % v(U_TMP))
+        o += write_back()
+        a("L_skip_%d_%%=:" % t)
+        # the next step's pair (requested before the bookkeeping: more instructions between the request and the use)
+        o += decode12(u, u.next_copy(t))
+        if u.closes(t) is None:
+            continue
+        # sweep bookkeeping: the sweep of U_BB is complete
+        a("s_mov_b64 %s, %s" % (CL, ACT))
+        a("v_and_b32 %s, %%[chg], %s" % (v(U_TMP2), v(U_BB)))
+        a("v_cmp_ne_u32 vcc, 0, %s" % v(U_TMP2))
+        a("s_and_b64 %s, vcc, %s" % (ST, CL))                        # rows (of closing problems) that rotated in it
+        a("v_mov_b32 %s, s70" % v(U_TMP2))
+        a("v_and_b32 %s, %s, %%[pm]" % (v(U_TMP2), v(U_TMP2)))
+        a("v_cmp_eq_u32 vcc, 0, %s" % v(U_TMP2))                     # no row of my problem did: JacobiSVDImpl_ stops
+        a("v_lshrrev_b32 %s, 24, %s" % (v(U_TMP), v(U_BB)))
+        a("v_cmp_ne_u32 %s, 0, %s" % (ST, v(U_TMP)))                  # 25 sweeps: not reproduced here (flag)
+        a("s_or_b64 vcc, vcc, %s" % ST)
+        a("s_and_b64 vcc, vcc, %s" % CL)
+        a("s_andn2_b64 %s, %s, vcc" % (ACT, ACT))
+        a("s_and_b64 %s, %s, %s" % (ST, ST, CL))
+        a("v_cndmask_b32_e64 %s, 0, 1, %s" % (v(U_TMP), ST))
+        a("v_or_b32 %%[flag], %%[flag], %s" % v(U_TMP))
+        a("s_and_b64 %s, %s, %s" % (VALID, VALID, ACT))      # a problem that has just stopped takes no part in the next step
+        a("v_lshlrev_b32 %s, 1, %s" % (v(U_BB), v(U_BB)))
+        a("s_cmp_lg_u64 %s, 0" % ACT)
+        a("s_cbranch_scc1 L_loop_%=" if u.next_copy(t) == u.pro else "s_cbranch_scc0 L_done_%=")
+    a("L_done_%=:")
+    a("s_waitcnt lgkmcnt(0)")
+    for dst, src in (("%[x0]", X0), ("%[x1]", X1), ("%[x2]", X2)):
+        a("v_mov_b64 %s, %s" % (dst, pair(src)))
+    return [l.replace('%%[', '%[') for l in o]
+
+
 def main():
     print("// generated by tools/gen_jacobi_asm.py - do not edit")
-    print("// The step loop of jacobi_rows (svo_epnp_ord_dev.h) for M = 12, 6, 3 columns of A; registers v140..v253, s60..s71.")
+    print("// The step loop of jacobi_rows (svo_epnp_ord_dev.h) for M = 12, 6, 3 columns of A; registers v140..v255, s60..s71.")
     for M in (12, 6, 3):
-        lines = program(M)
+        lines = program12() if M == 12 else program(M)
         print("#define EO_JACOBI_ASM_%d \\" % M)
         for i, l in enumerate(lines):
             end = " \\" if i + 1 < len(lines) else ""
             print('  "%s\\n\\t"%s' % (l, end))
         print("")
-    clob = ", ".join('"v%d"' % i for i in range(140, 254)) + ", " + ", ".join('"s%d"' % i for i in range(60, 72)) + ', "vcc", "scc", "memory"'
+    clob = ", ".join('"v%d"' % i for i in range(140, 256)) + ", " + ", ".join('"s%d"' % i for i in range(60, 72)) + ', "vcc", "scc", "memory"'
     print("#define EO_JACOBI_ASM_CLOBBERS " + clob)
 
 

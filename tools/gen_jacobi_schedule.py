@@ -136,7 +136,7 @@ def run_scheduled(A, n, m, tab, pro, per, spp):
             sbase += spp
 
 
-def build(n, m, trials, rnd):
+def build(n, m, trials, rnd, log=True):
     P = len(pairs_of(n))
     seq, steps = schedule(n, 12)
     found = None
@@ -170,9 +170,29 @@ def build(n, m, trials, rnd):
         assert all(x.hex() == y.hex() for ra, rb in zip(As, Ap) for x, y in zip(ra, rb)), "rows differ (n %d trial %d)" % (n, trial)
         assert all(x.hex() == y.hex() for x, y in zip(Ws, Wp))
         longest = max(longest, nsteps)
-    sys.stderr.write("n = %2d: prologue %d + period %d steps (%d sweep(s) per period), %d steps in all; verified on %d matrices, longest run %d steps\n"
-                     % (n, pro, per, spp, pro + per, trials, longest))
+    if log:
+        sys.stderr.write("n = %2d: prologue %d + period %d steps (%d sweep(s) per period), %d steps in all; verified on %d matrices, longest run %d steps\n"
+                         % (n, pro, per, spp, pro + per, trials, longest))
     return tab, pro, per, spp
+
+
+def entries(n, row):
+    """The 16-bit entries of one step (emit's encoding): one per matrix row."""
+    e = [r for r in range(n)]            # idle: partner = the row itself
+    closing = [s for (s, i, j) in row if (i, j) == (n - 2, n - 1)]
+    for (s, i, j) in row:
+        e[i] = j | (s << 5)
+        e[j] = i | (1 << 4) | (s << 5)
+    if closing:
+        e = [x | 0x80 | (closing[0] << 8) for x in e]
+    return e
+
+
+def table(n, m):
+    """(entries per step, prologue steps, period steps) of the n-row schedule, without the numerical verification of build()."""
+    tab, pro, per, spp = build(n, m, 0, None, log=False)
+    assert spp == 1
+    return [entries(n, row) for row in tab], pro, per
 
 
 def emit(n, tab, pro, per, spp, out):
@@ -181,13 +201,7 @@ def emit(n, tab, pro, per, spp, out):
     out.append("#define EO_TAB%d_SWEEPS %d      // sweeps per period" % (n, spp))
     out.append("static __constant__ unsigned short c_tab%d[EO_TAB%d_STEPS][%d] = {" % (n, n, n))
     for row in tab:
-        e = [r for r in range(n)]            # idle: partner = the row itself
-        closing = [s for (s, i, j) in row if (i, j) == (n - 2, n - 1)]
-        for (s, i, j) in row:
-            e[i] = j | (s << 5)
-            e[j] = i | (1 << 4) | (s << 5)
-        if closing:
-            e = [x | 0x80 | (closing[0] << 8) for x in e]
+        e = entries(n, row)
         out.append("  {" + ", ".join("0x%03x" % x for x in e) + "},")
     out.append("};")
 
