@@ -311,6 +311,31 @@ class Svo:
                                             _p(acc)))
         return bi, b, s, acc, assigned
 
+    def match_greedy_gated(self, q, t, assigned, max_dist, ratio, q_xy, t_xy, boxes, F, q_skip=None, vetoed=None):
+        """svo_match_greedy_gated: match_greedy with the epipolar veto of pass 1.  q_xy: M x 2 (last-frame point of each row),
+        t_xy: N x 2, boxes: n x {left, right, top, bottom} (None / empty: no gate), F: 3 x 3.  Returns match_greedy's tuple
+        plus `vetoed` (M uint8; `vetoed`, if given, is the buffer the entry writes into)."""
+        q = _u8(q).reshape(-1, 32); t = _u8(t).reshape(-1, 32)
+        M, N = len(q), len(t)
+        assigned = _u8(assigned).copy()
+        sk = None if q_skip is None else _u8(q_skip)
+        qxy = np.ascontiguousarray(q_xy, np.float32).reshape(-1, 2)
+        txy = np.ascontiguousarray(t_xy, np.float32).reshape(-1, 2)
+        if len(qxy) != M or len(txy) != N:
+            raise SvoError("match_greedy_gated: q_xy / t_xy must hold one point per descriptor row")
+        bx = None if boxes is None or len(boxes) == 0 else np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        nb = 0 if bx is None else len(bx)
+        Fm = np.ascontiguousarray(F, np.float64).reshape(9)
+        bi = np.zeros(M, np.int32); b = np.zeros(M, np.int32); s = np.zeros(M, np.int32)
+        acc = np.zeros(M, np.uint8)
+        vet = np.zeros(M, np.uint8) if vetoed is None else vetoed
+        if vet.dtype != np.uint8 or vet.shape != (M,) or not vet.flags.c_contiguous:
+            raise SvoError("match_greedy_gated: vetoed must be a contiguous uint8 array of M entries")
+        self._chk(self.lib.svo_match_greedy_gated(self.h, _p(q), _p(sk), M, _p(t), N, _p(assigned), int(max_dist),
+                                                  C.c_float(ratio), _p(qxy), _p(txy), _p(bx), nb, _p(Fm), _p(bi), _p(b),
+                                                  _p(s), _p(acc), _p(vet)))
+        return bi, b, s, acc, assigned, vet
+
     def bf_match(self, q, t):
         q = _u8(q).reshape(-1, 32); t = _u8(t).reshape(-1, 32)
         M, N = len(q), len(t)

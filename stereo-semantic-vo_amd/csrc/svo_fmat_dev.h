@@ -75,7 +75,7 @@ __device__ inline void fmat8_wave(EpnpWaveLds& S, uint32_t keep, const double (&
     }
   }
   EPNP_WAVE_SYNC();
-  epnp_eig12_wave(S);
+  epnp_eig12_wave<true>(S);   // clustered small eigenvalues: the tight exit test
   EPNP_WAVE_SYNC();
   int kmin = 0;
   double wmin = S.A[0];
