@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 7   /* 7, backward-compatible additions: svo_lk_track_bgr, svo_lk_batch_bgr_dev, svo_lk_chain_bgr_dev,
+#define SVO_ABI_VERSION 7   /* 7, backward-compatible additions: svo_sgbm_process_mode, svo_sgbm_process_bgr_mode, svo_sgbm_batch_mode_dev,
+                              svo_sgbm_batch_bgr_mode_dev and the option "sgbm_mode" (the eight-direction MODE_HH, see "semi-global block
+                              matching: MODE_HH" below); no existing entry changed.
+                              7, backward-compatible additions: svo_lk_track_bgr, svo_lk_batch_bgr_dev, svo_lk_chain_bgr_dev,
                               svo_lk_debug_level_bgr (Lucas-Kanade on 8UC3 BGR frames, see "sparse pyramidal Lucas-Kanade" below); no
                               existing entry changed.
                               7, backward-compatible additions: svo_bgr_to_gray, svo_track_frame_bgr, svo_track_batch_bgr_dev,
@@ -216,6 +219,9 @@ void svo_destroy(svo_ctx* ctx);
  * reference's live configuration, src/Tracking.cc:225-228 + src/frame.cc:82-91 - on the reference's colour input through the _bgr
  * entries; the gray entries hand MSA B = G = R copies of the gray), both read per keypoint as frame::computekeypoint_r /
  * disp2Depth do.
+ * "sgbm_mode" (default 0 = SVO_SGBM_MODE_SGBM; 1 = SVO_SGBM_MODE_HH): the mode of the SGBM maps of depth_source 3 - of the gray
+ * solver in the gray tracker entries and in the _bgr ones, and of the cn = 3 solver there with "sgbm_colour" = 1 (default 0: the
+ * _bgr entries run SGBM on the gray they make).  Other depth sources ignore it.
  * "fe_cu_percent" (default 12 = 32 of the 256 CUs, 10..100): share of the compute units (whole 32-bit words of the CU mask; measured
  * with tools/microbench/cu_mask_probe: the first word is FOUR CUs ON EACH of the eight XCDs, not one XCD) the front-end stream of
  * svo_track_batch_dev may use.  Its kernels would otherwise fill every CU while the ordered tail runs beside them, and the
@@ -774,6 +780,31 @@ int svo_sgbm_process_bgr(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int s
  * context's volumes (the path sums are int32 here).  Identical to B calls of svo_sgbm_process_bgr.  Synchronises. */
 int svo_sgbm_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int width, int height, int B,
                            const svo_sgbm_params* params, float* d_disp);
+
+/* ---- semi-global block matching: MODE_HH (ABI-7 additions; no existing entry changed) ---------------------------------------
+ * cv::StereoSGBM's full eight-path mode beside MODE_SGBM; the reference sets MODE_SGBM, which stays the default everywhere.
+ * Directions 0 to 4 are as above; 5, 6 and 7 have their predecessor at (+1,+1), (0,+1) and (-1,+1): OpenCV's second pass, rows
+ * bottom to top and columns right to left from zeroed buffers, so the border rule (a predecessor outside the image counts as all
+ * zeros with m = 0) is the same, mirrored.  sum4 = v0 + v1 + v2 + v3 and S4 = sat16(sum4) as before; sum8 = S4 + v4 + v5 + v6 + v7
+ * in int32 and S = sat16(sum8): one saturation of the second pass's four steps added together.  The winner reads S; there is no
+ * in-row fifth direction beyond v4.  With three channels the v are the unwrapped int32 steps and sum8 saturates on both sides.
+ * Everything else is the gray or the colour contract, unchanged.  The written contract is DESIGN.md section 8 "f-4 SGBM:
+ * MODE_HH" (parity with OpenCV unpinned); its executable form is tests/sgbm_hh_ref.py, which the device
+ * equals bit for bit.  The two further path volumes the mode needs are allocated the first time a context is asked for it. */
+enum { SVO_SGBM_MODE_SGBM = 0, SVO_SGBM_MODE_HH = 1 };   /* OpenCV's values; there is no MODE_SGBM_3WAY */
+
+/* svo_sgbm_process, svo_sgbm_process_bgr, svo_sgbm_batch_dev and svo_sgbm_batch_bgr_dev with a mode after the parameters (those
+ * four are these with SVO_SGBM_MODE_SGBM).  A mode other than the two above is SVO_E_INVALID, answered like the other argument
+ * checks on the host, before the context or a device is touched.  After a svo_sgbm_process*_mode call svo_sgbm_debug_volume's
+ * which = 1 is still S4 and which = 2 is S over all eight directions. */
+int svo_sgbm_process_mode(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int width, int height,
+                          const svo_sgbm_params* params, int mode, int16_t* disp16, float* disp);
+int svo_sgbm_process_bgr_mode(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int width, int height,
+                              const svo_sgbm_params* params, int mode, int16_t* disp16, float* disp);
+int svo_sgbm_batch_mode_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int width, int height, int B,
+                            const svo_sgbm_params* params, int mode, float* d_disp);
+int svo_sgbm_batch_bgr_mode_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int width, int height, int B,
+                                const svo_sgbm_params* params, int mode, float* d_disp);
 
 /* ---- sparse pyramidal Lucas-Kanade (ABI-7 additions; no existing entry changed) --------------------------------------------
  * The dynamic-keypoint loop of the reference's Tracking::Track (src/Tracking.cc:189-223, commented out there): points inside

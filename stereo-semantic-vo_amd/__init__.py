@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "svo_det_sync", "svo_det_debug_tensor", "svo_det_detect_planar", "svo_det_profile", "svo_det_layer_times",
     "svo_sgbm_default_params", "svo_sgbm_process", "svo_sgbm_batch_dev", "svo_sgbm_debug_volume", "svo_sgbm_filter_speckles",
     "svo_sgbm_default_params_bgr", "svo_sgbm_process_bgr", "svo_sgbm_batch_bgr_dev", "svo_debug_track_depths",
+    "svo_sgbm_process_mode", "svo_sgbm_process_bgr_mode", "svo_sgbm_batch_mode_dev", "svo_sgbm_batch_bgr_mode_dev",
     "svo_lk_default_params", "svo_lk_track", "svo_lk_batch_dev", "svo_lk_chain_dev", "svo_lk_debug_level",
     "svo_lk_track_bgr", "svo_lk_batch_bgr_dev", "svo_lk_chain_bgr_dev", "svo_lk_debug_level_bgr",
 ]
@@ -635,23 +636,24 @@ class Svo:
         return out
 
     # ---- semi-global block matching (include/svo.h: svo_sgbm_*; the body of the reference's frame::ElasMatch) ----
-    def sgbm_process(self, grayL, grayR, params=None):
+    # mode: SGBM_MODE_SGBM (0, five directions, what the reference sets) or SGBM_MODE_HH (1, all eight directions in two passes)
+    def sgbm_process(self, grayL, grayR, params=None, mode=0):
         """One gray pair -> (disp16 int16 H x W, -16 = invalid; disp float32 = disp16 / 16, -1 = invalid)."""
         gl, gr = _u8(grayL), _u8(grayR)
         H, W = gl.shape
         params = params or sgbm_default_params(H)
         d16 = np.zeros((H, W), np.int16); d = np.zeros((H, W), np.float32)
-        self._chk(self.lib.svo_sgbm_process(self.h, _p(gl), _p(gr), W, W, H, C.byref(params), _p(d16), _p(d)))
+        self._chk(self.lib.svo_sgbm_process_mode(self.h, _p(gl), _p(gr), W, W, H, C.byref(params), int(mode), _p(d16), _p(d)))
         self._sgbm_shape = (H, W, params.numDisparities)
         return d16, d
 
-    def sgbm_batch_dev(self, d_L, d_R, stride, W, H, B, d_disp, params=None):
+    def sgbm_batch_dev(self, d_L, d_R, stride, W, H, B, d_disp, params=None, mode=0):
         """B device-resident gray pairs -> B device-resident float disparity maps (disp16 / 16, -1 = invalid)."""
         params = params or sgbm_default_params(H)
-        self._chk(self.lib.svo_sgbm_batch_dev(self.h, C.c_void_p(d_L), C.c_void_p(d_R), int(stride), int(W), int(H), int(B),
-                                              C.byref(params), C.c_void_p(d_disp)))
+        self._chk(self.lib.svo_sgbm_batch_mode_dev(self.h, C.c_void_p(d_L), C.c_void_p(d_R), int(stride), int(W), int(H), int(B),
+                                                   C.byref(params), int(mode), C.c_void_p(d_disp)))
 
-    def sgbm_process_bgr(self, bgrL, bgrR, params=None):
+    def sgbm_process_bgr(self, bgrL, bgrR, params=None, mode=0):
         """One 8UC3 pair (H x W x 3) through the cn = 3 solver -> (disp16, disp) as sgbm_process; sgbm_debug_volume describes it."""
         a, b = _u8(bgrL), _u8(bgrR)
         H, W = a.shape[:2]
@@ -659,15 +661,15 @@ class Svo:
             raise SvoError("sgbm_process_bgr: two H x W x 3 uint8 images expected")
         params = params or sgbm_default_params_bgr(H)
         d16 = np.zeros((H, W), np.int16); d = np.zeros((H, W), np.float32)
-        self._chk(self.lib.svo_sgbm_process_bgr(self.h, _p(a), _p(b), 3 * W, W, H, C.byref(params), _p(d16), _p(d)))
+        self._chk(self.lib.svo_sgbm_process_bgr_mode(self.h, _p(a), _p(b), 3 * W, W, H, C.byref(params), int(mode), _p(d16), _p(d)))
         self._sgbm_shape = (H, W, params.numDisparities)
         return d16, d
 
-    def sgbm_batch_bgr_dev(self, d_L, d_R, stride, W, H, B, d_disp, params=None):
+    def sgbm_batch_bgr_dev(self, d_L, d_R, stride, W, H, B, d_disp, params=None, mode=0):
         """B device-resident 8UC3 pairs (rows `stride` >= 3 W bytes apart) -> B device-resident float disparity maps."""
         params = params or sgbm_default_params_bgr(H)
-        self._chk(self.lib.svo_sgbm_batch_bgr_dev(self.h, C.c_void_p(d_L), C.c_void_p(d_R), int(stride), int(W), int(H), int(B),
-                                                  C.byref(params), C.c_void_p(d_disp)))
+        self._chk(self.lib.svo_sgbm_batch_bgr_mode_dev(self.h, C.c_void_p(d_L), C.c_void_p(d_R), int(stride), int(W), int(H), int(B),
+                                                       C.byref(params), int(mode), C.c_void_p(d_disp)))
 
     def sgbm_filter_speckles(self, disp16):
         """cv::filterSpeckles(disp16, -16, 100, 512) on an int16 H x W map; returns the filtered copy."""
@@ -676,7 +678,8 @@ class Svo:
         return d
 
     def sgbm_debug_volume(self, which):
-        """Stage `which` of the last sgbm_process call: 0 C, 1 S4, 2 S (H x W x D int16), 3 disp2, 4 disp1 before the speckle filter (H x W)."""
+        """Stage `which` of the last sgbm_process call: 0 C, 1 S4, 2 S (H x W x D int16; over all eight directions after a mode 1
+        call), 3 disp2, 4 disp1 before the speckle filter (H x W)."""
         H, W, D = self._sgbm_shape
         out = np.zeros((H, W, D) if which < 3 else (H, W), np.int16)
         self._chk(self.lib.svo_sgbm_debug_volume(self.h, int(which), _p(out)))
@@ -799,6 +802,9 @@ def elas_default_params(setting=0):
     if rc != 0:
         raise SvoError("svo_elas_default_params failed")
     return p
+
+
+SGBM_MODE_SGBM, SGBM_MODE_HH = 0, 1     # include/svo.h: SVO_SGBM_MODE_*
 
 
 class SgbmParams(C.Structure):

@@ -428,6 +428,11 @@ extern "C" int svo_set_option(svo_ctx* ctx, const char* key, int value) {
     ctx->opt_depth_source = value;
     return SVO_OK;
   }
+  if (!strcmp(key, "sgbm_mode")) {   // depth_source 3: 0 MODE_SGBM (five directions, one pass), 1 MODE_HH (eight directions, two passes)
+    if (value != SVO_SGBM_MODE_SGBM && value != SVO_SGBM_MODE_HH) return SVO_E_INVALID;
+    ctx->opt_sgbm_mode = value;
+    return SVO_OK;
+  }
   if (!strcmp(key, "sgbm_colour")) {   // depth_source 3 in the _bgr tracker entries: 0 SGBM on the gray they make, 1 cn = 3 SGBM on the BGR frames
     if (value < 0 || value > 1) return SVO_E_INVALID;
     ctx->opt_sgbm_colour = value != 0;

@@ -195,6 +195,7 @@ struct svo_ctx {
   svo_camera cam{};
   int track_frame = 0;
 
+  int opt_sgbm_mode = 0;          // svo_set_option("sgbm_mode"): the mode of depth_source 3's maps, 0 MODE_SGBM (five directions), 1 MODE_HH (eight)
   bool opt_sgbm_colour = false;   // svo_set_option("sgbm_colour"): with depth_source 3 the _bgr tracker entries run the cn = 3 solver on their BGR frames
   int opt_depth_source = 0; // svo_set_option("depth_source"): 0 sparse epipolar stereo, 1 dense ELAS map, 2 dense MSA map, 3 dense SGBM map
   int opt_fast_cand_cap = 2048;   // svo_set_option("fast_cand_cap"): entries of k_fast's candidate list (<= 2048)
@@ -349,13 +350,13 @@ void svo_msa_release(svo_ctx* ctx);
 void svo_sgbm_release(svo_ctx* ctx);
 void svo_lk_release(svo_ctx* ctx);
 // svo_sgbm.hip: B resident gray pairs (pair b at dL / dR + b * frame) -> B float maps at d_disp, enqueued on `s` in chunks of
-// svo_sgbm_chunk() pairs; no synchronisation
+// svo_sgbm_chunk() pairs; no synchronisation.  mode: SVO_SGBM_MODE_SGBM or SVO_SGBM_MODE_HH
 int svo_sgbm_run_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,
-                     const svo_sgbm_params* p, float* d_disp);
+                     const svo_sgbm_params* p, int mode, float* d_disp);
 int svo_sgbm_chunk();
 // the same on 8UC3 pairs (stride >= 3 W, the cn = 3 parameter set), in chunks of svo_sgbm_chunk_bgr() pairs
 int svo_sgbm_run_bgr_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H,
-                         int B, const svo_sgbm_params* p, float* d_disp);
+                         int B, const svo_sgbm_params* p, int mode, float* d_disp);
 int svo_sgbm_chunk_bgr();
 void svo_track_release(svo_ctx* ctx);   // tracker states, work records, second stream, events
 int svo_upload_image(svo_ctx* ctx, const uint8_t* gray, int stride, int slot);

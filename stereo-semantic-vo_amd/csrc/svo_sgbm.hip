@@ -19,6 +19,11 @@
 // planes and accumulates into T; P1 and P2 are three times gray's; C is the low 16 bits of the true block sum; the carried
 // Lp and m are wrapped to int16 while the unwrapped int32 step goes into A and B, which are int32 volumes there (so a chunk
 // of the arena holds half as many colour pairs).
+//
+// MODE_HH (DESIGN.md section 8 "f-4 SGBM: MODE_HH"; the restatement is tests/sgbm_hh_ref.py): the second pass's directions 5,
+// 6 and 7 (predecessors below) run through the same k_sgbm_paths - 5 / 6, then 7 - into two further volumes X = L5 + L7 and
+// Y = L6 (two directions are the most an int16 holds; int32 with CN = 3), which the arena gets the first time a context asks
+// for the mode; k_sgbm_winner<.., 1> still walks direction 4 along the row and forms S = sat16(S4 + L4 + X + Y).
 #include "svo_internal.h"
 
 #include <limits.h>
@@ -36,6 +41,7 @@ constexpr int16_t SGBM_INVALID = -16;
 
 struct SgbmArena {
   int16_t *C = nullptr, *A = nullptr, *B = nullptr;       // cap_n volumes each (colour calls use A and B as int32 volumes of half as many pairs)
+  int16_t *X = nullptr, *Y = nullptr;                     // MODE_HH: L5 + L7 and L6, like A and B; null until a call asks for the mode
   int16_t *dbgS4 = nullptr, *dbgS = nullptr;              // svo_sgbm_process only (one volume each)
   int16_t *disp1 = nullptr, *dbg_disp2 = nullptr, *dbg_lr = nullptr;
   uint32_t* bid = nullptr;
@@ -44,7 +50,7 @@ struct SgbmArena {
   float* dispf = nullptr;                                 // svo_sgbm_process: the float map
   size_t cap_vol = 0, cap_pix = 0, cap_img_bytes = 0;     // elements per image the buffers were made for
   int cap_n = 0;
-  bool has_dbg = false;
+  bool has_dbg = false, has_hh = false;
   int W = 0, H = 0, D = 0;                                // the last svo_sgbm_process call (svo_sgbm_debug_volume)
   bool dbg_valid = false;
   hipStream_t last = nullptr;
@@ -134,22 +140,28 @@ __global__ void k_sgbm_vsum(const int16_t* T, int16_t* C, int W, int H, int D, s
   C[(size_t)y * row + off] = (int16_t)sum;
 }
 
-// Path p of direction `dir` (predecessor offsets (-1,0), (-1,-1), (0,-1), (+1,-1), (+1,0)): first pixel, step, length (0: no such path)
+// Path p of direction `dir` (predecessor offsets (-1,0), (-1,-1), (0,-1), (+1,-1), (+1,0), and MODE_HH's (+1,+1), (0,+1), (-1,+1)):
+// first pixel, step, length (0: no such path).  Directions 5 to 7 are 3 to 1 upside down: first pixel in the bottom row or a side
+// column, sy = -1.
 __device__ __forceinline__ void sgbm_path(int dir, int p, int W, int H, int D, int& x, int& y, int& sx, int& sy, int& len) {
   const int nx = W - D;
   len = 0; x = D; y = 0; sx = 0; sy = 0;
   if (p < 0) return;
+  const bool up = dir > 4;                       // rows bottom to top
   if (dir == 0 || dir == 4) {
     if (p >= H) return;
     y = p; x = dir == 0 ? D : W - 1; sx = dir == 0 ? 1 : -1; len = nx;
-  } else if (dir == 2) {
+  } else if (dir == 2 || dir == 6) {
     if (p >= nx) return;
-    x = D + p; sy = 1; len = H;
+    x = D + p; y = up ? H - 1 : 0; sy = up ? -1 : 1; len = H;
   } else {
     if (p >= nx + H - 1) return;
-    sy = 1; sx = dir == 1 ? 1 : -1;
-    if (p < nx) { x = D + p; y = 0; } else { x = dir == 1 ? D : W - 1; y = p - nx + 1; }
-    len = min(dir == 1 ? W - x : x - D + 1, H - y);
+    const bool right = dir == 1 || dir == 7;     // columns left to right
+    sy = up ? -1 : 1; sx = right ? 1 : -1;
+    int k = 0;                                   // rows between the first pixel and the row the direction starts from
+    if (p < nx) x = D + p; else { x = right ? D : W - 1; k = p - nx + 1; }
+    y = up ? H - 1 - k : k;
+    len = min(right ? W - x : x - D + 1, H - k);
   }
 }
 
@@ -218,10 +230,14 @@ __global__ void k_sgbm_paths(const int16_t* C, typename SgbmAcc<CN>::type* out0,
 }
 
 // Direction 4 along row p (right to left), the sums, and the winner of every pixel.  bid: H x W, 0xffffffff = no bid.
-template <int G, int CN>
-__global__ void k_sgbm_winner(const int16_t* C, const typename SgbmAcc<CN>::type* A, const typename SgbmAcc<CN>::type* B, int16_t* dbgS4, int16_t* dbgS, int16_t* disp1,
+// HH = 1 (MODE_HH): X = L5 + L7 and Y = L6 are read beside A and B, and S = sat16(S4 + L4 + X + Y) - one saturation of the
+// second pass's four steps added together.  HH = 0: X and Y are null and not touched.
+template <int G, int CN, int HH>
+__global__ void k_sgbm_winner(const int16_t* C, const typename SgbmAcc<CN>::type* A, const typename SgbmAcc<CN>::type* B,
+                              const typename SgbmAcc<CN>::type* X, const typename SgbmAcc<CN>::type* Y, int16_t* dbgS4, int16_t* dbgS, int16_t* disp1,
                               uint32_t* bid, int W, int H, int D, size_t vol, size_t pix) {
   C += blockIdx.z * vol; A += blockIdx.z * vol; B += blockIdx.z * vol;
+  if (HH) { X += blockIdx.z * vol; Y += blockIdx.z * vol; }
   disp1 += blockIdx.z * pix; bid += blockIdx.z * pix;
   const int d = threadIdx.x % G, y = blockIdx.x * (blockDim.x / G) + threadIdx.x / G;
   const bool row = y < H, lane = d < D && row;
@@ -232,7 +248,7 @@ __global__ void k_sgbm_winner(const int16_t* C, const typename SgbmAcc<CN>::type
   constexpr int U = 4;
   const int len = W - D;
   for (int k0 = 0; k0 < len; k0 += U) {
-    int c[U], s4[U];
+    int c[U], s4[U], xy[U];
     size_t idx[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -240,6 +256,7 @@ __global__ void k_sgbm_winner(const int16_t* C, const typename SgbmAcc<CN>::type
       idx[u] = ((size_t)yy * W + (W - 1 - k0 - u)) * D + d;
       c[u] = on ? C[idx[u]] : 0;
       s4[u] = on ? sat16((int)A[idx[u]] + (int)B[idx[u]]) : 0;
+      xy[u] = (HH && on) ? (int)X[idx[u]] + (int)Y[idx[u]] : 0;     // gray: at most 3 * 15 309; colour: int32 steps of bounded paths
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -247,7 +264,7 @@ __global__ void k_sgbm_winner(const int16_t* C, const typename SgbmAcc<CN>::type
       const int x = W - 1 - k0 - u;
       const int v = sgbm_step<G, CN>(c[u], Lp, m, d, D);
       sgbm_carry<G, CN>(v, lane, Lp, m);
-      const int s = sat16(s4[u] + v);
+      const int s = HH ? sat16(s4[u] + v + xy[u]) : sat16(s4[u] + v);
       if (on && dbgS) { dbgS4[idx[u]] = (int16_t)s4[u]; dbgS[idx[u]] = (int16_t)s; }
       // first minimum over d ascending: smallest (S, d)
       const int key = group_min<G>(d < D ? (((s + 32768) << 8) | d) : INT_MAX);
@@ -356,8 +373,9 @@ __global__ void k_sgbm_cc_apply(int16_t* disp, const int32_t* root, const int32_
   if (out) out[o] = (float)v / 16.0f;
 }
 
-int sgbm_check(const svo_sgbm_params* p, int W, int H, int cn = 1) {
+int sgbm_check(const svo_sgbm_params* p, int W, int H, int cn = 1, int mode = SVO_SGBM_MODE_SGBM) {
   if (!p) return SVO_E_INVALID;
+  if (mode != SVO_SGBM_MODE_SGBM && mode != SVO_SGBM_MODE_HH) return SVO_E_INVALID;
   svo_sgbm_params d;
   if (cn == 3) svo_sgbm_default_params_bgr(H, &d); else svo_sgbm_default_params(H, &d);
   const int D = p->numDisparities;
@@ -373,10 +391,14 @@ int sgbm_check(const svo_sgbm_params* p, int W, int H, int cn = 1) {
 
 // The parameters and sizes first (host arithmetic only, so that they are answered the same with or without a context or a
 // device), then the pointers; the reason goes to the context's last_error when there is one.
-int sgbm_args(svo_ctx* ctx, const char* who, bool pointers, const svo_sgbm_params* p, int W, int H, int stride, int cn = 1) {
-  int rc = sgbm_check(p, W, H, cn);
+int sgbm_args(svo_ctx* ctx, const char* who, bool pointers, const svo_sgbm_params* p, int W, int H, int stride, int cn, int mode) {
+  int rc = sgbm_check(p, W, H, cn, mode);
   if (rc == SVO_OK && (!ctx || !pointers || stride < cn * W)) rc = SVO_E_INVALID;
-  if (rc && ctx) ctx->last_error = std::string(who) + (rc == SVO_E_CAPACITY ? ": image larger than 3072 x 4096" : ": invalid argument or unsupported parameters");
+  if (rc && ctx)
+    ctx->last_error = std::string(who) + (rc == SVO_E_CAPACITY ? ": image larger than 3072 x 4096"
+                                          : mode != SVO_SGBM_MODE_SGBM && mode != SVO_SGBM_MODE_HH
+                                              ? ": invalid mode (SVO_SGBM_MODE_SGBM = 0 or SVO_SGBM_MODE_HH = 1)"
+                                              : ": invalid argument or unsupported parameters");
   return rc;
 }
 
@@ -393,8 +415,10 @@ int sgbm_alloc(svo_ctx* ctx, T** p, size_t count) {
 }
 
 // the context's arena: volumes for n gray pairs of W x H x D (the debug copies and the host path's staging with dbg; img_bytes:
-// the uploaded pair).  A colour call of k pairs asks for n = 2 k: its A and B are int32.
-int sgbm_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int D, int n, bool dbg, SgbmArena** out, size_t img_bytes = 0) {
+// the uploaded pair).  A colour call of k pairs asks for n = 2 k: its A and B are int32.  hh: the call runs MODE_HH and needs
+// X and Y, which are made at the first such call; a growth of the arena leaves them as they are (too small now, has_hh off) and
+// the next call with hh makes them again at the new size.  An arena never asked is what it was without the mode.
+int sgbm_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int D, int n, bool dbg, bool hh, SgbmArena** out, size_t img_bytes = 0) {
   if (!ctx->sgbm) ctx->sgbm = new SgbmArena();
   SgbmArena* A = static_cast<SgbmArena*>(ctx->sgbm);
   *out = A;
@@ -405,12 +429,17 @@ int sgbm_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int D, int n, bool d
     if (A->last) SVO_HIP(ctx, hipStreamSynchronize(A->last));
     const size_t v = std::max(vol, A->cap_vol), q = std::max(pix, A->cap_pix);
     const size_t m = (size_t)std::max(n, A->cap_n);
-    A->cap_vol = A->cap_pix = 0; A->cap_n = 0; A->has_dbg = false; A->dbg_valid = false; A->cap_img_bytes = 0;
+    A->cap_vol = A->cap_pix = 0; A->cap_n = 0; A->has_dbg = false; A->has_hh = false; A->dbg_valid = false; A->cap_img_bytes = 0;
     if ((rc = sgbm_alloc(ctx, &A->C, v * m)) || (rc = sgbm_alloc(ctx, &A->A, v * m)) || (rc = sgbm_alloc(ctx, &A->B, v * m)) ||
         (rc = sgbm_alloc(ctx, &A->disp1, q * m)) || (rc = sgbm_alloc(ctx, &A->bid, q * m)) || (rc = sgbm_alloc(ctx, &A->label, q * m)) ||
         (rc = sgbm_alloc(ctx, &A->root, q * m)) || (rc = sgbm_alloc(ctx, &A->cnt, q * m)))
       return rc;
     A->cap_vol = v; A->cap_pix = q; A->cap_n = (int)m;
+  }
+  if (hh && !A->has_hh) {
+    if (A->last) SVO_HIP(ctx, hipStreamSynchronize(A->last));
+    if ((rc = sgbm_alloc(ctx, &A->X, A->cap_vol * A->cap_n)) || (rc = sgbm_alloc(ctx, &A->Y, A->cap_vol * A->cap_n))) return rc;
+    A->has_hh = true;
   }
   if (dbg && !A->has_dbg) {
     if (A->last) SVO_HIP(ctx, hipStreamSynchronize(A->last));
@@ -432,15 +461,25 @@ int sgbm_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int D, int n, bool d
 }
 
 template <int G, int CN>
-void sgbm_launch_paths(hipStream_t s, SgbmArena* A, int W, int H, int D, int n, size_t vol, size_t pix, bool dbg) {
+void sgbm_launch_paths(hipStream_t s, SgbmArena* A, int W, int H, int D, int n, size_t vol, size_t pix, bool dbg, int mode) {
   typedef typename SgbmAcc<CN>::type acc_t;
   const int gpb = 256 / G, nx = W - D;
   const int n02 = std::max(H, nx), n13 = nx + H - 1;
   acc_t *a = reinterpret_cast<acc_t*>(A->A), *b = reinterpret_cast<acc_t*>(A->B);
   hipLaunchKernelGGL((k_sgbm_paths<G, CN>), dim3((n02 + gpb - 1) / gpb, 2, n), dim3(256), 0, s, A->C, a, b, 0, 2, 0, W, H, D, vol);
   hipLaunchKernelGGL((k_sgbm_paths<G, CN>), dim3((n13 + gpb - 1) / gpb, 2, n), dim3(256), 0, s, A->C, a, b, 1, 3, 1, W, H, D, vol);
-  hipLaunchKernelGGL((k_sgbm_winner<G, CN>), dim3((H + gpb - 1) / gpb, 1, n), dim3(256), 0, s, A->C, a, b, dbg ? A->dbgS4 : nullptr,
-                     dbg ? A->dbgS : nullptr, A->disp1, A->bid, W, H, D, vol, pix);
+  if (mode == SVO_SGBM_MODE_HH) {
+    // directions 5 (into X) and 6 (into Y; its nx paths are the first of the grid's n13), then 7 added to X: every entry with
+    // x >= D lies on one path of each direction, so the first launch overwrites what X and Y held
+    acc_t *x = reinterpret_cast<acc_t*>(A->X), *y = reinterpret_cast<acc_t*>(A->Y);
+    hipLaunchKernelGGL((k_sgbm_paths<G, CN>), dim3((n13 + gpb - 1) / gpb, 2, n), dim3(256), 0, s, A->C, x, y, 5, 6, 0, W, H, D, vol);
+    hipLaunchKernelGGL((k_sgbm_paths<G, CN>), dim3((n13 + gpb - 1) / gpb, 1, n), dim3(256), 0, s, A->C, x, x, 7, 7, 1, W, H, D, vol);
+    hipLaunchKernelGGL((k_sgbm_winner<G, CN, 1>), dim3((H + gpb - 1) / gpb, 1, n), dim3(256), 0, s, A->C, a, b, x, y, dbg ? A->dbgS4 : nullptr,
+                       dbg ? A->dbgS : nullptr, A->disp1, A->bid, W, H, D, vol, pix);
+    return;
+  }
+  hipLaunchKernelGGL((k_sgbm_winner<G, CN, 0>), dim3((H + gpb - 1) / gpb, 1, n), dim3(256), 0, s, A->C, a, b, (const acc_t*)nullptr,
+                     (const acc_t*)nullptr, dbg ? A->dbgS4 : nullptr, dbg ? A->dbgS : nullptr, A->disp1, A->bid, W, H, D, vol, pix);
 }
 
 // filterSpeckles(disp, -16, 100, 16 * 32) on the n maps in A->disp1, then the float maps (d_disp may be null)
@@ -457,7 +496,7 @@ void sgbm_speckles(hipStream_t s, SgbmArena* A, int W, int H, int n, float* d_di
 // (CN = 3: n <= cap_n / 2 pairs of interleaved three-channel rows)
 template <int CN>
 int sgbm_enqueue(svo_ctx* ctx, hipStream_t s, SgbmArena* A, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W,
-                 int H, int D, int n, float* d_disp, bool dbg) {
+                 int H, int D, int n, float* d_disp, bool dbg, int mode) {
   const size_t pix = (size_t)W * H, vol = pix * D;
   if (dbg) {   // the debug volumes are zero where nothing is defined
     SVO_HIP(ctx, hipMemsetAsync(A->C, 0, vol * sizeof(int16_t), s));
@@ -468,9 +507,9 @@ int sgbm_enqueue(svo_ctx* ctx, hipStream_t s, SgbmArena* A, const uint8_t* dL, c
   // (T goes through the front of A->A as int16; the paths overwrite it)
   hipLaunchKernelGGL(k_sgbm_hsum<CN>, dim3(H, n), dim3(D * (256 / D)), 20 * (size_t)W, s, dL, dR, stride, frame, W, H, D, A->A, vol);
   hipLaunchKernelGGL(k_sgbm_vsum, dim3(((W - D) * D + 255) / 256, H, n), dim3(256), 0, s, A->A, A->C, W, H, D, vol);
-  if (D == 16) sgbm_launch_paths<16, CN>(s, A, W, H, D, n, vol, pix, dbg);
-  else if (D == 32) sgbm_launch_paths<32, CN>(s, A, W, H, D, n, vol, pix, dbg);
-  else sgbm_launch_paths<64, CN>(s, A, W, H, D, n, vol, pix, dbg);
+  if (D == 16) sgbm_launch_paths<16, CN>(s, A, W, H, D, n, vol, pix, dbg, mode);
+  else if (D == 32) sgbm_launch_paths<32, CN>(s, A, W, H, D, n, vol, pix, dbg, mode);
+  else sgbm_launch_paths<64, CN>(s, A, W, H, D, n, vol, pix, dbg, mode);
   hipLaunchKernelGGL(k_sgbm_lr, dim3((W + 255) / 256, H, n), dim3(256), 0, s, A->disp1, A->bid, dbg ? A->dbg_disp2 : nullptr,
                      dbg ? A->dbg_lr : nullptr, W, H, pix);
   sgbm_speckles(s, A, W, H, n, d_disp);
@@ -509,17 +548,17 @@ namespace {
 // B resident pairs -> B float maps, a chunk of pairs at a time, enqueued on `s` (no synchronisation)
 template <int CN>
 int sgbm_run(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,
-             const svo_sgbm_params* p, float* d_disp) {
+             const svo_sgbm_params* p, int mode, float* d_disp) {
   constexpr int chunk = CN == 3 ? SGBM_CHUNK_BGR : SGBM_CHUNK, unit = SGBM_CHUNK / chunk;
-  int rc = sgbm_check(p, W, H, CN);
+  int rc = sgbm_check(p, W, H, CN, mode);
   if (rc) { ctx->last_error = "svo_sgbm: unsupported parameters or image size"; return rc; }
   SgbmArena* A = nullptr;
-  if ((rc = sgbm_reserve(ctx, s, W, H, p->numDisparities, std::min(B, chunk) * unit, false, &A))) return rc;
+  if ((rc = sgbm_reserve(ctx, s, W, H, p->numDisparities, std::min(B, chunk) * unit, false, mode == SVO_SGBM_MODE_HH, &A))) return rc;
   A->dbg_valid = false;
   for (int f0 = 0; f0 < B; f0 += chunk) {
     const int n = std::min(chunk, B - f0);
     if ((rc = sgbm_enqueue<CN>(ctx, s, A, dL + f0 * frame, dR + f0 * frame, stride, frame, W, H, p->numDisparities, n,
-                               d_disp + (size_t)f0 * W * H, false)))
+                               d_disp + (size_t)f0 * W * H, false, mode)))
       return rc;
   }
   return SVO_OK;
@@ -527,18 +566,18 @@ int sgbm_run(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, 
 
 template <int CN>
 int sgbm_process(svo_ctx* ctx, const char* who, const uint8_t* L, const uint8_t* R, int stride, int W, int H, const svo_sgbm_params* p,
-                 int16_t* disp16, float* disp) {
-  int rc = sgbm_args(ctx, who, L && R, p, W, H, stride, CN);
+                 int mode, int16_t* disp16, float* disp) {
+  int rc = sgbm_args(ctx, who, L && R, p, W, H, stride, CN, mode);
   if (rc) return rc;
   SVO_HIP(ctx, hipSetDevice(ctx->device));
   SgbmArena* A = nullptr;
   hipStream_t s = ctx->stream;
   const size_t pix = (size_t)W * H, row = (size_t)W * CN, img = pix * CN;
-  if ((rc = sgbm_reserve(ctx, s, W, H, p->numDisparities, SGBM_CHUNK / (CN == 3 ? SGBM_CHUNK_BGR : SGBM_CHUNK), true, &A, 2 * img))) return rc;
+  if ((rc = sgbm_reserve(ctx, s, W, H, p->numDisparities, SGBM_CHUNK / (CN == 3 ? SGBM_CHUNK_BGR : SGBM_CHUNK), true, mode == SVO_SGBM_MODE_HH, &A, 2 * img))) return rc;
   A->dbg_valid = false;
   SVO_HIP(ctx, hipMemcpy2DAsync(A->img, row, L, stride, row, H, hipMemcpyHostToDevice, s));
   SVO_HIP(ctx, hipMemcpy2DAsync(A->img + img, row, R, stride, row, H, hipMemcpyHostToDevice, s));
-  if ((rc = sgbm_enqueue<CN>(ctx, s, A, A->img, A->img + img, (int)row, img, W, H, p->numDisparities, 1, A->dispf, true))) return rc;
+  if ((rc = sgbm_enqueue<CN>(ctx, s, A, A->img, A->img + img, (int)row, img, W, H, p->numDisparities, 1, A->dispf, true, mode))) return rc;
   if (disp16) SVO_HIP(ctx, hipMemcpyAsync(disp16, A->disp1, pix * sizeof(int16_t), hipMemcpyDeviceToHost, s));
   if (disp) SVO_HIP(ctx, hipMemcpyAsync(disp, A->dispf, pix * sizeof(float), hipMemcpyDeviceToHost, s));
   SVO_HIP(ctx, hipStreamSynchronize(s));
@@ -549,46 +588,73 @@ int sgbm_process(svo_ctx* ctx, const char* who, const uint8_t* L, const uint8_t*
 }  // namespace
 
 int svo_sgbm_run_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,
-                     const svo_sgbm_params* p, float* d_disp) {
-  return sgbm_run<1>(ctx, s, dL, dR, stride, frame, W, H, B, p, d_disp);
+                     const svo_sgbm_params* p, int mode, float* d_disp) {
+  return sgbm_run<1>(ctx, s, dL, dR, stride, frame, W, H, B, p, mode, d_disp);
 }
 
 int svo_sgbm_run_bgr_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H,
-                         int B, const svo_sgbm_params* p, float* d_disp) {
-  return sgbm_run<3>(ctx, s, dL, dR, stride, frame, W, H, B, p, d_disp);
+                         int B, const svo_sgbm_params* p, int mode, float* d_disp) {
+  return sgbm_run<3>(ctx, s, dL, dR, stride, frame, W, H, B, p, mode, d_disp);
 }
 
 int svo_sgbm_chunk() { return SGBM_CHUNK; }
 int svo_sgbm_chunk_bgr() { return SGBM_CHUNK_BGR; }
 
+namespace {
+
+template <int CN>
+int sgbm_batch(svo_ctx* ctx, const char* who, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
+               const svo_sgbm_params* p, int mode, float* d_disp) {
+  int rc = sgbm_args(ctx, who, d_L && d_R && d_disp && B >= 1, p, W, H, stride, CN, mode);
+  if (rc) return rc;
+  SVO_HIP(ctx, hipSetDevice(ctx->device));
+  if ((rc = sgbm_run<CN>(ctx, ctx->stream, d_L, d_R, stride, (size_t)H * stride, W, H, B, p, mode, d_disp))) return rc;
+  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SVO_OK;
+}
+
+}  // namespace
+
+// The entries without a mode are the ones with a mode at SVO_SGBM_MODE_SGBM: one body each, which reports under the name of the
+// entry the caller called.
+extern "C" int svo_sgbm_process_mode(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int W, int H, const svo_sgbm_params* p,
+                                     int mode, int16_t* disp16, float* disp) {
+  return sgbm_process<1>(ctx, "svo_sgbm_process_mode", L, R, stride, W, H, p, mode, disp16, disp);
+}
+
+extern "C" int svo_sgbm_process_bgr_mode(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int W, int H,
+                                         const svo_sgbm_params* p, int mode, int16_t* disp16, float* disp) {
+  return sgbm_process<3>(ctx, "svo_sgbm_process_bgr_mode", L, R, stride, W, H, p, mode, disp16, disp);
+}
+
+extern "C" int svo_sgbm_batch_mode_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
+                                       const svo_sgbm_params* p, int mode, float* d_disp) {
+  return sgbm_batch<1>(ctx, "svo_sgbm_batch_mode_dev", d_L, d_R, stride, W, H, B, p, mode, d_disp);
+}
+
+extern "C" int svo_sgbm_batch_bgr_mode_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
+                                           const svo_sgbm_params* p, int mode, float* d_disp) {
+  return sgbm_batch<3>(ctx, "svo_sgbm_batch_bgr_mode_dev", d_L, d_R, stride, W, H, B, p, mode, d_disp);
+}
+
 extern "C" int svo_sgbm_process(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int W, int H, const svo_sgbm_params* p,
                                 int16_t* disp16, float* disp) {
-  return sgbm_process<1>(ctx, "svo_sgbm_process", L, R, stride, W, H, p, disp16, disp);
+  return sgbm_process<1>(ctx, "svo_sgbm_process", L, R, stride, W, H, p, SVO_SGBM_MODE_SGBM, disp16, disp);
 }
 
 extern "C" int svo_sgbm_process_bgr(svo_ctx* ctx, const uint8_t* L, const uint8_t* R, int stride, int W, int H, const svo_sgbm_params* p,
                                     int16_t* disp16, float* disp) {
-  return sgbm_process<3>(ctx, "svo_sgbm_process_bgr", L, R, stride, W, H, p, disp16, disp);
+  return sgbm_process<3>(ctx, "svo_sgbm_process_bgr", L, R, stride, W, H, p, SVO_SGBM_MODE_SGBM, disp16, disp);
 }
 
 extern "C" int svo_sgbm_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
                                   const svo_sgbm_params* p, float* d_disp) {
-  int rc = sgbm_args(ctx, "svo_sgbm_batch_dev", d_L && d_R && d_disp && B >= 1, p, W, H, stride);
-  if (rc) return rc;
-  SVO_HIP(ctx, hipSetDevice(ctx->device));
-  if ((rc = svo_sgbm_run_dev(ctx, ctx->stream, d_L, d_R, stride, (size_t)H * stride, W, H, B, p, d_disp))) return rc;
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SVO_OK;
+  return sgbm_batch<1>(ctx, "svo_sgbm_batch_dev", d_L, d_R, stride, W, H, B, p, SVO_SGBM_MODE_SGBM, d_disp);
 }
 
 extern "C" int svo_sgbm_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
                                       const svo_sgbm_params* p, float* d_disp) {
-  int rc = sgbm_args(ctx, "svo_sgbm_batch_bgr_dev", d_L && d_R && d_disp && B >= 1, p, W, H, stride, 3);
-  if (rc) return rc;
-  SVO_HIP(ctx, hipSetDevice(ctx->device));
-  if ((rc = svo_sgbm_run_bgr_dev(ctx, ctx->stream, d_L, d_R, stride, (size_t)H * stride, W, H, B, p, d_disp))) return rc;
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SVO_OK;
+  return sgbm_batch<3>(ctx, "svo_sgbm_batch_bgr_dev", d_L, d_R, stride, W, H, B, p, SVO_SGBM_MODE_SGBM, d_disp);
 }
 
 extern "C" int svo_sgbm_filter_speckles(svo_ctx* ctx, int16_t* disp16, int W, int H) {
@@ -598,7 +664,7 @@ extern "C" int svo_sgbm_filter_speckles(svo_ctx* ctx, int16_t* disp16, int W, in
   SVO_HIP(ctx, hipSetDevice(ctx->device));
   SgbmArena* A = nullptr;
   hipStream_t s = ctx->stream;
-  int rc = sgbm_reserve(ctx, s, W, H, 16, 1, false, &A);
+  int rc = sgbm_reserve(ctx, s, W, H, 16, 1, false, false, &A);
   if (rc) return rc;
   A->dbg_valid = false;
   const size_t bytes = (size_t)W * H * sizeof(int16_t);
@@ -624,7 +690,7 @@ extern "C" int svo_sgbm_debug_volume(svo_ctx* ctx, int which, int16_t* host) {
 void svo_sgbm_release(svo_ctx* ctx) {
   if (!ctx || !ctx->sgbm) return;
   SgbmArena* A = static_cast<SgbmArena*>(ctx->sgbm);
-  void* bufs[] = {A->C, A->A, A->B, A->dbgS4, A->dbgS, A->disp1, A->dbg_disp2, A->dbg_lr, A->bid, A->label, A->root, A->cnt, A->img, A->dispf};
+  void* bufs[] = {A->C, A->A, A->B, A->X, A->Y, A->dbgS4, A->dbgS, A->disp1, A->dbg_disp2, A->dbg_lr, A->bid, A->label, A->root, A->cnt, A->img, A->dispf};
   for (void* b : bufs)
     if (b) hipFree(b);
   delete A;

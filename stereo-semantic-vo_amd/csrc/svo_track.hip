@@ -1985,10 +1985,10 @@ int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_
     svo_sgbm_params sp;
     if (d_bgrL && ctx->opt_sgbm_colour) {
       svo_sgbm_default_params_bgr(g.H, &sp);
-      rc = svo_sgbm_run_bgr_dev(ctx, ctx->stream, d_bgrL, d_bgrR, bgr_pitch, (size_t)g.H * bgr_pitch, g.W, g.H, 1, &sp, ctx->d_dense);
+      rc = svo_sgbm_run_bgr_dev(ctx, ctx->stream, d_bgrL, d_bgrR, bgr_pitch, (size_t)g.H * bgr_pitch, g.W, g.H, 1, &sp, ctx->opt_sgbm_mode, ctx->d_dense);
     } else {
       svo_sgbm_default_params(g.H, &sp);
-      rc = svo_sgbm_run_dev(ctx, ctx->stream, dL, dR, ctx->stage_pitch, (size_t)g.H * ctx->stage_pitch, g.W, g.H, 1, &sp, ctx->d_dense);
+      rc = svo_sgbm_run_dev(ctx, ctx->stream, dL, dR, ctx->stage_pitch, (size_t)g.H * ctx->stage_pitch, g.W, g.H, 1, &sp, ctx->opt_sgbm_mode, ctx->d_dense);
     }
     if (rc) return rc;
     SvoTimer t(ctx, "k_tk_dense_depth");
@@ -2192,9 +2192,9 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
         const int b = std::min(step, B - f0);
         for (int k = 0; k < b; ++k) ctx->h_prod[f0 + k] = 1;
         rc = colour ? svo_sgbm_run_bgr_dev(ctx, ctx->stream_dense, bgr->L + f0 * bgr_img, bgr->R + f0 * bgr_img, bgr->stride, bgr_img,
-                                           ctx->g.W, ctx->g.H, b, &sp, dD1 + n * f0)
+                                           ctx->g.W, ctx->g.H, b, &sp, ctx->opt_sgbm_mode, dD1 + n * f0)
                     : svo_sgbm_run_dev(ctx, ctx->stream_dense, d_grayL + f0 * gray_img, d_grayR + f0 * gray_img, stride, gray_img, ctx->g.W,
-                              ctx->g.H, b, &sp, dD1 + n * f0);
+                              ctx->g.H, b, &sp, ctx->opt_sgbm_mode, dD1 + n * f0);
         if (rc == SVO_OK) rc = Hook::run(&hook, f0, b);
       }
       return rc;

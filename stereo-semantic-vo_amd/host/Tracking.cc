@@ -57,6 +57,7 @@ void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n,
   if (!ctx_batch) {
     if (svo_create(&ctx_batch, device, width, height, 500, batch_capacity) != SVO_OK) throw std::runtime_error("svo_create failed");
     if (svo_set_option(ctx_batch, "depth_source", depth_source) != SVO_OK || svo_set_option(ctx_batch, "sgbm_colour", sgbm_colour ? 1 : 0) != SVO_OK ||
+        svo_set_option(ctx_batch, "sgbm_mode", sgbm_mode) != SVO_OK ||
         svo_track_reset(ctx_batch, &K) != SVO_OK)
       throw std::runtime_error(std::string("TrackBatch: ") + svo_last_error(ctx_batch));
     batch_results.reserve(1 << 16);   // (the library writes into this array until FinishBatches: it must not move)
@@ -198,8 +199,8 @@ void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, co
     currentframe->disp2Depth(bf);
   } else if (depth_source == 3) {         // the same four calls with the body of the reference's ElasMatch (SGBM)
     currentframe->featuredetect(imLeft);
-    if (sgbm_colour && colLeft) currentframe->ElasMatchBgr(*colLeft, *colRight);
-    else currentframe->SGBMMatch(imLeft, imRight);
+    if (sgbm_colour && colLeft) currentframe->ElasMatchBgr(*colLeft, *colRight, sgbm_mode);
+    else currentframe->SGBMMatch(imLeft, imRight, sgbm_mode);
     currentframe->computekeypoint_r();
     currentframe->disp2Depth(bf);
   } else {

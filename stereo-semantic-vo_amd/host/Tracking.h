@@ -17,6 +17,8 @@ class Tracking {
   // With depth_source 3 and the colour Track() / TrackBatch(bgr): SGBM on the colour pair (frame::ElasMatchBgr, svo_set_option
   // "sgbm_colour"), as the reference calls it; otherwise on the gray
   bool sgbm_colour = false;
+  // With depth_source 3: SVO_SGBM_MODE_SGBM (0, the reference's) or SVO_SGBM_MODE_HH (1, eight directions; svo_set_option "sgbm_mode")
+  int sgbm_mode = 0;
   // The dynamic-keypoint loop of src/Tracking.cc:189-223 (commented out there): before featuredetect, the last frame's
   // DY_keypoints are followed into the current left image (frame::LKTrack), the status-0 points erased, the survivors become
   // the current frame's DY_keypoints.  Seeds - keypoints strictly inside a box, offline_box in place of the reference's online

@@ -100,22 +100,22 @@ int frame::ElasMatch(const GrayImage& left, const GrayImage& right) {
   return valid;
 }
 
-int frame::SGBMMatch(const GrayImage& left, const GrayImage& right) {
+int frame::SGBMMatch(const GrayImage& left, const GrayImage& right, int mode) {
   svo_sgbm_params sp;
   svo_sgbm_default_params(left.rows, &sp);   // numDisparities = ((rows / 8) + 15) & -16, src/frame.cc:100
   dispimg.assign((size_t)left.cols * left.rows, -1.f);
-  if (svo_sgbm_process(ctx, left.ptr(), right.ptr(), left.cols, left.cols, left.rows, &sp, nullptr, dispimg.data()) != SVO_OK) return 0;
+  if (svo_sgbm_process_mode(ctx, left.ptr(), right.ptr(), left.cols, left.cols, left.rows, &sp, mode, nullptr, dispimg.data()) != SVO_OK) return 0;
   int valid = 0;
   for (float d : dispimg) valid += d != -1.f;
   return valid;
 }
 
-int frame::ElasMatchBgr(const BgrImage& left, const BgrImage& right) {
+int frame::ElasMatchBgr(const BgrImage& left, const BgrImage& right, int mode) {
   svo_sgbm_params sp;
   svo_sgbm_default_params_bgr(left.rows, &sp);   // P1 = 8 * cn * 81, P2 = 32 * cn * 81 with cn = 3, src/frame.cc:96-104
   dispimg.assign((size_t)left.cols * left.rows, -1.f);
   if (left.cols != right.cols || left.rows != right.rows) return 0;
-  if (svo_sgbm_process_bgr(ctx, left.ptr(), right.ptr(), left.step(), left.cols, left.rows, &sp, nullptr, dispimg.data()) != SVO_OK) return 0;
+  if (svo_sgbm_process_bgr_mode(ctx, left.ptr(), right.ptr(), left.step(), left.cols, left.rows, &sp, mode, nullptr, dispimg.data()) != SVO_OK) return 0;
   int valid = 0;
   for (float d : dispimg) valid += d != -1.f;
   return valid;

@@ -38,10 +38,11 @@ class frame {
   // returns the number of valid pixels
   int ElasMatch(const svo_host::GrayImage& left, const svo_host::GrayImage& right);
   // the reference's ElasMatch body: semi-global block matching with its fixed parameter set, compute, convertTo(CV_32F, 1/16)
-  // into `dispimg` (-1 = invalid); returns the number of valid pixels
-  int SGBMMatch(const svo_host::GrayImage& left, const svo_host::GrayImage& right);
+  // into `dispimg` (-1 = invalid); returns the number of valid pixels.  mode: SVO_SGBM_MODE_SGBM (what the reference sets) or
+  // SVO_SGBM_MODE_HH (all eight directions, two passes)
+  int SGBMMatch(const svo_host::GrayImage& left, const svo_host::GrayImage& right, int mode = SVO_SGBM_MODE_SGBM);
   // the same on the colour pair, which is what the reference hands its ElasMatch: cn = leftImage.channels() = 3
-  int ElasMatchBgr(const svo_host::BgrImage& left, const svo_host::BgrImage& right);
+  int ElasMatchBgr(const svo_host::BgrImage& left, const svo_host::BgrImage& right, int mode = SVO_SGBM_MODE_SGBM);
   // the reference's own MB body: MSA dense disparity (0 = none) of the two images as B = G = R colour images
   int MBdense(const svo_host::GrayImage& left, const svo_host::GrayImage& right);
   // the same with the true colour pair (the reference's 8UC3 input, main.cpp:160-161): MSA's colour cost and tree weights

@@ -14,6 +14,8 @@
 // --dynamic-lk [--write-dynamic <dir>] (frame by frame only): Tracking::dynamic_lk, the reference's LK loop over the keypoints
 // inside boxes (src/Tracking.cc:189-223); each frame's dynamic keypoints go to <dir>/NNNNNN.txt, one "x y" per line.
 // --sgbm-colour (needs --colour and --depth-source 3): SGBM runs on the colour pair (cn = 3), as the reference's ElasMatch does.
+// --sgbm-mode sgbm|hh (hh needs --depth-source 3): SGBM's five-direction single pass (the reference's MODE_SGBM, default) or all
+// eight directions in two passes (MODE_HH).
 // --dynamic-lk-bgr (implies --dynamic-lk; needs --colour): the same loop on the colour left images, svo_lk_track_bgr.
 // stereo_kitti --decode-bgr in.(png|ppm|pgm) out.ppm: codec self-test of the colour decode (the PPM holds RGB, as the format says).
 #include <algorithm>
@@ -121,6 +123,17 @@ int main(int argc, char** argv) {
       break;
     }
   if (sgbm_colour && (!colour || depth_source != 3)) { std::cerr << "--sgbm-colour needs --colour and --depth-source 3" << std::endl; return 1; }
+  int sgbm_mode = SVO_SGBM_MODE_SGBM;   // --sgbm-mode sgbm|hh (hh needs --depth-source 3)
+  for (int i = 1; i + 1 < argc; ++i)
+    if (std::string(argv[i]) == "--sgbm-mode") {
+      const std::string m = argv[i + 1];
+      if (m != "sgbm" && m != "hh") { std::cerr << "--sgbm-mode: sgbm or hh" << std::endl; return 1; }
+      sgbm_mode = m == "hh" ? SVO_SGBM_MODE_HH : SVO_SGBM_MODE_SGBM;
+      for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+      argc -= 2;
+      break;
+    }
+  if (sgbm_mode == SVO_SGBM_MODE_HH && depth_source != 3) { std::cerr << "--sgbm-mode hh needs --depth-source 3" << std::endl; return 1; }
   // --dynamic-lk: Tracking::dynamic_lk (the reference's LK loop over the points inside boxes); --write-dynamic <dir>: each
   // frame's dynamic keypoints to <dir>/NNNNNN.txt, one "x y" per line (%.9g: the floats read back exactly)
   bool dynamic_lk = false, dynamic_lk_bgr = false;
@@ -150,7 +163,7 @@ int main(int argc, char** argv) {
   if (dynamic_lk_bgr && !colour) { std::cerr << "--dynamic-lk-bgr needs --colour" << std::endl; return 1; }
   if (!dynamic_dir.empty() && !dynamic_lk) { std::cerr << "--write-dynamic needs --dynamic-lk" << std::endl; return 1; }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--dynamic-lk | --dynamic-lk-bgr] [--write-dynamic dir] [--pipelined] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr] [--write-dynamic dir] [--pipelined] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -176,6 +189,7 @@ int main(int argc, char** argv) {
   Tracking* mpTracker = new Tracking(argv[2]);
   mpTracker->depth_source = depth_source;
   mpTracker->sgbm_colour = sgbm_colour;
+  mpTracker->sgbm_mode = sgbm_mode;
   mpTracker->dynamic_lk = dynamic_lk;
   mpTracker->dynamic_lk_bgr = dynamic_lk_bgr;
   std::ofstream f("cameratrajectory_kitti.txt"); f << std::fixed;

@@ -4,7 +4,10 @@ the median of --repeats timed runs after a warm-up, with the spread (min .. max)
 --bgr: the same three figures for the cn = 3 solver on 8UC3 pairs (svo_sgbm_process_bgr, svo_sgbm_batch_bgr_dev,
 svo_track_batch_bgr_dev with "sgbm_colour" 1).  --both: gray and colour in one session, and the colour / gray ratios of the
 medians (time per pair or frame: above 1 means colour is slower).
-Usage: python tools/sgbm_bench.py [--repeats N] [--only latency|batch|track] [--bgr | --both]"""
+--mode hh: the figures of the eight-direction mode (svo_sgbm_*_mode with SVO_SGBM_MODE_HH, "sgbm_mode" 1 in the tracker).
+--modes: MODE_SGBM and MODE_HH in one session, and the hh / sgbm ratios of the medians (time: above 1 means hh is slower); with
+--bgr for the colour solver.
+Usage: python tools/sgbm_bench.py [--repeats N] [--only latency|batch|track] [--bgr | --both] [--mode sgbm|hh | --modes]"""
 import argparse
 import importlib
 import json
@@ -28,7 +31,11 @@ ap.add_argument("--frames", type=int, default=256)
 ap.add_argument("--only", choices=["latency", "batch", "track"], default=None)
 ap.add_argument("--bgr", action="store_true", help="the cn = 3 solver on 8UC3 pairs")
 ap.add_argument("--both", action="store_true", help="gray and colour in one session, and their ratios")
+ap.add_argument("--mode", choices=["sgbm", "hh"], default="sgbm", help="five directions in one pass, or all eight in two")
+ap.add_argument("--modes", action="store_true", help="both modes in one session, and their ratios")
 a = ap.parse_args()
+if a.modes and a.both:
+    ap.error("--modes and --both: one comparison per session")
 svo = svo_loader.load()
 dev = torch.device("cuda", 0)
 
@@ -57,7 +64,7 @@ def colourise(g):
     return torch.stack([128 + torch.div(128 - g, 2, rounding_mode="floor"), g, torch.clamp(torch.div(3 * g, 4, rounding_mode="floor") + 32, 0, 255)], -1).to(torch.uint8)
 
 
-def measure(colour):
+def measure(colour, mode=0):
     cn = 3 if colour else 1
     out = {}
     L, R = util.urban_pair()
@@ -65,7 +72,7 @@ def measure(colour):
     stride = 3840 if colour else 1280
     if colour:
         L, R = colourise(L), colourise(R)
-    process = (lambda c: c.sgbm_process_bgr(L, R)) if colour else (lambda c: c.sgbm_process(L, R))
+    process = (lambda c: c.sgbm_process_bgr(L, R, mode=mode)) if colour else (lambda c: c.sgbm_process(L, R, mode=mode))
     if a.only in (None, "latency"):
         ctx = svo.Svo(W, H)
         ts = timed(lambda: process(ctx), a.repeats)
@@ -79,7 +86,7 @@ def measure(colour):
         D = torch.zeros((B, H, W), dtype=torch.float32, device=dev)
         torch.cuda.synchronize()
         entry = ctx.sgbm_batch_bgr_dev if colour else ctx.sgbm_batch_dev
-        ts = timed(lambda: entry(dL.data_ptr(), dR.data_ptr(), stride, W, H, B, D.data_ptr()), a.repeats)
+        ts = timed(lambda: entry(dL.data_ptr(), dR.data_ptr(), stride, W, H, B, D.data_ptr(), mode=mode), a.repeats)
         out["batch_%d_pairs_per_s" % B] = spread([B / t for t in ts], 1)
         assert np.array_equal(D[B - 1].cpu().numpy(), process(ctx)[1])
         ctx.close()
@@ -97,6 +104,7 @@ def measure(colour):
         ctx = svo.Svo(W, H, max_batch=N)
         ctx.set_option("depth_source", 3)
         ctx.set_option("sgbm_colour", 1 if colour else 0)
+        ctx.set_option("sgbm_mode", mode)
         cam = svo.Camera(**svo.KITTI_00_02)
         torch.cuda.synchronize()
         entry = ctx.track_batch_bgr_dev if colour else ctx.track_batch_dev
@@ -115,17 +123,28 @@ def measure(colour):
     return out
 
 
-if a.both:
-    out = {"workload": "semi-global block matching, 1241x376, D = 48, gray (cn = 1) and 8UC3 (cn = 3)", "repeats": a.repeats,
-           "gray": measure(False), "bgr": measure(True)}
+def time_ratios(base, other):
+    """other / base of the medians, as times per pair or frame."""
     ratios = {}
-    for k, g in out["gray"].items():
+    for k, g in base.items():
         if k == "track_last_frame":
             continue
-        b = out["bgr"][k]["median"]
+        b = other[k]["median"]
         ratios[k.replace("_ms", "").replace("_per_s", "") + "_time"] = round(b / g["median"] if k.endswith("_ms") else g["median"] / b, 3)
-    out["bgr_over_gray"] = ratios
+    return ratios
+
+
+MODE = 1 if a.mode == "hh" else 0
+what = "semi-global block matching, 1241x376, D = 48"
+if a.both:
+    out = {"workload": what + ", gray (cn = 1) and 8UC3 (cn = 3)" + (", MODE_HH" if MODE else ""), "repeats": a.repeats,
+           "gray": measure(False, MODE), "bgr": measure(True, MODE)}
+    out["bgr_over_gray"] = time_ratios(out["gray"], out["bgr"])
+elif a.modes:
+    out = {"workload": what + (", 8UC3 (cn = 3)" if a.bgr else "") + ", MODE_SGBM (5 directions) and MODE_HH (8 directions)",
+           "repeats": a.repeats, "sgbm": measure(a.bgr, 0), "hh": measure(a.bgr, 1)}
+    out["hh_over_sgbm"] = time_ratios(out["sgbm"], out["hh"])
 else:
-    out = {"workload": "semi-global block matching, 1241x376, D = 48" + (", 8UC3 (cn = 3)" if a.bgr else ""), "repeats": a.repeats}
-    out.update(measure(a.bgr))
+    out = {"workload": what + (", 8UC3 (cn = 3)" if a.bgr else "") + (", MODE_HH" if MODE else ""), "repeats": a.repeats}
+    out.update(measure(a.bgr, MODE))
 print(json.dumps(out))
