@@ -379,11 +379,12 @@ __device__ __forceinline__ void edge_terms(const double J[12], const double e[2]
 }
 
 // One edge's share of wave W's quantities (error, Huber weight, Jacobian, then the wave's seven terms)
+// (c: the edge's correspondence - world point, observation - as pose_edge_regs holds it)
 template <int W>
-__device__ __forceinline__ void edge_wave_terms(const Se3& est, const double* Xw, const double* obs, int i, const double* K,
+__device__ __forceinline__ void edge_wave_terms(const Se3& est, const double c[5], const double* K,
                                                 double delta, double dsqr, double t[POSE_QW]) {
   double e[2], pc[3], J[12], rz;
-  edge_error(est, Xw + 3 * i, obs + 2 * i, K, e, pc, &rz);
+  edge_error(est, c, c + 3, K, e, pc, &rz);
   double rho0 = e[0] * e[0] + e[1] * e[1], rho1 = 1.;
   huber(rho0, delta, dsqr, rho0, rho1);
   edge_jacobian(pc, K, J, rz);
@@ -391,13 +392,23 @@ __device__ __forceinline__ void edge_wave_terms(const Se3& est, const double* Xw
 }
 // wave W's terms of the edges e0 + lane and (TWO) e0 + 64 + lane into its slab: straight-line code for both edges (indices clamped,
 // stores masked), so that the two dependent chains - IEEE divisions, the rotation - fill each other's issue gaps
+// The correspondences of the FIRST chunk's two edges of a lane (edges lane and 64 + lane, clamped like the loads below) live in
+// registers through the LM (`first`, pose_edge_regs): they never change, every build starts with them, and a load at the head of
+// the build's dependent chain is a round trip to L2 per build and wave.  Further chunks (n > POSE_CHUNK) read memory.
 template <int W, bool TWO>
 __device__ __forceinline__ void wave_terms_to_lds(const Se3& est, const double* Xw, const double* obs, int n, int e0, int lane,
-                                                  const double* K, double delta, double dsqr, double* tw) {
+                                                  const double* K, double delta, double dsqr, double* tw, const double first[10]) {
   const int iA = e0 + lane, iB = e0 + 64 + lane;
-  double tA[POSE_QW], tB[POSE_QW];
-  edge_wave_terms<W>(est, Xw, obs, min(iA, n - 1), K, delta, dsqr, tA);
-  if (TWO) edge_wave_terms<W>(est, Xw, obs, min(iB, n - 1), K, delta, dsqr, tB);
+  double tA[POSE_QW], tB[POSE_QW], cA[5], cB[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) { cA[k] = first[k]; cB[k] = first[5 + k]; }
+  if (e0 != 0) {   // (uniform)
+    const int a = min(iA, n - 1), b = min(iB, n - 1);
+    cA[0] = Xw[3 * a]; cA[1] = Xw[3 * a + 1]; cA[2] = Xw[3 * a + 2]; cA[3] = obs[2 * a]; cA[4] = obs[2 * a + 1];
+    if (TWO) { cB[0] = Xw[3 * b]; cB[1] = Xw[3 * b + 1]; cB[2] = Xw[3 * b + 2]; cB[3] = obs[2 * b]; cB[4] = obs[2 * b + 1]; }
+  }
+  edge_wave_terms<W>(est, cA, K, delta, dsqr, tA);
+  if (TWO) edge_wave_terms<W>(est, cB, K, delta, dsqr, tB);
   // (every lane stores: rows beyond the last edge hold +0.0 - the sums run over whole groups of sixteen rows -, and so do the two
   // padding columns of every row, which the matrix-core sum's idle columns read)
 #pragma unroll
@@ -408,13 +419,20 @@ __device__ __forceinline__ void wave_terms_to_lds(const Se3& est, const double* 
   }
 }
 
+// this lane's two edges of the first chunk from memory (global or LDS; n >= 1; sx / so: doubles from one edge to the next)
+__device__ __forceinline__ void pose_edge_regs(const double* Xw, const double* obs, int n, double first[10], int sx = 3, int so = 2) {
+  const int lane = threadIdx.x & 63, a = min(lane, n - 1), b = min(64 + lane, n - 1);
+  first[0] = Xw[sx * a]; first[1] = Xw[sx * a + 1]; first[2] = Xw[sx * a + 2]; first[3] = obs[so * a]; first[4] = obs[so * a + 1];
+  first[5] = Xw[sx * b]; first[6] = Xw[sx * b + 1]; first[7] = Xw[sx * b + 2]; first[8] = obs[so * b]; first[9] = obs[so * b + 1];
+}
+
 // The normal equations at `est`: red[0..20] = upper triangle of H, red[21..26] = b, red[27] = chi2 - every entry the IEEE sum of
 // its edge terms in edge order, starting from +0.  256 threads: wave w owns the quantities 7 w .. 7 w + 6; it evaluates them for
 // up to 128 edges at a time (one or two edges per lane: error, Huber weight, Jacobian - recomputed by each of the four waves, which
 // is cheaper than handing them over), stores them to its LDS slab, and adds them to its running sums four edges per MFMA.
 __device__ __forceinline__ void build_system_ordered(const Se3& est, const double* Xw, const double* obs, int n, const double* K,
                                                      double delta, double dsqr, double* tw_all /*[4][POSE_CHUNK * POSE_TW]*/, double* red,
-                                                     bool on_mfma) {
+                                                     bool on_mfma, const double first[10]) {
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, c = lane & 15;
   double* tw = tw_all + wv * POSE_CHUNK * POSE_TW;
@@ -423,17 +441,17 @@ __device__ __forceinline__ void build_system_ordered(const Se3& est, const doubl
     const int cnt = min(POSE_CHUNK, n - e0);
     if (cnt > 64) {
       switch (wv) {                       // (uniform per wave: scalar branches)
-        case 0: wave_terms_to_lds<0, true>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw); break;
-        case 1: wave_terms_to_lds<1, true>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw); break;
-        case 2: wave_terms_to_lds<2, true>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw); break;
-        default: wave_terms_to_lds<3, true>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw); break;
+        case 0: wave_terms_to_lds<0, true>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw, first); break;
+        case 1: wave_terms_to_lds<1, true>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw, first); break;
+        case 2: wave_terms_to_lds<2, true>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw, first); break;
+        default: wave_terms_to_lds<3, true>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw, first); break;
       }
     } else {
       switch (wv) {
-        case 0: wave_terms_to_lds<0, false>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw); break;
-        case 1: wave_terms_to_lds<1, false>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw); break;
-        case 2: wave_terms_to_lds<2, false>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw); break;
-        default: wave_terms_to_lds<3, false>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw); break;
+        case 0: wave_terms_to_lds<0, false>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw, first); break;
+        case 1: wave_terms_to_lds<1, false>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw, first); break;
+        case 2: wave_terms_to_lds<2, false>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw, first); break;
+        default: wave_terms_to_lds<3, false>(est, Xw, obs, n, e0, lane, K, delta, dsqr, tw, first); break;
       }
     }
     POSE_WSYNC();
@@ -495,6 +513,21 @@ __device__ __forceinline__ void build_system_one_lane(const Se3& est, const doub
   __syncthreads();
 }
 
+// What a caller that prepared the LM's inputs itself hands over (the fused pose launch, svo_track.hip); all of it written before
+// the caller's last barrier.  est: the start estimate as the plain entry forms it from T (se3_from_T of the CV_32F-rounded T), or
+// null: formed here from T.  With `prep`, K is already in L.K.  first: this thread's pose_edge_regs.
+struct PosePrepared { const Se3* est; const double* first; };
+// the start estimate of the LM from a row-major 4x4 (round_in_f32: the reference stores the PnP pose as CV_32F before optimising it)
+__device__ __forceinline__ void pose_start_estimate(const double* T, int round_in_f32, Se3& est0) {
+  if (round_in_f32) {
+    double Tf[16];
+    for (int j = 0; j < 16; ++j) Tf[j] = (double)(float)T[j];
+    se3_from_T(Tf, est0);
+  } else {
+    se3_from_T(T, est0);
+  }
+}
+
 // Pose-only LM, called by all NT = 256 threads of the workgroup.  T: row-major 4x4 in/out (global or LDS); stats may be null.
 // use_ordered_mfma (svo_set_option "pose_mfma"): 1 (default) the sums over the edges on the matrix core (v_mfma_f64_4x4x4, A = 1:
 // four edges per dependent step); 2 the same sums by one lane per quantity, plain additions in order (a little slower); 0 everything
@@ -506,28 +539,38 @@ __device__ __forceinline__ void build_system_one_lane(const Se3& est, const doub
 // ordered sums of the build; so here every trial builds the whole system at its estimate: its chi2 entry IS the trial's chi2
 // (same values, same order: same bits), and an accepted trial's system IS the next iteration's - one pass over the edges per
 // trial instead of two, on all four waves.  The scalar LM state (lambda, the pose, H, b) lives in thread 0's registers.
+// T_lds (may be null): the final pose goes there too (thread 0; the caller's barrier publishes it).  iters_out (thread 0): the LM's
+// iteration count.
 template <int NT = 256>
 __device__ __forceinline__ void pose_opt_block(PoseLds& L, const double* __restrict__ Xw, const double* __restrict__ obs, int n,
                                                const double* __restrict__ Kp, double* T, svo_lm_stats* stats,
-                                               int round_in_f32, int use_ordered_mfma) {
+                                               int round_in_f32, int use_ordered_mfma, long long* t_first_build = nullptr,
+                                               const PosePrepared* prep = nullptr, double* T_lds = nullptr, int* iters_out = nullptr) {
   static_assert(NT == 256, "pose_opt_block: four waves (wave w owns the quantities 7 w .. 7 w + 6 of the normal equations)");
   double* red = L.red; LmShared& sh = L.sh; double* K = L.K;
   const int tid = threadIdx.x;
   const double delta = (double)(float)sqrt(5.991);
   const double dsqr = delta * delta;
-  __syncthreads();
-  if (tid < 4) K[tid] = Kp[tid];
   Se3 est0{};                 // thread 0: the current estimate
-  if (tid == 0) {
-    if (round_in_f32) {  // the reference stores the PnP pose as CV_32F before optimising it
-      double Tf[16];
-      for (int j = 0; j < 16; ++j) Tf[j] = (double)(float)T[j];
-      se3_from_T(Tf, est0);
-    } else {
-      se3_from_T(T, est0);
+  double first[10];           // this lane's two edges of the first chunk (pose_edge_regs)
+  if (prep && prep->est) {    // (uniform) nothing is read back from memory: the estimate and K are in LDS, the edges in registers
+    if (tid == 0) { est0 = *prep->est; sh.est = est0; sh.done = 0; }
+#pragma unroll
+    for (int k = 0; k < 10; ++k) first[k] = prep->first[k];
+  } else {
+    __syncthreads();
+    if (!prep && tid < 4) K[tid] = Kp[tid];
+    if (tid == 0) {
+      pose_start_estimate(T, round_in_f32, est0);
+      sh.est = est0;
+      sh.done = 0;
     }
-    sh.est = est0;
-    sh.done = 0;
+    if (prep) {
+#pragma unroll
+      for (int k = 0; k < 10; ++k) first[k] = prep->first[k];
+    } else if (n > 0) {
+      pose_edge_regs(Xw, obs, n, first);
+    }
   }
   __syncthreads();
   double lambda = -1., ni = 2., currentChi = 0, chi_init = 0;
@@ -537,6 +580,9 @@ __device__ __forceinline__ void pose_opt_block(PoseLds& L, const double* __restr
       stats->n_edges = 0; stats->iterations = 0; stats->trials_total = 0; stats->terminated = 0;
       stats->chi2_initial = 0; stats->chi2_final = 0; stats->lambda_final = 0;
     }
+    if (tid == 0 && T_lds)
+      for (int j = 0; j < 16; ++j) T_lds[j] = T[j];   // (no LM: the pose stays)
+    if (tid == 0 && iters_out) *iters_out = 0;
     return;
   }
 #ifdef POSE_PROF
@@ -548,9 +594,10 @@ __device__ __forceinline__ void pose_opt_block(PoseLds& L, const double* __restr
 #endif
   auto build = [&]() {        // the system at sh.est into red[] (ends with a barrier)
     const Se3 est = sh.est;
-    if (use_ordered_mfma) build_system_ordered(est, Xw, obs, n, K, delta, dsqr, L.tw, red, use_ordered_mfma == 1);
+    if (use_ordered_mfma) build_system_ordered(est, Xw, obs, n, K, delta, dsqr, L.tw, red, use_ordered_mfma == 1, first);
     else build_system_one_lane(est, Xw, obs, n, K, delta, dsqr, red);
   };
+  if (t_first_build && tid == 0) *t_first_build = wall_clock64();   // (diagnostics; not waited for here)
   build();
   PF(pf_build);
   double H[36], b[6], x[6] = {0, 0, 0, 0, 0, 0};
@@ -628,6 +675,8 @@ __device__ __forceinline__ void pose_opt_block(PoseLds& L, const double* __restr
   }
   if (tid == 0) {
     se3_to_T(est0, T);
+    if (T_lds) se3_to_T(est0, T_lds);
+    if (iters_out) *iters_out = iters;
     if (stats) {
       stats->n_edges = n; stats->iterations = iters; stats->trials_total = trials_total;
       stats->terminated = terminated; stats->chi2_initial = chi_init;
@@ -740,7 +789,8 @@ struct PnpOrdLds { epnp_ord::Lds S; epnp_exact::Work W; };
 // device-coherent level by themselves (no release fence: see tp_wait_work in svo_track.hip).
 template <bool AGENT_OUT = false>
 __device__ __forceinline__ void pnp_hyp_ord_wave(PnpOrdLds& L, const double* Xw, const double* uv, int n, const double* K,
-                                                 const uint16_t* subset, PnpHyp* out, int k, bool force_seq = false) {
+                                                 const uint16_t* subset, PnpHyp* out, int k, bool force_seq = false,
+                                                 unsigned* word = nullptr /* lane 0: ok << 31 | consensus */) {
   const int lane = threadIdx.x & 63;
   if (k >= PNP_HYP) return;
   if (lane < 5) {
@@ -755,6 +805,7 @@ __device__ __forceinline__ void pnp_hyp_ord_wave(PnpOrdLds& L, const double* Xw,
     for (int e = lane; e < n; e += 64) cnt += pnp_inlier(R, t, Xw + 3 * e, uv + 2 * e, K) ? 1 : 0;
   cnt = wave_sum_i32_dpp(cnt);
   if (lane == 0) {
+    if (word) *word = (ok ? 0x80000000u : 0u) | (unsigned)cnt;
     if (AGENT_OUT) {
       PnpHyp* o = out + k;
 #pragma unroll
@@ -853,6 +904,32 @@ __device__ __forceinline__ int pnp_select_pre_bound(const int* cnt, const int* o
     }
   }
   return iter;   // = samples visited (niters = 0 leaves after the sample that set it)
+}
+
+// pnp_select_pre_bound and pnp_select_pre in ONE walk over the first m samples: returns what pnp_select_pre_bound returns; if that
+// is <= m - the rule ended within them - it is also pnp_select_pre's *iters, and *best / *good are its winner and consensus.
+__device__ __forceinline__ int pnp_select_pre_early(const int* cnt, const int* ok, const double* ld, const int* r, int n, int m,
+                                                    int* best_out, int* good) {
+  int niters = PNP_HYP, maxGood = 0, best = -1;
+  if (n == 5) {
+    *good = ok[0] ? 5 : 0; *best_out = ok[0] ? 0 : -1;
+    return 1;
+  }
+  const double num = log(fmax(1. - 0.99, 2.2250738585072014e-308));
+  int iter = 0;
+  for (; iter < niters; ++iter) {
+    if (iter >= m) return m + 1;
+    if (!ok[iter]) continue;
+    const int g = cnt[iter];
+    if (g > max(maxGood, 4)) {
+      maxGood = g; best = iter;
+      const double d = ld[iter];
+      if (d == 1.0) niters = 0;
+      else niters = d >= 0 || -num >= niters * (-d) ? niters : r[iter];
+    }
+  }
+  *good = maxGood; *best_out = best;
+  return iter;
 }
 
 // RANSACPointSetRegistrator::run over the precomputed samples (one thread): sample `iter` replaces the best one iff its

@@ -84,7 +84,9 @@ struct TrackWork {
   int32_t frame_id, nkp, n_stereo, n_pass1, n_pass2, n_new, n_local, skip_match;
   long long ts[8];               // diagnostics: s_memtime at begin / pass 1 / pass 2 / frame end / done, dense rows, late rows
   long long rt[6];               // diagnostics: s_memrealtime (100 MHz, one clock for the chip) at k_ti_resolve start / end,
-                                 // k_tp_hyp start (its workgroup 0), k_tp_frame end, k_tp_frame start, (unused)
+                                 // k_tp_hyp start (its workgroup 0), k_tp_frame end, k_tp_frame start, and [5] a DURATION: fused
+                                 // launch, frame decided within the TP_EARLY awaited samples - from the latest of their announcement
+                                 // clocks (hyp_rt) to the LM's first build; 0 otherwise
   int32_t diag[2];               // [0] rows of pass 1 | rounds << 16, [1] rows of pass 2 | rounds << 16
   int32_t n_edges;               // 3D-2D correspondences of the frame (src/pnpmatch.cc:216-224), in keypoint order:
   int32_t edge_gid[TRK_MAXKP];   //   id of the map point (CurrentFrame->MapPoints[j]->...) ...
@@ -94,8 +96,11 @@ struct TrackWork {
   int32_t pnp_best, pnp_iterations, pnp_inliers, pnp_ok;
   double T_pnp[16];
   int32_t hyp_done, pad_hyp;     // fused pose launch (k_tp_tail_ord): RANSAC samples of this frame that have stored their result
-  int32_t hyp_early[TP_FLAGS];   // ... and, for the first TP_FLAGS samples, frame id + 1 once that sample's result is stored (ids only grow
-                                 // between two resets and a reset clears the records: a stale value never equals the current one)
+  long long hyp_early[TP_FLAGS]; // ... and, for the first TP_FLAGS samples, ONE word once that sample's result is stored: frame id + 1 in
+                                 // the high half (ids only grow between two resets and a reset clears the records: a stale value never
+                                 // equals the current one), the sample's ok << 31 | consensus in the low half - whoever sees the
+                                 // announcement has the rule's inputs with it (tp_early_word)
+  long long hyp_rt[TP_EARLY];    // diagnostics: s_memrealtime of an awaited sample just before it announced itself (-> rt[5])
 };
 
 struct TrackState {
@@ -186,6 +191,11 @@ __device__ __forceinline__ long long ld_agent(const long long* p) { return __hip
 __device__ __forceinline__ void st_agent(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_agent(long long* p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #define TP_STORES_DONE() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+// work->hyp_early[k]: the frame's tag and the sample's outcome (ok << 31 | consensus) in one 8-byte word
+__device__ __forceinline__ long long tp_early_word(int frame_tag, unsigned ok_cnt) { return (long long)(((unsigned long long)(unsigned)frame_tag << 32) | ok_cnt); }
+__device__ __forceinline__ int tp_early_tag(long long w) { return (int)((unsigned long long)w >> 32); }
+__device__ __forceinline__ int tp_early_cnt(long long w) { return (int)((unsigned)w & 0x7fffffffu); }
+__device__ __forceinline__ int tp_early_ok(long long w) { return (int)(((unsigned)w >> 31) & 1u); }
 
 // ================================================================================================
 // Index chain 1/2: distances of every live pool row to the frame's keypoints -> sparse candidate lists
@@ -1174,11 +1184,12 @@ __device__ __forceinline__ void tp_hyp_ord_body(TpHypOrdLds& S, TrackState* st, 
     if (!leave && sample >= 2 * semi) {   // (the bound after `semi` samples reaches beyond 2 semi: all of semi .. 2 semi - 1 are being solved)
       if (tid >= semi && tid < 2 * semi) {
         int spins = 0;
-        while (ld_agent(&work->hyp_early[tid]) != frame_tag && spins < (1 << 22)) { __builtin_amdgcn_s_sleep(2); ++spins; }
+        long long w = 0;
+        while (tp_early_tag(w = ld_agent(&work->hyp_early[tid])) != frame_tag && spins < (1 << 22)) { __builtin_amdgcn_s_sleep(2); ++spins; }
         // (a sample that never reported: this one is solved whatever the rule would have said - solving more samples than the rule
         // visits changes no outcome; the frame part's own bounded wait reports the loss)
         const bool late = spins >= (1 << 22);
-        S.cnt[tid] = late ? 0 : ld_agent(&st->hyp[tid].cnt); S.ok[tid] = late ? 0 : ld_agent(&st->hyp[tid].ok);
+        S.cnt[tid] = late ? 0 : tp_early_cnt(w); S.ok[tid] = late ? 0 : tp_early_ok(w);   // (the word carries them: no second round trip)
       }
       __syncthreads();
       if (tid == 0) S.bound = pnp_bound_after(S.cnt, S.ok, n, 2 * semi);
@@ -1187,7 +1198,7 @@ __device__ __forceinline__ void tp_hyp_ord_body(TpHypOrdLds& S, TrackState* st, 
     }
     if (leave) {
       if (tid == 0) {
-        if (sample < TP_FLAGS) st_agent(&work->hyp_early[sample], frame_tag);
+        if (sample < TP_FLAGS) st_agent(&work->hyp_early[sample], tp_early_word(frame_tag, 0u));   // (not solved, never visited: no consensus)
         __hip_atomic_fetch_add(&work->hyp_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       return;
@@ -1216,11 +1227,13 @@ __device__ __forceinline__ void tp_hyp_ord_body(TpHypOrdLds& S, TrackState* st, 
     if (threadIdx.x < 4) st->K[threadIdx.x] = K[threadIdx.x];
   }
   const long long t_gather = clock64();
-  pnp_hyp_ord_wave<FUSED>(S.ord, S.Xw, S.uv, n, K, subsets + (size_t)min(n, 512) * 500, st->hyp, sample, (force_seq & 0xff) != 0);
+  unsigned ok_cnt = 0;
+  pnp_hyp_ord_wave<FUSED>(S.ord, S.Xw, S.uv, n, K, subsets + (size_t)min(n, 512) * 500, st->hyp, sample, (force_seq & 0xff) != 0, &ok_cnt);
   if (FUSED) {
+    if (threadIdx.x == 0 && sample < TP_EARLY) st_agent(&work->hyp_rt[sample], (long long)wall_clock64());
     TP_STORES_DONE();   // (lane 0's agent-scope stores of the sample's result have reached the coherent level)
     if (threadIdx.x == 0) {
-      if (sample < TP_FLAGS) st_agent(&work->hyp_early[sample], frame_tag);
+      if (sample < TP_FLAGS) st_agent(&work->hyp_early[sample], tp_early_word(frame_tag, ok_cnt));
       __hip_atomic_fetch_add(&work->hyp_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
@@ -1253,8 +1266,15 @@ __global__ __launch_bounds__(64) void k_tp_hyp_ord_first(TrackState* st, TrackWo
 struct TpLds {
   PoseLds pose;
   alignas(16) int sm[16];
-  float sT[16], sRwc[9], stwc[3];
   int cnt[PNP_HYP], ok[PNP_HYP], upd_r[PNP_HYP], best, good, iters;
+  long long hrt[TP_EARLY];    // fused launch: the awaited samples' announcement clocks (work->hyp_rt)
+  // fused launch, prepared while the samples run or by their pollers: pnp_update_terms(g, n_edges) for every consensus g a sample can
+  // report; each awaited sample's pose as solvePnPRansac would return it (row-major 4x4) and the LM's start estimate from it; the
+  // final pose (SetPose reads it from here)
+  double tab_ld[PNP_MAXN + 1]; int tab_r[PNP_MAXN + 1];
+  double pre_T[TP_EARLY][16]; Se3 pre_est[TP_EARLY];
+  double T_end[16];
+  long long t_samples, t_build;   // wall clock (thread 0): the samples are done / just before the LM's first build
   int late[TP_EARLY], lost;   // fused launch: a wait for the samples ran into its bound (the frame then counts as a PnP failure)
   int recf[8];   // the record's counters, fetched at the kernel's start
   double upd_ld[PNP_HYP];
@@ -1311,40 +1331,85 @@ __device__ __forceinline__ void tp_frame_body(TpLds& S, TrackState* st, TrackWor
     }
     st->Xw[3 * e] = (double)xyz[0]; st->Xw[3 * e + 1] = (double)xyz[1]; st->Xw[3 * e + 2] = (double)xyz[2];
     st->obs[2 * e] = (double)k.x; st->obs[2 * e + 1] = (double)k.y;
+    if (FUSED && e < POSE_CHUNK) {   // the LM's first chunk, staged for its register copies (below; the slabs are idle until the LM)
+      double* c5 = S.pose.tw + 5 * e;
+      c5[0] = (double)xyz[0]; c5[1] = (double)xyz[1]; c5[2] = (double)xyz[2]; c5[3] = (double)k.x; c5[4] = (double)k.y;
+    }
   }
   if (tid < 4 && !have_corr) st->K[tid] = (double)((const float*)&st->cam)[tid];
   // ---- PnP initial pose (src/pnpmatch.cc:212-247): no prior; if solvePnPRansac fails the last pose stays ----------
   const bool ran = !skip && n_edges >= 5;
   bool decided_early = false;
+  double first[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // FUSED: this thread's two edges of the LM's first chunk (pose_edge_regs)
+  if (FUSED) {
+    // While the samples run (~80 us): everything the hand-over from them to the LM would otherwise fetch or compute behind the last
+    // of them.  K into the LM's workspace; the pow / log terms of the rule's iteration bound for EVERY consensus a sample can report
+    // (pnp_update_terms(g, n_edges), g = 5 .. n_edges: the function and the arguments the sample's poller used to call it with).
+    if (tid < 4) S.pose.K[tid] = (double)((const float*)&st->cam)[tid];
+    if (ran) {
+      if (n_edges > 5)
+        for (int g = 5 + tid; g <= n_edges; g += TPF_NT) {
+          double ld; int r;
+          pnp_update_terms(g, n_edges, &ld, &r);
+          S.tab_ld[g] = ld; S.tab_r[g] = r;
+        }
+      if (tid >= TP_EARLY && tid < PNP_HYP) { S.cnt[tid] = 0; S.ok[tid] = 0; S.upd_ld[tid] = 1.0; S.upd_r[tid] = 0; }   // (never visited when the rule ends early)
+    }
+    __syncthreads();
+    pose_edge_regs(S.pose.tw, S.pose.tw + 3, max(min(n_edges, POSE_CHUNK), 1), first, 5, 5);
+  }
   if (FUSED && ran) {
-    // The samples of this launch.  First the TP_EARLY lowest ones, each awaited by a thread of its own (which fetches the sample's
-    // consensus and prepares its pow / log terms as soon as it sees it): if the rule ends within them - it nearly always does -
-    // the slowest of the other samples is not waited for.  (Bounded waits, as tp_wait_work's.)
+    // The samples of this launch.  First the TP_EARLY lowest ones, each awaited by a thread of its own: the word that announces a
+    // sample carries its consensus, so the poller has the rule's inputs at once (terms: from the table) and requests the sample's
+    // pose in the same breath - if the rule ends within these samples, which it nearly always does, the slowest of the other
+    // samples is not waited for, and the winner's pose is already here when the rule names it.  (Bounded waits, as tp_wait_work's.)
+    long long hp[12], hclk = 0;
+    bool late = false;
     if (tid < TP_EARLY) {
       int spins = 0;
-      while (ld_agent(&work->hyp_early[tid]) != id + 1 && spins < (1 << 22)) { __builtin_amdgcn_s_sleep(1); ++spins; }
+      long long w = 0;
+      while (tp_early_tag(w = ld_agent(&work->hyp_early[tid])) != id + 1 && spins < (1 << 22)) { __builtin_amdgcn_s_sleep(1); ++spins; }
       // A sample that did not report (forward progress of a workgroup that waits for others of its launch rests on in-order
       // dispatch, which the hardware does and HIP does not promise): NOTHING of this launch's samples is used - the frame is
       // treated as cv::solvePnPRansac returning false (the last pose stays), the record says so (n_pnp_inliers = -1), the
       // sticky flag becomes 4 and the next svo_sync / svo_track_overflowed reports it (SVO_E_TIMEOUT) and switches the
       // context to the two-launch pose chain ("tail_fused" = 0).
-      const bool late = spins >= (1 << 22);
+      late = spins >= (1 << 22);
       if (late) atomicOr(&st->overflow, 4);
+      const PnpHyp& h = st->hyp[tid];
+#pragma unroll
+      for (int i = 0; i < 12; ++i) hp[i] = ld_agent(reinterpret_cast<const long long*>(i < 9 ? &h.R[i] : &h.t[i - 9]));   // (all in flight together)
+      hclk = ld_agent(&work->hyp_rt[tid]);
       S.late[tid] = late ? 1 : 0;
-      const int c = late ? 0 : ld_agent(&st->hyp[tid].cnt), o = late ? 0 : ld_agent(&st->hyp[tid].ok);
+      const int c = late ? 0 : tp_early_cnt(w), o = late ? 0 : tp_early_ok(w);
       S.cnt[tid] = c; S.ok[tid] = o;
-      double ld = 1.0; int r = 0;
-      if (o && c > 4 && n_edges > 5) pnp_update_terms(c, n_edges, &ld, &r);
-      S.upd_ld[tid] = ld; S.upd_r[tid] = r;
-    } else if (tid < PNP_HYP) {
-      S.cnt[tid] = 0; S.ok[tid] = 0; S.upd_ld[tid] = 1.0; S.upd_r[tid] = 0;   // (never visited when the rule ends early)
+      const bool bound = o && c > 4 && n_edges > 5;
+      const int g = min(max(c, 5), max(n_edges, 5));
+      S.upd_ld[tid] = bound ? S.tab_ld[g] : 1.0; S.upd_r[tid] = bound ? S.tab_r[g] : 0;
     }
     __syncthreads();
-    if (tid == 0) {
+    // the rule over the awaited samples in ONE walk (a thread of the second wave), beside the pollers, which form what the LM
+    // starts from for each of their samples: the pose as solvePnPRansac returns it and pose_opt_block's start estimate from it
+    if (tid == 64) {
       int l = 0;
       for (int k = 0; k < TP_EARLY; ++k) l |= S.late[k];
       S.lost = l;
-      S.iters = l ? 0 : pnp_select_pre_bound(S.cnt, S.ok, S.upd_ld, S.upd_r, n_edges, TP_EARLY);
+      int best = -1, good = 0;
+      S.iters = l ? 0 : pnp_select_pre_early(S.cnt, S.ok, S.upd_ld, S.upd_r, n_edges, TP_EARLY, &best, &good);
+      S.best = best; S.good = good;
+    }
+    if (tid < TP_EARLY) {
+      double Tp[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int r = q >> 2, c = q & 3;
+        Tp[q] = r == 3 ? (c == 3 ? 1.0 : 0.0) : __builtin_bit_cast(double, c == 3 ? hp[9 + r] : hp[3 * r + c]);
+        S.pre_T[tid][q] = Tp[q];
+      }
+      Se3 e0;
+      pose_start_estimate(Tp, 1, e0);
+      S.pre_est[tid] = e0;
+      S.hrt[tid] = late ? 0 : hclk;
     }
     __syncthreads();
     decided_early = S.lost || S.iters <= TP_EARLY;   // (lost: nothing more is waited for)
@@ -1359,80 +1424,97 @@ __device__ __forceinline__ void tp_frame_body(TpLds& S, TrackState* st, TrackWor
   } else if (tid == 0) {
     S.lost = 0;
   }
-  if (FUSED && tid == 0) work->rt[4] = wall_clock64();   // the frame part proper starts here (rt[2] .. rt[4]: the samples)
-  if (ran && !decided_early && !(FUSED && S.lost))
-    for (int h = tid; h < PNP_HYP; h += TPF_NT) {
-      // every sample's thread prepares the pow / log terms the iteration bound would need if that sample became the best
-      const int c = FUSED ? ld_agent(&st->hyp[h].cnt) : st->hyp[h].cnt, o = FUSED ? ld_agent(&st->hyp[h].ok) : st->hyp[h].ok;
-      S.cnt[h] = c; S.ok[h] = o;
-      double ld = 1.0; int r = 0;
-      if (o && c > 4 && n_edges > 5) pnp_update_terms(c, n_edges, &ld, &r);
-      S.upd_ld[h] = ld; S.upd_r[h] = r;
+  if (FUSED && tid == 0) S.t_samples = wall_clock64();   // the frame part proper starts here (rt[2] .. rt[4]: the samples); stored at the end
+  // fast: the awaited samples decided the frame - winner, consensus and iteration count are in LDS, and so is the winner's pose
+  const bool fast = FUSED && ran && decided_early;
+  if (!fast) {
+    if (ran && !decided_early && !(FUSED && S.lost))
+      for (int h = tid; h < PNP_HYP; h += TPF_NT) {
+        // every sample's thread prepares the pow / log terms the iteration bound would need if that sample became the best
+        const int c = FUSED ? ld_agent(&st->hyp[h].cnt) : st->hyp[h].cnt, o = FUSED ? ld_agent(&st->hyp[h].ok) : st->hyp[h].ok;
+        S.cnt[h] = c; S.ok[h] = o;
+        double ld = 1.0; int r = 0;
+        if (o && c > 4 && n_edges > 5) pnp_update_terms(c, n_edges, &ld, &r);
+        S.upd_ld[h] = ld; S.upd_r[h] = r;
+      }
+    __syncthreads();
+    if (tid == 0) {
+      int good = 0, iters = 0;
+      S.best = (ran && !S.lost) ? pnp_select_pre(S.cnt, S.ok, S.upd_ld, S.upd_r, n_edges, &good, &iters) : -1;
+      S.good = good; S.iters = iters;
     }
-  __syncthreads();
-  if (tid == 0) {
-    int good = 0, iters = 0;
-    S.best = (ran && !S.lost) ? pnp_select_pre(S.cnt, S.ok, S.upd_ld, S.upd_r, n_edges, &good, &iters) : -1;
-    S.good = good; S.iters = iters;
+    __syncthreads();
   }
-  __syncthreads();
-  if (tid < 16) {
-    double v = (double)st->lastTcw[tid];
+  // (FUSED: the stores below are the last wave's - the first wave, whose thread 0 carries the LM's serial part, and with it the
+  // frame, has no store in flight that a later wait for a load of its would have to sit out)
+  const int tb = FUSED ? TPF_NT - 64 : 0;
+  if (tid >= tb && tid < tb + 16) {
+    const int q = tid - tb;
+    double v;
     if (S.best >= 0) {
       const PnpHyp& h = st->hyp[S.best];
-      const int r = tid >> 2, c = tid & 3;
-      if (FUSED) {
+      const int r = q >> 2, c = q & 3;
+      if (fast) {
+        v = S.pre_T[S.best][q];
+      } else if (FUSED) {
         const double* src = r == 3 ? nullptr : (c == 3 ? &h.t[r] : &h.R[3 * r + c]);
         v = src ? __builtin_bit_cast(double, ld_agent(reinterpret_cast<const long long*>(src))) : (c == 3 ? 1.0 : 0.0);
       } else {
         v = r == 3 ? (c == 3 ? 1.0 : 0.0) : (c == 3 ? h.t[r] : h.R[3 * r + c]);
       }
+    } else {
+      v = (double)st->lastTcw[q];
     }
-    st->T[tid] = v;
-    work->T_pnp[tid] = v;
+    st->T[q] = v;
+    work->T_pnp[q] = v;
   }
-  if (tid == 0) {
+  if (tid == tb) {
     st->pnp.n_points = n_edges; st->pnp.n_inliers = S.best >= 0 ? S.good : 0; st->pnp.best_hypothesis = S.best;
     st->pnp.ok = S.best >= 0 ? 1 : 0; st->pnp.iterations = S.iters;
     work->pnp_best = S.best; work->pnp_iterations = S.iters; work->pnp_inliers = S.best >= 0 ? S.good : 0;
     work->pnp_ok = S.best >= 0 ? 1 : 0;
   }
-  __syncthreads();
+  if (!fast) __syncthreads();
   const long long tf1 = clock64();
   // ---- Optimizer::PoseOptimization (src/Optimizer.cc:15-86) from the CV_32F-stored PnP pose ----------------------
-  pose_opt_block<TPF_NT>(S.pose, st->Xw, st->obs, n_edges, st->K, st->T, &st->lm, 1, use_mfma);
+  // (fast with a winner: the start estimate is the one its poller formed - nothing is read back from st->T; otherwise from st->T)
+  int lm_iters = 0;        // (thread 0)
+  const PosePrepared prep{(fast && S.best >= 0) ? &S.pre_est[S.best] : nullptr, first};
+  pose_opt_block<TPF_NT>(S.pose, st->Xw, st->obs, n_edges, st->K, st->T, &st->lm, 1, use_mfma, &S.t_build, FUSED ? &prep : nullptr, S.T_end, &lm_iters);
   __syncthreads();
   const long long tf2 = clock64();
   // ---- SetPose (CV_32F, src/Optimizer.cc:82-83), positions of the points created this frame -------
-  if (tid < 16) S.sT[tid] = (float)st->T[tid];
-  __syncthreads();
-  if (tid < 9) S.sRwc[tid] = S.sT[4 * (tid % 3) + tid / 3];
-  __syncthreads();
-  if (tid < 3) {
-    const double acc = (double)S.sRwc[3 * tid] * (double)S.sT[3] + (double)S.sRwc[3 * tid + 1] * (double)S.sT[7] +
-                       (double)S.sRwc[3 * tid + 2] * (double)S.sT[11];
-    S.stwc[tid] = (float)(-acc);
+  // (every thread for itself, from the LM's pose in LDS)
+  float sT[16], sRwc[9], stwc[3];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) sT[i] = (float)S.T_end[i];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) sRwc[i] = sT[4 * (i % 3) + i / 3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double acc = (double)sRwc[3 * i] * (double)sT[3] + (double)sRwc[3 * i + 1] * (double)sT[7] +
+                       (double)sRwc[3 * i + 2] * (double)sT[11];
+    stwc[i] = (float)(-acc);
   }
-  __syncthreads();
 #pragma unroll
   for (int q = 0; q < NEWS; ++q) {
     const int g = tid + q * TPF_NT < nkp ? new_g[q] : -1;
     if (g < 0) continue;
     float xyz[3];
-    tk_unproject(st->cam, new_k[q].x, new_k[q].y, new_d[q], S.sRwc, S.stwc, xyz);
+    tk_unproject(st->cam, new_k[q].x, new_k[q].y, new_d[q], sRwc, stwc, xyz);
     float* gp = gpos + 3 * (size_t)(g & (TRK_GPOS - 1));
     gp[0] = xyz[0]; gp[1] = xyz[1]; gp[2] = xyz[2];
   }
   if (tid == 0) {
     svo_track_result r;
-    for (int i = 0; i < 16; ++i) { r.Tcw[i] = S.sT[i]; st->lastTcw[i] = S.sT[i]; }
+    for (int i = 0; i < 16; ++i) { r.Tcw[i] = sT[i]; st->lastTcw[i] = sT[i]; }
     r.frame_id = id; r.n_kp = nkp; r.n_stereo = S.recf[0];
     r.n_match_pass1 = S.recf[1]; r.n_match_pass2 = S.recf[2];
-    r.n_pnp_inliers = skip ? 0 : (S.lost ? -1 : st->pnp.n_inliers);   // (-1: the samples of a fused launch did not report in time)
+    r.n_pnp_inliers = skip ? 0 : (S.lost ? -1 : (S.best >= 0 ? S.good : 0));   // (-1: the samples of a fused launch did not report in time)
     r.n_lm_edges = n_edges;
     r.n_new_mappoints = S.recf[3];
     r.n_local_map = S.recf[4];
-    r.lm_iterations = st->lm.iterations;
+    r.lm_iterations = lm_iters;
     // diagnostics: rows of pass 1 / pass 2 that could match at all.  (The ROUNDS a pass took are not part of the record: a
     // dense row may or may not see a claim made earlier in the same phase - the outcome is the same either way, the
     // number of rounds is not, and records are compared byte for byte.  svo_debug_track_frames reports them.)
@@ -1440,7 +1522,15 @@ __device__ __forceinline__ void tp_frame_body(TpLds& S, TrackState* st, TrackWor
     r.reserved[1] = S.recf[6] & 0xffff;
     *res_out = r;
     st->pose_ts[8] = tf0; st->pose_ts[9] = tf1; st->pose_ts[10] = tf2; st->pose_ts[11] = clock64();
+    if (FUSED) work->rt[4] = S.t_samples;
     work->rt[3] = wall_clock64();
+    long long handover = 0;   // rt[5]: latest announcement of an awaited sample -> the LM's first build
+    if (fast && !S.lost) {
+      long long t_ann = S.hrt[0];
+      for (int k = 1; k < TP_EARLY; ++k) t_ann = max(t_ann, S.hrt[k]);
+      handover = S.t_build - t_ann;
+    }
+    work->rt[5] = handover;
   }
 }
 __global__ __launch_bounds__(TPF_NT) void k_tp_frame(TrackState* st, TrackWork* work, const svo_kp* kp,
