@@ -22,7 +22,10 @@
 //     12 x 12 problem, sweeps overlapped, verified bit-identical to the sequential loop); problems on disjoint rows - the
 //     three EPnP candidates' decompositions - share the steps.  V is not accumulated for M^T M: epnp only asks for U.
 //   * the small decompositions (3 x 3: control points, barycentric inverse, absolute orientation; 6 x 3 / 6 x 4 / 6 x 5:
-//     the three beta initialisations) go through the same engine, the three EPnP candidates side by side.
+//     the three beta initialisations) go through the same engine, the three EPnP candidates side by side.  The 3 x 3 ones keep
+//     ALL THREE rows of a problem in every lane of that problem (columns g and 4 + g): both rows of a pair are at hand, so their
+//     step loop has no row exchange through LDS and no schedule table - three copies of the step body, one per pair of the
+//     cyclic order (0, 1), (0, 2), (1, 2); same operations on the same operands.
 //   * everything else (M, M^T M, L_6x10, rho, cvInvert / cvSolve back-substitution, compute_ccs / pcs, estimate_R_and_t,
 //     reprojection_error) is one lane per OUTPUT element, each lane summing its element in the loop's own order; the
 //     five Gauss-Newton steps with epnp::qr_solve are scalar code, one candidate per DPP row, arrays in registers.
@@ -79,7 +82,9 @@ struct Lds {
                             // 4 its finish by lane 0 (zero / equal singular values), 8 a small decomposition finished by lane 0, 16 forced
   long long stamp[8];
 #ifdef EO_PROFILE
-  long long prof[8];
+  long long prof[8];        // [0..2] ticks of the three jacobi_rows<3> calls (control points, cvInvert(CC), the candidates' ABt), [3..5] the
+                            // sweeps each ran (of the slowest of its problems; a sweep is three steps), [6] the call's first clock
+  int j3sweeps;
 #endif
 };
 
@@ -268,10 +273,20 @@ EO_FN double row_norm2(double n0, double n1, double n2, double mk) {
   return a;
 }
 
+#ifdef EO_PROFILE   // ticks and sweeps of the idx-th jacobi_rows<3> call of a solve (the default build has neither)
+#define EO_PROF3_BEGIN() if (lane == 0) { S.j3sweeps = 0; S.prof[6] = clock64(); } EO_SYNC()
+#define EO_PROF3_END(idx) if (lane == 0) { S.prof[idx] = clock64() - S.prof[6]; S.prof[3 + (idx)] = S.j3sweeps; } EO_SYNC()
+#else
+#define EO_PROF3_BEGIN() do {} while (0)
+#define EO_PROF3_END(idx) do {} while (0)
+#endif
+
 // ---- JacobiSVDImpl_<double> on the rows of S.jr, all problems of the wave together ------------------------------------------
 // Lane 16 g + r works on matrix row r (a row of S.jr: M columns of A, then V, 12 columns in all - the columns behind V must hold
 // finite values, they are rotated along) and holds its columns g, 4 + g, 8 + g.  (n, base): the problem row r belongs to -
 // n rows starting at row `base`, n in {3, 4, 5, 12} - or n = 0: the row idles.
+// M = 3 takes three-row problems only (n in {3, 0}); its loop holds columns g and 4 + g of the problem's three rows in the lane and
+// leaves columns 8 + g as they are (no caller reads a column >= 6 of such a problem).
 // On return the rows are what JacobiSVDImpl_ leaves before its sort: rotated, the A part scaled by 1 / W[i], and
 // W[i] = sqrt(sum At[i][k]^2) in column 15 of the row.
 // Returns (uniform) the lanes whose step loop ran out of sweeps.
@@ -282,9 +297,19 @@ EO_FN unsigned long long jacobi_rows(Lds& S, int n, int base, int lane) {
   // (finite) x * 0.0 adds nothing to a sum that started at +0.0
   const double mk = M == 6 ? (g < 2 ? 1.0 : 0.0) : (M == 3 ? (g < 3 ? 1.0 : 0.0) : 1.0);
   const double eps = 2.220446049250313e-16 * 10;
-  double x0 = S.jr[r * 16 + g], x1 = S.jr[r * 16 + 4 + g], x2 = S.jr[r * 16 + 8 + g];
+  // M = 3 (three-row problems only): the block EO_JACOBI_ASM_3R keeps the problem's three rows in the lane's registers - it reads them
+  // from S.jr itself and needs neither the exchange nor the schedule table; -DEO_JACOBI3_TABLE builds the table-driven block instead
+#ifdef EO_JACOBI3_TABLE
+  constexpr bool regs3 = false;
+#else
+  constexpr bool regs3 = M == 3;
+#endif
+  double x0 = 0, x1 = 0, x2 = S.jr[r * 16 + 8 + g];
   double* const mine = S.xch[r][g];
-  { d2 lo; lo.x = x0; lo.y = x1; *reinterpret_cast<d2*>(mine) = lo; mine[2] = x2; }
+  if (!regs3) {
+    x0 = S.jr[r * 16 + g]; x1 = S.jr[r * 16 + 4 + g];
+    d2 lo; lo.x = x0; lo.y = x1; *reinterpret_cast<d2*>(mine) = lo; mine[2] = x2;
+  }
   const int tb = n == 12 ? EO_TAB12_OFF : (n == 5 ? EO_TAB5_OFF : (n == 4 ? EO_TAB4_OFF : EO_TAB3_OFF));
   const int steps = n == 12 ? EO_TAB12_STEPS : (n == 5 ? EO_TAB5_STEPS : (n == 4 ? EO_TAB4_STEPS : EO_TAB3_STEPS));
   const int pro = n == 12 ? EO_TAB12_PROLOGUE : (n == 5 ? EO_TAB5_PROLOGUE : (n == 4 ? EO_TAB4_PROLOGUE : EO_TAB3_PROLOGUE));
@@ -309,10 +334,10 @@ EO_FN unsigned long long jacobi_rows(Lds& S, int n, int base, int lane) {
   const double eps2hi = eps2 * (1.0 + 9.094947017729282e-13), eps2lo = eps2 * (1.0 - 9.094947017729282e-13);   // 2^-40
   unsigned chg = 0, nst = 0, flag = 0;
   int tt = 0, tp = n > 0 ? tb + q : 0, sb = 0;
-  const unsigned e0 = S.tab[tp];                             // step 0
+  const unsigned e0 = regs3 ? 0u : S.tab[tp];                // step 0
   ++tt; tp += n;
   if (tt == steps) { tt = pro; tp = n > 0 ? tb + pro * n + q : 0; ++sb; }
-  const unsigned e1 = S.tab[tp];                             // step 1
+  const unsigned e1 = regs3 ? 0u : S.tab[tp];                // step 1
   const unsigned tpa = a_tab + 4u * (unsigned)tp;
   const unsigned act = n >= 2 ? 1u : 0u;
   const unsigned amine = lds(mine), axch = lds(&S.xch[0][g][0]);
@@ -330,8 +355,23 @@ EO_FN unsigned long long jacobi_rows(Lds& S, int n, int base, int lane) {
                    [eps2hi] "v"(eps2hi), [eps2lo] "v"(eps2lo), [amine] "v"(amine), [axch] "v"(axch)
                  : EO_JACOBI_ASM_CLOBBERS);
   else if (M == 6) asm volatile(EO_JACOBI_ASM_6 EO_JACOBI_OPERANDS);
-  else asm volatile(EO_JACOBI_ASM_3 EO_JACOBI_OPERANDS);
+  else if (!regs3) asm volatile(EO_JACOBI_ASM_3 EO_JACOBI_OPERANDS);
+  else {
+    // rows base .. base + 2 of the lane's problem, columns g and 4 + g (an idle lane reads rows 0 .. 2: in bounds, never committed)
+    const unsigned ajr = lds(&S.jr[(n > 0 ? base : 0) * 16 + g]);
+    asm volatile(EO_JACOBI_ASM_3R
+                 : [x0] "=&v"(x0), [x1] "=&v"(x1), [chg] "=&v"(chg), [flag] "+v"(flag)
+                 : [ajr] "v"(ajr), [lane] "v"(lane), [base] "v"(base), [act] "v"(act), [mk] "v"(mk), [eps] "v"(eps), [eps2hi] "v"(eps2hi),
+                   [eps2lo] "v"(eps2lo)
+                 : EO_JACOBI_ASM_CLOBBERS);
+  }
 #undef EO_JACOBI_OPERANDS
+#ifdef EO_PROFILE
+  if (M == 3) {               // sweeps the loop ran: the block's counter, or (table-driven) one more than the last sweep a row rotated in (25 at the most)
+    const int sw = regs3 ? (int)chg : (33 - __clz(chg) < 25 ? 33 - __clz(chg) : 25);
+    if (n > 0) atomicMax(&S.j3sweeps, sw);
+  }
+#endif
   // 25 sweeps without convergence: the sequential code decides - the whole sample for the 12 x 12 problem, this decomposition
   // alone for a small one (the caller, svd_small_seq)
   const unsigned long long exhausted = __ballot(flag != 0 && n > 0);
@@ -653,7 +693,9 @@ EO_FN bool solve5_wave(Lds& S, epnp_exact::Work& xw, const double* K, double* R_
     EO_SYNC();
   };
   load_pw0();
+  EO_PROF3_BEGIN();
   unsigned long long ex = jacobi_rows<3>(S, r16 < 3 ? 3 : 0, r16 < 3 ? 0 : r16, lane);
+  EO_PROF3_END(0);
   unsigned long long bd = svd_rank(S, slot == 0 ? 3 : 0, 0, 0, lane);
   if (ex | bd) {             // (uniform) e.g. exactly coplanar world points: a zero singular value
     load_pw0();
@@ -680,7 +722,9 @@ EO_FN bool solve5_wave(Lds& S, epnp_exact::Work& xw, const double* K, double* R_
     EO_SYNC();
   };
   load_cc();
+  EO_PROF3_BEGIN();
   ex = jacobi_rows<3>(S, r16 < 3 ? 3 : 0, r16 < 3 ? 0 : r16, lane);
+  EO_PROF3_END(1);
   bd = svd_rank(S, slot == 0 ? 3 : 0, 0, 0, lane);
   if (ex | bd) {
     load_cc();
@@ -890,7 +934,9 @@ EO_FN bool solve5_wave(Lds& S, epnp_exact::Work& xw, const double* K, double* R_
   load_abt(-1);
   {
     const bool mine = r16 < 15 && r16 % 5 < 3;
+    EO_PROF3_BEGIN();
     ex = jacobi_rows<3>(S, mine ? 3 : 0, mine ? 5 * (r16 / 5) : r16, lane);
+    EO_PROF3_END(2);
   }
   bd = svd_rank(S, slot < 3 ? 3 : 0, base, cand, lane);
   if (ex | bd) {             // (uniform)

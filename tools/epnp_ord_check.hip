@@ -131,6 +131,19 @@ int main(int argc, char** argv) {
   printf("\n  (control points + barycentric | M, MtM | 12x12 SVD | L, rho, beta init SVDs | gauss-newton | R, t, error | selection)\n");
   { long long pf[8] = {0}; for (int s = 0; s < n; ++s) for (int i = 0; i < 8; ++i) pf[i] += O[s].prof[i];
     if (pf[7]) { printf("12x12 loop, mean ticks per step: top+loads %.0f | pair test %.0f | rotation %.0f | update+norm %.0f | stores+sync %.0f | close+loop %.0f  (steps per solve %.1f)\n", (double)pf[0] / pf[7], (double)pf[1] / pf[7], (double)pf[2] / pf[7], (double)pf[3] / pf[7], (double)pf[4] / pf[7], (double)pf[5] / pf[7], (double)pf[7] / n); } }
+  { // EO_PROFILE: the three jacobi_rows<3> calls - ticks, sweeps (three steps each), and the least-squares line ticks = fixed + per sweep * sweeps
+    bool any = false; for (int s = 0; s < n; ++s) any = any || O[s].prof[0] != 0;
+    static const char* name[3] = {"control points", "cvInvert(CC)", "ABt x3"};
+    double tot = 0;
+    for (int c = 0; any && c < 3; ++c) {
+      double st_ = 0, ss = 0, sss = 0, sst = 0;
+      for (int s = 0; s < n; ++s) { const double t = (double)O[s].prof[c], w = (double)O[s].prof[3 + c]; st_ += t; ss += w; sss += w * w; sst += w * t; }
+      const double den = n * sss - ss * ss, slope = den > 0 ? (n * sst - ss * st_) / den : 0.0, icpt = (st_ - slope * ss) / n;
+      printf("jacobi_rows<3> %-14s mean ticks %.0f  sweeps %.2f (steps %.2f)  ticks per step overall %.1f  | line ticks = A + B * sweeps: B / 3 (a step of a rotating sweep) %.1f, A (set-up, epilogue, what the closing sweep's non-rotating steps save) %.0f\n",
+             name[c], st_ / n, ss / n, 3 * ss / n, st_ / (3 * ss), slope / 3, icpt);
+      tot += st_ / n;
+    }
+    if (any) printf("jacobi_rows<3> three calls together, mean ticks %.0f\n", tot); }
   { long long sf[8] = {0}; int nf = 0; for (int s = 0; s < n; ++s) if (O[s].flag) { ++nf; for (int i = 1; i < 8; ++i) sf[i] += O[s].stamp[i] - O[s].stamp[i - 1]; }
     if (nf) { printf("flagged samples, mean ticks per stage:"); for (int i = 1; i < 8; ++i) printf(" %.0f", (double)sf[i] / nf); printf("\n"); } }
   { long long st2 = 0; int n2 = 0; for (int s = 0; s < n; ++s) if (O[s].sweeps >= 1000000) { st2 += O[s].sweeps - 1000000; ++n2; O[s].sweeps = 0; }

@@ -1,5 +1,5 @@
 """Generates csrc/svo_epnp_ord_asm.h: the step loop of the wave Jacobi engine (jacobi_rows of svo_epnp_ord_dev.h) as ONE
-inline-assembly block per column count M in {12, 6, 3} - the compiler's version of the same loop spends more than half of a
+inline-assembly block per column count M in {12, 6, 3}, plus the block jacobi_rows<3> uses (3R) - the compiler's version of the same loop spends more than half of a
 step on copies of the loop-carried rows, lane-mask bookkeeping and branches (measured: 675 of 1200 ticks per step with the
 arithmetic and the LDS traffic removed).
 
@@ -9,7 +9,7 @@ result is read, 2 between a VALU write of an SGPR / VCC and a VALU read of it as
 and a DMFMA read of it, 4 between dependent 4x4x4 DMFMAs (SrcC), 6 before a VALU read and 9 before an LDS read of a DMFMA
 result.
 
-Two layouts:
+Three layouts:
   M = 6, M = 3 (program): ONE copy of the step body that walks the schedule table in LDS - the entry of step t + 2 is read while
     step t computes (TT / TP / SB, wrap to the prologue's end), decode() turns an entry into the partner's address, the lane mask
     VALID, the sign and the sweep bit, and every step tests the entry's closing bit.  Three problems of different sizes share
@@ -23,6 +23,12 @@ Two layouts:
     last), where the base bit U_BB is doubled.  No table read, no walk, no decode and no closing test per step.  pair_test,
     decide, the rotation, the commit and the write-back are the same instruction sequences as in the table-driven layout.
 
+  M = 3, rows in registers (program3r, EO_JACOBI_ASM_3R): three-row problems only - what every caller of jacobi_rows<3> passes.  Each
+    lane holds columns g and 4 + g of all three rows of its problem, so a step needs no partner row from LDS: three copies of the
+    step body for the pairs (0, 1), (0, 2), (1, 2) behind .p2align with ONE backward branch, both rows updated in the lane, scalar
+    sweep bookkeeping in the third copy only.  pair_test's, decide's and the rotation's instruction sequences as in the other layouts.
+    The table-driven M = 3 block stays (jacobi_rows<3> with -DEO_JACOBI3_TABLE; its text is pinned by tests/test_jacobi_unrolled.py).
+
 Registers: the block owns v140..v255 and s60..s71 (clobbers); the row (x0, x1, x2) lives in v150..v155 while the loop runs.
   v140..v149, v174..v175  U0..U2, V0..V2 (squares for the DMFMA chains)       v150..v157  X0..X2, WW
   v160..v173  division / square-root temporaries, QQ, TA..TC                  v180..v199  ONE, T0..T2, AB, Y, G, H, RR, D
@@ -30,7 +36,10 @@ Registers: the block owns v140..v255 and s60..s71 (clobbers); the row (x0, x1, x
   table-driven: v234..v253  E, E1, E2, TT, TP, SB, SBE, SBE1, SGN, SWBIT, AP, AW, TMP, TMP2, ROW, QI, ONEI, STEPS, PRO, TSTEP
   unrolled:     v234..v245  U_AP[0..11] partner addresses per slot; v158, v159, v176..v179, v246..v251  U_K[0..11] sign | sweep
                 v252 U_SGN, v253 U_TMP, v254 U_BB (1 << sweep base), v255 U_TMP2; N0 / N1 hold the row and its index during set-up
+  rows in registers: v234..v245  R3[row][column group], v246 R3_QI (row index in the problem), v247 R3_TMP; the rotated rows go through
+                N0..N2, V0 and T0..T2, U0
   s[60:61] ACT, s[62:63] VALID, s[64:65] ROT, s[66:67] SAVE (exec), s[68:69] CL, s[70:71] ST
+  (rows in registers: ACT stands for VALID, CL collects the lanes that rotated in the sweep under way, s66 counts sweeps)
 """
 
 import os
@@ -125,9 +134,10 @@ def pair_test(M, wait=1):
     return out
 
 
-def decide(tag=""):
-    """ROT = VALID & !(|p| <= eps sqrt(W[i] W[j])).  Decided on the squares with a margin of 2^-40 (the roundings of either side are
+def decide(tag="", valid=None):
+    """ROT = VALID & !(|p| <= eps sqrt(W[i] W[j])) (`valid`: the lane mask that stands for VALID; the register layout has none of its own).  Decided on the squares with a margin of 2^-40 (the roundings of either side are
     of the order 2^-52); a pair inside the margin - or with a NaN - takes the exact expression for the whole wave."""
+    valid = valid or VALID
     return [
         "v_mul_f64 %s, %s, %s" % (pair(AB), pair(WW), pair(WP)),
         "v_mul_f64 %s, %s, %s" % (pair(G), pair(P), pair(P)),
@@ -136,24 +146,25 @@ def decide(tag=""):
         "v_cmp_gt_f64 vcc, %s, %s" % (pair(G), pair(H)),            # p^2 well above: rotates
         "v_cmp_lt_f64 %s, %s, %s" % (ST, pair(G), pair(RR)),        # well below: does not
         "s_or_b64 %s, vcc, %s" % (ST, ST),
-        "s_andn2_b64 %s, %s, %s" % (ST, VALID, ST),                 # undecided (valid pairs only)
+        "s_andn2_b64 %s, %s, %s" % (ST, valid, ST),                 # undecided (valid pairs only)
         "s_cbranch_scc0 L_decided_%s%%=" % tag,
     ] + nsqrt(pair(THR), pair(AB)) + [
         "v_mul_f64 %s, %s, %%[eps]" % (pair(THR), pair(THR)),
         "v_cmp_nle_f64 vcc, |%s|, %s" % (pair(P), pair(THR)),
         "L_decided_%s%%=:" % tag,
-        "s_and_b64 %s, vcc, %s" % (ROT, VALID),
+        "s_and_b64 %s, vcc, %s" % (ROT, valid),
     ]
 
 
-def rotation(sgn):
-    """(c, s) of the pair by OpenCV's formulas and the rotated row N0..N2 = c mine + (+-s) theirs; `sgn`: the register that holds
-    0x80000000 in the lanes of the pair's second (j) row."""
+def rotation_cs(sgn):
+    """(c, s) of the pair by OpenCV's formulas, into CC and SS; `sgn`: the register that holds 0x80000000 in the lanes of the pair's
+    second (j) row (there WW / WP are W[j] / W[i] and the lane gets -s), or None: every lane is on the first row's side."""
     o = []
     a = o.append
     a("v_add_f64 %s, %s, %s" % (pair(P), pair(P), pair(P)))
     a("v_add_f64 %s, %s, -%s" % (pair(BETA), pair(WW), pair(WP)))
-    a("v_xor_b32 %s, %s, %s" % (v(BETA + 1), v(BETA + 1), v(sgn)))
+    if sgn is not None:
+        a("v_xor_b32 %s, %s, %s" % (v(BETA + 1), v(BETA + 1), v(sgn)))
     a("v_cmp_gt_f64 vcc, |%s|, |%s|" % (pair(P), pair(BETA)))
     a("s_nop 1")
     a("v_cndmask_b32 %s, %s, %s, vcc" % (v(HI), v(BETA), v(P)))
@@ -178,7 +189,15 @@ def rotation(sgn):
     a("v_cndmask_b32 %s, %s, %s, vcc" % (v(SS + 1), v(R2 + 1), v(R1 + 1)))
     a("v_cndmask_b32 %s, %s, %s, vcc" % (v(CC), v(R1), v(R2)))
     a("v_cndmask_b32 %s, %s, %s, vcc" % (v(CC + 1), v(R1 + 1), v(R2 + 1)))
-    a("v_xor_b32 %s, %s, %s" % (v(SS + 1), v(SS + 1), v(sgn)))
+    if sgn is not None:
+        a("v_xor_b32 %s, %s, %s" % (v(SS + 1), v(SS + 1), v(sgn)))
+    return o
+
+
+def rotation(sgn):
+    """(c, s) and the rotated row N0..N2 = c mine + (+-s) theirs."""
+    o = rotation_cs(sgn)
+    a = o.append
     for n_, x_, q_, t_ in ((N0, X0, Q0, T0), (N1, X1, Q1, T1), (N2, X2, P2, T2)):
         a("v_mul_f64 %s, %s, %s" % (pair(n_), pair(CC), pair(x_)))
         a("v_mul_f64 %s, %s, %s" % (pair(t_), pair(SS), pair(q_)))
@@ -500,9 +519,104 @@ def program12():
     return [l.replace('%%[', '%[') for l in o]
 
 
+# ---- M = 3, three-row problems only: the rows in registers --------------------------------------------------------------
+# Every caller of jacobi_rows<3> passes three-row problems.  Their cyclic order is (0, 1), (0, 2), (1, 2) - one pair per step, the
+# third closes the sweep - so the block is three copies of the step body with the pair fixed per copy.  Lane 16 g + r belongs to
+# the problem row r belongs to and holds columns g and 4 + g of ALL THREE rows of that problem (R3[row][column group], read by the
+# block from S.jr; the lanes of a problem hold identical copies and take identical decisions): both rows of a pair are in the
+# lane, nothing goes through LDS between the first step and the last, no table, no exec change, no sign register.  The column
+# sums work as in the other layouts (the DMFMA adds the four lane groups of a row; every row of the problem gets the same sum);
+# columns 8 + g of the row are not rotated along - no caller reads a column >= 6 of a three-row problem.
+#   s66: sweeps completed (uniform: the problems side by side run their sweeps in step), CL: lanes whose problem rotated in the
+#   sweep under way, ACT: lanes whose problem is still iterating - stands for VALID as well.  Only copy 2 carries the bookkeeping.
+R3 = [[234, 236], [238, 240], [242, 244]]      # [row][column group] -> register pair
+R3_QI, R3_TMP = 246, 247
+R3_N = [[N0, N1], [N2, V0]]                    # the rotated rows i, j of the pair per column group
+R3_T = [[T0, T1], [T2, U0]]
+R3_PAIRS = [(0, 1), (0, 2), (1, 2)]
+R3_SWEEPS = "s66"
+R3_MAX_SWEEPS = 25
+
+
+def program3r():
+    o = []
+    a = o.append
+    # ---- set-up
+    a("v_mov_b64 %s, 1.0" % pair(ONE))
+    for i in range(3):                             # the problem's three rows: columns g and 4 + g (row stride 16 doubles)
+        a("ds_read2_b64 v[%d:%d], %%[ajr] offset0:%d offset1:%d" % (R3[i][0], R3[i][0] + 3, 16 * i, 16 * i + 4))
+    a("v_and_b32 %s, 15, %%[lane]" % v(R3_QI))
+    a("v_sub_u32 %s, %s, %%[base]" % (v(R3_QI), v(R3_QI)))
+    a("v_cmp_ne_u32 %s, 0, %%[act]" % ACT)
+    a("s_mov_b64 %s, 0" % CL)
+    a("s_mov_b32 %s, 0" % R3_SWEEPS)
+    a("s_waitcnt lgkmcnt(0)")
+    a("s_cmp_lg_u64 %s, 0" % ACT)
+    a("s_cbranch_scc0 L_done_%=")
+    a(".p2align %d" % LOOP_ALIGN)
+    a("L_loop_%=:")
+    for k, (i, j) in enumerate(R3_PAIRS):
+        ai, aj = R3[i], R3[j]
+        # p = sum_k Ai[k] Aj[k], W[i], W[j] over the A columns (column group 0, V's column masked by mk): pair_test(3) with both rows at hand
+        a("v_mul_f64 %s, %s, %s" % (pair(U0), pair(ai[0]), pair(ai[0])))
+        a("v_mul_f64 %s, %s, %s" % (pair(T0), pair(ai[0]), pair(aj[0])))
+        a("v_mul_f64 %s, %s, %s" % (pair(V0), pair(aj[0]), pair(aj[0])))
+        for r in (T0, U0, V0):
+            a("v_mul_f64 %s, %s, %%[mk]" % (pair(r), pair(r)))
+        a("s_nop 0")
+        o += [mfma(pair(WW), pair(U0), "0"), mfma(pair(WP), pair(V0), "0"), mfma(pair(P), pair(T0), "0")]
+        a("s_nop 4")
+        o += decide("%d_" % k, valid=ACT)
+        a("s_cbranch_scc0 L_skip_%d_%%=" % k)
+        o += rotation_cs(None)
+        for c in range(2):                         # t0 = c Ai + s Aj
+            a("v_mul_f64 %s, %s, %s" % (pair(R3_N[0][c]), pair(CC), pair(ai[c])))
+            a("v_mul_f64 %s, %s, %s" % (pair(R3_T[0][c]), pair(SS), pair(aj[c])))
+        for c in range(2):                         # t1 = -s Ai + c Aj
+            a("v_mul_f64 %s, -%s, %s" % (pair(R3_T[1][c]), pair(SS), pair(ai[c])))
+            a("v_mul_f64 %s, %s, %s" % (pair(R3_N[1][c]), pair(CC), pair(aj[c])))
+        for c in range(2):
+            a("v_add_f64 %s, %s, %s" % (pair(R3_N[0][c]), pair(R3_N[0][c]), pair(R3_T[0][c])))
+        for c in range(2):
+            a("v_add_f64 %s, %s, %s" % (pair(R3_N[1][c]), pair(R3_T[1][c]), pair(R3_N[1][c])))
+        for row, regs in ((0, ai), (1, aj)):       # the problems that rotate take the rotated rows
+            for c in range(2):
+                for h in range(2):
+                    a("v_cndmask_b32_e64 %s, %s, %s, %s" % (v(regs[c] + h), v(regs[c] + h), v(R3_N[row][c] + h), ROT))
+        a("s_or_b64 %s, %s, %s" % (CL, CL, ROT))
+        a("L_skip_%d_%%=:" % k)
+    # sweep bookkeeping: a problem none of whose pairs rotated in the sweep stops; sweep 25 is not reproduced here (flag)
+    a("s_mov_b64 %s, %s" % (ST, ACT))
+    a("s_and_b64 %s, %s, %s" % (ACT, ACT, CL))
+    a("s_mov_b64 %s, 0" % CL)
+    a("s_add_u32 %s, %s, 1" % (R3_SWEEPS, R3_SWEEPS))
+    a("s_cmp_lt_u32 %s, %d" % (R3_SWEEPS, R3_MAX_SWEEPS))
+    a("s_cbranch_scc1 L_more_%=")
+    a("v_cndmask_b32_e64 %s, 0, 1, %s" % (v(R3_TMP), ST))
+    a("v_or_b32 %%[flag], %%[flag], %s" % v(R3_TMP))
+    a("s_mov_b64 %s, 0" % ACT)
+    a("L_more_%=:")
+    a("s_cmp_lg_u64 %s, 0" % ACT)
+    a("s_cbranch_scc1 L_loop_%=")
+    a("L_done_%=:")
+    # the lane's own row (row q = r - base of its problem) goes out as the table-driven block leaves it
+    for dst, c in ((X0, 0), (X1, 1)):
+        a("v_mov_b64 %s, %s" % (pair(dst), pair(R3[0][c])))
+    for q in (1, 2):
+        a("v_cmp_eq_u32 vcc, %d, %s" % (q, v(R3_QI)))
+        a("s_nop 1")
+        for dst, c in ((X0, 0), (X1, 1)):
+            for h in range(2):
+                a("v_cndmask_b32 %s, %s, %s, vcc" % (v(dst + h), v(dst + h), v(R3[q][c] + h)))
+    a("v_mov_b32 %%[chg], %s" % R3_SWEEPS)          # diagnostics (EO_PROFILE): sweeps the loop ran
+    for dst, src in (("%[x0]", X0), ("%[x1]", X1)):
+        a("v_mov_b64 %s, %s" % (dst, pair(src)))
+    return [l.replace('%%[', '%[') for l in o]
+
+
 def main():
     print("// generated by tools/gen_jacobi_asm.py - do not edit")
-    print("// The step loop of jacobi_rows (svo_epnp_ord_dev.h) for M = 12, 6, 3 columns of A; registers v140..v255, s60..s71.")
+    print("// The step loop of jacobi_rows (svo_epnp_ord_dev.h) for M = 12, 6, 3 columns of A, and for M = 3 with the rows in registers (3R); registers v140..v255, s60..s71.")
     for M in (12, 6, 3):
         lines = program12() if M == 12 else program(M)
         print("#define EO_JACOBI_ASM_%d \\" % M)
@@ -510,6 +624,12 @@ def main():
             end = " \\" if i + 1 < len(lines) else ""
             print('  "%s\\n\\t"%s' % (l, end))
         print("")
+    lines = program3r()
+    print("#define EO_JACOBI_ASM_3R \\")
+    for i, l in enumerate(lines):
+        end = " \\" if i + 1 < len(lines) else ""
+        print('  "%s\\n\\t"%s' % (l, end))
+    print("")
     clob = ", ".join('"v%d"' % i for i in range(140, 256)) + ", " + ", ".join('"s%d"' % i for i in range(60, 72)) + ', "vcc", "scc", "memory"'
     print("#define EO_JACOBI_ASM_CLOBBERS " + clob)
 
