@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 7   /* 7, backward-compatible additions: svo_sgbm_process_mode, svo_sgbm_process_bgr_mode, svo_sgbm_batch_mode_dev,
+#define SVO_ABI_VERSION 7   /* 7, backward-compatible additions: svo_dyn_default_params, svo_track_dynamic, svo_track_dynamic_out (the
+                              dynamic-keypoint Lucas-Kanade loop inside the device-resident tracker, see "LK inside the tracker" below);
+                              no existing entry changed.
+                              7, backward-compatible additions: svo_sgbm_process_mode, svo_sgbm_process_bgr_mode, svo_sgbm_batch_mode_dev,
                               svo_sgbm_batch_bgr_mode_dev and the option "sgbm_mode" (the eight-direction MODE_HH, see "semi-global block
                               matching: MODE_HH" below); no existing entry changed.
                               7, backward-compatible additions: svo_lk_track_bgr, svo_lk_batch_bgr_dev, svo_lk_chain_bgr_dev,
@@ -881,6 +884,52 @@ int svo_lk_chain_bgr_dev(svo_ctx* ctx, const uint8_t* d_frames, int stride, int 
  * height x width x 6 int16 (for channel c, entry 2 c is dx and entry 2 c + 1 is dy).  Otherwise as svo_lk_debug_level; it answers
  * only while the context's last LK call is an svo_lk_track_bgr, after a gray one it is SVO_E_INVALID. */
 int svo_lk_debug_level_bgr(svo_ctx* ctx, int which, int frame, int level, void* host, int* w, int* h, int* top);
+
+/* ---- LK inside the tracker (ABI-7 additions; no existing entry changed) ---------------------------------------------------
+ * The same dynamic-keypoint loop, run by the tracker itself beside its chains: per frame the pose record AND the list of the
+ * points followed on moving objects stay in HBM, nothing comes to the host in between.  For frame f of a sequence (id = frames
+ * since svo_track_reset)
+ *     list(f) = survivors(f) ++ init_seeds(f) ++ create_seeds(f)        (cut at max_pts)
+ *   survivors(f)     list(f - 1) tracked from left image f - 1 into left image f as svo_lk_track / svo_lk_track_bgr track it, the
+ *                    status-0 points erased in order (empty at f = 0);
+ *   init_seeds(f)    at id 0 only (and only if seed_frames != 0): every keypoint strictly inside one of the frame's boxes
+ *                    (u > left && u < right && v > top && v < bottom), in keypoint order (src/Tracking.cc:70-85);
+ *   create_seeds(f)  while id < seed_frames: every keypoint strictly inside a box that has no map point after both matching passes,
+ *                    in keypoint order (src/frame.cc:209-222) - at frame 0 an inside keypoint therefore appears twice, as in the
+ *                    reference.
+ * Seeds that do not fit are dropped from the end and counted per frame; erase and append are svo_lk_chain_dev's.  The boxes
+ * are the ones the tracker call is given.  Nothing feeds back: records, debug records and trajectory are those of the loop
+ * switched off. */
+typedef struct svo_dyn_params {
+  int32_t enable;       /* 0 (default) / 1 */
+  int32_t colour;       /* 1: LK on the 8UC3 left frames of the _bgr entries (the reference's call, cn = 3);
+                           0: on gray (the gray entries' images, or the gray the _bgr entries make) */
+  int32_t seed_frames;  /* create_seeds while id < seed_frames; 2 = the reference's `id <= 1` (default);
+                           -1 = every frame; 0 = none (init_seeds still only at id 0 and only if seed_frames != 0) */
+  int32_t max_pts;      /* list capacity, 1 .. 4096, default 512 */
+  svo_lk_params lk;     /* svo_lk_default_params */
+} svo_dyn_params;
+
+/* enable 0, colour 0, seed_frames 2, max_pts 512, lk = svo_lk_default_params.  Host only. */
+int svo_dyn_default_params(svo_dyn_params* params);
+
+/* Sets the loop's parameters.  Checked on the host first, with svo_lk_track's rules in its order (the images are the context's
+ * width x height, the point count is max_pts): anything svo_lk_track does not accept, or enable / colour / seed_frames out of
+ * range, is SVO_E_INVALID, max_pts > 4096 SVO_E_CAPACITY.  The parameters come into force with the next svo_track_reset, which also
+ * empties the list; until then the context behaves as before.  While the loop is enabled, svo_track_frame, svo_track_frame_bgr,
+ * svo_track_batch_dev, svo_track_batch_bgr_dev, svo_track_batch_host and svo_track_batch_bgr_host run it, with every
+ * "depth_source"; colour = 1 through a gray entry is SVO_E_INVALID at that call; svo_track_tail_dev, svo_track_sharded_* and
+ * svo_track_multi_step_dev return SVO_E_INVALID (svo_last_error says why), enqueue nothing and leave the context usable.
+ * Consecutive calls of a sequence continue one chain: the first frame of a call is tracked from the last left image of the call
+ * before, which the context keeps in storage of its own. */
+int svo_track_dynamic(svo_ctx* ctx, const svo_dyn_params* params);
+
+/* One-shot: the NEXT tracker call on the context writes frame f's list to lists + f * 2 * max_pts (x, y pairs), its length to
+ * counts[f] and the seeds it dropped to dropped[f] (dropped may be NULL).  Device pointers for the _dev entries; host pointers for
+ * svo_track_frame[_bgr] (complete when the call returns) and for the _host entries (complete under the rule of their `results`:
+ * after svo_sync, or once the second following host-fed call has returned).  A call without it still advances the chain and
+ * keeps the lists inside the context.  SVO_E_INVALID unless the loop is in force. */
+int svo_track_dynamic_out(svo_ctx* ctx, float* lists, int32_t* counts, int32_t* dropped);
 
 /* ---- darknet YOLO detector on the device (ABI-7 additions; no existing entry changed) -------------------------------------
  * The online half of semantic gating: Semantic::Run (src/semantic.cc) calls YOLOv3::Detect(leftimg, 0.8), which goes through

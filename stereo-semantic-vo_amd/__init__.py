@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "svo_sgbm_process_mode", "svo_sgbm_process_bgr_mode", "svo_sgbm_batch_mode_dev", "svo_sgbm_batch_bgr_mode_dev",
     "svo_lk_default_params", "svo_lk_track", "svo_lk_batch_dev", "svo_lk_chain_dev", "svo_lk_debug_level",
     "svo_lk_track_bgr", "svo_lk_batch_bgr_dev", "svo_lk_chain_bgr_dev", "svo_lk_debug_level_bgr",
+    "svo_dyn_default_params", "svo_track_dynamic", "svo_track_dynamic_out",
 ]
 
 # svo_create_ex flags (include/svo.h)
@@ -442,6 +443,16 @@ class Svo:
         out = np.zeros(self.max_kp, np.int32)
         self._chk(self.lib.svo_debug_track_matches(self.h, _p(out)))
         return out
+
+    # ---- the dynamic-keypoint LK loop inside the tracker (include/svo.h: "LK inside the tracker") ----
+    def track_dynamic(self, params):
+        """svo_track_dynamic: a DynParams; in force from the next track_reset on."""
+        self._chk(self.lib.svo_track_dynamic(self.h, C.byref(params)))
+
+    def track_dynamic_out(self, lists, counts, dropped=None):
+        """svo_track_dynamic_out: where the NEXT tracker call leaves its frames' lists (frame f at lists + f * 2 * max_pts
+        floats), their lengths and dropped seeds - device pointers for the _dev entries, numpy arrays / host pointers otherwise."""
+        self._chk(self.lib.svo_track_dynamic_out(self.h, _p(lists), _p(counts), _p(dropped)))
 
     # ---- throughput mode (device pointers, e.g. torch tensors' data_ptr()) --------------------
     def frontend_batch_dev(self, d_grayL, d_grayR, stride, B, cam, d_kpL=None, d_descL=None,
@@ -844,6 +855,21 @@ def lk_default_params():
     rc = load_library().svo_lk_default_params(C.byref(p))
     if rc != 0:
         raise SvoError("svo_lk_default_params failed")
+    return p
+
+
+class DynParams(C.Structure):
+    """svo_dyn_params: the dynamic-keypoint loop inside the tracker (enable, colour, seed_frames, max_pts, lk)."""
+    _fields_ = [("enable", C.c_int32), ("colour", C.c_int32), ("seed_frames", C.c_int32), ("max_pts", C.c_int32),
+                ("lk", LkParams)]
+
+
+def dyn_default_params():
+    """svo_dyn_default_params: off, gray, seeds while id < 2, 512 points, LK defaults (needs no GPU)."""
+    p = DynParams()
+    rc = load_library().svo_dyn_default_params(C.byref(p))
+    if rc != 0:
+        raise SvoError("svo_dyn_default_params failed")
     return p
 
 

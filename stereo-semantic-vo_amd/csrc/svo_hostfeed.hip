@@ -339,6 +339,7 @@ int reclaim_set(svo_ctx* ctx, HostFeed* hf, int p) {
 // Everything the host-fed entries still owe the caller: records (and front-end outputs) that wait in pinned buffers are copied
 // into the arrays they were promised to.  Called by svo_sync, svo_track_reset, svo_destroy and before a set is reused.
 int svo_hostfeed_flush(svo_ctx* ctx) {
+  { const int rcd = svo_track_dyn_flush(ctx); if (rcd) return rcd; }   // (the dynamic-keypoint loop's lists, staged the same way)
   HostFeed* hf = feed_of(ctx);
   if (!hf) return SVO_OK;
   for (int p = 0; p < 2; ++p) {
@@ -444,6 +445,7 @@ extern "C" int svo_track_sharded_host(svo_ctx* const* ctxs, int G, const uint8_t
     if (!ctxs[g] || ctxs[g]->g.W != c0->g.W || ctxs[g]->g.H != c0->g.H || ctxs[g]->max_kp != c0->max_kp) return SVO_E_INVALID;
     if ((B - g + G - 1) / G > ctxs[g]->max_batch) return SVO_E_CAPACITY;
   }
+  { const int rcd = svo_track_dyn_refuse(c0, "svo_track_sharded_host"); if (rcd) return rcd; }
   hipSetDevice(c0->device);
   { const int rcs = svo_track_fe_batch_stream(c0); if (rcs) return rcs; }
   int rc = SVO_OK;

@@ -190,6 +190,7 @@ struct svo_ctx {
   void* msa_arenas = nullptr;   // MsaArenas: device buffers of svo_msa_solve and of the tracker's MSA mode
   void* sgbm = nullptr;         // SgbmArena (svo_sgbm.hip): cost / path volumes of svo_sgbm_* and of the tracker's SGBM mode
   void* lk = nullptr;           // LkArena (svo_lk.hip): pyramids, derivatives and point buffers of svo_lk_*
+  void* dyn = nullptr;          // DynState (svo_track.hip): the dynamic-keypoint loop inside the tracker, made by svo_track_dynamic
   float* d_dense = nullptr;     // dense maps of svo_track_batch_dev with depth_source 1: 2 x dense_cap x W*H
   int dense_cap = 0;
   svo_camera cam{};
@@ -349,6 +350,40 @@ extern "C" void svo_elas_release(svo_ctx* ctx);
 void svo_msa_release(svo_ctx* ctx);
 void svo_sgbm_release(svo_ctx* ctx);
 void svo_lk_release(svo_ctx* ctx);
+// svo_lk.hip: the LK machinery, for the tracker's dynamic-keypoint loop (svo_track.hip) as for svo_lk_* itself.  An arena holds the
+// pyramids and derivatives of a run of frames ("slots"), optionally their level-0 images, and the buffers of one track step.
+struct LkArena {
+  uint8_t* img = nullptr;       // level-0 images the arena holds itself (svo_lk_track / svo_lk_track_bgr: the pair), rows cn W bytes apart
+  uint8_t* pyr = nullptr;       // levels 1.. of every frame (cn bytes a pixel)
+  uint32_t* der = nullptr;      // (dx, dy) of every level of every frame (cn entries a pixel)
+  float *pts = nullptr, *next = nullptr, *err = nullptr;
+  uint8_t* status = nullptr;
+  size_t cap_img = 0, cap_pyr = 0, cap_der = 0, cap_pts = 0;   // (in elements: a gray and a colour call share them, the larger need stays)
+  hipStream_t last = nullptr;
+  int dbg_cn = 0;               // channels of the last single-pair call, 0: none to report
+  bool dbg_next_der = false;    // svo_lk_track builds the previous frame's derivatives only; svo_lk_debug_level adds the next frame's when asked
+  int W = 0, H = 0, top = 0;
+};
+int lk_top_level(int W, int H, int max_level);   // the effective top level of a W x H image
+int lk_check(const svo_lk_params* p, int W, int H, int n, int frames);   // svo_lk_track's host-side checks, in its order
+int lk_reserve_in(svo_ctx* ctx, void** holder, hipStream_t s, int W, int H, int cn, int top, int frames, size_t pts, int img_frames,
+                  LkArena** out);
+void lk_arena_free(void** holder);
+void lk_slot_px(int W, int H, int top, size_t* pyr_px, size_t* der_px);   // one channel's pixels of a frame's pyramid / derivative slot
+// pyramid levels 1 .. top of `frames` images from A->pyr on (image i at img0 + i * frame0), derivatives of images der_first ..
+void lk_build(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top, int frames,
+              int der_first, int der_frames);
+// `pairs` pairs (fprev0 + i, fprev0 + i + 1) of the arena's slots, pair i's points at pts + i * 2 max_pts (counts[i], or n_fixed)
+void lk_launch_track(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top,
+                     int fprev0, int pairs, const float* pts, const int32_t* counts, int n_fixed, int max_pts, float* next,
+                     uint8_t* status, float* err);
+// k_lk_compact: the tracked points with status != 0 in order (n_prev == nullptr: none), then the seeds while the list has room
+void lk_launch_compact(hipStream_t s, const float* trk, const uint8_t* st, const int32_t* n_prev, const float* seeds, const int32_t* n_seed,
+                       int max_seeds, int max_pts, float* list, int32_t* n_out, int32_t* dropped);
+// svo_track.hip: lists of the dynamic-keypoint loop that wait in pinned buffers -> the caller's host arrays (svo_hostfeed_flush)
+int svo_track_dyn_flush(svo_ctx* ctx);
+// svo_track.hip: SVO_E_INVALID with a message while that loop is enabled (the entries that do not run it)
+int svo_track_dyn_refuse(svo_ctx* ctx, const char* who);
 // svo_sgbm.hip: B resident gray pairs (pair b at dL / dR + b * frame) -> B float maps at d_disp, enqueued on `s` in chunks of
 // svo_sgbm_chunk() pairs; no synchronisation.  mode: SVO_SGBM_MODE_SGBM or SVO_SGBM_MODE_HH
 int svo_sgbm_run_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,

@@ -300,18 +300,7 @@ __global__ __launch_bounds__(256) void k_lk_compact(const float* __restrict__ tr
   if (tid == 0) { *n_out = base + take; *dropped = ns - take; }
 }
 
-struct LkArena {
-  uint8_t* img = nullptr;       // svo_lk_track / svo_lk_track_bgr: the two level-0 images, rows cn W bytes apart
-  uint8_t* pyr = nullptr;       // levels 1.. of every frame (cn bytes a pixel)
-  uint32_t* der = nullptr;      // (dx, dy) of every level of every frame (cn entries a pixel)
-  float *pts = nullptr, *next = nullptr, *err = nullptr;
-  uint8_t* status = nullptr;
-  size_t cap_img = 0, cap_pyr = 0, cap_der = 0, cap_pts = 0;   // (in elements: a gray and a colour call share them, the larger need stays)
-  hipStream_t last = nullptr;
-  int dbg_cn = 0;               // channels of the last single-pair call, 0: none to report
-  bool dbg_next_der = false;    // svo_lk_track builds the previous frame's derivatives only; svo_lk_debug_level adds the next frame's when asked
-  int W = 0, H = 0, top = 0;
-};
+}  // namespace
 
 int lk_top_level(int W, int H, int max_level) {
   int top = 0;
@@ -335,6 +324,8 @@ int lk_check(const svo_lk_params* p, int W, int H, int n, int frames) {
   if (W > LK_MAX_DIM || H > LK_MAX_DIM || n > LK_MAX_PTS || frames > LK_MAX_FRAMES) return SVO_E_CAPACITY;
   return SVO_OK;
 }
+
+namespace {
 
 int lk_args(svo_ctx* ctx, const char* who, bool pointers, const svo_lk_params* p, int W, int H, int stride, int cn, int n, int frames) {
   int rc = lk_check(p, W, H, n, frames);
@@ -361,10 +352,14 @@ int lk_grow(svo_ctx* ctx, LkArena* A, T** p, size_t* cap, size_t count) {
   return SVO_OK;
 }
 
-// the context's arena: pyramids and derivatives of `frames` images of cn channels, point buffers for `pts` points (0: untouched)
-int lk_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int cn, int top, int frames, size_t pts, bool host_images, LkArena** out) {
-  if (!ctx->lk) ctx->lk = new LkArena();
-  LkArena* A = static_cast<LkArena*>(ctx->lk);
+}  // namespace
+
+// the arena `*holder` (made on first use): pyramids and derivatives of `frames` images of cn channels, point buffers for `pts` points
+// (0: untouched), level-0 storage for `img_frames` images (0: none)
+int lk_reserve_in(svo_ctx* ctx, void** holder, hipStream_t s, int W, int H, int cn, int top, int frames, size_t pts, int img_frames,
+                  LkArena** out) {
+  if (!*holder) *holder = new LkArena();
+  LkArena* A = static_cast<LkArena*>(*holder);
   *out = A;
   if (A->last && A->last != s) SVO_HIP(ctx, hipStreamSynchronize(A->last));   // one user at a time
   A->dbg_cn = 0;
@@ -373,7 +368,7 @@ int lk_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int cn, int top, int f
   if ((rc = lk_grow(ctx, A, &A->pyr, &A->cap_pyr, std::max<size_t>(end.ioff, 1) * cn * frames)) ||
       (rc = lk_grow(ctx, A, &A->der, &A->cap_der, end.doff * cn * frames)))
     return rc;
-  if (host_images && (rc = lk_grow(ctx, A, &A->img, &A->cap_img, (size_t)W * H * cn * 2))) return rc;
+  if (img_frames > 0 && (rc = lk_grow(ctx, A, &A->img, &A->cap_img, (size_t)W * H * cn * img_frames))) return rc;
   if (pts && A->cap_pts < pts) {
     size_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
     A->cap_pts = 0;
@@ -384,6 +379,28 @@ int lk_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int cn, int top, int f
   }
   A->last = s;
   return SVO_OK;
+}
+
+void lk_arena_free(void** holder) {
+  if (!*holder) return;
+  LkArena* A = static_cast<LkArena*>(*holder);
+  void* bufs[] = {A->img, A->pyr, A->der, A->pts, A->next, A->err, A->status};
+  for (void* b : bufs)
+    if (b) hipFree(b);
+  delete A;
+  *holder = nullptr;
+}
+
+void lk_slot_px(int W, int H, int top, size_t* pyr_px, size_t* der_px) {
+  const LkLevel end = lk_level(W, H, top + 1);
+  *pyr_px = end.ioff; *der_px = end.doff;
+}
+
+namespace {
+
+// the context's own arena (svo_lk_*)
+int lk_reserve(svo_ctx* ctx, hipStream_t s, int W, int H, int cn, int top, int frames, size_t pts, bool host_images, LkArena** out) {
+  return lk_reserve_in(ctx, &ctx->lk, s, W, H, cn, top, frames, pts, host_images ? 2 : 0, out);
 }
 
 // pyramid levels 1 .. top of `frames` resident images, and the derivatives of levels 0 .. top of frames der_first ..
@@ -408,6 +425,8 @@ void lk_build_cn(hipStream_t s, LkArena* A, const uint8_t* img0, int stride0, si
   }
 }
 
+}  // namespace
+
 void lk_build(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top, int frames,
               int der_first, int der_frames) {
   if (cn == 3) lk_build_cn<3>(s, A, img0, stride0, frame0, W, H, top, frames, der_first, der_frames);
@@ -423,6 +442,13 @@ void lk_launch_track(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int
                      A->pyr, cn * end.ioff, A->der, cn * end.doff, W, H, top, fprev0, pts, counts, n_fixed, max_pts, next, status,
                      err);
 }
+
+void lk_launch_compact(hipStream_t s, const float* trk, const uint8_t* st, const int32_t* n_prev, const float* seeds, const int32_t* n_seed,
+                       int max_seeds, int max_pts, float* list, int32_t* n_out, int32_t* dropped) {
+  hipLaunchKernelGGL(k_lk_compact, dim3(1), dim3(256), 0, s, trk, st, n_prev, seeds, n_seed, max_seeds, max_pts, list, n_out, dropped);
+}
+
+namespace {
 
 int lk_track_pair(svo_ctx* ctx, const char* who, int cn, const uint8_t* prev, const uint8_t* next, int stride, int W, int H,
                   const svo_lk_params* p, const float* pts, int n, float* next_pts, uint8_t* status, float* err) {
@@ -581,11 +607,5 @@ extern "C" int svo_lk_debug_level_bgr(svo_ctx* ctx, int which, int frame, int le
 }
 
 void svo_lk_release(svo_ctx* ctx) {
-  if (!ctx || !ctx->lk) return;
-  LkArena* A = static_cast<LkArena*>(ctx->lk);
-  void* bufs[] = {A->img, A->pyr, A->der, A->pts, A->next, A->err, A->status};
-  for (void* b : bufs)
-    if (b) hipFree(b);
-  delete A;
-  ctx->lk = nullptr;
+  if (ctx) lk_arena_free(&ctx->lk);
 }

@@ -1564,6 +1564,48 @@ __global__ __launch_bounds__(TPF_NT) void k_tp_tail_ord(TrackState* st, TrackWor
   }
 }
 
+// ================================================================================================
+// The dynamic-keypoint loop inside the tracker (svo_track_dynamic): a frame's seeds
+// ================================================================================================
+// One workgroup behind the frame's k_ti_resolve on the index stream, one thread per keypoint.  The seeds the reference pushes to
+// DY_keypoints: Tracking::init (src/Tracking.cc:70-85, frame id 0) every keypoint strictly inside a box, then frame::createmappoint
+// (src/frame.cc:209-222) every keypoint strictly inside a box that has no map point after both matching passes - not in the
+// frame's correspondence list work->edge_kp[0 .. n_edges).  Both parts in keypoint order, the init part first, compacted by a
+// block-wide prefix sum; at frame 0 an inside keypoint appears in both.
+#define DYN_MAX_SEEDS (2 * TRK_MAXKP)
+__global__ __launch_bounds__(TRK_MAXKP) void k_td_seeds(const TrackWork* __restrict__ work, const svo_kp* __restrict__ kp,
+                                                        const int32_t* __restrict__ boxes, const int32_t* __restrict__ nboxes,
+                                                        float* __restrict__ seeds, int32_t* __restrict__ n_seed) {
+  __shared__ alignas(16) int sm[16];
+  __shared__ int sbox[SVO_MAX_BOXES * 4];
+  __shared__ uint8_t has_mp[TRK_MAXKP];
+  const int tid = threadIdx.x;
+  const int nkp = min(max(work->nkp, 0), TRK_MAXKP), n_edges = min(max(work->n_edges, 0), TRK_MAXKP);
+  const int n_boxes = (boxes && nboxes) ? min(max(*nboxes, 0), SVO_MAX_BOXES) : 0;
+  if (tid < 4 * n_boxes) sbox[tid] = boxes[tid];
+  has_mp[tid] = 0;
+  __syncthreads();
+  if (tid < n_edges) {
+    const int j = work->edge_kp[tid];
+    if (j >= 0 && j < TRK_MAXKP) has_mp[j] = 1;
+  }
+  __syncthreads();
+  bool inside = false;
+  float x = 0.f, y = 0.f;
+  if (tid < nkp) {
+    x = kp[tid].x; y = kp[tid].y;
+    for (int b = 0; b < n_boxes; ++b)
+      inside = inside || (x > (float)sbox[4 * b] && x < (float)sbox[4 * b + 1] && y > (float)sbox[4 * b + 2] && y < (float)sbox[4 * b + 3]);
+  }
+  const bool s_init = inside && work->frame_id == 0, s_create = inside && !has_mp[tid];
+  int n_init, n_create;
+  const int o_init = block_excl_scan(s_init ? 1 : 0, sm, &n_init);
+  const int o_create = n_init + block_excl_scan(s_create ? 1 : 0, sm, &n_create);
+  if (s_init) { seeds[2 * o_init] = x; seeds[2 * o_init + 1] = y; }
+  if (s_create) { seeds[2 * o_create] = x; seeds[2 * o_create + 1] = y; }   // (o_create < n_init + n_create <= 2 TRK_MAXKP)
+  if (tid == 0) *n_seed = n_init + n_create;
+}
+
 // --------------------------------------------------------------------------------------------
 // Host side
 // --------------------------------------------------------------------------------------------
@@ -1599,8 +1641,10 @@ static int fe_sets_alloc(SvoFeBufs* sets, int n, size_t images, size_t pairs, si
   }
   return SVO_OK;
 }
+static void dyn_release(svo_ctx* ctx);
 void svo_track_release(svo_ctx* ctx) {
   shard_gather_free(ctx);
+  dyn_release(ctx);
   fe_sets_free(ctx->tb_out, 2);
   for (int q = 0; q < 2; ++q) {
     if (ctx->tb_done[q]) { hipEventDestroy(ctx->tb_done[q]); ctx->tb_done[q] = nullptr; }
@@ -1732,6 +1776,226 @@ static int track_resources(svo_ctx* ctx, int frames, int nseq) {
   return ctx->track_lds_state > 0 ? SVO_OK : SVO_E_HIP;
 }
 
+// ---- the dynamic-keypoint loop inside the tracker (svo_track_dynamic) ------------------------------------------------------
+// list(f) = list(f - 1) tracked from left image f - 1 into left image f (k_lk_track) with the status-0 points erased, then the
+// frame's seeds (k_td_seeds) while the list has room (k_lk_compact) - svo_lk_chain_dev's loop, driven here frame by frame on the
+// INDEX stream: a group's seed kernels sit behind their k_ti_resolve; its track + compact steps - and, once per sub-batch of the
+// front end, the level-0 copies, pyramids and derivatives of that sub-batch's left images - behind the group's ev_frame record,
+// so the pose chain's wait is never behind LK work.  Everything of the loop is
+// ordered by that one stream; the pose stream joins it once, at the end of a call (what svo_sync and the calls' result copies
+// wait for then covers the lists).  The left images live in an arena of this state: a ring of slots in which slot `pos` is the
+// previous frame - a later call never reads an earlier call's image buffers.
+struct DynOut { float* lists = nullptr; int32_t *counts = nullptr, *dropped = nullptr; };
+struct DynState {
+  svo_dyn_params next{};        // svo_track_dynamic's: adopted by the next reset
+  svo_dyn_params p{};           // in force
+  bool active = false;
+  int cn = 1, top = 0, cap = 0, slots = 0, pos = 0;   // cap: frames per call; slots of the arena, `pos` holds the previous left image
+  int built_until = 0;          // frames of the tail call being enqueued whose images, pyramids and derivatives are in the arena (slots pos + 1 ..)
+  void* arena = nullptr;        // LkArena of its own (the context's serves svo_lk_*)
+  float *d_lists = nullptr, *d_seeds = nullptr;   // (cap + 1) lists, list 0 = the last one of the call before; cap seed lists
+  int32_t* d_ints = nullptr;    // cap + 1 counts, cap + 1 dropped, cap + 1 seed counts (the last one stays 0: a frame that cannot seed)
+  hipEvent_t ev_lk = nullptr;   // behind a call's last LK step (index stream)
+  bool ev_lk_valid = false;
+  DynOut out; bool attached = false;              // svo_track_dynamic_out, for the next call
+  // the call being enqueued
+  bool in_call = false, cur_on = false, cur_host = false, cur_direct = false;
+  DynOut cur; int cur_off = 0, cur_q = 0;
+  const uint8_t* src = nullptr; int src_stride = 0;   // its left images, cn channels: image i at src + i * H * src_stride
+  // lists for host arrays of the batched entries wait in pinned memory, two sets alternate between calls
+  float* h_lists[2] = {nullptr, nullptr}; int32_t* h_ints[2] = {nullptr, nullptr};
+  hipEvent_t ev_out[2] = {nullptr, nullptr};
+  DynOut pending[2]; int pending_n[2] = {0, 0}; int hparity = 0;
+  int32_t* counts() const { return d_ints; }
+  int32_t* dropped() const { return d_ints + cap + 1; }
+  int32_t* nseed() const { return d_ints + 2 * (cap + 1); }
+};
+static DynState* dyn_of(svo_ctx* ctx) { return reinterpret_cast<DynState*>(ctx->dyn); }
+static bool dyn_active(const svo_ctx* ctx) { return ctx->dyn && reinterpret_cast<const DynState*>(ctx->dyn)->active; }
+static void dyn_free_buffers(DynState* D) {
+  lk_arena_free(&D->arena);
+  if (D->d_lists) hipFree(D->d_lists);
+  if (D->d_seeds) hipFree(D->d_seeds);
+  if (D->d_ints) hipFree(D->d_ints);
+  D->d_lists = D->d_seeds = nullptr; D->d_ints = nullptr;
+  for (int q = 0; q < 2; ++q) {
+    if (D->h_lists[q]) hipHostFree(D->h_lists[q]);
+    if (D->h_ints[q]) hipHostFree(D->h_ints[q]);
+    D->h_lists[q] = nullptr; D->h_ints[q] = nullptr; D->pending[q] = DynOut{}; D->pending_n[q] = 0;
+  }
+  D->cap = 0; D->slots = 0;
+}
+static void dyn_release(svo_ctx* ctx) {
+  DynState* D = dyn_of(ctx);
+  if (!D) return;
+  dyn_free_buffers(D);
+  if (D->ev_lk) hipEventDestroy(D->ev_lk);
+  for (hipEvent_t e : D->ev_out) if (e) hipEventDestroy(e);
+  delete D;
+  ctx->dyn = nullptr;
+}
+static int dyn_flush_set(svo_ctx* ctx, DynState* D, int q) {
+  if (!D->pending_n[q]) return SVO_OK;
+  SVO_HIP(ctx, hipEventSynchronize(D->ev_out[q]));
+  const size_t n = (size_t)D->pending_n[q], mp = (size_t)D->p.max_pts;
+  memcpy(D->pending[q].lists, D->h_lists[q], n * 2 * mp * sizeof(float));
+  memcpy(D->pending[q].counts, D->h_ints[q], n * sizeof(int32_t));
+  if (D->pending[q].dropped) memcpy(D->pending[q].dropped, D->h_ints[q] + D->cap, n * sizeof(int32_t));
+  D->pending_n[q] = 0;
+  return SVO_OK;
+}
+int svo_track_dyn_flush(svo_ctx* ctx) {
+  DynState* D = dyn_of(ctx);
+  if (!D) return SVO_OK;
+  for (int q = 0; q < 2; ++q) { const int rc = dyn_flush_set(ctx, D, q); if (rc) return rc; }
+  return SVO_OK;
+}
+// svo_track_reset / svo_track_multi_reset, every stream idle: svo_track_dynamic's parameters come into force, the list is empty
+static int dyn_adopt(svo_ctx* ctx) {
+  DynState* D = dyn_of(ctx);
+  if (!D) return SVO_OK;
+  D->attached = false; D->in_call = false; D->ev_lk_valid = false; D->pos = 0; D->hparity = 0;
+  if (!D->next.enable) {
+    if (D->active) dyn_free_buffers(D);
+    D->active = false; D->p = D->next;
+    return SVO_OK;
+  }
+  const int W = ctx->g.W, H = ctx->g.H, cn = D->next.colour ? 3 : 1, top = lk_top_level(W, H, D->next.lk.maxLevel);
+  const int cap = std::max(ctx->max_batch, 1), slots = std::min(cap, 64) + 1;
+  if (!D->active || cn != D->cn || top != D->top || D->next.max_pts != D->p.max_pts || cap != D->cap) {
+    dyn_free_buffers(D);
+    D->active = false;
+    LkArena* A = nullptr;
+    int rc = lk_reserve_in(ctx, &D->arena, ctx->stream, W, H, cn, top, slots, (size_t)D->next.max_pts, slots, &A);
+    if (rc) { dyn_free_buffers(D); return rc; }
+    A->last = nullptr;   // (sized once: nothing ever grows it while work is in flight)
+    const size_t mp = (size_t)D->next.max_pts;
+    if (hipMalloc(reinterpret_cast<void**>(&D->d_lists), (size_t)(cap + 1) * 2 * mp * sizeof(float)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&D->d_seeds), (size_t)cap * 2 * DYN_MAX_SEEDS * sizeof(float)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&D->d_ints), 3 * (size_t)(cap + 1) * sizeof(int32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      dyn_free_buffers(D);
+      ctx->last_error = "svo_track_dynamic: device allocation failed";
+      return SVO_E_NOMEM;
+    }
+    D->cn = cn; D->top = top; D->cap = cap; D->slots = slots;
+    if (!D->ev_lk) SVO_HIP(ctx, hipEventCreateWithFlags(&D->ev_lk, hipEventDisableTiming));
+    for (int q = 0; q < 2; ++q)
+      if (!D->ev_out[q]) SVO_HIP(ctx, hipEventCreateWithFlags(&D->ev_out[q], hipEventDisableTiming));
+  }
+  D->p = D->next;
+  SVO_HIP(ctx, hipMemsetAsync(D->d_ints, 0, 3 * (size_t)(D->cap + 1) * sizeof(int32_t), ctx->stream));   // (the caller waits for the stream)
+  D->active = true;
+  return SVO_OK;
+}
+// A tracker entry that runs the loop starts a call: its left images (cn channels, consecutive images H * stride bytes apart), and
+// where svo_track_dynamic_out's arrays live - `host`: host memory, `direct`: the entry synchronises before it returns
+static int dyn_begin(svo_ctx* ctx, const uint8_t* src, int stride, bool host, bool direct) {
+  DynState* D = dyn_of(ctx);
+  D->in_call = true; D->src = src; D->src_stride = stride; D->cur_off = 0; D->built_until = 0;
+  D->cur = D->out; D->cur_on = D->attached; D->cur_host = host; D->cur_direct = direct;
+  D->attached = false; D->out = DynOut{};
+  if (D->cur_on && host && !direct) {
+    const int q = D->hparity;
+    D->cur_q = q; D->hparity ^= 1;
+    const int rc = dyn_flush_set(ctx, D, q);   // (what the call two back left in this set)
+    if (rc) return rc;
+    if (!D->h_lists[q]) {
+      if (hipHostMalloc(reinterpret_cast<void**>(&D->h_lists[q]), (size_t)D->cap * 2 * D->p.max_pts * sizeof(float)) != hipSuccess ||
+          hipHostMalloc(reinterpret_cast<void**>(&D->h_ints[q]), 2 * (size_t)D->cap * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->last_error = "svo_track_dynamic_out: out of pinned memory";
+        return SVO_E_NOMEM;
+      }
+    }
+  }
+  return SVO_OK;
+}
+static void dyn_end(svo_ctx* ctx) {
+  DynState* D = dyn_of(ctx);
+  D->in_call = false; D->cur_on = false; D->cur = DynOut{}; D->src = nullptr;
+}
+static bool dyn_can_seed(const DynState* D, int id) { return D->p.seed_frames < 0 || id < D->p.seed_frames; }
+// frames f0 .. f1 - 1 of the tail call being enqueued (`frames` in all), whose index kernels (and seed kernels) are on `s`: track +
+// compact frame by frame.  Images go into the arena, with their pyramids and derivatives, AHEAD of the steps: as far as the
+// stream has already waited for the call's images - to the end of the front end's sub-batch (the next non-null fe_events entry),
+// so that a sub-batch costs the index stream one set of launches, not one per group.  id0: frame 0 of the tail call counted
+// from the reset
+static int dyn_enqueue_group(svo_ctx* ctx, DynState* D, hipStream_t s, int f0, int f1, int id0, bool boxes, const hipEvent_t* fe_events,
+                             int frames) {
+  LkArena* A = static_cast<LkArena*>(D->arena);
+  const int W = ctx->g.W, H = ctx->g.H, cn = D->cn, mp = D->p.max_pts;
+  const size_t row = (size_t)cn * W, img = row * H;
+  size_t pyr_px, der_px;
+  lk_slot_px(W, H, D->top, &pyr_px, &der_px);
+  int f = f0;
+  while (f < f1) {
+    if (f >= D->built_until) {   // (every built frame has had its step: slot `pos` is frame f - 1)
+      int e = f1;
+      while (e < frames && !(fe_events && fe_events[e])) ++e;
+      const int n = std::min(e - f, D->slots - 1);
+      if (D->pos + n > D->slots - 1) {   // the ring is used up: the previous frame moves to slot 0
+        const size_t q = (size_t)D->pos;
+        SVO_HIP(ctx, hipMemcpyAsync(A->img, A->img + q * img, img, hipMemcpyDeviceToDevice, s));
+        if (pyr_px) SVO_HIP(ctx, hipMemcpyAsync(A->pyr, A->pyr + q * cn * pyr_px, cn * pyr_px, hipMemcpyDeviceToDevice, s));
+        SVO_HIP(ctx, hipMemcpyAsync(A->der, A->der + q * cn * der_px, cn * der_px * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        D->pos = 0;
+      }
+      const size_t first = (size_t)D->pos + 1;
+      SVO_HIP(ctx, hipMemcpy2DAsync(A->img + first * img, row, D->src + (size_t)(D->cur_off + f) * H * D->src_stride, D->src_stride, row,
+                                    (size_t)H * n, hipMemcpyDeviceToDevice, s));
+      LkArena V = *A;   // the slots from `first` on
+      V.pyr += first * cn * pyr_px; V.der += first * cn * der_px;
+      lk_build(s, &V, cn, A->img + first * img, (int)row, img, W, H, D->top, n, 0, n);
+      D->built_until = f + n;
+    }
+    for (const int stop = std::min(f1, D->built_until); f < stop; ++f) {
+      const int id = id0 + f;
+      const bool seeds = boxes && dyn_can_seed(D, id);
+      if (id > 0)
+        lk_launch_track(s, A, cn, A->img, (int)row, img, W, H, D->top, D->pos, 1, D->d_lists + (size_t)f * 2 * mp, D->counts() + f, 0, mp,
+                        A->next, A->status, nullptr);
+      lk_launch_compact(s, A->next, A->status, id > 0 ? D->counts() + f : nullptr, D->d_seeds + (size_t)f * 2 * DYN_MAX_SEEDS,
+                        D->nseed() + (seeds ? f : D->cap), DYN_MAX_SEEDS, mp, D->d_lists + (size_t)(f + 1) * 2 * mp, D->counts() + f + 1,
+                        D->dropped() + f + 1);
+      ++D->pos;
+    }
+  }
+  return SVO_OK;
+}
+// the end of a tail call of `frames` frames: its lists to the attached arrays, its last list to list 0, the pose stream joins
+static int dyn_finish(svo_ctx* ctx, DynState* D, hipStream_t s, hipStream_t pose, int frames) {
+  const size_t mp = (size_t)D->p.max_pts, off = (size_t)D->cur_off, n = (size_t)frames;
+  if (D->cur_on) {
+    const bool staged = D->cur_host && !D->cur_direct;
+    const int q = D->cur_q;
+    float* lists = staged ? D->h_lists[q] : D->cur.lists;
+    int32_t* counts = staged ? D->h_ints[q] : D->cur.counts;
+    int32_t* dropped = staged ? D->h_ints[q] + D->cap : D->cur.dropped;
+    const hipMemcpyKind kind = D->cur_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    SVO_HIP(ctx, hipMemcpyAsync(lists + off * 2 * mp, D->d_lists + 2 * mp, n * 2 * mp * sizeof(float), kind, s));
+    SVO_HIP(ctx, hipMemcpyAsync(counts + off, D->counts() + 1, n * sizeof(int32_t), kind, s));
+    if (dropped) SVO_HIP(ctx, hipMemcpyAsync(dropped + off, D->dropped() + 1, n * sizeof(int32_t), kind, s));
+    if (staged) {
+      SVO_HIP(ctx, hipEventRecord(D->ev_out[q], s));
+      D->pending[q] = D->cur; D->pending_n[q] = (int)(off + n);
+    }
+  }
+  SVO_HIP(ctx, hipMemcpyAsync(D->d_lists, D->d_lists + n * 2 * mp, 2 * mp * sizeof(float), hipMemcpyDeviceToDevice, s));
+  SVO_HIP(ctx, hipMemcpyAsync(D->counts(), D->counts() + n, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  D->cur_off += frames; D->built_until = 0;
+  SVO_HIP(ctx, hipEventRecord(D->ev_lk, s));
+  SVO_HIP(ctx, hipStreamWaitEvent(pose, D->ev_lk, 0));
+  D->ev_lk_valid = true;
+  return SVO_OK;
+}
+// the entries that have no such loop refuse while it is enabled
+int svo_track_dyn_refuse(svo_ctx* ctx, const char* who) {
+  if (!dyn_active(ctx)) return SVO_OK;
+  ctx->last_error = std::string(who) + ": the dynamic-keypoint loop is enabled on this context (svo_track_dynamic); this entry does not run it";
+  return SVO_E_INVALID;
+}
+
 // The ordered tail for front-end results that are already in HBM (`kstride` keypoints per frame slot):
 //   nseq == 1: `frames` consecutive frames of the one sequence, record f into d_res[f];
 //   nseq  > 1: one frame of each of nseq sequences (frames == 1), sequence q from frame slot q into d_res[q].
@@ -1770,6 +2034,7 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
   // per-kernel HIP-event timing (svo_profile_enable) costs ~2.5 us per event pair on the host - more than a tail kernel's
   // launch; the tail is therefore SAMPLED: every 32nd frame of a call is timed (an event pair around a kernel also holds the chain up by ~5 us), the others run untimed
   const bool prof = ctx->profiling;
+  DynState* D = dyn_active(ctx) && dyn_of(ctx)->in_call && nseq == 1 ? dyn_of(ctx) : nullptr;   // the dynamic-keypoint loop runs with this call
   // frame f's front-end results sit in row f of the arrays unless the caller says otherwise (svo_track_sharded_dev)
   auto row = [&](int f) { return (size_t)(row_of_frame ? row_of_frame[f] : f); };
   // gated frames of ONE sequence whose front-end rows are consecutive: brute-force matches + F for groups of frames in one
@@ -1825,6 +2090,11 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
       SvoTimer t(ctx, "k_ti_resolve", s1);
       hipLaunchKernelGGL(k_ti_resolve, dim3(1, ny), dim3(1024), sizeof(TiLds), s1, st, work + f, kpf, descf, nkpf, depf, kstride,
                          bxf, nbf, bstride, pre_f ? gpre[f].F : nullptr);
+    }
+    if (D && bx && dyn_can_seed(D, ctx->track_frame + f)) {
+      SvoTimer t(ctx, "k_td_seeds", s1);
+      hipLaunchKernelGGL(k_td_seeds, dim3(1), dim3(TRK_MAXKP), 0, s1, work + f, kpf, bxf, nbf, D->d_seeds + (size_t)f * 2 * DYN_MAX_SEEDS,
+                         D->nseed() + f);
     }
   };
   // one sequence: the pose kernels find out by themselves when their frame's record is there (tp_wait_work) - no stream event
@@ -1910,6 +2180,10 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
       cur0 = g0; cur1 = std::min(frames, g0 + gsize);
       for (int f = cur0; f < cur1; ++f) enqueue_index(f);
       if (!flagged) hipEventRecord(ctx->ev_frame[cur0], s1);
+      if (D) {   // (behind the group's record: the pose chain's wait is never behind LK work)
+        ctx->profiling = false;
+        if ((rc = dyn_enqueue_group(ctx, D, s1, cur0, cur1, ctx->track_frame, bx != nullptr, fe_events, frames))) { ctx->profiling = prof; return rc; }
+      }
       g0 = cur1;
       ++ngroup;
       if (ngroup >= 2) gsize = std::min(2 * gsize, ctx->opt_track_group > 0 ? ctx->opt_track_group : 1);
@@ -1921,6 +2195,7 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
     prev0 = cur0; prev1 = cur1;
   }
   ctx->profiling = prof;
+  if (D && (rc = dyn_finish(ctx, D, s1, s0, frames))) return rc;
   if (bx && ctx->det_ready) {   // a detector feeds this context: its next call may overwrite these boxes once both chains read them
     for (int k = 0; k < 2; ++k)
       if (!ctx->det_read[k]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->det_read[k], hipEventDisableTiming));
@@ -1961,6 +2236,7 @@ static int track_reset_n(svo_ctx* ctx, const svo_camera* cam, int nseq) {
     SVO_HIP(ctx, hipMemcpyAsync(st->lastTcw, I, sizeof I, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(&st->cam, cam, sizeof *cam, hipMemcpyHostToDevice, ctx->stream));
   }
+  { const int rcd = dyn_adopt(ctx); if (rcd) return rcd; }   // (svo_track_dynamic's parameters; the list is empty again)
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->cam = *cam;
   ctx->track_frame = 0;
@@ -2027,8 +2303,24 @@ extern "C" int svo_track_frame(svo_ctx* ctx, const uint8_t* grayL, int strideL,
 }
 
 // svo_track_frame / svo_track_frame_bgr from the point where the pair's gray images are in staging slots 0 / 1
+static int track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
+                              const uint8_t* d_bgrR, int bgr_pitch);
+static int dyn_colour_needs_bgr(svo_ctx* ctx, const char* who) {
+  ctx->last_error = std::string(who) + ": svo_track_dynamic asked for LK on the colour frames (colour = 1), which a gray entry does not have";
+  return SVO_E_INVALID;
+}
 int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
                            const uint8_t* d_bgrR, int bgr_pitch) {
+  if (!dyn_active(ctx)) return track_frame_staged(ctx, boxes, n_boxes, res, d_bgrL, d_bgrR, bgr_pitch);
+  const bool colour = dyn_of(ctx)->p.colour != 0;
+  if (colour && !d_bgrL) return dyn_colour_needs_bgr(ctx, "svo_track_frame");
+  int rc = dyn_begin(ctx, colour ? d_bgrL : ctx->d_stage, colour ? bgr_pitch : ctx->stage_pitch, true, true);
+  if (rc == SVO_OK) rc = track_frame_staged(ctx, boxes, n_boxes, res, d_bgrL, d_bgrR, bgr_pitch);
+  dyn_end(ctx);
+  return rc;
+}
+static int track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
+                              const uint8_t* d_bgrR, int bgr_pitch) {
   const SvoGeom& g = ctx->g;
   TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
   uint8_t* dL = ctx->d_stage;
@@ -2117,6 +2409,7 @@ extern "C" int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, co
                                         int stride, int n_seq, const svo_boxes_dev* boxes, svo_track_result* d_results) {
   if (!ctx || !d_grayL || !d_grayR || !d_results || stride < ctx->g.W) return SVO_E_INVALID;
   if (!ctx->d_track || n_seq != ctx->n_seq) return SVO_E_INVALID;   // svo_track_multi_reset(n_seq) first
+  { const int rcd = svo_track_dyn_refuse(ctx, "svo_track_multi_step_dev"); if (rcd) return rcd; }
   if (ctx->opt_depth_source != 0) {   // the many-sequence mode has the sparse matcher only
     ctx->last_error = "svo_track_multi_step_dev: depth_source must be 0";
     return SVO_E_INVALID;
@@ -2176,8 +2469,20 @@ extern "C" int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, co
   return SVO_OK;
 }
 
+static int track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
+                           const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr);
 int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
                         const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr) {
+  if (!ctx || !dyn_active(ctx)) return track_batch_fed(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, pair_ready, bgr);
+  const bool colour = dyn_of(ctx)->p.colour != 0;
+  if (colour && !bgr) return dyn_colour_needs_bgr(ctx, "svo_track_batch");
+  int rc = dyn_begin(ctx, colour ? bgr->L : d_grayL, colour ? bgr->stride : stride, pair_ready != nullptr, false);
+  if (rc == SVO_OK) rc = track_batch_fed(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, pair_ready, bgr);
+  dyn_end(ctx);
+  return rc;
+}
+static int track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
+                           const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr) {
   if (!ctx || !d_grayL || !d_grayR || !d_results || B < 1 || stride < ctx->g.W) return SVO_E_INVALID;
   if (B > ctx->max_batch) return SVO_E_CAPACITY;
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;
@@ -2189,6 +2494,8 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
   const size_t gray_img = (size_t)ctx->g.H * stride, bgr_img = bgr ? (size_t)ctx->g.H * bgr->stride : 0;
   auto bgr_wait = [&](hipStream_t s) -> int {   // the readers of the gray staging in the previous colour call
     for (int k = 0; convert && k < bgr->n_wait; ++k) SVO_HIP(ctx, hipStreamWaitEvent(s, bgr->wait[k], 0));
+    // (the dynamic-keypoint loop of the previous call read the gray this call writes anew)
+    if (convert && dyn_active(ctx) && !dyn_of(ctx)->p.colour && dyn_of(ctx)->ev_lk_valid) SVO_HIP(ctx, hipStreamWaitEvent(s, dyn_of(ctx)->ev_lk, 0));
     return SVO_OK;
   };
   auto bgr_convert = [&](hipStream_t s, int f0, int b) {
@@ -2376,6 +2683,46 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
   return SVO_OK;
 }
 
+extern "C" int svo_dyn_default_params(svo_dyn_params* p) {
+  if (!p) return SVO_E_INVALID;
+  p->enable = 0;
+  p->colour = 0;
+  p->seed_frames = 2;
+  p->max_pts = 512;
+  return svo_lk_default_params(&p->lk);
+}
+
+// Checked on the host alone, in lk_check's order; in force from the next svo_track_reset on
+extern "C" int svo_track_dynamic(svo_ctx* ctx, const svo_dyn_params* p) {
+  if (!ctx || !p) return SVO_E_INVALID;
+  int rc = SVO_OK;
+  if (p->enable < 0 || p->enable > 1 || p->colour < 0 || p->colour > 1 || p->seed_frames < -1 || p->max_pts < 1) rc = SVO_E_INVALID;
+  if (rc == SVO_OK) rc = lk_check(&p->lk, ctx->g.W, ctx->g.H, p->max_pts, 1);
+  if (rc) {
+    ctx->last_error = rc == SVO_E_CAPACITY ? "svo_track_dynamic: image larger than 4096 x 4096 or more than 4096 points"
+                                           : "svo_track_dynamic: invalid argument or unsupported parameters";
+    return rc;
+  }
+  if (!ctx->dyn) {
+    if (!p->enable) return SVO_OK;   // (nothing to switch off)
+    ctx->dyn = new DynState();
+  }
+  dyn_of(ctx)->next = *p;
+  return SVO_OK;
+}
+
+extern "C" int svo_track_dynamic_out(svo_ctx* ctx, float* lists, int32_t* counts, int32_t* dropped) {
+  if (!ctx || !lists || !counts) return SVO_E_INVALID;
+  if (!dyn_active(ctx)) {
+    ctx->last_error = "svo_track_dynamic_out: the dynamic-keypoint loop is not enabled (svo_track_dynamic, then svo_track_reset)";
+    return SVO_E_INVALID;
+  }
+  DynState* D = dyn_of(ctx);
+  D->out.lists = lists; D->out.counts = counts; D->out.dropped = dropped;
+  D->attached = true;
+  return SVO_OK;
+}
+
 extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR,
                                    int stride, int B, const svo_boxes_dev* boxes, svo_track_result* d_results) {
   return svo_track_batch_fed(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, nullptr);
@@ -2388,6 +2735,7 @@ extern "C" int svo_track_tail_dev(svo_ctx* ctx, const svo_kp* d_kp, const uint8_
                                   svo_track_result* d_results) {
   if (!ctx || !d_kp || !d_desc || !d_n || !d_depth || !d_results || B < 1 || kp_stride < 1) return SVO_E_INVALID;
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset first
+  { const int rcd = svo_track_dyn_refuse(ctx, "svo_track_tail_dev"); if (rcd) return rcd; }
   hipSetDevice(ctx->device);
   { const int rcs = svo_shard_quiesce(ctx); if (rcs) return rcs; }   // (a sharded call of this context may still be in flight: staging sets, work records)
   int rc = tail_enqueue(ctx, d_kp, d_desc, d_n, d_depth, kp_stride, B, 1, d_results, boxes);
@@ -2642,6 +2990,7 @@ int svo_track_sharded_fed(svo_ctx* const* ctxs, int G, const uint8_t* const* d_g
       return SVO_E_INVALID;
     if ((B - g + G - 1) / G > ctxs[g]->max_batch) return SVO_E_CAPACITY;
   }
+  { const int rcd = svo_track_dyn_refuse(c0, "svo_track_sharded_dev"); if (rcd) return rcd; }
   ShardGather* sg = shard_gather(c0);
   SVO_HIP(c0, hipSetDevice(c0->device));
   { const int rcf = svo_track_fe_batch_stream(c0); if (rcf) return rcf; }

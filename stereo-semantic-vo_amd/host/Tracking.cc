@@ -57,9 +57,15 @@ void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n,
   if (!ctx_batch) {
     if (svo_create(&ctx_batch, device, width, height, 500, batch_capacity) != SVO_OK) throw std::runtime_error("svo_create failed");
     if (svo_set_option(ctx_batch, "depth_source", depth_source) != SVO_OK || svo_set_option(ctx_batch, "sgbm_colour", sgbm_colour ? 1 : 0) != SVO_OK ||
-        svo_set_option(ctx_batch, "sgbm_mode", sgbm_mode) != SVO_OK ||
-        svo_track_reset(ctx_batch, &K) != SVO_OK)
+        svo_set_option(ctx_batch, "sgbm_mode", sgbm_mode) != SVO_OK)
       throw std::runtime_error(std::string("TrackBatch: ") + svo_last_error(ctx_batch));
+    if (dynamic_dev || dynamic_dev_bgr) {   // (before the reset: that is when the parameters come into force)
+      svo_dyn_params dp;
+      svo_dyn_default_params(&dp);
+      dp.enable = 1; dp.colour = dynamic_dev_bgr ? 1 : 0; dp.max_pts = dynamic_max_pts;
+      if (svo_track_dynamic(ctx_batch, &dp) != SVO_OK) throw std::runtime_error(std::string("TrackBatch: ") + svo_last_error(ctx_batch));
+    }
+    if (svo_track_reset(ctx_batch, &K) != SVO_OK) throw std::runtime_error(std::string("TrackBatch: ") + svo_last_error(ctx_batch));
     batch_results.reserve(1 << 16);   // (the library writes into this array until FinishBatches: it must not move)
   }
   const size_t first = batch_results.size();
@@ -79,6 +85,14 @@ void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n,
       for (int j = 0; j < 4; ++j) flat[((size_t)k * most + b) * 4 + j] = detection_box[k][b][j];
   }
   const svo_boxes_host bx{flat.data(), cnt.data(), std::max(most, 1)};
+  if (dynamic_dev || dynamic_dev_bgr) {
+    if (dynamic_dev_bgr && !bgr) throw std::runtime_error("Tracking::dynamic_dev_bgr needs TrackBatch(bgr = true)");
+    batch_dyn_calls.emplace_back(new DynCall());
+    DynCall& c = *batch_dyn_calls.back();
+    c.lists.assign((size_t)n * 2 * dynamic_max_pts, 0.f); c.counts.assign((size_t)n, 0); c.dropped.assign((size_t)n, 0);
+    if (svo_track_dynamic_out(ctx_batch, c.lists.data(), c.counts.data(), c.dropped.data()) != SVO_OK)
+      throw std::runtime_error(std::string("svo_track_dynamic_out: ") + svo_last_error(ctx_batch));
+  }
   const int rc = (bgr ? svo_track_batch_bgr_host : svo_track_batch_host)(ctx_batch, L, R, stride, n, most > 0 ? &bx : nullptr,
                                                                        batch_results.data() + first);
   if (rc != SVO_OK)
@@ -89,6 +103,13 @@ void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n,
 void Tracking::FinishBatches(std::ofstream& f, std::ofstream& f2) {
   if (!ctx_batch) return;
   if (svo_sync(ctx_batch) != SVO_OK) throw std::runtime_error(std::string("FinishBatches: ") + svo_last_error(ctx_batch));
+  for (const auto& c : batch_dyn_calls)   // (complete now: the lists of every batched frame, in order)
+    for (size_t k = 0; k < c->counts.size(); ++k) {
+      const Point2f* p = reinterpret_cast<const Point2f*>(c->lists.data() + k * 2 * (size_t)dynamic_max_pts);
+      batch_dynamic.emplace_back(p, p + c->counts[k]);
+      batch_dynamic_dropped.push_back(c->dropped[k]);
+    }
+  batch_dyn_calls.clear();
   frame fr;   // SetPose's Rwc / twc arithmetic (src/frame.cc:66-73), SaveTrajectoryAndDraw's formats
   for (size_t k = 0; k < batch_results.size(); ++k) {
     Mat44f T;

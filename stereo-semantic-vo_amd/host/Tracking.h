@@ -1,6 +1,7 @@
 // Tracking.h - per-frame orchestrator, mirrors the reference's include/Tracking.h.
 #pragma once
 #include <fstream>
+#include <memory>
 #include <set>
 #include <string>
 
@@ -28,6 +29,14 @@ class Tracking {
   // With dynamic_lk: run that loop on the colour left images (frame::LKTrackBgr), as the reference's call would - its leftimg
   // is the 8UC3 image.  Needs the colour Track(); the seeds and everything else are unchanged.
   bool dynamic_lk_bgr = false;
+  // The same loop inside the device-resident tracker (svo_track_dynamic), for TrackBatch(): set before the first TrackBatch().
+  // ctx_batch is configured before its reset, every call attaches storage of its own, and after FinishBatches() batched frame
+  // k's list is batch_dynamic[k] (batch_dynamic_dropped[k]: seeds that did not fit into dynamic_max_pts; the host loop's lists
+  // have no capacity).  dynamic_dev_bgr: on the colour left images (svo_dyn_params.colour = 1), needs TrackBatch(bgr = true).
+  bool dynamic_dev = false, dynamic_dev_bgr = false;
+  int dynamic_max_pts = 4096;
+  std::vector<std::vector<svo_host::Point2f>> batch_dynamic;
+  std::vector<int> batch_dynamic_dropped;
   Tracking(const svo_camera& cam, int width, int height, int device = 0);
   ~Tracking();
   void init();                                                          // src/Tracking.cc:42-97
@@ -62,6 +71,8 @@ class Tracking {
   int batch_capacity = 64;
   std::vector<svo_track_result> batch_results;   // one record per batched frame (stable storage: reserved for the sequence)
   std::vector<double> batch_timestamps;
+  struct DynCall { std::vector<float> lists; std::vector<int32_t> counts, dropped; };   // one TrackBatch()'s svo_track_dynamic_out arrays
+  std::vector<std::unique_ptr<DynCall>> batch_dyn_calls;                               // (complete after svo_sync: FinishBatches collects them)
   int width = 0, height = 0;
   int device;
   frame lastframe;

@@ -16,6 +16,8 @@
 // --sgbm-colour (needs --colour and --depth-source 3): SGBM runs on the colour pair (cn = 3), as the reference's ElasMatch does.
 // --sgbm-mode sgbm|hh (hh needs --depth-source 3): SGBM's five-direction single pass (the reference's MODE_SGBM, default) or all
 // eight directions in two passes (MODE_HH).
+// --dynamic-dev / --dynamic-dev-bgr (with --pipelined only): the same loop inside the device-resident tracker (svo_track_dynamic,
+// Tracking::dynamic_dev), on gray or - needs --colour - on the colour left images; --write-dynamic writes the same files.
 // --dynamic-lk-bgr (implies --dynamic-lk; needs --colour): the same loop on the colour left images, svo_lk_track_bgr.
 // stereo_kitti --decode-bgr in.(png|ppm|pgm) out.ppm: codec self-test of the colour decode (the PPM holds RGB, as the format says).
 #include <algorithm>
@@ -136,13 +138,16 @@ int main(int argc, char** argv) {
   if (sgbm_mode == SVO_SGBM_MODE_HH && depth_source != 3) { std::cerr << "--sgbm-mode hh needs --depth-source 3" << std::endl; return 1; }
   // --dynamic-lk: Tracking::dynamic_lk (the reference's LK loop over the points inside boxes); --write-dynamic <dir>: each
   // frame's dynamic keypoints to <dir>/NNNNNN.txt, one "x y" per line (%.9g: the floats read back exactly)
-  bool dynamic_lk = false, dynamic_lk_bgr = false;
+  // --dynamic-dev / --dynamic-dev-bgr (with --pipelined): the same loop inside the device-resident tracker (Tracking::dynamic_dev)
+  bool dynamic_lk = false, dynamic_lk_bgr = false, dynamic_dev = false, dynamic_dev_bgr = false;
   std::string dynamic_dir;
   for (int i = 1; i < argc;) {
     const std::string a = argv[i];
     int take = 0;
     if (a == "--dynamic-lk") { dynamic_lk = true; take = 1; }
     else if (a == "--dynamic-lk-bgr") { dynamic_lk = dynamic_lk_bgr = true; take = 1; }
+    else if (a == "--dynamic-dev") { dynamic_dev = true; take = 1; }
+    else if (a == "--dynamic-dev-bgr") { dynamic_dev = dynamic_dev_bgr = true; take = 1; }
     else if (a == "--write-dynamic" && i + 1 < argc) { dynamic_dir = argv[i + 1]; take = 2; }
     if (!take) { ++i; continue; }
     for (int j = i; j + take < argc; ++j) argv[j] = argv[j + take];
@@ -156,14 +161,19 @@ int main(int argc, char** argv) {
     for (int i = 1; i < 4; ++i) argv[i] = argv[i + 1];
     argc = 4;
   }
-  if (pipelined && (dynamic_lk || !dynamic_dir.empty())) {
-    std::cerr << "--dynamic-lk / --dynamic-lk-bgr / --write-dynamic: frame by frame only (not with --pipelined)" << std::endl;
+  if (pipelined && dynamic_lk) {
+    std::cerr << "--dynamic-lk / --dynamic-lk-bgr: frame by frame only (not with --pipelined, which has --dynamic-dev / --dynamic-dev-bgr)" << std::endl;
     return 1;
   }
+  if (dynamic_dev && !pipelined) { std::cerr << "--dynamic-dev / --dynamic-dev-bgr need --pipelined (frame by frame: --dynamic-lk / --dynamic-lk-bgr)" << std::endl; return 1; }
   if (dynamic_lk_bgr && !colour) { std::cerr << "--dynamic-lk-bgr needs --colour" << std::endl; return 1; }
-  if (!dynamic_dir.empty() && !dynamic_lk) { std::cerr << "--write-dynamic needs --dynamic-lk" << std::endl; return 1; }
+  if (dynamic_dev_bgr && !colour) { std::cerr << "--dynamic-dev-bgr needs --colour" << std::endl; return 1; }
+  if (!dynamic_dir.empty() && !dynamic_lk && !dynamic_dev) {
+    std::cerr << "--write-dynamic needs --dynamic-lk or, with --pipelined, --dynamic-dev" << std::endl;
+    return 1;
+  }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr] [--write-dynamic dir] [--pipelined] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--pipelined] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -192,6 +202,15 @@ int main(int argc, char** argv) {
   mpTracker->sgbm_mode = sgbm_mode;
   mpTracker->dynamic_lk = dynamic_lk;
   mpTracker->dynamic_lk_bgr = dynamic_lk_bgr;
+  mpTracker->dynamic_dev = dynamic_dev;
+  mpTracker->dynamic_dev_bgr = dynamic_dev_bgr;
+  auto write_dynamic = [&](int ni, const std::vector<Point2f>& pts) {
+    FILE* o = fopen((dynamic_dir + "/" + name("", ni, ".txt").substr(seq.size() + 2)).c_str(), "w");
+    if (!o) { std::cerr << "cannot write into " << dynamic_dir << std::endl; return false; }
+    for (const Point2f& p : pts) fprintf(o, "%.9g %.9g\n", p.x, p.y);
+    fclose(o);
+    return true;
+  };
   std::ofstream f("cameratrajectory_kitti.txt"); f << std::fixed;
   std::ofstream f2("cameratrajectory_tum.txt"); f2 << std::fixed;
   std::vector<float> vTimesTrack(nImages);
@@ -245,6 +264,13 @@ int main(int argc, char** argv) {
       mpTracker->TrackBatch(bufL.data(), bufR.data(), cols, n, &vTimestamps[n0], boxes, colour);
     }
     mpTracker->FinishBatches(f, f2);
+    if (dynamic_dev) {
+      int lost = 0;
+      for (int d : mpTracker->batch_dynamic_dropped) lost += d;
+      if (lost) std::cerr << "--dynamic-dev: " << lost << " seeds did not fit into the list of " << mpTracker->dynamic_max_pts << " points" << std::endl;
+      for (int ni = 0; ni < nImages && !dynamic_dir.empty(); ++ni)
+        if (!write_dynamic(ni, mpTracker->batch_dynamic[(size_t)ni])) return 1;
+    }
     const double total = std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t0).count();
     f.close(); f2.close();
     std::cout << std::endl << "trajectory saved!" << std::endl << "-------" << std::endl << std::endl;
@@ -269,12 +295,7 @@ int main(int argc, char** argv) {
     else mpTracker->Track(imLeft, imRight, vTimestamps[ni], f, f2, boxes);
     const auto t2 = std::chrono::steady_clock::now();
     vTimesTrack[ni] = (float)std::chrono::duration_cast<std::chrono::duration<double>>(t2 - t1).count();
-    if (!dynamic_dir.empty()) {
-      FILE* o = fopen((dynamic_dir + "/" + name("", ni, ".txt").substr(seq.size() + 2)).c_str(), "w");
-      if (!o) { std::cerr << "cannot write into " << dynamic_dir << std::endl; return 1; }
-      for (const Point2f& p : mpTracker->lastframe.DY_keypoints) fprintf(o, "%.9g %.9g\n", p.x, p.y);
-      fclose(o);
-    }
+    if (!dynamic_dir.empty() && !write_dynamic(ni, mpTracker->lastframe.DY_keypoints)) return 1;
   }
   f.close(); f2.close();
   std::cout << std::endl << "trajectory saved!" << std::endl;
