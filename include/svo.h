@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 7   /* 7, backward-compatible additions: svo_dyn_default_params, svo_track_dynamic, svo_track_dynamic_out (the
+#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_debug_stereo_match (the sparse stereo matcher on the caller's keypoints, a
+                              parity probe; see there); no existing entry changed.
+                              7, backward-compatible additions: svo_dyn_default_params, svo_track_dynamic, svo_track_dynamic_out (the
                               dynamic-keypoint Lucas-Kanade loop inside the device-resident tracker, see "LK inside the tracker" below);
                               no existing entry changed.
                               7, backward-compatible additions: svo_sgbm_process_mode, svo_sgbm_process_bgr_mode, svo_sgbm_batch_mode_dev,
@@ -319,6 +321,18 @@ int svo_stereo_frame_ex(svo_ctx* ctx, const uint8_t* grayL, int strideL, const u
                         int strideR, const svo_camera* cam, svo_kp* kpL, uint8_t* descL,
                         int32_t* nL, float* uR, float* depth, svo_kp* kpR, uint8_t* descR,
                         int32_t* nR);
+
+/* Parity probe of the matcher alone (same kernels as svo_stereo_frame): uploads the pair and builds the context's own
+ * pyramids as svo_stereo_frame_ex does, then replaces the keypoints, descriptors and counts of both images with the
+ * caller's (kpL / descL: nL entries, kpR / descR: nR entries, 32 bytes per descriptor; only x, y and octave are read)
+ * and runs the matcher on them.  uR, depth, sad: max_kp entries each.  sad[i] is the best SAD of left keypoint i BEFORE
+ * the median cut, -1 where the matcher did not accept it (the cut turns uR / depth to -1 and leaves sad); entries
+ * >= nL are -1 in all three.  SVO_E_INVALID: nL or nR outside 0 .. max_kp, an octave outside 0 .. 7, a non-finite x or
+ * y, y outside [0, H), x outside [-W, 2W] (x < 0 is legal: such a left keypoint has no candidate).  The keypoints may
+ * sit anywhere else - at a level's border, where the matcher must reject them, included. */
+int svo_debug_stereo_match(svo_ctx* ctx, const uint8_t* grayL, int strideL, const uint8_t* grayR, int strideR,
+                           const svo_camera* cam, const svo_kp* kpL, const uint8_t* descL, int nL, const svo_kp* kpR,
+                           const uint8_t* descR, int nR, float* uR, float* depth, int32_t* sad);
 
 /* frame::disp2Depth (src/frame.cc:140-164): depth = bf/disp where disp != 0, else
  * -1, over a dense H x W float map. */

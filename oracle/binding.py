@@ -121,6 +121,32 @@ def stereo_frame(grayL, grayR, bf, fx, nfeatures=500):
                 kpR=kpR[:nr].copy(), dR=dR[:nr].copy())
 
 
+def stereo_match(pyrL, pyrR, W, H, kpL, dL, kpR, dR, bf, fx):
+    """orc_stereo_match on given pyramids (build_pyramid's packed levels) and arbitrary keypoints: (uR, depth, n_valid)."""
+    pyrL = np.ascontiguousarray(pyrL, np.uint8); pyrR = np.ascontiguousarray(pyrR, np.uint8)
+    kpL = np.ascontiguousarray(kpL, KP_DTYPE); kpR = np.ascontiguousarray(kpR, KP_DTYPE)
+    dL = np.ascontiguousarray(dL, np.uint8).reshape(-1, 32); dR = np.ascontiguousarray(dR, np.uint8).reshape(-1, 32)
+    psz = lib().orc_pyramid_size(int(W), int(H))
+    if pyrL.shape != (psz,) or pyrR.shape != (psz,):
+        raise ValueError("stereo_match: a pyramid of %d x %d holds %d bytes" % (W, H, psz))
+    if len(dL) != len(kpL) or len(dR) != len(kpR):
+        raise ValueError("stereo_match: one descriptor per keypoint")
+    for k in (kpL, kpR):      # the oracle indexes scale[] by the octave and rows by y
+        if len(k) and (k["octave"].min() < 0 or k["octave"].max() > 7):
+            raise ValueError("stereo_match: octave outside 0..7")
+        if not (np.isfinite(k["x"]).all() and np.isfinite(k["y"]).all()):
+            raise ValueError("stereo_match: non-finite keypoint coordinate")
+        if len(k) and (k["y"].min() < 0 or k["y"].max() >= H):
+            raise ValueError("stereo_match: y outside [0, H)")
+        if len(k) and (k["x"].min() < -W or k["x"].max() > 2 * W):
+            raise ValueError("stereo_match: x outside [-W, 2W]")
+    nL = len(kpL)
+    uR = np.zeros(max(nL, 1), np.float32); depth = np.zeros(max(nL, 1), np.float32)
+    nv = lib().orc_stereo_match(_p(pyrL), _p(pyrR), int(W), int(H), _p(kpL), _p(dL), nL, _p(kpR), _p(dR), len(kpR),
+                                C.c_float(bf), C.c_float(fx), _p(uR), _p(depth))
+    return uR[:nL].copy(), depth[:nL].copy(), nv
+
+
 def descriptor_distance(a, b):
     a = np.ascontiguousarray(a, np.uint8).reshape(-1, 32); b = np.ascontiguousarray(b, np.uint8).reshape(-1, 32)
     return np.array([lib().orc_descriptor_distance(_p(a[i]), _p(b[i])) for i in range(len(a))], np.int32)

@@ -99,6 +99,8 @@ int orc_stereo_match(const uint8_t* pyrL, const uint8_t* pyrR, int W, int H, con
     const float d1 = (float)dists[SAD_L + bestinc - 1], d2 = (float)dists[SAD_L + bestinc],
                 d3 = (float)dists[SAD_L + bestinc + 1];
     const float deltaR = (d1 - d3) / (2.0f * (d1 + d3 - 2.0f * d2));
+    /* Unreachable (as is 0 / 0), kept as the algorithm states it: bestinc is the FIRST strict minimum, so d1 > d2 and
+     * d3 >= d2; hence d1 + d3 - 2 d2 > 0, and |d1 - d3| <= d1 + d3 - 2 d2 gives |deltaR| <= 0.5. */
     if (deltaR < -1 || deltaR > 1) continue;
     float bestuR = scale[levelL] * ((float)sr0 + (float)bestinc + deltaR);
     float disparity = uL - bestuR;

@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "svo_lk_default_params", "svo_lk_track", "svo_lk_batch_dev", "svo_lk_chain_dev", "svo_lk_debug_level",
     "svo_lk_track_bgr", "svo_lk_batch_bgr_dev", "svo_lk_chain_bgr_dev", "svo_lk_debug_level_bgr",
     "svo_dyn_default_params", "svo_track_dynamic", "svo_track_dynamic_out",
+    "svo_debug_stereo_match",
 ]
 
 # svo_create_ex flags (include/svo.h)
@@ -271,6 +272,22 @@ class Svo:
         nl, nr = nL.value, nR.value
         return dict(kpL=kpL[:nl].copy(), dL=dL[:nl].copy(), uR=uR[:nl].copy(),
                     depth=depth[:nl].copy(), kpR=kpR[:nr].copy(), dR=dR[:nr].copy())
+
+    def debug_stereo_match(self, grayL, grayR, cam, kpL, dL, kpR, dR):
+        """svo_debug_stereo_match: the matcher of stereo_frame on the caller's keypoints (KP_DTYPE; x, y, octave are read) and
+        descriptors, over the context's own pyramids of the pair.  Returns (uR, depth, sad), max_kp entries each: sad is the
+        best SAD before the median cut, -1 where the matcher did not accept; entries >= len(kpL) are -1."""
+        grayL = _u8(grayL); grayR = _u8(grayR)
+        assert grayL.shape == (self.H, self.W) and grayR.shape == (self.H, self.W)
+        kpL = np.ascontiguousarray(kpL, KP_DTYPE); kpR = np.ascontiguousarray(kpR, KP_DTYPE)
+        dL = _u8(dL).reshape(-1, 32); dR = _u8(dR).reshape(-1, 32)
+        if len(dL) != len(kpL) or len(dR) != len(kpR):
+            raise SvoError("debug_stereo_match: one descriptor per keypoint")
+        K = self.max_kp
+        uR = np.zeros(K, np.float32); depth = np.zeros(K, np.float32); sad = np.zeros(K, np.int32)
+        self._chk(self.lib.svo_debug_stereo_match(self.h, _p(grayL), self.W, _p(grayR), self.W, C.byref(cam), _p(kpL), _p(dL),
+                                                  len(kpL), _p(kpR), _p(dR), len(kpR), _p(uR), _p(depth), _p(sad)))
+        return uR, depth, sad
 
     def disp2depth(self, disp, bf):
         disp = np.ascontiguousarray(disp, np.float32); out = np.zeros_like(disp)

@@ -254,8 +254,11 @@ extern "C" int svo_create_ex(svo_ctx** out, int device, int W, int H, int max_kp
   TRY(dalloc(ctx, &ctx->d_xalpha, xalpha.size()));
   TRY(dalloc(ctx, &ctx->d_yofs, yofs.size()));
   TRY(dalloc(ctx, &ctx->d_ybeta, ybeta.size()));
-  TRY(dalloc(ctx, &ctx->d_stage, I * (size_t)H * ctx->stage_pitch));
-  TRY(dalloc(ctx, &ctx->d_pyr, I * (size_t)g.pyr_bytes));
+  // + 64 bytes each: k_stereo_match's unconditional 16- / 24-byte window loads end up to 5 bytes past a level's width; in the last row
+  // of a level whose pitch has no such slack (w within 4 of a multiple of 64) that is past the level - past the allocation for
+  // level 0 / level 7 of the last image slot (see the loads in svo_stereo.hip)
+  TRY(dalloc(ctx, &ctx->d_stage, I * (size_t)H * ctx->stage_pitch + 64));
+  TRY(dalloc(ctx, &ctx->d_pyr, I * (size_t)g.pyr_bytes + 64));
   TRY(dalloc(ctx, &ctx->d_corners, I * (size_t)g.corner_entries));
   TRY(dalloc(ctx, &ctx->d_counters, I * SVO_NLEVELS));
   TRY(dalloc(ctx, &ctx->d_hist, I * SVO_NLEVELS * 256));
@@ -594,6 +597,50 @@ extern "C" int svo_stereo_frame(svo_ctx* ctx, const uint8_t* grayL, int strideL,
                                 svo_kp* kpL, uint8_t* descL, int32_t* nL, float* uR, float* depth) {
   return svo_stereo_frame_ex(ctx, grayL, strideL, grayR, strideR, cam, kpL, descL, nL, uR, depth,
                              nullptr, nullptr, nullptr);
+}
+
+// The matcher of svo_stereo_frame_ex on the caller's keypoints (parity probe): the pyramids are the context's own.
+extern "C" int svo_debug_stereo_match(svo_ctx* ctx, const uint8_t* grayL, int strideL, const uint8_t* grayR, int strideR,
+                                      const svo_camera* cam, const svo_kp* kpL, const uint8_t* descL, int nL, const svo_kp* kpR,
+                                      const uint8_t* descR, int nR, float* uR, float* depth, int32_t* sad) {
+  if (!ctx || !grayL || !grayR || !cam || !uR || !depth || !sad || strideL < ctx->g.W || strideR < ctx->g.W ||
+      nL < 0 || nL > ctx->max_kp || nR < 0 || nR > ctx->max_kp || (nL > 0 && (!kpL || !descL)) || (nR > 0 && (!kpR || !descR)))
+    return SVO_E_INVALID;
+  const float W = (float)ctx->g.W, H = (float)ctx->g.H;
+  for (int side = 0; side < 2; ++side) {
+    const svo_kp* k = side ? kpR : kpL;
+    for (int i = 0; i < (side ? nR : nL); ++i)
+      if (k[i].octave < 0 || k[i].octave >= SVO_NLEVELS || !std::isfinite(k[i].x) || !std::isfinite(k[i].y) ||
+          !(k[i].y >= 0.f && k[i].y < H) || !(k[i].x >= -W && k[i].x <= 2.f * W)) {
+        ctx->last_error = "svo_debug_stereo_match: keypoint outside the accepted range";
+        return SVO_E_INVALID;
+      }
+  }
+  hipSetDevice(ctx->device);
+  int rc = upload_image(ctx, grayL, strideL, 0);
+  if (rc) return rc;
+  rc = upload_image(ctx, grayR, strideR, 1);
+  if (rc) return rc;
+  const uint8_t* dL = ctx->d_stage;
+  const uint8_t* dR = ctx->d_stage + (size_t)ctx->g.H * ctx->stage_pitch;
+  const SvoFeBufs fb = svo_fe_own(ctx);
+  rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 2);
+  if (rc) return rc;
+  const size_t K = ctx->max_kp;
+  const int32_t cnt[2] = {nL, nR};
+  // (in stream order after the ORB kernels, whose keypoints they replace; the sources live until the synchronisation below)
+  SVO_HIP(ctx, hipMemcpyAsync(ctx->d_nkp, cnt, 8, hipMemcpyHostToDevice, ctx->stream));
+  if (nL) SVO_HIP(ctx, hipMemcpyAsync(ctx->d_kp, kpL, sizeof(svo_kp) * (size_t)nL, hipMemcpyHostToDevice, ctx->stream));
+  if (nL) SVO_HIP(ctx, hipMemcpyAsync(ctx->d_desc, descL, 32 * (size_t)nL, hipMemcpyHostToDevice, ctx->stream));
+  if (nR) SVO_HIP(ctx, hipMemcpyAsync(ctx->d_kp + K, kpR, sizeof(svo_kp) * (size_t)nR, hipMemcpyHostToDevice, ctx->stream));
+  if (nR) SVO_HIP(ctx, hipMemcpyAsync(ctx->d_desc + 32 * K, descR, 32 * (size_t)nR, hipMemcpyHostToDevice, ctx->stream));
+  rc = svo_launch_stereo(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, cam);
+  if (rc) return rc;
+  SVO_HIP(ctx, hipMemcpyAsync(uR, ctx->d_uR, 4 * K, hipMemcpyDeviceToHost, ctx->stream));
+  SVO_HIP(ctx, hipMemcpyAsync(depth, ctx->d_depth, 4 * K, hipMemcpyDeviceToHost, ctx->stream));
+  SVO_HIP(ctx, hipMemcpyAsync(sad, ctx->d_sad, 4 * K, hipMemcpyDeviceToHost, ctx->stream));
+  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SVO_OK;
 }
 
 #define H2D(dst, src, bytes) SVO_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream))

@@ -180,6 +180,18 @@ __global__ __launch_bounds__(256) void k_stereo_match(SvoGeom g, StereoSrc s, co
       const int rowi = lane < 16 ? min(lane, 10) : min(lane - 16, 10);
       const uint8_t* p = lane < 16 ? IL + (size_t)(svc + rowi - SAD_W) * pl + suc - SAD_W
                                    : IR + (size_t)(svc + rowi - SAD_W) * pr + src - SAD_L - SAD_W;
+      // Where the loads end.  In the last legal row of a level (sv + 5 == lh - 1) at the last legal column, the left lanes' 16 bytes
+      // end at column su + 10 <= lw + 4 and the right lanes' 24 bytes at sr0 + 13 <= lw + 2: up to 5 / 3 bytes past the level's
+      // width.  With a row pitch >= lw + 5 that is the row's own padding; with less (pitch = lw rounded up to 64, so lw within 4 of
+      // a multiple of 64) it is the start of the next row, and after the LAST row the bytes behind the level: the next level or
+      // image slot, and for level 0 / level 7 of the last slot the 64 bytes svo_create adds to d_stage and d_pyr for this.  The
+      // bytes read there are columns 11 .. 15 / 21 .. 23 of a window row, which the SAD never uses.  (Not refined: the window is
+      // clamped to rows 0 .. 10, columns 0 .. 23; every level is at least 27 x 27.)
+      // The batch entries read level 0 from the caller's buffer, where stride == W is legal and nothing is padded.  They take
+      // their keypoints from ORB alone, which keeps them SVO_EDGE = 31 px inside their level: su <= lw - 32, and a right
+      // keypoint of octave levelL + 1 lands at sr0 <= lw - 36 of levelL (lower octaves further in), so the loads end at column
+      // lw - 22 at the latest and stay inside the row: no over-read of a caller's buffer.  Another producer of keypoints
+      // (svo_track_tail_dev, a view of SvoFeBufs) that goes nearer a level's right edge than that needs 5 bytes after the image.
       wreg[j][0] = *reinterpret_cast<const u64u*>(p);
       wreg[j][1] = *reinterpret_cast<const u64u*>(p + 8);
       wreg[j][2] = *reinterpret_cast<const u64u*>(p + (lane < 16 ? 8 : 16));
@@ -242,6 +254,9 @@ __global__ __launch_bounds__(256) void k_stereo_match(SvoGeom g, StereoSrc s, co
           for (int k = 1; k < 10; ++k)
             if (k - SAD_L == binc) { d1 = (float)dists[k - 1]; d2 = (float)dists[k]; d3 = (float)dists[k + 1]; }
           const float deltaR = (d1 - d3) / (2.0f * (d1 + d3 - 2.0f * d2));
+          // This rejection (and 0 / 0) cannot happen; the branch stays as the algorithm states it.  binc is the FIRST strict
+          // minimum, so d1 > d2 and d3 >= d2: the denominator 2 (d1 + d3 - 2 d2) is > 0, and |d1 - d3| <= d1 + d3 - 2 d2 gives
+          // |deltaR| <= 0.5.  (SADs are integers < 2^24: every term is exact in float32 but the quotient.)
           if (!(deltaR < -1 || deltaR > 1)) {
             float bestuR = sc * ((float)sr0 + (float)binc + deltaR);
             float disparity = uL - bestuR;

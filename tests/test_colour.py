@@ -49,7 +49,7 @@ def test_colour_entries_declared_bound_and_exported(pkg):
     for name in NEW:
         assert re.search(r"\bint\s+%s\s*\(" % name, hdr), name
         assert name in pkg.ABI_SYMBOLS, name
-    assert re.search(r"#define SVO_ABI_VERSION 7\b", hdr)
+    assert re.search(r"#define SVO_ABI_VERSION 8\b", hdr)
     lib = os.path.join(ROOT, "stereo-semantic-vo_amd", "libsvo_hip.so")
     syms = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in syms.splitlines() if ln.strip()}

@@ -222,6 +222,54 @@ def test_bf_match_against_oracle(svo_small, orc):
         assert np.array_equal(a, r)
 
 
+@pytest.mark.parametrize("N", [512, 513, 1024])
+def test_matchers_at_the_column_padding_switch_and_the_full_table(svo_small, orc, N):
+    """The distance matrix has 512 or 1024 columns (N <= 512: 512) and the train table in LDS holds 1024 rows: the last N of
+    the narrow matrix, the first of the wide one, and the full table - planted neighbours and ties in the last columns too."""
+    M = 300
+    q, t = util.planted_descriptors(900 + N, M, N)
+    rng = np.random.default_rng(N)
+    t[N - 1] = util.random_descriptors(N, 1)[0]
+    q[0] = util.flip_bits(t[N - 1], 3, rng)           # the last column is the nearest, and ties with an earlier one
+    t[N // 2] = t[N - 1]
+    q[1] = t[N - 1]
+    mask = (rng.random(N) < 0.3).astype(np.uint8)
+    for m in (None, mask):
+        for a, r in zip(svo_small.hamming_argmin(q, t, m), orc.hamming_argmin(q, t, m)):
+            assert np.array_equal(a, r)
+    assert svo_small.hamming_argmin(q, t)[0][1] == N // 2          # the tie goes to the lower index
+    skip = (rng.random(M) < 0.2).astype(np.uint8)
+    for md, ratio in ((15, 0.0), (30, 2.0)):
+        got = svo_small.match_greedy(q, t, mask, md, ratio, q_skip=skip)
+        ref = orc.match_greedy(q, t, mask, md, ratio, q_skip=skip)
+        for a, r in zip(got, ref):
+            assert np.array_equal(a, r)
+        assert got[3].sum() > 0
+    for a, r in zip(svo_small.bf_match(q, t), orc.bf_match(q, t)):
+        assert np.array_equal(a, r)
+
+
+def test_matchers_reject_more_than_1024_train_rows(pkg, svo_small):
+    q, t = util.random_descriptors(1, 4), util.random_descriptors(2, 1025)
+    for call in (lambda: svo_small.hamming_argmin(q, t), lambda: svo_small.match_greedy(q, t, np.zeros(1025, np.uint8), 30, 2.0),
+                 lambda: svo_small.bf_match(q, t)):
+        with pytest.raises(pkg.SvoError, match="capacity"):
+            call()
+    bi, _, _ = svo_small.hamming_argmin(q, t[:1024])                # and 1024 still runs afterwards
+    assert (bi >= 0).all()
+
+
+@pytest.mark.parametrize("N", [7, 512, 600])
+def test_greedy_with_every_column_assigned(svo_small, orc, N):
+    q, t = util.planted_descriptors(300 + N, 40, N)
+    assigned = np.ones(N, np.uint8)
+    bi, b, s, acc, asg = svo_small.match_greedy(q, t, assigned, 30, 2.0)
+    assert (bi == -1).all() and (b == 256).all() and (s == 256).all() and (acc == 0).all()
+    assert np.array_equal(asg, assigned)
+    for a, r in zip((bi, b, s, acc, asg), orc.match_greedy(q, t, assigned, 30, 2.0)):
+        assert np.array_equal(a, r)
+
+
 def test_empty_inputs(svo_small):
     z = np.zeros((0, 32), np.uint8)
     assert len(svo_small.descriptor_distance(z, z)) == 0

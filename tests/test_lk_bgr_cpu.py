@@ -21,7 +21,7 @@ def test_the_four_entries_are_declared_bound_and_listed(pkg):
         assert name in declared and name in pkg.ABI_SYMBOLS and hasattr(lib, name), name
     for name in ("lk_track_bgr", "lk_batch_bgr_dev", "lk_chain_bgr_dev", "lk_debug_level_bgr"):
         assert callable(getattr(pkg.Svo, name)), name
-    assert lib.svo_abi_version() == 7
+    assert lib.svo_abi_version() == 8
 
 
 def test_arguments_are_answered_on_the_host_without_a_context(pkg):

@@ -18,7 +18,7 @@ def test_abi_agreement_holds_with_the_sgbm_entries(pkg):
     lib = C.CDLL(pkg.LIB_PATH)
     for n in names:
         assert hasattr(lib, n), n
-    assert lib.svo_abi_version() == 7
+    assert lib.svo_abi_version() == 8
 
 
 def test_default_params_are_elasmatch_s(pkg):
