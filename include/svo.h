@@ -35,6 +35,9 @@ extern "C" {
 
 #define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_debug_stereo_match (the sparse stereo matcher on the caller's keypoints, a
                               parity probe; see there); no existing entry changed.
+                              8, backward-compatible addition: svo_track_multi_step_bgr_dev, and the dynamic-keypoint loop in the
+                              many-sequence mode (svo_track_dynamic then svo_track_multi_reset; see "LK inside the tracker" below); no
+                              existing entry changed.
                               7, backward-compatible additions: svo_dyn_default_params, svo_track_dynamic, svo_track_dynamic_out (the
                               dynamic-keypoint Lucas-Kanade loop inside the device-resident tracker, see "LK inside the tracker" below);
                               no existing entry changed.
@@ -539,7 +542,8 @@ int svo_frontend_batch_host(svo_ctx* ctx, const uint8_t* grayL, const uint8_t* g
  * gray), and computes its own 0.299 / 0.587 / 0.114 gray from it, as the reference does.  Argument checks, contracts and overlap
  * rules are those of the gray counterparts, with stride >= 3 * W; gray and colour calls may follow each other within one
  * sequence, each frame's record being what its own pixels imply.  A context allocates its colour staging on the first colour
- * call.  svo_track_sharded_*, svo_track_multi_step_dev and svo_frontend_batch_* stay gray-only. */
+ * call.  The many-sequence mode has svo_track_multi_step_bgr_dev (below, with svo_track_multi_step_dev); svo_track_sharded_* and
+ * svo_frontend_batch_* stay gray-only. */
 
 /* BGR -> gray with cv::cvtColor(COLOR_BGR2GRAY)'s fixed-point weights; host buffers in and out (any width x height, rows
  * bgr_stride >= 3 * width and gray_stride >= width bytes apart).  Synchronises. */
@@ -600,10 +604,21 @@ int svo_debug_stream_pipes(svo_ctx* ctx, int32_t out[4]);
  * The front end runs batched over the n_seq pairs and every kernel of the temporal tail runs one
  * workgroup per sequence, so the strictly serial chain of one sequence overlaps with the others'.
  * Results are identical to n_seq separate single-sequence trackers.  boxes (may be NULL): entry q = the detection boxes
- * of sequence q's frame of this step. */
+ * of sequence q's frame of this step.  Both entries want "depth_source" 0.
+ * Image lifetime: a step's images are read by work the step enqueues and must stay unchanged until that work is done - until
+ * svo_sync(ctx), or until work the caller orders behind svo_stream(ctx) after the step returned runs.  That rule is the same with
+ * and without the dynamic-keypoint loop (whose copy of the left images is the step's last reader: the context's stream waits for
+ * it) and with "multi_pipeline" 0 and 1. */
 int svo_track_multi_reset(svo_ctx* ctx, int n_seq, const svo_camera* cam);
 int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride,
                              int n_seq, const svo_boxes_dev* boxes, svo_track_result* d_results);
+/* svo_track_multi_step_dev for n_seq 8UC3 BGR pairs back to back (pair q at d_bgrL + q * H * stride), stride >= 3 * W (a backward-
+ * compatible ABI-8 addition).  The gray of the 2 n_seq images is written on the device (svo_bgr_to_gray's fixed point) into the
+ * context's colour staging, on the stream the step's front end runs on; from that gray on it is svo_track_multi_step_dev, records
+ * byte-identical to it on that gray and to n_seq svo_track_batch_bgr_dev chains.  Gray and colour steps may alternate within a run.
+ * SVO_E_INVALID for a bad stride or n_seq. */
+int svo_track_multi_step_bgr_dev(svo_ctx* ctx, const uint8_t* d_bgrL, const uint8_t* d_bgrR, int stride,
+                                 int n_seq, const svo_boxes_dev* boxes, svo_track_result* d_results);
 
 /* Names + accumulated HIP-event time (ms) and launch count of the kernels the ctx
  * has timed since svo_profile_reset (only when svo_profile_enable(ctx,1)). */
@@ -929,20 +944,32 @@ int svo_dyn_default_params(svo_dyn_params* params);
 
 /* Sets the loop's parameters.  Checked on the host first, with svo_lk_track's rules in its order (the images are the context's
  * width x height, the point count is max_pts): anything svo_lk_track does not accept, or enable / colour / seed_frames out of
- * range, is SVO_E_INVALID, max_pts > 4096 SVO_E_CAPACITY.  The parameters come into force with the next svo_track_reset, which also
- * empties the list; until then the context behaves as before.  While the loop is enabled, svo_track_frame, svo_track_frame_bgr,
- * svo_track_batch_dev, svo_track_batch_bgr_dev, svo_track_batch_host and svo_track_batch_bgr_host run it, with every
- * "depth_source"; colour = 1 through a gray entry is SVO_E_INVALID at that call; svo_track_tail_dev, svo_track_sharded_* and
- * svo_track_multi_step_dev return SVO_E_INVALID (svo_last_error says why), enqueue nothing and leave the context usable.
+ * range, is SVO_E_INVALID, max_pts > 4096 SVO_E_CAPACITY.  The parameters come into force with the next svo_track_reset or
+ * svo_track_multi_reset, which also empties the lists; until then the context behaves as before.  The loop belongs to the KIND of
+ * reset that adopted it (the context remembers which, also for n_seq = 1):
+ *   adopted by svo_track_reset: svo_track_frame, svo_track_frame_bgr, svo_track_batch_dev, svo_track_batch_bgr_dev,
+ *     svo_track_batch_host and svo_track_batch_bgr_host run it, with every "depth_source"; svo_track_multi_step_dev and
+ *     svo_track_multi_step_bgr_dev refuse;
+ *   adopted by svo_track_multi_reset(n_seq): svo_track_multi_step_dev and svo_track_multi_step_bgr_dev run it for the n_seq
+ *     sequences at once - sequence q's list is, bit for bit, that of a single-sequence context with the same parameters fed
+ *     sequence q's frames and boxes; a sequence's frame id is the number of steps since the reset; per step one launch per
+ *     stage (seeds, level building, track, compact) whatever n_seq is, with "multi_pipeline" 0 and 1 alike.  The single-sequence
+ *     entries above refuse.
+ *   svo_track_tail_dev and svo_track_sharded_* refuse either way.
+ * A refusal is SVO_E_INVALID (svo_last_error names the entry and says why), enqueues nothing and leaves the context usable.
+ * colour = 1 through a gray entry is SVO_E_INVALID at that call (svo_track_multi_step_bgr_dev: colour = 1 tracks on its BGR left
+ * frames, colour = 0 on the gray it makes; with colour = 0 gray and colour steps may alternate).
  * Consecutive calls of a sequence continue one chain: the first frame of a call is tracked from the last left image of the call
- * before, which the context keeps in storage of its own. */
+ * before, which the context keeps in storage of its own (many sequences: two halves of n_seq images that alternate by step). */
 int svo_track_dynamic(svo_ctx* ctx, const svo_dyn_params* params);
 
 /* One-shot: the NEXT tracker call on the context writes frame f's list to lists + f * 2 * max_pts (x, y pairs), its length to
  * counts[f] and the seeds it dropped to dropped[f] (dropped may be NULL).  Device pointers for the _dev entries; host pointers for
  * svo_track_frame[_bgr] (complete when the call returns) and for the _host entries (complete under the rule of their `results`:
  * after svo_sync, or once the second following host-fed call has returned).  A call without it still advances the chain and
- * keeps the lists inside the context.  SVO_E_INVALID unless the loop is in force. */
+ * keeps the lists inside the context.  SVO_E_INVALID unless the loop is in force.
+ * Many sequences (device pointers): the next step writes sequence q's list to lists + q * 2 * max_pts, its length to counts[q]
+ * and its dropped seeds to dropped[q]; complete after svo_sync, or for work ordered behind svo_stream(ctx) after the step. */
 int svo_track_dynamic_out(svo_ctx* ctx, float* lists, int32_t* counts, int32_t* dropped);
 
 /* ---- darknet YOLO detector on the device (ABI-7 additions; no existing entry changed) -------------------------------------

@@ -62,7 +62,7 @@ ABI_SYMBOLS = [
     "svo_sgbm_process_mode", "svo_sgbm_process_bgr_mode", "svo_sgbm_batch_mode_dev", "svo_sgbm_batch_bgr_mode_dev",
     "svo_lk_default_params", "svo_lk_track", "svo_lk_batch_dev", "svo_lk_chain_dev", "svo_lk_debug_level",
     "svo_lk_track_bgr", "svo_lk_batch_bgr_dev", "svo_lk_chain_bgr_dev", "svo_lk_debug_level_bgr",
-    "svo_dyn_default_params", "svo_track_dynamic", "svo_track_dynamic_out",
+    "svo_dyn_default_params", "svo_track_dynamic", "svo_track_dynamic_out", "svo_track_multi_step_bgr_dev",
     "svo_debug_stereo_match",
 ]
 
@@ -548,6 +548,12 @@ class Svo:
     def track_multi_step_dev(self, d_grayL, d_grayR, stride, n_seq, d_results, boxes=None):
         self._chk(self.lib.svo_track_multi_step_dev(self.h, C.c_void_p(d_grayL), C.c_void_p(d_grayR), int(stride),
                                                      int(n_seq), _bx(boxes), C.c_void_p(d_results)))
+
+    def track_multi_step_bgr_dev(self, d_bgrL, d_bgrR, stride, n_seq, d_results, boxes=None):
+        """svo_track_multi_step_bgr_dev: track_multi_step_dev for n_seq BGR pairs in HBM (pair q at d_bgrL + q * H * stride,
+        stride >= 3 W); their gray is made on the device."""
+        self._chk(self.lib.svo_track_multi_step_bgr_dev(self.h, _p(d_bgrL), _p(d_bgrR), int(stride), int(n_seq), _bx(boxes),
+                                                         _p(d_results)))
 
     def profile_enable(self, on=True):
         self._chk(self.lib.svo_profile_enable(self.h, 1 if on else 0))

@@ -136,6 +136,7 @@ extern "C" int svo_track_frame_bgr(svo_ctx* ctx, const uint8_t* bgrL, int stride
       n_boxes > SVO_MAX_BOXES || (n_boxes > 0 && !boxes))
     return SVO_E_INVALID;
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset first
+  { const int rcd = svo_track_dyn_refuse_single(ctx, "svo_track_frame_bgr"); if (rcd) return rcd; }
   hipSetDevice(ctx->device);
   { const int rcq = svo_track_quiesce(ctx); if (rcq) return rcq; }
   const int W = ctx->g.W, H = ctx->g.H;
@@ -167,29 +168,38 @@ extern "C" int svo_track_frame_bgr(svo_ctx* ctx, const uint8_t* bgrL, int stride
   return svo_track_frame_staged(ctx, boxes, n_boxes, res, c->d_pair, c->d_pair + img, c->pair_pitch);
 }
 
+namespace {
+// the gray staging of the device-fed colour entries (max_batch left grays, then max_batch right grays), made by the first of them
+int gray_staging(svo_ctx* ctx, SvoColour* c, const char* who) {
+  if (c->d_gray) return SVO_OK;
+  const size_t img = (size_t)ctx->g.H * ctx->stage_pitch;
+  { const int rcq = svo_track_quiesce(ctx); if (rcq) return rcq; }
+  if (hipMalloc(reinterpret_cast<void**>(&c->d_gray), 2 * (size_t)ctx->max_batch * img) != hipSuccess) {
+    (void)hipGetLastError();
+    c->d_gray = nullptr;
+    ctx->last_error = std::string(who) + ": out of memory for the gray staging";
+    return SVO_E_NOMEM;
+  }
+  // (rows are W bytes wide in a pitch of stage_pitch: the padding is never read as image content, but keep it defined)
+  SVO_HIP(ctx, hipMemsetAsync(c->d_gray, 0, 2 * (size_t)ctx->max_batch * img, ctx->stream));
+  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int k = 0; k < 4; ++k)
+    if (!c->gray_free[k]) SVO_HIP(ctx, hipEventCreateWithFlags(&c->gray_free[k], hipEventDisableTiming));
+  c->n_free = 0;
+  return SVO_OK;
+}
+}  // namespace
+
 extern "C" int svo_track_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_bgrL, const uint8_t* d_bgrR, int stride, int B,
                                        const svo_boxes_dev* boxes, svo_track_result* d_results) {
   if (!ctx || !d_bgrL || !d_bgrR || !d_results || B < 1 || stride < 3 * ctx->g.W) return SVO_E_INVALID;
   if (B > ctx->max_batch) return SVO_E_CAPACITY;
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset first
+  { const int rcd = svo_track_dyn_refuse_single(ctx, "svo_track_batch_bgr_dev"); if (rcd) return rcd; }
   hipSetDevice(ctx->device);
   SvoColour* c = colour_of(ctx);
   const size_t img = (size_t)ctx->g.H * ctx->stage_pitch;
-  if (!c->d_gray) {
-    { const int rcq = svo_track_quiesce(ctx); if (rcq) return rcq; }
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_gray), 2 * (size_t)ctx->max_batch * img) != hipSuccess) {
-      (void)hipGetLastError();
-      c->d_gray = nullptr;
-      ctx->last_error = "svo_track_batch_bgr_dev: out of memory for the gray staging";
-      return SVO_E_NOMEM;
-    }
-    // (rows are W bytes wide in a pitch of stage_pitch: the padding is never read as image content, but keep it defined)
-    SVO_HIP(ctx, hipMemsetAsync(c->d_gray, 0, 2 * (size_t)ctx->max_batch * img, ctx->stream));
-    SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 4; ++k)
-      if (!c->gray_free[k]) SVO_HIP(ctx, hipEventCreateWithFlags(&c->gray_free[k], hipEventDisableTiming));
-    c->n_free = 0;
-  }
+  { const int rcg = gray_staging(ctx, c, "svo_track_batch_bgr_dev"); if (rcg) return rcg; }
   uint8_t* gL = c->d_gray;
   uint8_t* gR = c->d_gray + (size_t)ctx->max_batch * img;
   SvoBgrSrc src;
@@ -208,5 +218,29 @@ extern "C" int svo_track_batch_bgr_dev(svo_ctx* ctx, const uint8_t* d_bgrL, cons
     SVO_HIP(ctx, hipEventRecord(c->gray_free[nf++], ctx->stream));
   }
   c->n_free = nf;
+  return SVO_OK;
+}
+
+// svo_track_multi_step_dev for n_seq BGR pairs: their gray goes to the same staging, on the stream the step's front end runs on
+// (svo_track_multi_step_fed); the staging's readers - that front end, and the copy the dynamic-keypoint loop takes of the left
+// grays with colour = 0 - are what the next colour call's conversion waits for
+extern "C" int svo_track_multi_step_bgr_dev(svo_ctx* ctx, const uint8_t* d_bgrL, const uint8_t* d_bgrR, int stride, int n_seq,
+                                            const svo_boxes_dev* boxes, svo_track_result* d_results) {
+  if (!ctx || !d_bgrL || !d_bgrR || !d_results || stride < 3 * ctx->g.W) return SVO_E_INVALID;
+  if (!ctx->d_track || n_seq != ctx->n_seq) return SVO_E_INVALID;   // svo_track_multi_reset(n_seq) first
+  { const int rcc = svo_track_multi_step_check(ctx, "svo_track_multi_step_bgr_dev", true); if (rcc) return rcc; }
+  hipSetDevice(ctx->device);
+  SvoColour* c = colour_of(ctx);
+  { const int rcg = gray_staging(ctx, c, "svo_track_multi_step_bgr_dev"); if (rcg) return rcg; }
+  const size_t img = (size_t)ctx->g.H * ctx->stage_pitch;
+  SvoBgrSrc src;
+  src.L = d_bgrL; src.R = d_bgrR; src.stride = stride; src.convert = true;
+  src.wait = c->gray_free; src.n_wait = c->n_free;
+  src.done = c->gray_free[3];   // (never among the events waited for: at most three were recorded by a batched call, one by a step)
+  const int rc = svo_track_multi_step_fed(ctx, c->d_gray, c->d_gray + (size_t)ctx->max_batch * img,
+                                          ctx->stage_pitch, n_seq, boxes, d_results, &src);
+  if (rc) return rc;
+  std::swap(c->gray_free[0], c->gray_free[3]);
+  c->n_free = 1;
   return SVO_OK;
 }

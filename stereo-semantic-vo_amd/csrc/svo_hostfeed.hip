@@ -382,6 +382,7 @@ int track_batch_host(svo_ctx* ctx, const uint8_t* grayL, const uint8_t* grayR, i
   if (!ctx || !grayL || !grayR || !results || B < 1 || stride < (bgr ? 3 : 1) * ctx->g.W) return SVO_E_INVALID;
   if (B > ctx->max_batch) return SVO_E_CAPACITY;
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset first
+  { const int rcd = svo_track_dyn_refuse_single(ctx, bgr ? "svo_track_batch_bgr_host" : "svo_track_batch_host"); if (rcd) return rcd; }
   hipSetDevice(ctx->device);
   { const int rcs = svo_track_fe_batch_stream(ctx); if (rcs) return rcs; }
   int rc = feed_reserve(ctx, ctx->max_batch);

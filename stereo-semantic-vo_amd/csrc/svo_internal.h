@@ -325,6 +325,7 @@ struct SvoBgrSrc {
   bool convert = false;
   const hipEvent_t* wait = nullptr;
   int n_wait = 0;
+  hipEvent_t done = nullptr;   // svo_track_multi_step_fed: recorded behind the front end that read the gray (the stream is its choice)
 };
 int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
                         const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready,
@@ -380,10 +381,25 @@ void lk_launch_track(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int
 // k_lk_compact: the tracked points with status != 0 in order (n_prev == nullptr: none), then the seeds while the list has room
 void lk_launch_compact(hipStream_t s, const float* trk, const uint8_t* st, const int32_t* n_prev, const float* seeds, const int32_t* n_seed,
                        int max_seeds, int max_pts, float* list, int32_t* n_out, int32_t* dropped);
+// the many-sequence forms (svo_track_multi_step_dev's loop): `nseq` pairs (fprev0 + q, fnext0 + q) of the arena's slots, one
+// launch; sequence q's points at pts + q * 2 max_pts (counts[q]), its results at next + q * 2 max_pts, status + q * max_pts
+void lk_launch_track_seqs(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top,
+                          int fprev0, int fnext0, int nseq, const float* pts, const int32_t* counts, int max_pts, float* next,
+                          uint8_t* status);
+// workgroup q = sequence q: everything q * (its row) further on, the counts arrays over the sequences (n_prev == nullptr: none)
+void lk_launch_compact_seqs(hipStream_t s, int nseq, const float* trk, const uint8_t* st, const int32_t* n_prev, const float* seeds,
+                            const int32_t* n_seed, int max_seeds, int max_pts, float* list, int32_t* n_out, int32_t* dropped);
 // svo_track.hip: lists of the dynamic-keypoint loop that wait in pinned buffers -> the caller's host arrays (svo_hostfeed_flush)
 int svo_track_dyn_flush(svo_ctx* ctx);
 // svo_track.hip: SVO_E_INVALID with a message while that loop is enabled (the entries that do not run it)
 int svo_track_dyn_refuse(svo_ctx* ctx, const char* who);
+// svo_track.hip: the same for the single-sequence entries while the loop in force was adopted by svo_track_multi_reset
+int svo_track_dyn_refuse_single(svo_ctx* ctx, const char* who);
+// svo_track.hip: svo_track_multi_step_dev's work; `bgr` (svo_track_multi_step_bgr_dev): the step's colour pairs, whose gray this call
+// writes to d_grayL / d_grayR on the stream its front end runs on - after bgr->wait, and bgr->done is recorded behind the front end
+int svo_track_multi_step_check(svo_ctx* ctx, const char* who, bool has_bgr);   // their refusals (loop adopted by svo_track_reset, depth_source, colour = 1 without colour)
+int svo_track_multi_step_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int n_seq,
+                             const svo_boxes_dev* boxes, svo_track_result* d_results, const SvoBgrSrc* bgr);
 // svo_sgbm.hip: B resident gray pairs (pair b at dL / dR + b * frame) -> B float maps at d_disp, enqueued on `s` in chunks of
 // svo_sgbm_chunk() pairs; no synchronisation.  mode: SVO_SGBM_MODE_SGBM or SVO_SGBM_MODE_HH
 int svo_sgbm_run_dev(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int stride, size_t frame, int W, int H, int B,

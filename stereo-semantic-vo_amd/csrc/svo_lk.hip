@@ -143,14 +143,17 @@ struct LkPatch<1> {
 };
 
 // Pairs (fprev0 + blockIdx.y, fprev0 + blockIdx.y + 1) of the resident frames of CN interleaved channels; point list blockIdx.y
-// at pts + blockIdx.y * 2 max_pts with counts[blockIdx.y] entries (counts == nullptr: n_fixed); one wavefront per point, every
+// at pts + blockIdx.y * 2 max_pts with counts[blockIdx.y] entries (counts == nullptr: aux = n_fixed); one wavefront per point, every
 // lane holds the CN channels of its 7 pixels (7 CN samples).  pyr_bytes and der_entries are a frame's slot sizes (all channels),
 // a level's offsets are CN times the one-channel ones.
-template <int CN>
+// SEQS (svo_track_multi_step_dev's loop, many sequences that advance together): the resident frames are two halves of n_seq slots,
+// pair blockIdx.y = (fprev0 + blockIdx.y, aux + blockIdx.y) - sequence blockIdx.y's previous and current left image -, counts is
+// never null.  Otherwise aux is n_fixed.  The arithmetic is the same code.
+template <int CN, bool SEQS = false>
 __global__ __launch_bounds__(256) void k_lk_track(const uint8_t* __restrict__ img0, int stride0, size_t frame0,
                                                   const uint8_t* __restrict__ pyr, size_t pyr_bytes, const uint32_t* __restrict__ der,
                                                   size_t der_entries, int w0, int h0, int top, int fprev0,
-                                                  const float* __restrict__ pts, const int32_t* __restrict__ counts, int n_fixed,
+                                                  const float* __restrict__ pts, const int32_t* __restrict__ counts, int aux,
                                                   int max_pts, float* __restrict__ next, uint8_t* __restrict__ status,
                                                   float* __restrict__ err) {
   // I <= 8160 and |gx|, |gy| <= 4080 (16 * 255).  A lane's int32 partial sums of 7 CN products, and the wave's error sum:
@@ -159,10 +162,10 @@ __global__ __launch_bounds__(256) void k_lk_track(const uint8_t* __restrict__ im
   static_assert((long long)LK_NPIX * CN * 8160 < (1LL << 24), "err: exact in an int32 and in a float");   // 1323 * 8160
   const int lane = threadIdx.x & 63;
   const int idx = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int n = min(counts ? counts[blockIdx.y] : n_fixed, max_pts);
+  const int n = min(SEQS || counts ? counts[blockIdx.y] : aux, max_pts);
   if (idx >= n) return;                                     // (whole wavefronts leave: the DPP sums below see all 64 lanes)
   const size_t slot = (size_t)blockIdx.y * max_pts + idx;
-  const int fprev = fprev0 + blockIdx.y, fnext = fprev + 1;
+  const int fprev = fprev0 + blockIdx.y, fnext = SEQS ? aux + (int)blockIdx.y : fprev + 1;
   const float ptx = pts[2 * slot], pty = pts[2 * slot + 1];
 
   int wx[7], wy[7];
@@ -272,11 +275,10 @@ __global__ __launch_bounds__(256) void k_lk_track(const uint8_t* __restrict__ im
 }
 
 // One workgroup: the tracked points with status != 0 in order, then the frame's seeds while the list has room
-__global__ __launch_bounds__(256) void k_lk_compact(const float* __restrict__ trk, const uint8_t* __restrict__ st,
-                                                    const int32_t* __restrict__ n_prev, const float* __restrict__ seeds,
-                                                    const int32_t* __restrict__ n_seed, int max_seeds, int max_pts,
-                                                    float* __restrict__ list, int32_t* __restrict__ n_out, int32_t* __restrict__ dropped) {
-  __shared__ int wsum[4];
+__device__ __forceinline__ void lk_compact_body(int* wsum, const float* __restrict__ trk, const uint8_t* __restrict__ st,
+                                                const int32_t* __restrict__ n_prev, const float* __restrict__ seeds,
+                                                const int32_t* __restrict__ n_seed, int max_seeds, int max_pts,
+                                                float* __restrict__ list, int32_t* __restrict__ n_out, int32_t* __restrict__ dropped) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int n = n_prev ? min(max(*n_prev, 0), max_pts) : 0;
   int base = 0;
@@ -298,6 +300,26 @@ __global__ __launch_bounds__(256) void k_lk_compact(const float* __restrict__ tr
   const int ns = min(max(*n_seed, 0), max_seeds), take = min(ns, max_pts - base);
   for (int j = tid; j < take; j += 256) { list[2 * (base + j)] = seeds[2 * j]; list[2 * (base + j) + 1] = seeds[2 * j + 1]; }
   if (tid == 0) { *n_out = base + take; *dropped = ns - take; }
+}
+__global__ __launch_bounds__(256) void k_lk_compact(const float* __restrict__ trk, const uint8_t* __restrict__ st,
+                                                    const int32_t* __restrict__ n_prev, const float* __restrict__ seeds,
+                                                    const int32_t* __restrict__ n_seed, int max_seeds, int max_pts,
+                                                    float* __restrict__ list, int32_t* __restrict__ n_out, int32_t* __restrict__ dropped) {
+  __shared__ int wsum[4];
+  lk_compact_body(wsum, trk, st, n_prev, seeds, n_seed, max_seeds, max_pts, list, n_out, dropped);
+}
+// The same for many sequences, workgroup q = sequence q: its tracked points at trk + q * 2 max_pts (status at st + q * max_pts), its
+// seeds at seeds + q * 2 max_seeds, its list at list + q * 2 max_pts; the counts are arrays over the sequences (n_prev == nullptr:
+// no sequence has a previous list)
+__global__ __launch_bounds__(256) void k_lk_compact_seqs(const float* __restrict__ trk, const uint8_t* __restrict__ st,
+                                                         const int32_t* __restrict__ n_prev, const float* __restrict__ seeds,
+                                                         const int32_t* __restrict__ n_seed, int max_seeds, int max_pts,
+                                                         float* __restrict__ list, int32_t* __restrict__ n_out,
+                                                         int32_t* __restrict__ dropped) {
+  __shared__ int wsum[4];
+  const size_t q = blockIdx.x;
+  lk_compact_body(wsum, trk + q * 2 * max_pts, st + q * max_pts, n_prev ? n_prev + q : nullptr, seeds + q * 2 * max_seeds,
+                  n_seed + q, max_seeds, max_pts, list + q * 2 * max_pts, n_out + q, dropped + q);
 }
 
 }  // namespace
@@ -446,6 +468,24 @@ void lk_launch_track(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int
 void lk_launch_compact(hipStream_t s, const float* trk, const uint8_t* st, const int32_t* n_prev, const float* seeds, const int32_t* n_seed,
                        int max_seeds, int max_pts, float* list, int32_t* n_out, int32_t* dropped) {
   hipLaunchKernelGGL(k_lk_compact, dim3(1), dim3(256), 0, s, trk, st, n_prev, seeds, n_seed, max_seeds, max_pts, list, n_out, dropped);
+}
+
+// svo_track_multi_step_dev's loop: `nseq` pairs (fprev0 + q, fnext0 + q) of the arena's slots, sequence q's points at
+// pts + q * 2 max_pts with counts[q] entries, results at next + q * 2 max_pts and status + q * max_pts
+void lk_launch_track_seqs(hipStream_t s, LkArena* A, int cn, const uint8_t* img0, int stride0, size_t frame0, int W, int H, int top,
+                          int fprev0, int fnext0, int nseq, const float* pts, const int32_t* counts, int max_pts, float* next,
+                          uint8_t* status) {
+  const LkLevel end = lk_level(W, H, top + 1);
+  const auto kernel = cn == 3 ? k_lk_track<3, true> : k_lk_track<1, true>;
+  hipLaunchKernelGGL(kernel, dim3((max_pts + 3) / 4, nseq), dim3(256), 0, s, img0, stride0,
+                     frame0, A->pyr, cn * end.ioff, A->der, cn * end.doff, W, H, top, fprev0, pts, counts, fnext0, max_pts, next, status,
+                     (float*)nullptr);
+}
+
+void lk_launch_compact_seqs(hipStream_t s, int nseq, const float* trk, const uint8_t* st, const int32_t* n_prev, const float* seeds,
+                            const int32_t* n_seed, int max_seeds, int max_pts, float* list, int32_t* n_out, int32_t* dropped) {
+  hipLaunchKernelGGL(k_lk_compact_seqs, dim3(nseq), dim3(256), 0, s, trk, st, n_prev, seeds, n_seed, max_seeds, max_pts, list, n_out,
+                     dropped);
 }
 
 namespace {

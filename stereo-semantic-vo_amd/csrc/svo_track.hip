@@ -1573,9 +1573,9 @@ __global__ __launch_bounds__(TPF_NT) void k_tp_tail_ord(TrackState* st, TrackWor
 // frame's correspondence list work->edge_kp[0 .. n_edges).  Both parts in keypoint order, the init part first, compacted by a
 // block-wide prefix sum; at frame 0 an inside keypoint appears in both.
 #define DYN_MAX_SEEDS (2 * TRK_MAXKP)
-__global__ __launch_bounds__(TRK_MAXKP) void k_td_seeds(const TrackWork* __restrict__ work, const svo_kp* __restrict__ kp,
-                                                        const int32_t* __restrict__ boxes, const int32_t* __restrict__ nboxes,
-                                                        float* __restrict__ seeds, int32_t* __restrict__ n_seed) {
+__device__ __forceinline__ void td_seeds_body(const TrackWork* __restrict__ work, const svo_kp* __restrict__ kp,
+                                              const int32_t* __restrict__ boxes, const int32_t* __restrict__ nboxes,
+                                              float* __restrict__ seeds, int32_t* __restrict__ n_seed) {
   __shared__ alignas(16) int sm[16];
   __shared__ int sbox[SVO_MAX_BOXES * 4];
   __shared__ uint8_t has_mp[TRK_MAXKP];
@@ -1604,6 +1604,20 @@ __global__ __launch_bounds__(TRK_MAXKP) void k_td_seeds(const TrackWork* __restr
   if (s_init) { seeds[2 * o_init] = x; seeds[2 * o_init + 1] = y; }
   if (s_create) { seeds[2 * o_create] = x; seeds[2 * o_create + 1] = y; }   // (o_create < n_init + n_create <= 2 TRK_MAXKP)
   if (tid == 0) *n_seed = n_init + n_create;
+}
+__global__ __launch_bounds__(TRK_MAXKP) void k_td_seeds(const TrackWork* __restrict__ work, const svo_kp* __restrict__ kp,
+                                                        const int32_t* __restrict__ boxes, const int32_t* __restrict__ nboxes,
+                                                        float* __restrict__ seeds, int32_t* __restrict__ n_seed) {
+  td_seeds_body(work, kp, boxes, nboxes, seeds, n_seed);
+}
+// Many sequences (svo_track_multi_step_dev): workgroup q = sequence q, behind the step's k_ti_resolve - its work record, keypoints
+// and boxes where the many-sequence kernels find them (q records, q * kstride keypoints, q * bstride boxes further on), seed list
+// q and seed count q.  A sequence without boxes (nboxes[q] == 0) writes count 0.
+__global__ __launch_bounds__(TRK_MAXKP) void k_td_seeds_seqs(const TrackWork* __restrict__ work, const svo_kp* __restrict__ kp, int kstride,
+                                                             const int32_t* __restrict__ boxes, const int32_t* __restrict__ nboxes,
+                                                             int bstride, float* __restrict__ seeds, int32_t* __restrict__ n_seed) {
+  const size_t q = blockIdx.x;
+  td_seeds_body(work + q, kp + q * kstride, boxes + q * bstride * 4, nboxes + q, seeds + q * 2 * DYN_MAX_SEEDS, n_seed + q);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1785,12 +1799,21 @@ static int track_resources(svo_ctx* ctx, int frames, int nseq) {
 // ordered by that one stream; the pose stream joins it once, at the end of a call (what svo_sync and the calls' result copies
 // wait for then covers the lists).  The left images live in an arena of this state: a ring of slots in which slot `pos` is the
 // previous frame - a later call never reads an earlier call's image buffers.
+enum DynMode { DYN_NONE = 0, DYN_SINGLE, DYN_MULTI };   // which reset adopted the loop in force: svo_track_reset / svo_track_multi_reset
 struct DynOut { float* lists = nullptr; int32_t *counts = nullptr, *dropped = nullptr; };
 struct DynState {
   svo_dyn_params next{};        // svo_track_dynamic's: adopted by the next reset
   svo_dyn_params p{};           // in force
   bool active = false;
+  DynMode mode = DYN_NONE;
   int cn = 1, top = 0, cap = 0, slots = 0, pos = 0;   // cap: frames per call; slots of the arena, `pos` holds the previous left image
+  // many sequences (DYN_MULTI, see dyn_multi_step): cap = n_seq, the arena's 2 n_seq slots and the 2 n_seq lists are two halves that
+  // alternate by step - `half` holds the previous step's left images and lists; d_ints: counts of half 0, counts of half 1, dropped,
+  // seed counts, n_seq zeros (the seed counts of a step that cannot seed)
+  int half = 0;
+  bool in_step = false;
+  hipEvent_t ev_img = nullptr;  // behind a step's copy of its left images into the arena (index stream)
+  bool ev_img_valid = false;
   int built_until = 0;          // frames of the tail call being enqueued whose images, pyramids and derivatives are in the arena (slots pos + 1 ..)
   void* arena = nullptr;        // LkArena of its own (the context's serves svo_lk_*)
   float *d_lists = nullptr, *d_seeds = nullptr;   // (cap + 1) lists, list 0 = the last one of the call before; cap seed lists
@@ -1809,6 +1832,11 @@ struct DynState {
   int32_t* counts() const { return d_ints; }
   int32_t* dropped() const { return d_ints + cap + 1; }
   int32_t* nseed() const { return d_ints + 2 * (cap + 1); }
+  // DYN_MULTI's layout of d_ints (5 cap entries): counts of list half h, dropped, seed counts, zeros
+  int32_t* m_counts(int h) const { return d_ints + (size_t)h * cap; }
+  int32_t* m_dropped() const { return d_ints + 2 * (size_t)cap; }
+  int32_t* m_nseed() const { return d_ints + 3 * (size_t)cap; }
+  int32_t* m_zeros() const { return d_ints + 4 * (size_t)cap; }
 };
 static DynState* dyn_of(svo_ctx* ctx) { return reinterpret_cast<DynState*>(ctx->dyn); }
 static bool dyn_active(const svo_ctx* ctx) { return ctx->dyn && reinterpret_cast<const DynState*>(ctx->dyn)->active; }
@@ -1830,6 +1858,7 @@ static void dyn_release(svo_ctx* ctx) {
   if (!D) return;
   dyn_free_buffers(D);
   if (D->ev_lk) hipEventDestroy(D->ev_lk);
+  if (D->ev_img) hipEventDestroy(D->ev_img);
   for (hipEvent_t e : D->ev_out) if (e) hipEventDestroy(e);
   delete D;
   ctx->dyn = nullptr;
@@ -1850,29 +1879,36 @@ int svo_track_dyn_flush(svo_ctx* ctx) {
   for (int q = 0; q < 2; ++q) { const int rc = dyn_flush_set(ctx, D, q); if (rc) return rc; }
   return SVO_OK;
 }
-// svo_track_reset / svo_track_multi_reset, every stream idle: svo_track_dynamic's parameters come into force, the list is empty
-static int dyn_adopt(svo_ctx* ctx) {
+// svo_track_reset (multi_nseq = 0) / svo_track_multi_reset (its n_seq), every stream idle: svo_track_dynamic's parameters come into
+// force for that kind of reset, the lists are empty.  Everything is sized here, once: one sequence - max_batch frames per call and
+// a ring of slots; many - the two halves of n_seq slots and lists
+static int dyn_adopt(svo_ctx* ctx, int multi_nseq) {
   DynState* D = dyn_of(ctx);
   if (!D) return SVO_OK;
   D->attached = false; D->in_call = false; D->ev_lk_valid = false; D->pos = 0; D->hparity = 0;
+  D->in_step = false; D->ev_img_valid = false; D->half = 0;
   if (!D->next.enable) {
     if (D->active) dyn_free_buffers(D);
-    D->active = false; D->p = D->next;
+    D->active = false; D->mode = DYN_NONE; D->p = D->next;
     return SVO_OK;
   }
   const int W = ctx->g.W, H = ctx->g.H, cn = D->next.colour ? 3 : 1, top = lk_top_level(W, H, D->next.lk.maxLevel);
-  const int cap = std::max(ctx->max_batch, 1), slots = std::min(cap, 64) + 1;
-  if (!D->active || cn != D->cn || top != D->top || D->next.max_pts != D->p.max_pts || cap != D->cap) {
+  const DynMode mode = multi_nseq > 0 ? DYN_MULTI : DYN_SINGLE;
+  const bool many = mode == DYN_MULTI;
+  const int cap = many ? multi_nseq : std::max(ctx->max_batch, 1), slots = many ? 2 * cap : std::min(cap, 64) + 1;
+  const size_t n_ints = many ? 5 * (size_t)cap : 3 * (size_t)(cap + 1);
+  if (!D->active || mode != D->mode || cn != D->cn || top != D->top || D->next.max_pts != D->p.max_pts || cap != D->cap) {
     dyn_free_buffers(D);
-    D->active = false;
+    D->active = false; D->mode = DYN_NONE;
     LkArena* A = nullptr;
-    int rc = lk_reserve_in(ctx, &D->arena, ctx->stream, W, H, cn, top, slots, (size_t)D->next.max_pts, slots, &A);
+    const size_t mp = (size_t)D->next.max_pts;
+    int rc = lk_reserve_in(ctx, &D->arena, ctx->stream, W, H, cn, top, slots, many ? mp * cap : mp, slots, &A);
     if (rc) { dyn_free_buffers(D); return rc; }
     A->last = nullptr;   // (sized once: nothing ever grows it while work is in flight)
-    const size_t mp = (size_t)D->next.max_pts;
-    if (hipMalloc(reinterpret_cast<void**>(&D->d_lists), (size_t)(cap + 1) * 2 * mp * sizeof(float)) != hipSuccess ||
+    const size_t n_lists = many ? 2 * (size_t)cap : (size_t)(cap + 1);
+    if (hipMalloc(reinterpret_cast<void**>(&D->d_lists), n_lists * 2 * mp * sizeof(float)) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&D->d_seeds), (size_t)cap * 2 * DYN_MAX_SEEDS * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&D->d_ints), 3 * (size_t)(cap + 1) * sizeof(int32_t)) != hipSuccess) {
+        hipMalloc(reinterpret_cast<void**>(&D->d_ints), n_ints * sizeof(int32_t)) != hipSuccess) {
       (void)hipGetLastError();
       dyn_free_buffers(D);
       ctx->last_error = "svo_track_dynamic: device allocation failed";
@@ -1880,12 +1916,13 @@ static int dyn_adopt(svo_ctx* ctx) {
     }
     D->cn = cn; D->top = top; D->cap = cap; D->slots = slots;
     if (!D->ev_lk) SVO_HIP(ctx, hipEventCreateWithFlags(&D->ev_lk, hipEventDisableTiming));
+    if (!D->ev_img) SVO_HIP(ctx, hipEventCreateWithFlags(&D->ev_img, hipEventDisableTiming));
     for (int q = 0; q < 2; ++q)
       if (!D->ev_out[q]) SVO_HIP(ctx, hipEventCreateWithFlags(&D->ev_out[q], hipEventDisableTiming));
   }
   D->p = D->next;
-  SVO_HIP(ctx, hipMemsetAsync(D->d_ints, 0, 3 * (size_t)(D->cap + 1) * sizeof(int32_t), ctx->stream));   // (the caller waits for the stream)
-  D->active = true;
+  SVO_HIP(ctx, hipMemsetAsync(D->d_ints, 0, n_ints * sizeof(int32_t), ctx->stream));   // (the caller waits for the stream)
+  D->active = true; D->mode = mode;
   return SVO_OK;
 }
 // A tracker entry that runs the loop starts a call: its left images (cn channels, consecutive images H * stride bytes apart), and
@@ -1995,6 +2032,53 @@ int svo_track_dyn_refuse(svo_ctx* ctx, const char* who) {
   ctx->last_error = std::string(who) + ": the dynamic-keypoint loop is enabled on this context (svo_track_dynamic); this entry does not run it";
   return SVO_E_INVALID;
 }
+// The loop's state belongs to the kind of reset that adopted it (svo_track_reset and svo_track_multi_reset(1) are otherwise the
+// same call): the entries of the other kind refuse in the same way
+int svo_track_dyn_refuse_single(svo_ctx* ctx, const char* who) {
+  if (!dyn_active(ctx) || dyn_of(ctx)->mode != DYN_MULTI) return SVO_OK;
+  ctx->last_error = std::string(who) + ": the dynamic-keypoint loop on this context was adopted by svo_track_multi_reset; only the many-sequence entries run it";
+  return SVO_E_INVALID;
+}
+static int dyn_refuse_multi(svo_ctx* ctx, const char* who) {
+  if (!dyn_active(ctx) || dyn_of(ctx)->mode == DYN_MULTI) return SVO_OK;
+  return svo_track_dyn_refuse(ctx, who);   // (adopted by svo_track_reset: today's refusal, today's words)
+}
+// One step of the many-sequence loop, on the index stream `s` behind the step's ev_frame record (the pose chain's wait is never
+// behind LK work): ONE 2-D copy of the n_seq left images into the arena half that is not the previous step's, one lk_build over
+// them (their derivatives serve the NEXT step, when they are the previous images), one track launch over the n_seq pairs
+// (previous half's slot q, this half's slot q) - none at id 0 -, one compact launch of n_seq workgroups.  Everything of the loop
+// is ordered by this one stream, so step t + 1's copy into the half step t's track launch read as "previous" cannot overtake it,
+// with or without "multi_pipeline".  `seeded`: the step's k_td_seeds_seqs ran (behind its k_ti_resolve).
+static int dyn_multi_step(svo_ctx* ctx, DynState* D, hipStream_t s, int id, bool seeded) {
+  LkArena* A = static_cast<LkArena*>(D->arena);
+  const int W = ctx->g.W, H = ctx->g.H, cn = D->cn, mp = D->p.max_pts, nseq = D->cap;
+  const size_t row = (size_t)cn * W, img = row * H;
+  size_t pyr_px, der_px;
+  lk_slot_px(W, H, D->top, &pyr_px, &der_px);
+  const int prev = D->half, cur = prev ^ 1;
+  const size_t first = (size_t)cur * nseq;
+  SVO_HIP(ctx, hipMemcpy2DAsync(A->img + first * img, row, D->src, D->src_stride, row, (size_t)H * nseq, hipMemcpyDeviceToDevice, s));
+  SVO_HIP(ctx, hipEventRecord(D->ev_img, s));   // (a colour step's gray staging may be written anew from here on)
+  D->ev_img_valid = true;
+  LkArena V = *A;   // this half's slots
+  V.pyr += first * cn * pyr_px; V.der += first * cn * der_px;
+  lk_build(s, &V, cn, A->img + first * img, (int)row, img, W, H, D->top, nseq, 0, nseq);
+  int32_t *n_prev = D->m_counts(prev), *n_cur = D->m_counts(cur), *dropped = D->m_dropped(), *n_seed = D->m_nseed(), *zeros = D->m_zeros();
+  float *l_prev = D->d_lists + (size_t)prev * nseq * 2 * mp, *l_cur = D->d_lists + (size_t)cur * nseq * 2 * mp;
+  if (id > 0)
+    lk_launch_track_seqs(s, A, cn, A->img, (int)row, img, W, H, D->top, prev * nseq, cur * nseq, nseq, l_prev, n_prev, mp, A->next, A->status);
+  lk_launch_compact_seqs(s, nseq, A->next, A->status, id > 0 ? n_prev : nullptr, D->d_seeds, seeded ? n_seed : zeros, DYN_MAX_SEEDS, mp, l_cur,
+                         n_cur, dropped);
+  if (D->cur_on) {   // svo_track_dynamic_out: sequence q's list at lists + q * 2 max_pts, counts[q], dropped[q]
+    SVO_HIP(ctx, hipMemcpyAsync(D->cur.lists, l_cur, (size_t)nseq * 2 * mp * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SVO_HIP(ctx, hipMemcpyAsync(D->cur.counts, n_cur, (size_t)nseq * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (D->cur.dropped) SVO_HIP(ctx, hipMemcpyAsync(D->cur.dropped, dropped, (size_t)nseq * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  }
+  D->half = cur;
+  SVO_HIP(ctx, hipEventRecord(D->ev_lk, s));   // (the pose stream joins behind the step's pose kernels: tail_enqueue)
+  D->ev_lk_valid = true;
+  return SVO_OK;
+}
 
 // The ordered tail for front-end results that are already in HBM (`kstride` keypoints per frame slot):
 //   nseq == 1: `frames` consecutive frames of the one sequence, record f into d_res[f];
@@ -2035,6 +2119,8 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
   // launch; the tail is therefore SAMPLED: every 32nd frame of a call is timed (an event pair around a kernel also holds the chain up by ~5 us), the others run untimed
   const bool prof = ctx->profiling;
   DynState* D = dyn_active(ctx) && dyn_of(ctx)->in_call && nseq == 1 ? dyn_of(ctx) : nullptr;   // the dynamic-keypoint loop runs with this call
+  DynState* DM = dyn_active(ctx) && dyn_of(ctx)->in_step && frames == 1 ? dyn_of(ctx) : nullptr;   // ... with this step of many sequences
+  const bool dm_seeds = DM && bx && dyn_can_seed(DM, ctx->track_frame);
   // frame f's front-end results sit in row f of the arrays unless the caller says otherwise (svo_track_sharded_dev)
   auto row = [&](int f) { return (size_t)(row_of_frame ? row_of_frame[f] : f); };
   // gated frames of ONE sequence whose front-end rows are consecutive: brute-force matches + F for groups of frames in one
@@ -2095,6 +2181,11 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
       SvoTimer t(ctx, "k_td_seeds", s1);
       hipLaunchKernelGGL(k_td_seeds, dim3(1), dim3(TRK_MAXKP), 0, s1, work + f, kpf, bxf, nbf, D->d_seeds + (size_t)f * 2 * DYN_MAX_SEEDS,
                          D->nseed() + f);
+    }
+    if (dm_seeds) {
+      SvoTimer t(ctx, "k_td_seeds_seqs", s1);
+      hipLaunchKernelGGL(k_td_seeds_seqs, dim3(ny), dim3(TRK_MAXKP), 0, s1, work + f, kpf, kstride, bxf, nbf, bstride, DM->d_seeds,
+                         DM->m_nseed());
     }
   };
   // one sequence: the pose kernels find out by themselves when their frame's record is there (tp_wait_work) - no stream event
@@ -2184,6 +2275,10 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
         ctx->profiling = false;
         if ((rc = dyn_enqueue_group(ctx, D, s1, cur0, cur1, ctx->track_frame, bx != nullptr, fe_events, frames))) { ctx->profiling = prof; return rc; }
       }
+      if (DM) {
+        ctx->profiling = false;
+        if ((rc = dyn_multi_step(ctx, DM, s1, ctx->track_frame, dm_seeds))) { ctx->profiling = prof; return rc; }
+      }
       g0 = cur1;
       ++ngroup;
       if (ngroup >= 2) gsize = std::min(2 * gsize, ctx->opt_track_group > 0 ? ctx->opt_track_group : 1);
@@ -2196,6 +2291,9 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
   }
   ctx->profiling = prof;
   if (D && (rc = dyn_finish(ctx, D, s1, s0, frames))) return rc;
+  // many sequences: the pose stream joins the loop here, BEHIND the step's pose kernels, which therefore run beside the step's LK
+  // work; what svo_sync, ms_tail_done and work ordered behind the context's stream wait for covers the lists and the image copy
+  if (DM) SVO_HIP(ctx, hipStreamWaitEvent(s0, DM->ev_lk, 0));
   if (bx && ctx->det_ready) {   // a detector feeds this context: its next call may overwrite these boxes once both chains read them
     for (int k = 0; k < 2; ++k)
       if (!ctx->det_read[k]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->det_read[k], hipEventDisableTiming));
@@ -2208,7 +2306,7 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
 }
 
 // (Re)allocate `nseq` tracker states and reset them: pose I, empty map, frame counter 0.
-static int track_reset_n(svo_ctx* ctx, const svo_camera* cam, int nseq) {
+static int track_reset_n(svo_ctx* ctx, const svo_camera* cam, int nseq, bool multi) {
   if (!ctx || !cam || nseq < 1) return SVO_E_INVALID;
   if (ctx->max_kp > TRK_MAXKP) return SVO_E_CAPACITY;
   hipSetDevice(ctx->device);
@@ -2236,7 +2334,7 @@ static int track_reset_n(svo_ctx* ctx, const svo_camera* cam, int nseq) {
     SVO_HIP(ctx, hipMemcpyAsync(st->lastTcw, I, sizeof I, hipMemcpyHostToDevice, ctx->stream));
     SVO_HIP(ctx, hipMemcpyAsync(&st->cam, cam, sizeof *cam, hipMemcpyHostToDevice, ctx->stream));
   }
-  { const int rcd = dyn_adopt(ctx); if (rcd) return rcd; }   // (svo_track_dynamic's parameters; the list is empty again)
+  { const int rcd = dyn_adopt(ctx, multi ? nseq : 0); if (rcd) return rcd; }   // (svo_track_dynamic's parameters; the lists are empty again)
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->cam = *cam;
   ctx->track_frame = 0;
@@ -2244,12 +2342,12 @@ static int track_reset_n(svo_ctx* ctx, const svo_camera* cam, int nseq) {
   return SVO_OK;
 }
 
-extern "C" int svo_track_reset(svo_ctx* ctx, const svo_camera* cam) { return track_reset_n(ctx, cam, 1); }
+extern "C" int svo_track_reset(svo_ctx* ctx, const svo_camera* cam) { return track_reset_n(ctx, cam, 1, false); }
 
 extern "C" int svo_track_multi_reset(svo_ctx* ctx, int n_seq, const svo_camera* cam) {
   if (!ctx) return SVO_E_INVALID;
   if (n_seq < 1 || n_seq > ctx->max_batch) return SVO_E_CAPACITY;
-  return track_reset_n(ctx, cam, n_seq);
+  return track_reset_n(ctx, cam, n_seq, true);
 }
 
 // Depth source 1 (svo_set_option "depth_source"): the reference's live data flow - a dense disparity map
@@ -2294,6 +2392,7 @@ extern "C" int svo_track_frame(svo_ctx* ctx, const uint8_t* grayL, int strideL,
       n_boxes > SVO_MAX_BOXES || (n_boxes > 0 && !boxes))
     return SVO_E_INVALID;
   if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset first
+  { const int rcd = svo_track_dyn_refuse_single(ctx, "svo_track_frame"); if (rcd) return rcd; }
   hipSetDevice(ctx->device);
   { const int rcq = svo_track_quiesce(ctx); if (rcq) return rcq; }
   int rc = svo_upload_image(ctx, grayL, strideL, 0);
@@ -2409,14 +2508,57 @@ extern "C" int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, co
                                         int stride, int n_seq, const svo_boxes_dev* boxes, svo_track_result* d_results) {
   if (!ctx || !d_grayL || !d_grayR || !d_results || stride < ctx->g.W) return SVO_E_INVALID;
   if (!ctx->d_track || n_seq != ctx->n_seq) return SVO_E_INVALID;   // svo_track_multi_reset(n_seq) first
-  { const int rcd = svo_track_dyn_refuse(ctx, "svo_track_multi_step_dev"); if (rcd) return rcd; }
+  { const int rcc = svo_track_multi_step_check(ctx, "svo_track_multi_step_dev", false); if (rcc) return rcc; }
+  return svo_track_multi_step_fed(ctx, d_grayL, d_grayR, stride, n_seq, boxes, d_results, nullptr);
+}
+
+static int multi_step_enqueue(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int n_seq,
+                              const svo_boxes_dev* boxes, svo_track_result* d_results, const SvoBgrSrc* bgr);
+// what both many-sequence entries refuse before anything is allocated or enqueued
+int svo_track_multi_step_check(svo_ctx* ctx, const char* who, bool has_bgr) {
+  { const int rcd = dyn_refuse_multi(ctx, who); if (rcd) return rcd; }
   if (ctx->opt_depth_source != 0) {   // the many-sequence mode has the sparse matcher only
-    ctx->last_error = "svo_track_multi_step_dev: depth_source must be 0";
+    ctx->last_error = std::string(who) + ": depth_source must be 0";
     return SVO_E_INVALID;
   }
+  if (dyn_active(ctx) && dyn_of(ctx)->p.colour && !has_bgr) return dyn_colour_needs_bgr(ctx, who);
+  return SVO_OK;
+}
+// The step of the two many-sequence entries, which have checked their arguments and called svo_track_multi_step_check; with the
+// loop in force (adopted by svo_track_multi_reset) its images are the gray the front end reads, or - colour = 1 - the colour left frames
+int svo_track_multi_step_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int n_seq,
+                             const svo_boxes_dev* boxes, svo_track_result* d_results, const SvoBgrSrc* bgr) {
+  DynState* D = dyn_active(ctx) ? dyn_of(ctx) : nullptr;
+  if (D) {
+    D->in_step = true;
+    D->src = D->p.colour ? bgr->L : d_grayL; D->src_stride = D->p.colour ? bgr->stride : stride;
+    D->cur = D->out; D->cur_on = D->attached;   // (one-shot)
+    D->attached = false; D->out = DynOut{};
+  }
+  const int rc = multi_step_enqueue(ctx, d_grayL, d_grayR, stride, n_seq, boxes, d_results, bgr);
+  if (D) { D->in_step = false; D->cur_on = false; D->cur = DynOut{}; D->src = nullptr; }
+  return rc;
+}
+static int multi_step_enqueue(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int n_seq,
+                              const svo_boxes_dev* boxes, svo_track_result* d_results, const SvoBgrSrc* bgr) {
   hipSetDevice(ctx->device);
   { const int rcs = svo_shard_quiesce(ctx); if (rcs) return rcs; }   // (a sharded call of this context may still be in flight: staging sets, work records)
   int rc;
+  // colour entry: the gray of the 2 n_seq images, on the stream the front end runs on, once the readers of the staging are done
+  // with it - the previous colour call's front end, and the copy the loop's previous step took of it (colour = 0)
+  auto bgr_convert = [&](hipStream_t s) -> int {
+    if (!bgr || !bgr->convert) return SVO_OK;
+    for (int k = 0; k < bgr->n_wait; ++k) SVO_HIP(ctx, hipStreamWaitEvent(s, bgr->wait[k], 0));
+    if (dyn_active(ctx) && !dyn_of(ctx)->p.colour && dyn_of(ctx)->ev_img_valid) SVO_HIP(ctx, hipStreamWaitEvent(s, dyn_of(ctx)->ev_img, 0));
+    const size_t gray_img = (size_t)ctx->g.H * stride, bgr_img = (size_t)ctx->g.H * bgr->stride;
+    svo_launch_bgr2gray(s, bgr->L, bgr->stride, bgr_img, const_cast<uint8_t*>(d_grayL), stride, gray_img, ctx->g.W, ctx->g.H, n_seq);
+    svo_launch_bgr2gray(s, bgr->R, bgr->stride, bgr_img, const_cast<uint8_t*>(d_grayR), stride, gray_img, ctx->g.W, ctx->g.H, n_seq);
+    return SVO_OK;
+  };
+  auto bgr_done = [&](hipStream_t s) -> int {
+    if (bgr && bgr->convert && bgr->done) SVO_HIP(ctx, hipEventRecord(bgr->done, s));
+    return SVO_OK;
+  };
   if (ctx->opt_multi_pipeline) {
     // Pipelined steps (svo_set_option("multi_pipeline", 1)): the front end is stateless, so step t + 1's may run while
     // step t's tail is still busy - on its own stream, into the other of two private output sets.  Contract: between
@@ -2448,8 +2590,10 @@ extern "C" int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, co
       SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_fe, ctx->ev_frontend, 0));
     }
     const SvoFeBufs fb = svo_fe_own(ctx).with_outputs(ctx->ms_out[p]);   // (right x and SAD: the context's own arrays)
+    if ((rc = bgr_convert(ctx->stream_fe))) return rc;
     rc = svo_launch_orb(ctx, ctx->stream_fe, fb, d_grayL, d_grayR, stride, n_seq, 2 * n_seq);
     if (rc == SVO_OK) rc = svo_launch_stereo(ctx, ctx->stream_fe, fb, d_grayL, d_grayR, stride, n_seq, &ctx->cam);
+    if (rc == SVO_OK) rc = bgr_done(ctx->stream_fe);
     if (rc) return rc;
     SVO_HIP(ctx, hipEventRecord(ctx->ms_fe_done[p], ctx->stream_fe));
     SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ms_fe_done[p], 0));
@@ -2461,9 +2605,11 @@ extern "C" int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, co
     return SVO_OK;
   }
   const SvoFeBufs fb = svo_fe_own(ctx);
+  if ((rc = bgr_convert(ctx->stream))) return rc;
   rc = svo_launch_orb(ctx, ctx->stream, fb, d_grayL, d_grayR, stride, n_seq, 2 * n_seq);
   if (rc) return rc;
   if ((rc = svo_launch_stereo(ctx, ctx->stream, fb, d_grayL, d_grayR, stride, n_seq, &ctx->cam))) return rc;
+  if ((rc = bgr_done(ctx->stream))) return rc;
   if ((rc = tail_enqueue(ctx, ctx->d_kp, ctx->d_desc, ctx->d_nkp, ctx->d_depth, ctx->max_kp, 1, n_seq, d_results, boxes))) return rc;
   ctx->track_frame++;
   return SVO_OK;
@@ -2714,7 +2860,7 @@ extern "C" int svo_track_dynamic(svo_ctx* ctx, const svo_dyn_params* p) {
 extern "C" int svo_track_dynamic_out(svo_ctx* ctx, float* lists, int32_t* counts, int32_t* dropped) {
   if (!ctx || !lists || !counts) return SVO_E_INVALID;
   if (!dyn_active(ctx)) {
-    ctx->last_error = "svo_track_dynamic_out: the dynamic-keypoint loop is not enabled (svo_track_dynamic, then svo_track_reset)";
+    ctx->last_error = "svo_track_dynamic_out: the dynamic-keypoint loop is not enabled (svo_track_dynamic, then svo_track_reset or svo_track_multi_reset)";
     return SVO_E_INVALID;
   }
   DynState* D = dyn_of(ctx);
@@ -2725,6 +2871,7 @@ extern "C" int svo_track_dynamic_out(svo_ctx* ctx, float* lists, int32_t* counts
 
 extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR,
                                    int stride, int B, const svo_boxes_dev* boxes, svo_track_result* d_results) {
+  if (ctx) { const int rcd = svo_track_dyn_refuse_single(ctx, "svo_track_batch_dev"); if (rcd) return rcd; }
   return svo_track_batch_fed(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, nullptr);
 }
 

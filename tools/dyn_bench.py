@@ -8,7 +8,12 @@
            (restated on the host from the front end's keypoints and the run's debug records; its lists must equal the run's)
   host     the frame-by-frame path: svo_track_frame + svo_lk_track host to host, erase and append on the host (32 frames, once)
 Medians of --reps runs after one warm-up; prints one JSON line.  The yardstick: on <= off + chain (the parent's way to the same
-output on resident frames), margin = the larger of the two components' min..max spreads."""
+output on resident frames), margin = the larger of the two components' min..max spreads.
+
+--sequences S [--steps T] [--bgr] [--pipeline 0|1]: the many-sequence mode instead - S staggered sequences (sequence q walks
+frames q, q + 1, ... with that frame's moving boxes) advanced by svo_track_multi_step_dev (--bgr: svo_track_multi_step_bgr_dev),
+T steps per run; per STEP the median time with the loop off, on (lists left in HBM, attached at every step), and off again, in
+one session; the records with the loop on must equal those with it off."""
 import argparse
 import importlib
 import json
@@ -23,6 +28,75 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+def many(args):
+    import torch
+    import bench
+    import svo_loader
+    pkg = svo_loader.load()
+    synth = importlib.import_module("stereo_semantic_vo_amd.synth")
+    dev = torch.device("cuda", 0)
+    S, T, W, H, P, mp = args.sequences, args.steps, bench.W, bench.H, bench.PITCH, args.max_pts
+    n = S + T
+    gL, gR, _ = bench.render_frames(synth, n, dev, synth.BASE_SEED)
+    cam = pkg.Camera(**pkg.KITTI_00_02)
+    _, (tb, tn) = bench.boxes_hbm(pkg, n, dev)   # frame k's boxes: sequence q's at step t are frame t + q's
+    if args.bgr:   # B = R = the gray, G a little brighter: rows 3 W bytes apart
+        def colour(g):
+            c = torch.stack([g[:, :, :W], torch.clamp(g[:, :, :W].to(torch.int32) + 9, 0, 255).to(torch.uint8), g[:, :, :W]], dim=3)
+            return c.reshape(n, H, 3 * W).contiguous()
+        dL, dR, pitch = colour(gL), colour(gR), 3 * W
+    else:
+        dL, dR, pitch = gL, gR, P
+    rec = pkg.TRACK_DTYPE.itemsize
+    res = torch.zeros((T, S, rec), dtype=torch.uint8, device=dev)
+    lists = torch.zeros((T, S, mp, 2), dtype=torch.float32, device=dev)
+    counts = torch.zeros((T, S), dtype=torch.int32, device=dev); dropped = torch.zeros((T, S), dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    svo = pkg.Svo(W, H, max_batch=S)
+    svo.set_option("multi_pipeline", args.pipeline)
+    entry = svo.track_multi_step_bgr_dev if args.bgr else svo.track_multi_step_dev
+
+    def run(on):
+        p = pkg.dyn_default_params()
+        p.enable, p.colour, p.seed_frames, p.max_pts = int(on), int(args.bgr), args.seed_frames, mp
+        svo.track_dynamic(p)
+        times = []
+        for r in range(args.reps + 1):
+            svo.track_multi_reset(S, cam)
+            svo.sync()
+            t0 = time.perf_counter()
+            for t in range(T):
+                if on:
+                    svo.track_dynamic_out(lists[t].data_ptr(), counts[t].data_ptr(), dropped[t].data_ptr())
+                entry(dL.data_ptr() + t * H * pitch, dR.data_ptr() + t * H * pitch, pitch, S, res[t].data_ptr(),
+                      boxes=pkg.boxes_dev(tb.data_ptr() + t * 2 * 16, tn.data_ptr() + t * 4, 2))
+            svo.sync()
+            times.append((time.perf_counter() - t0) * 1e6 / T)
+        return times[1:], res.cpu().numpy().tobytes()
+
+    t_off, rec_off = run(False)
+    t_on, rec_on = run(True)
+    c, d = counts.cpu().numpy(), dropped.cpu().numpy()
+    t_off2, _ = run(False)   # (off once more, after on: drift of the session)
+    svo.close()
+    med = lambda v: float(np.median(v))
+    spread = lambda v: float(max(v) - min(v))
+    off, on = med(t_off), med(t_on)
+    out = {
+        "tool": "dyn_bench", "mode": "many sequences", "sequences": S, "steps": T, "reps": args.reps, "bgr": bool(args.bgr),
+        "multi_pipeline": args.pipeline, "seed_frames": args.seed_frames, "max_pts": mp,
+        "us_per_step": {"off": off, "on": on, "off_again": med(t_off2)},
+        "spread_us": {"off": spread(t_off), "on": spread(t_on), "off_again": spread(t_off2)},
+        "us_per_frame": {"off": off / S, "on": on / S},
+        "frames_per_s": {"off": 1e6 * S / off, "on": 1e6 * S / on},
+        "ratio_on_off": on / off,
+        "mean_list_length": float(c.mean()), "last_step_mean_list_length": float(c[-1].mean()), "seeds_dropped": int(d.sum()),
+        "records_identical_on_off": rec_on == rec_off,
+    }
+    print(json.dumps(out))
+    return 0 if rec_on == rec_off else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=256)
@@ -31,7 +105,12 @@ def main():
     ap.add_argument("--seed-frames", type=int, default=2)
     ap.add_argument("--max-pts", type=int, default=512)
     ap.add_argument("--host-frames", type=int, default=32)
+    ap.add_argument("--sequences", type=int, default=0, help="many-sequence mode: S sequences advanced together")
+    ap.add_argument("--steps", type=int, default=48)
+    ap.add_argument("--pipeline", type=int, default=1, help="many-sequence mode: the multi_pipeline option")
     args = ap.parse_args()
+    if args.sequences > 0:
+        return many(args)
     import torch
     import bench
     import dyn_ref
