@@ -413,6 +413,11 @@ int svo_pnp_ransac(svo_ctx* ctx, const double* Xw, const double* obs, int n, con
 int svo_debug_epnp5(svo_ctx* ctx, const double Xw5[15], const double uv5[10], const double K[4], double R[9],
                     double t[3], double rep_err[3]);
 
+/* Parity probe: epnp::gauss_newton (five steps, each one epnp::qr_solve on the 6 x 4 system) of that solve alone, as one
+ * wave runs it - the three beta candidates side by side.  L 6 x 10 row-major, rho[6], betas_in / betas_out 3 x 4. */
+int svo_debug_epnp_gn(svo_ctx* ctx, const double L[60], const double rho[6], const double betas_in[12],
+                      double betas_out[12]);
+
 /* ---- a-5: Optimizer::PoseOptimization (src/Optimizer.cc:15-86) -------------- */
 /* Pose-only Levenberg-Marquardt exactly as g2o runs it for this graph: one SE3
  * vertex, n unary EdgeSE3ProjectXYZOnlyPose edges, information I2, Huber

@@ -47,7 +47,7 @@ ABI_SYMBOLS = [
     "svo_debug_fast_corners", "svo_stereo_frame", "svo_stereo_frame_ex", "svo_disp2depth",
     "svo_unproject", "svo_descriptor_distance", "svo_hamming_argmin", "svo_match_greedy",
     "svo_match_greedy_gated",
-    "svo_bf_match", "svo_pnp_ransac", "svo_debug_epnp5", "svo_pose_opt", "svo_track_reset", "svo_track_frame",
+    "svo_bf_match", "svo_pnp_ransac", "svo_debug_epnp5", "svo_debug_epnp_gn", "svo_pose_opt", "svo_track_reset", "svo_track_frame",
     "svo_debug_track_matches", "svo_debug_track_gate", "svo_debug_track_pnp", "svo_debug_track_frames", "svo_fundamental_8point",
     "svo_frontend_batch_dev", "svo_track_batch_dev", "svo_profile_enable", "svo_profile_reset",
     "svo_profile_get",
@@ -378,6 +378,13 @@ class Svo:
         K = np.ascontiguousarray(K, np.float64); R = np.zeros(9); t = np.zeros(3); rep = np.zeros(3)
         self._chk(self.lib.svo_debug_epnp5(self.h, _p(Xw5), _p(uv5), _p(K), _p(R), _p(t), _p(rep)))
         return R.reshape(3, 3), t, rep
+
+    def debug_epnp_gn(self, L, rho, betas):
+        """epnp::gauss_newton of the order-preserving solver alone, one wave: betas 3 x 4 (the three candidates) -> 3 x 4."""
+        L = np.ascontiguousarray(L, np.float64).reshape(60); rho = np.ascontiguousarray(rho, np.float64).reshape(6)
+        betas = np.ascontiguousarray(betas, np.float64).reshape(12); out = np.zeros(12)
+        self._chk(self.lib.svo_debug_epnp_gn(self.h, _p(L), _p(rho), _p(betas), _p(out)))
+        return out.reshape(3, 4)
 
     # ---- Optimizer::PoseOptimization ------------------------------------------------------
     def pose_opt(self, Xw, obs, K, T):

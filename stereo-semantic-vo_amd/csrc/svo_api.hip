@@ -917,6 +917,20 @@ extern "C" int svo_debug_epnp5(svo_ctx* ctx, const double Xw5[15], const double 
   return o[12] != 0.0 ? SVO_OK : SVO_E_INVALID;
 }
 
+extern "C" int svo_debug_epnp_gn(svo_ctx* ctx, const double L[60], const double rho[6], const double betas_in[12], double betas_out[12]) {
+  if (!ctx || !L || !rho || !betas_in || !betas_out) return SVO_E_INVALID;
+  hipSetDevice(ctx->device);
+  Bump bm{ctx};
+  double* dL = bm.take<double>(60); double* dR = bm.take<double>(6); double* dB = bm.take<double>(12); double* dO = bm.take<double>(12);
+  if (!bm.ok()) return SVO_E_CAPACITY;
+  H2D(dL, L, 480); H2D(dR, rho, 48); H2D(dB, betas_in, 96);
+  int rc = svo_launch_epnp_gn_probe(ctx, dL, dR, dB, dO);
+  if (rc) return rc;
+  D2H(betas_out, dO, 96);
+  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SVO_OK;
+}
+
 // ---- throughput mode ---------------------------------------------------------------------
 // The front end of pairs p0 .. p0 + b - 1 of a batch on stream `st`, in image slots 2 p0 .. 2 p0 + 2 b - 1 of the working
 // set (left images first, then the right ones), results copied to the caller's arrays.

@@ -27,8 +27,10 @@
 //     step loop has no row exchange through LDS and no schedule table - three copies of the step body, one per pair of the
 //     cyclic order (0, 1), (0, 2), (1, 2); same operations on the same operands.
 //   * everything else (M, M^T M, L_6x10, rho, cvInvert / cvSolve back-substitution, compute_ccs / pcs, estimate_R_and_t,
-//     reprojection_error) is one lane per OUTPUT element, each lane summing its element in the loop's own order; the
-//     five Gauss-Newton steps with epnp::qr_solve are scalar code, one candidate per DPP row, arrays in registers.
+//     reprojection_error) is one lane per OUTPUT element, each lane summing its element in the loop's own order.
+//   * the five Gauss-Newton steps with epnp::qr_solve: one candidate per DPP row; a Householder step's column updates are
+//     independent of each other and `b <- Q^T b` is one more column, so within a quad three lanes own a column of A each and the
+//     fourth owns b, the pivot column's scalars are recomputed by every lane, and columns go round by DPP quad broadcasts.
 //   * the branches OpenCV takes once in a blue moon - a zero singular value (JacobiSVDImpl_ then draws a random vector),
 //     two equal singular values (the selection sort's swap order would matter) - are not reproduced here: the wave
 //     notices them and lane 0 re-solves the sample with the sequential restatement (epnp_exact::solve5).
@@ -574,7 +576,115 @@ __device__ __attribute__((noinline)) void svd12_finish_seq(Lds& S, epnp_exact::W
   S.flag |= 2; S.why |= 4;
 }
 
-// ---- epnp::gauss_newton + qr_solve for one candidate, scalar code (arrays in registers) ---------------------------------
+#ifndef EO_GN_SCALAR
+// ---- epnp::gauss_newton + qr_solve for one candidate, one column of the 6 x 4 system per lane ------------------------------
+// `cand`: this lane's candidate (its DPP row), `col`: lane within the row.  The six rows of A and b are built by six lanes of the
+// row (compute_A_and_b_gauss_newton is elementwise in the row index) and handed round through S.gn, stored column by column:
+// S.gn[cand][c] is column c of A (c = 4: b), six rows.
+//
+// qr_solve's Householder step k reads column k (rows k..5), works out eta, the scaled column, sigma, A1[k], A2[k], and then
+// updates every column j > k on its own: sum_i A[i][k] A[i][j] in row order, tau = sum / A1[k], A[i][j] -= tau A[i][k].  No
+// step >= j touches column j again except as step j's pivot.  `b <- Q^T b` applies reflector j to b with the very same three
+// loops after the factorisation, and reflector j only needs column j as step j left it and b as reflectors 0..j-1 left it: b
+// is a fifth column that takes part in every step.  So lane q of a quad (q = col & 3; the four quads of a row are identical
+// copies) owns column q + 1 of A, q = 3 owns b, as o[6]; every lane holds the pivot column p[6] and does the pivot work on it from
+// identical operands.  A lane whose column is final (q < k) leaves it alone.  After step k quad lane k hands rows k + 1..5 of its
+// column round as the next pivot column, and row k of every column j > k and of b - final now - goes to all lanes for the
+// back-substitution, which every lane runs as qr_solve writes it.  Element by element the same IEEE operations on the same
+// operands in the same order as the scalar routine (-DEO_GN_SCALAR builds that one: A/B runs).
+template <int Q>
+EO_FN double quad_bcast(double v) {   // quad lane Q's value in every lane: lane Q of the DPP row to the whole row, one 64-bit move
+  return __longlong_as_double(__builtin_amdgcn_mov_dpp(__double_as_longlong(v), 0x150 + Q, 0xf, 0xf, false));   // row_newbcast:Q
+}
+template <int K>
+EO_FN void gn_step(int q, double (&p)[6], double (&o)[6], double (&R)[4][4], double* A2, bool& alive) {
+  // the pivot work, literally (the `eta` scan looks at the diagonal element twice and never at the last row)
+  double eta = fabs(p[K]);
+#pragma unroll
+  for (int i = K + 1; i < 6; ++i) {
+    const double elt = fabs(p[i - 1]);
+    if (eta < elt) eta = elt;
+  }
+  if (eta == 0) alive = false;
+  const double inv_eta = 1. / eta;
+  double sum2 = 0.0;
+#pragma unroll
+  for (int i = K; i < 6; ++i) {
+    p[i] *= inv_eta;
+    sum2 += p[i] * p[i];
+  }
+  double sigma = xsqrt(sum2);
+  if (p[K] < 0) sigma = -sigma;
+  p[K] += sigma;
+  const double A1 = sigma * p[K];
+  A2[K] = -eta * sigma;
+  // the owner's column: columns K + 1..3 of A and b (q >= K); K = 0: every lane's
+  if (K == 0 || q >= K) {
+    double sum = 0;
+#pragma unroll
+    for (int i = K; i < 6; ++i) sum += p[i] * o[i];
+    const double tau = sum / A1;
+#pragma unroll
+    for (int i = K; i < 6; ++i) o[i] -= tau * p[i];
+  }
+  // row K of the columns behind the pivot and of b is final: R[K][1..3] = A[K][1..3], R[K][0] = b[K]
+  if (K < 1) R[K][1] = quad_bcast<0>(o[K]);
+  if (K < 2) R[K][2] = quad_bcast<1>(o[K]);
+  if (K < 3) R[K][3] = quad_bcast<2>(o[K]);
+  R[K][0] = quad_bcast<3>(o[K]);
+  if (K < 3) {
+#pragma unroll
+    for (int i = K + 1; i < 6; ++i) p[i] = quad_bcast<K>(o[i]);
+  }
+}
+EO_FN void gauss_newton(Lds& S, int cand, int col, bool owner, const double* L, const double* rho, double* betas) {
+  const int q = col & 3;
+#pragma unroll 1
+  for (int it = 0; it < 5; ++it) {
+    {
+      const int i = col < 6 ? col : 0;
+      const double* rl = L + 10 * i;
+      double (*g)[6] = S.gn[cand];
+      const double a0 = 2 * rl[0] * betas[0] + rl[1] * betas[1] + rl[3] * betas[2] + rl[6] * betas[3];
+      const double a1 = rl[1] * betas[0] + 2 * rl[2] * betas[1] + rl[4] * betas[2] + rl[7] * betas[3];
+      const double a2 = rl[3] * betas[0] + rl[4] * betas[1] + 2 * rl[5] * betas[2] + rl[8] * betas[3];
+      const double a3 = rl[6] * betas[0] + rl[7] * betas[1] + rl[8] * betas[2] + 2 * rl[9] * betas[3];
+      const double bi = rho[i] - (rl[0] * betas[0] * betas[0] + rl[1] * betas[0] * betas[1] + rl[2] * betas[1] * betas[1] +
+                                  rl[3] * betas[0] * betas[2] + rl[4] * betas[1] * betas[2] + rl[5] * betas[2] * betas[2] +
+                                  rl[6] * betas[0] * betas[3] + rl[7] * betas[1] * betas[3] + rl[8] * betas[2] * betas[3] +
+                                  rl[9] * betas[3] * betas[3]);
+      if (owner && col < 6) { g[0][i] = a0; g[1][i] = a1; g[2][i] = a2; g[3][i] = a3; g[4][i] = bi; }   // (the idle fourth DPP row shadows candidate 0: it must not write)
+    }
+    EO_SYNC();
+    double p[6], o[6];
+    {
+      const double* g0 = S.gn[cand][0];
+      const double* gq = S.gn[cand][q + 1];
+#pragma unroll
+      for (int i = 0; i < 6; ++i) { p[i] = g0[i]; o[i] = gq[i]; }
+    }
+    EO_SYNC();
+    // the early `return` on eta == 0 (x stays 0) becomes the `alive` predicate
+    double R[4][4], A2[4], x[4];
+    bool alive = true;
+    gn_step<0>(q, p, o, R, A2, alive);
+    gn_step<1>(q, p, o, R, A2, alive);
+    gn_step<2>(q, p, o, R, A2, alive);
+    gn_step<3>(q, p, o, R, A2, alive);
+    x[3] = R[3][0] / A2[3];
+#pragma unroll
+    for (int i = 2; i >= 0; --i) {
+      double sum = 0;
+#pragma unroll
+      for (int j = i + 1; j < 4; ++j) sum += R[i][j] * x[j];
+      x[i] = (R[i][0] - sum) / A2[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) betas[i] += alive ? x[i] : 0.0;
+  }
+}
+#else
+// ---- epnp::gauss_newton + qr_solve for one candidate, scalar code (arrays in registers): -DEO_GN_SCALAR -------------------
 // `cand`: this lane's candidate (its DPP row), `col`: lane within the row.  The six rows of A and b are built by six lanes of the
 // row (compute_A_and_b_gauss_newton is elementwise in the row index), handed round through S.gn, and every lane then walks
 // qr_solve on its own copy.
@@ -658,6 +768,7 @@ EO_FN void gauss_newton(Lds& S, int cand, int col, bool owner, const double* L, 
     for (int i = 0; i < 4; ++i) betas[i] += alive ? x[i] : 0.0;
   }
 }
+#endif
 
 EO_FN double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 

@@ -277,6 +277,7 @@ int svo_launch_pnp(svo_ctx* ctx, const double* Xw, const double* obs, int n, con
                    svo_pnp_stats* stats);
 size_t svo_pnp_hyp_bytes();
 int svo_launch_epnp5_probe(svo_ctx* ctx, const double* X5, const double* u5, const double* K, double* Rt, int reps);
+int svo_launch_epnp_gn_probe(svo_ctx* ctx, const double* L60, const double* rho6, const double* betas_in, double* betas_out);
 void svo_pnp_subsets(uint64_t state, int n, uint16_t* out /*[100 * 5]*/);
 int svo_pose_lds_optin(svo_ctx* ctx);   // dynamic-LDS opt-in of the pose kernels (PoseLds > 64 KB)
 template <typename T>

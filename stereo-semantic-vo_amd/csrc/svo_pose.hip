@@ -141,6 +141,25 @@ __global__ __launch_bounds__(64) void k_epnp5_probe_ord(const double* X5, const 
     Rt[23] = (double)L.S.flag;
   }
 }
+// parity probe of the order-preserving solver's gauss_newton alone: one wave, the three candidates' betas (3 x 4) side by side, one
+// per DPP row as in solve5_wave (the fourth row shadows candidate 0 and writes nothing)
+__global__ __launch_bounds__(64) void k_epnp_gn_probe(const double* L60, const double* rho6, const double* betas_in, double* betas_out) {
+  __shared__ epnp_ord::Lds S;
+  const int lane = threadIdx.x, slot = lane >> 4, col = lane & 15, cand = slot < 3 ? slot : 0;
+  if (lane < 60) S.L[lane] = L60[lane];
+  EO_SYNC();
+  double rho[6], betas[4];
+  for (int k = 0; k < 6; ++k) rho[k] = rho6[k];
+  for (int k = 0; k < 4; ++k) betas[k] = betas_in[4 * cand + k];
+  epnp_ord::gauss_newton(S, cand, col, slot < 3, S.L, rho, betas);
+  if (slot < 3 && col < 4 && blockIdx.x == 0) betas_out[4 * cand + col] = col == 0 ? betas[0] : (col == 1 ? betas[1] : (col == 2 ? betas[2] : betas[3]));
+}
+int svo_launch_epnp_gn_probe(svo_ctx* ctx, const double* L60, const double* rho6, const double* betas_in, double* betas_out) {
+  hipLaunchKernelGGL(k_epnp_gn_probe, dim3(1), dim3(64), 0, ctx->stream, L60, rho6, betas_in, betas_out);
+  SVO_HIP(ctx, hipGetLastError());
+  return SVO_OK;
+}
+
 int svo_launch_epnp5_probe(svo_ctx* ctx, const double* X5, const double* u5, const double* K, double* Rt, int reps) {
   if (ctx->opt_epnp_exact == 2) {
     hipLaunchKernelGGL(k_epnp5_probe_ord, dim3(1), dim3(64), 0, ctx->stream, X5, u5, K, Rt, ctx->opt_epnp_force_seq);
