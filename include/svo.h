@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_debug_stereo_match (the sparse stereo matcher on the caller's keypoints, a
+#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_track_map_out, svo_map_obs (each tracked frame's map points and observations
+                              in HBM; see "the map behind a tracked frame" below); no existing entry changed.
+                              8, backward-compatible addition: svo_debug_stereo_match (the sparse stereo matcher on the caller's keypoints, a
                               parity probe; see there); no existing entry changed.
                               8, backward-compatible addition: svo_track_multi_step_bgr_dev, and the dynamic-keypoint loop in the
                               many-sequence mode (svo_track_dynamic then svo_track_multi_reset; see "LK inside the tracker" below); no
@@ -976,6 +978,41 @@ int svo_track_dynamic(svo_ctx* ctx, const svo_dyn_params* params);
  * Many sequences (device pointers): the next step writes sequence q's list to lists + q * 2 * max_pts, its length to counts[q]
  * and its dropped seeds to dropped[q]; complete after svo_sync, or for work ordered behind svo_stream(ctx) after the step. */
 int svo_track_dynamic_out(svo_ctx* ctx, float* lists, int32_t* counts, int32_t* dropped);
+
+/* ---- the map behind a tracked frame (backward-compatible addition; no existing entry changed) ------------------------------
+ * What the reference keeps in CurrentFrame->MapPoints[j] / mappoint::worldpos and its viewer, local mapping or an evaluator would
+ * read (src/view.cc:7-37): for every keypoint of a frame that has a map point when the frame ends - matched by Tracking::init,
+ * pass 1 or pass 2, or the one frame::createmappoint made a point from; exactly one of the two holds per keypoint - one record,
+ * in ascending keypoint order.  A match the epipolar veto took away is no record. */
+enum { SVO_MAP_NEW = 1 };
+typedef struct svo_map_obs {   /* 32 bytes */
+  int32_t  gid;      /* identity of the map point: creation sequence number since svo_track_reset
+                        (the numbers svo_track_debug's match_gid / new_gid carry) */
+  int16_t  kp;       /* index j of the keypoint in the frame's keypoint list */
+  uint16_t flags;    /* SVO_MAP_NEW: the point exists since this frame (Tracking::init's points at frame 0,
+                        frame::createmappoint's at the end of any frame) */
+  float    u, v;     /* keypoints_l[j].pt */
+  float    depth;    /* the depth the frame's depth source gave keypoint j (what createmappoint reads); <= 0: none */
+  float    X, Y, Z;  /* mappoint::worldpos, as the frame's PnP / LM read it or as createmappoint wrote it */
+} svo_map_obs;
+
+/* One-shot, stateless: the NEXT tracker call on the context writes frame f's records to obs + f * max_kp (max_kp: svo_create's)
+ * and their number to counts[f] (<= max_kp; entries of obs beyond counts[f] are not touched).  One extra launch behind the call's
+ * last pose launch on svo_stream(ctx), nothing when not armed; nothing feeds back - records, debug records, trajectory and the
+ * dynamic-keypoint lists are byte for byte those of a call without it.
+ * Pointers: device pointers for svo_track_batch_dev, svo_track_batch_bgr_dev and svo_track_tail_dev (complete for work ordered
+ * behind svo_stream(ctx), or after svo_sync); host pointers for svo_track_frame[_bgr] (complete when the call returns) and for
+ * svo_track_batch_host / svo_track_batch_bgr_host (complete under the rule of their `results`: after svo_sync, or once the
+ * second following host-fed call has returned).  obs must be 16-byte aligned (the records are written as two 16-byte stores).
+ * It runs with every "depth_source", with boxes, and with the dynamic-keypoint loop on or off.
+ * X, Y, Z are read from the tracker's position table - a ring over 2^20 map-point ids - at the END of the call, not frame by
+ * frame: a frame's record is right as long as no more than 2^20 - 1024 map points are created between that frame and the end of
+ * its call.  A frame creates at most 512, so any call of up to 2046 frames is safe whatever the frames hold (KITTI frames
+ * create ~120: ~8,000 frames); svo_track_overflowed's flag 1 reports a live point that was lapped.
+ * svo_track_multi_step[_bgr]_dev and svo_track_sharded_* called while it is armed return SVO_E_INVALID (svo_last_error names the
+ * entry), enqueue nothing, leave the context usable and the attachment armed.  A NULL argument (checked on the host before a
+ * device is touched), a misaligned obs, or a call before any svo_track_reset is SVO_E_INVALID. */
+int svo_track_map_out(svo_ctx* ctx, svo_map_obs* obs, int32_t* counts);
 
 /* ---- darknet YOLO detector on the device (ABI-7 additions; no existing entry changed) -------------------------------------
  * The online half of semantic gating: Semantic::Run (src/semantic.cc) calls YOLOv3::Detect(leftimg, 0.8), which goes through

@@ -39,6 +39,11 @@ TRACK_DEBUG_DTYPE = np.dtype([("match_gid", "<i4", (512,)), ("new_gid", "<i4", (
                               ("active_rows", "<i4", (2,)), ("rounds", "<i4", (2,)), ("resolve_us", "<i4"),
                               ("rt", "<i8", (6,)), ("T_pnp", "<f8", (16,))])
 
+# svo_map_obs (include/svo.h): one map point seen by one keypoint of a tracked frame (svo_track_map_out)
+MAP_OBS_DTYPE = np.dtype([("gid", "<i4"), ("kp", "<i2"), ("flags", "<u2"), ("u", "<f4"), ("v", "<f4"), ("depth", "<f4"),
+                          ("X", "<f4"), ("Y", "<f4"), ("Z", "<f4")])
+MAP_NEW = 1   # svo_map_obs.flags: the point exists since this frame
+
 # Every symbol include/svo.h declares (checked by tests/test_abi.py without a GPU).
 ABI_SYMBOLS = [
     "svo_abi_version", "svo_strerror", "svo_last_error", "svo_create", "svo_destroy", "svo_sync",
@@ -63,7 +68,7 @@ ABI_SYMBOLS = [
     "svo_lk_default_params", "svo_lk_track", "svo_lk_batch_dev", "svo_lk_chain_dev", "svo_lk_debug_level",
     "svo_lk_track_bgr", "svo_lk_batch_bgr_dev", "svo_lk_chain_bgr_dev", "svo_lk_debug_level_bgr",
     "svo_dyn_default_params", "svo_track_dynamic", "svo_track_dynamic_out", "svo_track_multi_step_bgr_dev",
-    "svo_debug_stereo_match",
+    "svo_debug_stereo_match", "svo_track_map_out",
 ]
 
 # svo_create_ex flags (include/svo.h)
@@ -477,6 +482,12 @@ class Svo:
         """svo_track_dynamic_out: where the NEXT tracker call leaves its frames' lists (frame f at lists + f * 2 * max_pts
         floats), their lengths and dropped seeds - device pointers for the _dev entries, numpy arrays / host pointers otherwise."""
         self._chk(self.lib.svo_track_dynamic_out(self.h, _p(lists), _p(counts), _p(dropped)))
+
+    # ---- each tracked frame's map points and observations (include/svo.h: "the map behind a tracked frame") ----
+    def track_map_out(self, obs, counts):
+        """svo_track_map_out: where the NEXT tracker call leaves its frames' MAP_OBS_DTYPE records (frame f at obs + f * max_kp
+        records, their number in counts[f]) - device pointers for the _dev entries, numpy arrays / host pointers otherwise."""
+        self._chk(self.lib.svo_track_map_out(self.h, _p(obs), _p(counts)))
 
     # ---- throughput mode (device pointers, e.g. torch tensors' data_ptr()) --------------------
     def frontend_batch_dev(self, d_grayL, d_grayR, stride, B, cam, d_kpL=None, d_descL=None,

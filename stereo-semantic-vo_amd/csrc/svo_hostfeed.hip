@@ -340,6 +340,7 @@ int reclaim_set(svo_ctx* ctx, HostFeed* hf, int p) {
 // into the arrays they were promised to.  Called by svo_sync, svo_track_reset, svo_destroy and before a set is reused.
 int svo_hostfeed_flush(svo_ctx* ctx) {
   { const int rcd = svo_track_dyn_flush(ctx); if (rcd) return rcd; }   // (the dynamic-keypoint loop's lists, staged the same way)
+  { const int rcm = svo_track_map_flush(ctx); if (rcm) return rcm; }   // (svo_track_map_out's records, staged the same way)
   HostFeed* hf = feed_of(ctx);
   if (!hf) return SVO_OK;
   for (int p = 0; p < 2; ++p) {
@@ -447,6 +448,7 @@ extern "C" int svo_track_sharded_host(svo_ctx* const* ctxs, int G, const uint8_t
     if ((B - g + G - 1) / G > ctxs[g]->max_batch) return SVO_E_CAPACITY;
   }
   { const int rcd = svo_track_dyn_refuse(c0, "svo_track_sharded_host"); if (rcd) return rcd; }
+  { const int rcm = svo_track_map_refuse(c0, "svo_track_sharded_host"); if (rcm) return rcm; }
   hipSetDevice(c0->device);
   { const int rcs = svo_track_fe_batch_stream(c0); if (rcs) return rcs; }
   int rc = SVO_OK;

@@ -191,6 +191,7 @@ struct svo_ctx {
   void* sgbm = nullptr;         // SgbmArena (svo_sgbm.hip): cost / path volumes of svo_sgbm_* and of the tracker's SGBM mode
   void* lk = nullptr;           // LkArena (svo_lk.hip): pyramids, derivatives and point buffers of svo_lk_*
   void* dyn = nullptr;          // DynState (svo_track.hip): the dynamic-keypoint loop inside the tracker, made by svo_track_dynamic
+  void* map = nullptr;          // MapState (svo_track.hip): svo_track_map_out's attachment and its staging, made by the first arming
   float* d_dense = nullptr;     // dense maps of svo_track_batch_dev with depth_source 1: 2 x dense_cap x W*H
   int dense_cap = 0;
   svo_camera cam{};
@@ -392,6 +393,10 @@ void lk_launch_compact_seqs(hipStream_t s, int nseq, const float* trk, const uin
                             const int32_t* n_seed, int max_seeds, int max_pts, float* list, int32_t* n_out, int32_t* dropped);
 // svo_track.hip: lists of the dynamic-keypoint loop that wait in pinned buffers -> the caller's host arrays (svo_hostfeed_flush)
 int svo_track_dyn_flush(svo_ctx* ctx);
+// svo_track.hip: svo_track_map_out's records that wait in pinned buffers -> the caller's host arrays (svo_hostfeed_flush)
+int svo_track_map_flush(svo_ctx* ctx);
+// svo_track.hip: SVO_E_INVALID with a message while svo_track_map_out is armed (the entries that do not deliver it); stays armed
+int svo_track_map_refuse(svo_ctx* ctx, const char* who);
 // svo_track.hip: SVO_E_INVALID with a message while that loop is enabled (the entries that do not run it)
 int svo_track_dyn_refuse(svo_ctx* ctx, const char* who);
 // svo_track.hip: the same for the single-sequence entries while the loop in force was adopted by svo_track_multi_reset

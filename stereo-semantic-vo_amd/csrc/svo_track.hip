@@ -1656,9 +1656,11 @@ static int fe_sets_alloc(SvoFeBufs* sets, int n, size_t images, size_t pairs, si
   return SVO_OK;
 }
 static void dyn_release(svo_ctx* ctx);
+static void map_release(svo_ctx* ctx);
 void svo_track_release(svo_ctx* ctx) {
   shard_gather_free(ctx);
   dyn_release(ctx);
+  map_release(ctx);
   fe_sets_free(ctx->tb_out, 2);
   for (int q = 0; q < 2; ++q) {
     if (ctx->tb_done[q]) { hipEventDestroy(ctx->tb_done[q]); ctx->tb_done[q] = nullptr; }
@@ -2080,6 +2082,140 @@ static int dyn_multi_step(svo_ctx* ctx, DynState* D, hipStream_t s, int id, bool
   return SVO_OK;
 }
 
+// ---- each tracked frame's map points and observations (svo_track_map_out) ---------------------------------------------------
+// A one-shot attachment like svo_track_dynamic_out, without state of its own: ONE launch (k_tm_obs, at the end of this file) of one
+// workgroup per frame behind the call's last pose launch on the pose stream, which reads what the call left in HBM anyway - the
+// frames' work records (edge list, new_gid), the call's keypoint and depth arrays, the position table - and writes the records in
+// keypoint order.  On the pose stream, inside tail_enqueue: every event that lets a later call's index chain rewrite this half of
+// the work records or this front-end output set (ev_frontend at the next call's start, tb_done[p] / the callers' own events behind
+// tail_enqueue) is recorded on that stream after it.  Host destinations (svo_track_frame, the _host entries): the kernel writes
+// staging in HBM, a copy on the pose stream takes it to one of two pinned sets, and the flush hands each frame's counts[f]
+// records to the caller's array - at the entry's end (svo_track_frame has synchronised) or with the host-fed records (svo_hostfeed_flush).
+__global__ __launch_bounds__(TRK_MAXKP) void k_tm_obs(const TrackState* st, const TrackWork* work, const svo_kp* kp, const float* depth, int kstride, int tag0,
+                         int max_kp, svo_map_obs* obs, int32_t* counts);
+struct MapOut { svo_map_obs* obs = nullptr; int32_t* counts = nullptr; };
+struct MapState {
+  MapOut out; bool attached = false;        // svo_track_map_out, for the next call
+  // the call being enqueued
+  bool in_call = false, cur_host = false;
+  MapOut cur; int cur_off = 0, cur_q = 0;
+  // host destinations: staging in HBM for `cap` frames, two pinned sets that alternate between calls
+  int cap = 0;
+  svo_map_obs* d_obs = nullptr; int32_t* d_counts = nullptr;
+  svo_map_obs* h_obs[2] = {nullptr, nullptr}; int32_t* h_counts[2] = {nullptr, nullptr};
+  hipEvent_t ev_out[2] = {nullptr, nullptr};
+  MapOut pending[2]; int pending_n[2] = {0, 0}; int hparity = 0;
+};
+static MapState* map_of(svo_ctx* ctx) { return reinterpret_cast<MapState*>(ctx->map); }
+static void map_release(svo_ctx* ctx) {
+  MapState* M = map_of(ctx);
+  if (!M) return;
+  if (M->d_obs) hipFree(M->d_obs);
+  if (M->d_counts) hipFree(M->d_counts);
+  for (int q = 0; q < 2; ++q) {
+    if (M->h_obs[q]) hipHostFree(M->h_obs[q]);
+    if (M->h_counts[q]) hipHostFree(M->h_counts[q]);
+    if (M->ev_out[q]) hipEventDestroy(M->ev_out[q]);
+  }
+  delete M;
+  ctx->map = nullptr;
+}
+static int map_flush_set(svo_ctx* ctx, MapState* M, int q) {
+  if (!M->pending_n[q]) return SVO_OK;
+  SVO_HIP(ctx, hipEventSynchronize(M->ev_out[q]));
+  const size_t K = (size_t)ctx->max_kp;
+  for (int f = 0; f < M->pending_n[q]; ++f) {   // (a frame's records only: what lies behind them in the caller's array stays as it is)
+    const int n = std::min(std::max(M->h_counts[q][f], 0), ctx->max_kp);
+    M->pending[q].counts[f] = n;
+    memcpy(M->pending[q].obs + (size_t)f * K, M->h_obs[q] + (size_t)f * K, (size_t)n * sizeof(svo_map_obs));
+  }
+  M->pending_n[q] = 0;
+  return SVO_OK;
+}
+int svo_track_map_flush(svo_ctx* ctx) {
+  MapState* M = map_of(ctx);
+  if (!M) return SVO_OK;
+  for (int q = 0; q < 2; ++q) { const int rc = map_flush_set(ctx, M, q); if (rc) return rc; }
+  return SVO_OK;
+}
+// the entries that do not deliver it refuse while it is armed - and leave it armed
+int svo_track_map_refuse(svo_ctx* ctx, const char* who) {
+  if (!ctx->map || !map_of(ctx)->attached) return SVO_OK;
+  ctx->last_error = std::string(who) + ": svo_track_map_out is armed on this context; this entry does not deliver map observations";
+  return SVO_E_INVALID;
+}
+// A tracker entry that delivers the records starts a call; `host`: svo_track_map_out's arrays are host memory
+static int map_begin(svo_ctx* ctx, bool host) {
+  MapState* M = map_of(ctx);
+  if (!M || !M->attached) return SVO_OK;
+  M->cur = M->out; M->cur_host = host; M->cur_off = 0;
+  M->attached = false; M->out = MapOut{};
+  if (host) {
+    const int q = M->hparity;
+    M->cur_q = q; M->hparity ^= 1;
+    const int rc = map_flush_set(ctx, M, q);   // (what the call two back left in this set)
+    if (rc) return rc;
+    const size_t cap = (size_t)std::max(ctx->max_batch, 1), K = (size_t)ctx->max_kp;
+    bool ok = true;
+    if (!M->d_obs) {
+      ok = hipMalloc(reinterpret_cast<void**>(&M->d_obs), cap * K * sizeof(svo_map_obs)) == hipSuccess &&
+           hipMalloc(reinterpret_cast<void**>(&M->d_counts), cap * sizeof(int32_t)) == hipSuccess;
+      M->cap = (int)cap;
+    }
+    if (ok && !M->h_obs[q])
+      ok = hipHostMalloc(reinterpret_cast<void**>(&M->h_obs[q]), cap * K * sizeof(svo_map_obs)) == hipSuccess &&
+           hipHostMalloc(reinterpret_cast<void**>(&M->h_counts[q]), cap * sizeof(int32_t)) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      ctx->last_error = "svo_track_map_out: out of memory for the staging of host arrays";
+      return SVO_E_NOMEM;
+    }
+    if (!M->ev_out[q]) SVO_HIP(ctx, hipEventCreateWithFlags(&M->ev_out[q], hipEventDisableTiming));
+  }
+  M->in_call = true;
+  return SVO_OK;
+}
+// `direct`: the entry has synchronised the pose stream (svo_track_frame) - the caller's arrays are complete when it returns
+static int map_end(svo_ctx* ctx, bool direct, int rc) {
+  MapState* M = map_of(ctx);
+  if (!M || !M->in_call) return rc;
+  M->in_call = false; M->cur = MapOut{};
+  if (direct && M->cur_host) { const int rcf = map_flush_set(ctx, M, M->cur_q); if (rc == SVO_OK) rc = rcf; }
+  return rc;
+}
+// the end of a tail call of `frames` frames (tail_enqueue's arguments): the launch behind the call's last pose launch on `pose`
+static int map_enqueue(svo_ctx* ctx, MapState* M, hipStream_t pose, const TrackWork* work, const svo_kp* kp, const float* depth, int kstride,
+                       int frames, const int* row_of_frame) {
+  const size_t K = (size_t)ctx->max_kp, off = (size_t)M->cur_off;
+  if (M->cur_host && off + (size_t)frames > (size_t)M->cap) {
+    ctx->last_error = "svo_track_map_out: more frames than max_batch";
+    return SVO_E_CAPACITY;
+  }
+  svo_map_obs* obs = (M->cur_host ? M->d_obs : M->cur.obs) + off * K;
+  int32_t* counts = (M->cur_host ? M->d_counts : M->cur.counts) + off;
+  const TrackState* st = reinterpret_cast<const TrackState*>(ctx->d_track);
+  const int tag0 = ctx->track_frame + 1;   // k_ti_resolve's tag of the call's frame 0
+  {
+    SvoTimer t(ctx, "k_tm_obs", pose);
+    if (!row_of_frame) {
+      hipLaunchKernelGGL(k_tm_obs, dim3(frames), dim3(TRK_MAXKP), 0, pose, st, work, kp, depth, kstride, tag0, (int)K, obs, counts);
+    } else {   // (front-end rows that are not the frames' order: a launch per frame)
+      for (int f = 0; f < frames; ++f)
+        hipLaunchKernelGGL(k_tm_obs, dim3(1), dim3(TRK_MAXKP), 0, pose, st, work + f, kp + (size_t)row_of_frame[f] * kstride,
+                           depth + (size_t)row_of_frame[f] * kstride, kstride, tag0 + f, (int)K, obs + (size_t)f * K, counts + f);
+    }
+  }
+  if (M->cur_host) {
+    const int q = M->cur_q;
+    SVO_HIP(ctx, hipMemcpyAsync(M->h_obs[q] + off * K, M->d_obs + off * K, (size_t)frames * K * sizeof(svo_map_obs), hipMemcpyDeviceToHost, pose));
+    SVO_HIP(ctx, hipMemcpyAsync(M->h_counts[q] + off, M->d_counts + off, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, pose));
+    SVO_HIP(ctx, hipEventRecord(M->ev_out[q], pose));
+    M->pending[q] = M->cur; M->pending_n[q] = (int)off + frames;
+  }
+  M->cur_off += frames;
+  return SVO_OK;
+}
+
 // The ordered tail for front-end results that are already in HBM (`kstride` keypoints per frame slot):
 //   nseq == 1: `frames` consecutive frames of the one sequence, record f into d_res[f];
 //   nseq  > 1: one frame of each of nseq sequences (frames == 1), sequence q from frame slot q into d_res[q].
@@ -2291,6 +2427,8 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
   }
   ctx->profiling = prof;
   if (D && (rc = dyn_finish(ctx, D, s1, s0, frames))) return rc;
+  // svo_track_map_out: behind the call's last pose launch, and in front of whatever the callers record on the pose stream
+  if (ctx->map && map_of(ctx)->in_call && nseq == 1 && (rc = map_enqueue(ctx, map_of(ctx), s0, work, kp, depth, kstride, frames, row_of_frame))) return rc;
   // many sequences: the pose stream joins the loop here, BEHIND the step's pose kernels, which therefore run beside the step's LK
   // work; what svo_sync, ms_tail_done and work ordered behind the context's stream wait for covers the lists and the image copy
   if (DM) SVO_HIP(ctx, hipStreamWaitEvent(s0, DM->ev_lk, 0));
@@ -2335,6 +2473,7 @@ static int track_reset_n(svo_ctx* ctx, const svo_camera* cam, int nseq, bool mul
     SVO_HIP(ctx, hipMemcpyAsync(&st->cam, cam, sizeof *cam, hipMemcpyHostToDevice, ctx->stream));
   }
   { const int rcd = dyn_adopt(ctx, multi ? nseq : 0); if (rcd) return rcd; }   // (svo_track_dynamic's parameters; the lists are empty again)
+  if (ctx->map) { MapState* M = map_of(ctx); M->attached = false; M->out = MapOut{}; M->in_call = false; }   // (svo_track_map_out is disarmed; its staged records were flushed above)
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->cam = *cam;
   ctx->track_frame = 0;
@@ -2408,8 +2547,16 @@ static int dyn_colour_needs_bgr(svo_ctx* ctx, const char* who) {
   ctx->last_error = std::string(who) + ": svo_track_dynamic asked for LK on the colour frames (colour = 1), which a gray entry does not have";
   return SVO_E_INVALID;
 }
+static int track_frame_staged_dyn(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
+                                  const uint8_t* d_bgrR, int bgr_pitch);
 int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
                            const uint8_t* d_bgrR, int bgr_pitch) {
+  int rc = map_begin(ctx, true);   // (svo_track_map_out: host arrays, complete when the entry returns)
+  if (rc == SVO_OK) rc = track_frame_staged_dyn(ctx, boxes, n_boxes, res, d_bgrL, d_bgrR, bgr_pitch);
+  return map_end(ctx, true, rc);
+}
+static int track_frame_staged_dyn(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
+                                  const uint8_t* d_bgrR, int bgr_pitch) {
   if (!dyn_active(ctx)) return track_frame_staged(ctx, boxes, n_boxes, res, d_bgrL, d_bgrR, bgr_pitch);
   const bool colour = dyn_of(ctx)->p.colour != 0;
   if (colour && !d_bgrL) return dyn_colour_needs_bgr(ctx, "svo_track_frame");
@@ -2517,6 +2664,7 @@ static int multi_step_enqueue(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_
 // what both many-sequence entries refuse before anything is allocated or enqueued
 int svo_track_multi_step_check(svo_ctx* ctx, const char* who, bool has_bgr) {
   { const int rcd = dyn_refuse_multi(ctx, who); if (rcd) return rcd; }
+  { const int rcm = svo_track_map_refuse(ctx, who); if (rcm) return rcm; }
   if (ctx->opt_depth_source != 0) {   // the many-sequence mode has the sparse matcher only
     ctx->last_error = std::string(who) + ": depth_source must be 0";
     return SVO_E_INVALID;
@@ -2617,8 +2765,17 @@ static int multi_step_enqueue(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_
 
 static int track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
                            const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr);
+static int track_batch_fed_dyn(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
+                               const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr);
 int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
                         const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr) {
+  if (!ctx || !ctx->map) return track_batch_fed_dyn(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, pair_ready, bgr);
+  int rc = map_begin(ctx, pair_ready != nullptr);   // (svo_track_map_out: host arrays for the host-fed entries)
+  if (rc == SVO_OK) rc = track_batch_fed_dyn(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, pair_ready, bgr);
+  return map_end(ctx, false, rc);
+}
+static int track_batch_fed_dyn(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
+                               const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr) {
   if (!ctx || !dyn_active(ctx)) return track_batch_fed(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, pair_ready, bgr);
   const bool colour = dyn_of(ctx)->p.colour != 0;
   if (colour && !bgr) return dyn_colour_needs_bgr(ctx, "svo_track_batch");
@@ -2869,6 +3026,23 @@ extern "C" int svo_track_dynamic_out(svo_ctx* ctx, float* lists, int32_t* counts
   return SVO_OK;
 }
 
+extern "C" int svo_track_map_out(svo_ctx* ctx, svo_map_obs* obs, int32_t* counts) {
+  if (!ctx || !obs || !counts) return SVO_E_INVALID;   // (host only: no device is touched before this)
+  if (!ctx->d_track) {
+    ctx->last_error = "svo_track_map_out: svo_track_reset first";
+    return SVO_E_INVALID;
+  }
+  if ((reinterpret_cast<uintptr_t>(obs) & 15) || (reinterpret_cast<uintptr_t>(counts) & 3)) {
+    ctx->last_error = "svo_track_map_out: obs must be 16-byte aligned, counts 4-byte aligned";
+    return SVO_E_INVALID;
+  }
+  if (!ctx->map) ctx->map = new MapState();
+  MapState* M = map_of(ctx);
+  M->out.obs = obs; M->out.counts = counts;
+  M->attached = true;
+  return SVO_OK;
+}
+
 extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR,
                                    int stride, int B, const svo_boxes_dev* boxes, svo_track_result* d_results) {
   if (ctx) { const int rcd = svo_track_dyn_refuse_single(ctx, "svo_track_batch_dev"); if (rcd) return rcd; }
@@ -2885,8 +3059,9 @@ extern "C" int svo_track_tail_dev(svo_ctx* ctx, const svo_kp* d_kp, const uint8_
   { const int rcd = svo_track_dyn_refuse(ctx, "svo_track_tail_dev"); if (rcd) return rcd; }
   hipSetDevice(ctx->device);
   { const int rcs = svo_shard_quiesce(ctx); if (rcs) return rcs; }   // (a sharded call of this context may still be in flight: staging sets, work records)
-  int rc = tail_enqueue(ctx, d_kp, d_desc, d_n, d_depth, kp_stride, B, 1, d_results, boxes);
-  if (rc) return rc;
+  int rc = map_begin(ctx, false);
+  if (rc == SVO_OK) rc = tail_enqueue(ctx, d_kp, d_desc, d_n, d_depth, kp_stride, B, 1, d_results, boxes);
+  if ((rc = map_end(ctx, false, rc))) return rc;
   ctx->track_frame += B;
   return SVO_OK;
 }
@@ -3138,6 +3313,7 @@ int svo_track_sharded_fed(svo_ctx* const* ctxs, int G, const uint8_t* const* d_g
     if ((B - g + G - 1) / G > ctxs[g]->max_batch) return SVO_E_CAPACITY;
   }
   { const int rcd = svo_track_dyn_refuse(c0, "svo_track_sharded_dev"); if (rcd) return rcd; }
+  { const int rcm = svo_track_map_refuse(c0, "svo_track_sharded_dev"); if (rcm) return rcm; }
   ShardGather* sg = shard_gather(c0);
   SVO_HIP(c0, hipSetDevice(c0->device));
   { const int rcf = svo_track_fe_batch_stream(c0); if (rcf) return rcf; }
@@ -3381,4 +3557,61 @@ extern "C" int svo_debug_track_pose_stamps(svo_ctx* ctx, int64_t ts[16]) {
   TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
   SVO_HIP(ctx, svo_memcpy_sync(ctx, ts, st->pose_ts, sizeof(long long) * 16, hipMemcpyDeviceToHost));
   return SVO_OK;
+}
+
+// ================================================================================================
+// svo_track_map_out: a call's map points and observations, frame by frame (host side: map_enqueue)
+// ================================================================================================
+// Workgroup f = frame f of the call, thread j = keypoint j.  Behind the call's last pose launch on the pose stream: every frame's
+// pose launch has finished, so its record was published (the pose kernels waited for the tag) and the position table holds every
+// point the call created.  The record is read the way the pose kernels read it - the index chain wrote it on another stream with
+// agent-scope stores, and the XCDs' L2s are not coherent for plain loads: the tag first, then agent-scope loads; a record whose tag
+// is not the frame's (a lost hand-over: the pose chain treated the frame as a PnP failure) gives count 0, never stale records.
+// "matched" comes from the frame's correspondence list (edge_kp is ascending), "created" from new_gid - exactly one per keypoint -;
+// a block-wide prefix sum puts the records in keypoint order, two 16-byte stores each.  Defined last in this file: no existing
+// kernel's place in the code object moves (k_tp_tail_ord's Jacobi loop is sensitive to its fetch alignment).
+__global__ __launch_bounds__(TRK_MAXKP) void k_tm_obs(const TrackState* __restrict__ st, const TrackWork* __restrict__ work,
+                                                      const svo_kp* __restrict__ kp, const float* __restrict__ depth, int kstride,
+                                                      int tag0, int max_kp, svo_map_obs* __restrict__ obs, int32_t* __restrict__ counts) {
+  static_assert(sizeof(svo_map_obs) == 32, "svo_map_obs: two 16-byte stores");
+  __shared__ alignas(16) int sm[16];
+  __shared__ int mgid[TRK_MAXKP];
+  const int f = blockIdx.x, tid = threadIdx.x;
+  work += f; kp += (size_t)f * kstride; depth += (size_t)f * kstride; obs += (size_t)f * max_kp;
+  const bool have = ld_agent(&work->ready) == tag0 + f;
+  // (keypoints and depths were written with plain stores by front-end kernels on other streams: as in tp_wait_work)
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  const int nkp = have ? min(max(ld_agent(&work->nkp), 0), min(TRK_MAXKP, kstride)) : 0;
+  const int n_edges = have ? min(max(ld_agent(&work->n_edges), 0), TRK_MAXKP) : 0;
+  const int id = ld_agent(&work->frame_id);
+  mgid[tid] = -1;
+  __syncthreads();
+  if (tid < n_edges) {
+    const int j = ld_agent(&work->edge_kp[tid]);
+    if (j >= 0 && j < TRK_MAXKP) mgid[j] = ld_agent(&work->edge_gid[tid]);
+  }
+  __syncthreads();
+  int gid = -1;
+  uint32_t flags = 0;
+  if (tid < nkp) {
+    gid = mgid[tid];
+    if (gid >= 0) {
+      flags = id == 0 ? (uint32_t)SVO_MAP_NEW : 0u;   // Tracking::init's points
+    } else {
+      gid = ld_agent(&work->new_gid[tid]);            // frame::createmappoint's
+      flags = (uint32_t)SVO_MAP_NEW;
+    }
+  }
+  int total;
+  const int pos = block_excl_scan(gid >= 0 ? 1 : 0, sm, &total);
+  if (gid >= 0 && pos < max_kp) {
+    const svo_kp k = kp[tid];
+    const float* gp = st->gpos + 3 * (size_t)(gid & (TRK_GPOS - 1));
+    uint4 a, b;
+    a.x = (uint32_t)gid; a.y = (uint32_t)tid | (flags << 16); a.z = __float_as_uint(k.x); a.w = __float_as_uint(k.y);
+    b.x = __float_as_uint(depth[tid]); b.y = __float_as_uint(gp[0]); b.z = __float_as_uint(gp[1]); b.w = __float_as_uint(gp[2]);
+    uint4* dst = reinterpret_cast<uint4*>(obs + pos);
+    dst[0] = a; dst[1] = b;
+  }
+  if (tid == 0) counts[f] = min(total, max_kp);
 }

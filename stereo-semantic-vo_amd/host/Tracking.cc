@@ -1,5 +1,6 @@
 #include "Tracking.h"
 
+#include <algorithm>
 #include <iomanip>
 #include <sstream>
 #include <stdexcept>
@@ -47,6 +48,7 @@ Tracking::Tracking(const svo_camera& cam, int w, int h, int dev) : device(dev), 
 }
 Tracking::~Tracking() {
   if (ctx_batch) svo_destroy(ctx_batch);
+  if (ctx_map) svo_destroy(ctx_map);
   svo_destroy(ctx);
 }
 
@@ -93,6 +95,13 @@ void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n,
     if (svo_track_dynamic_out(ctx_batch, c.lists.data(), c.counts.data(), c.dropped.data()) != SVO_OK)
       throw std::runtime_error(std::string("svo_track_dynamic_out: ") + svo_last_error(ctx_batch));
   }
+  if (map_out) {
+    batch_map_calls.emplace_back(new MapCall());
+    MapCall& c = *batch_map_calls.back();
+    c.obs.assign((size_t)n * 500, svo_map_obs{}); c.counts.assign((size_t)n, 0);
+    if (svo_track_map_out(ctx_batch, c.obs.data(), c.counts.data()) != SVO_OK)
+      throw std::runtime_error(std::string("svo_track_map_out: ") + svo_last_error(ctx_batch));
+  }
   const int rc = (bgr ? svo_track_batch_bgr_host : svo_track_batch_host)(ctx_batch, L, R, stride, n, most > 0 ? &bx : nullptr,
                                                                        batch_results.data() + first);
   if (rc != SVO_OK)
@@ -110,6 +119,9 @@ void Tracking::FinishBatches(std::ofstream& f, std::ofstream& f2) {
       batch_dynamic_dropped.push_back(c->dropped[k]);
     }
   batch_dyn_calls.clear();
+  for (const auto& c : batch_map_calls)   // (the same for the observations of every batched frame)
+    for (size_t k = 0; k < c->counts.size(); ++k) observations.emplace_back(c->obs.begin() + k * 500, c->obs.begin() + k * 500 + c->counts[k]);
+  batch_map_calls.clear();
   frame fr;   // SetPose's Rwc / twc arithmetic (src/frame.cc:66-73), SaveTrajectoryAndDraw's formats
   for (size_t k = 0; k < batch_results.size(); ++k) {
     Mat44f T;
@@ -120,6 +132,42 @@ void Tracking::FinishBatches(std::ofstream& f, std::ofstream& f2) {
     SaveTrajectoryAndDraw(f, f2);
   }
   currentframe = nullptr;
+}
+
+const std::vector<svo_map_obs>& Tracking::Observations(size_t frame_id) const {
+  if (frame_id >= observations.size()) throw std::runtime_error("Tracking::Observations: no such frame (map_out set? FinishBatches() called?)");
+  return observations[frame_id];
+}
+const svo_map_obs* Tracking::ObservationOf(size_t frame_id, int kp) const {
+  const std::vector<svo_map_obs>& o = Observations(frame_id);   // (ascending kp)
+  const auto it = std::lower_bound(o.begin(), o.end(), kp, [](const svo_map_obs& r, int j) { return r.kp < j; });
+  return it != o.end() && it->kp == kp ? &*it : nullptr;
+}
+
+// Track() with map_out: the pair through svo_track_frame[_bgr] on ctx_map, armed - the colour pair where Track() was given one,
+// as TrackBatch(bgr) would
+void Tracking::MapFrame(const GrayImage& imLeft, const GrayImage& imRight, const BgrImage* colLeft, const BgrImage* colRight, double timestamp,
+                        const std::vector<std::vector<int>>& detection_box) {
+  if (!ctx_map) {
+    if (svo_create(&ctx_map, device, width, height, 500, 1) != SVO_OK) throw std::runtime_error("svo_create failed");
+    if (svo_set_option(ctx_map, "depth_source", depth_source) != SVO_OK || svo_set_option(ctx_map, "sgbm_colour", sgbm_colour ? 1 : 0) != SVO_OK ||
+        svo_set_option(ctx_map, "sgbm_mode", sgbm_mode) != SVO_OK || svo_track_reset(ctx_map, &K) != SVO_OK)
+      throw std::runtime_error(std::string("Tracking::map_out: ") + svo_last_error(ctx_map));
+  }
+  std::vector<int32_t> flat;
+  for (const auto& b : detection_box)
+    for (int j = 0; j < 4; ++j) flat.push_back(b[j]);
+  std::vector<svo_map_obs> obs(500);
+  int32_t count = 0;
+  svo_track_result res;
+  if (svo_track_map_out(ctx_map, obs.data(), &count) != SVO_OK) throw std::runtime_error(std::string("svo_track_map_out: ") + svo_last_error(ctx_map));
+  const int nb = (int)detection_box.size();
+  const int rc = colLeft ? svo_track_frame_bgr(ctx_map, colLeft->ptr(), colLeft->step(), colRight->ptr(), colRight->step(), timestamp,
+                                               nb ? flat.data() : nullptr, nb, &res)
+                         : svo_track_frame(ctx_map, imLeft.ptr(), imLeft.cols, imRight.ptr(), imRight.cols, timestamp, nb ? flat.data() : nullptr, nb, &res);
+  if (rc != SVO_OK) throw std::runtime_error(std::string("Tracking::map_out: ") + svo_last_error(ctx_map));
+  obs.resize((size_t)count);
+  observations.push_back(std::move(obs));
 }
 
 void Tracking::init() {
@@ -198,6 +246,7 @@ void Tracking::Track(const BgrImage& imLeft, const BgrImage& imRight, double tim
 
 void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, const BgrImage* colLeft, const BgrImage* colRight,
                            double timestamp, std::ofstream& f, std::ofstream& f2, const std::vector<std::vector<int>>& detection_box) {
+  if (map_out) MapFrame(imLeft, imRight, colLeft, colRight, timestamp, detection_box);
   currentframe = new frame(ctx, imLeft, imRight, timestamp, K, detection_box);
   if (dynamic_lk) {                       // src/Tracking.cc:189-223: LK on the last list, erase by status, survivors -> DY_keypoints
     currentframe->dynamic_lk = true;      // (status and error live in the current frame here, in lastframe there)

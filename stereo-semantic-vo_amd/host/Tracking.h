@@ -37,6 +37,16 @@ class Tracking {
   int dynamic_max_pts = 4096;
   std::vector<std::vector<svo_host::Point2f>> batch_dynamic;
   std::vector<int> batch_dynamic_dropped;
+  // The map behind every tracked frame (svo_track_map_out): set before the first Track() / TrackBatch().  Observations(k) are
+  // frame k's records - one per keypoint that has a map point when the frame ends (the reference's CurrentFrame->MapPoints[j] and
+  // mappoint::worldpos, what View::DrawMappoints / DrawGraph read) -, in keypoint order, and ObservationOf(k, j) is keypoint j's
+  // (null: no map point).  Both modes hand out the DEVICE-RESIDENT tracker's records, so a frame's map does not depend on the
+  // mode: TrackBatch() arms the attachment for every call (complete after FinishBatches()); Track() feeds the same pair and boxes
+  // to svo_track_frame[_bgr] on a context of its own, armed (complete when Track() returns) - the stage-by-stage classes' own
+  // poses differ from the device tracker's in their last bits, and so would positions derived from them.
+  bool map_out = false;
+  const std::vector<svo_map_obs>& Observations(size_t frame_id) const;
+  const svo_map_obs* ObservationOf(size_t frame_id, int kp) const;
   Tracking(const svo_camera& cam, int width, int height, int device = 0);
   ~Tracking();
   void init();                                                          // src/Tracking.cc:42-97
@@ -61,6 +71,8 @@ class Tracking {
   void SaveTrajectoryAndDraw(std::ofstream& f, std::ofstream& f2);      // :124-144
 
  private:
+  void MapFrame(const svo_host::GrayImage& imLeft, const svo_host::GrayImage& imRight, const svo_host::BgrImage* colLeft,
+                const svo_host::BgrImage* colRight, double timestamp, const std::vector<std::vector<int>>& detection_box);
   void TrackImages(const svo_host::GrayImage& imLeft, const svo_host::GrayImage& imRight, const svo_host::BgrImage* colLeft,
                    const svo_host::BgrImage* colRight, double timestamp, std::ofstream& f, std::ofstream& f2,
                    const std::vector<std::vector<int>>& detection_box);
@@ -73,6 +85,10 @@ class Tracking {
   std::vector<double> batch_timestamps;
   struct DynCall { std::vector<float> lists; std::vector<int32_t> counts, dropped; };   // one TrackBatch()'s svo_track_dynamic_out arrays
   std::vector<std::unique_ptr<DynCall>> batch_dyn_calls;                               // (complete after svo_sync: FinishBatches collects them)
+  svo_ctx* ctx_map = nullptr;             // Track() with map_out: the device-resident tracker beside the classes (max_batch = 1)
+  std::vector<std::vector<svo_map_obs>> observations;   // per tracked frame
+  struct MapCall { std::vector<svo_map_obs> obs; std::vector<int32_t> counts; };       // one TrackBatch()'s svo_track_map_out arrays
+  std::vector<std::unique_ptr<MapCall>> batch_map_calls;                               // (complete after svo_sync: FinishBatches collects them)
   int width = 0, height = 0;
   int device;
   frame lastframe;

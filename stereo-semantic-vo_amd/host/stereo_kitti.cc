@@ -19,6 +19,8 @@
 // --dynamic-dev / --dynamic-dev-bgr (with --pipelined only): the same loop inside the device-resident tracker (svo_track_dynamic,
 // Tracking::dynamic_dev), on gray or - needs --colour - on the colour left images; --write-dynamic writes the same files.
 // --dynamic-lk-bgr (implies --dynamic-lk; needs --colour): the same loop on the colour left images, svo_lk_track_bgr.
+// --write-map <dir> / --write-cloud <file.ply> (any mode): each frame's map points and observations (svo_track_map_out,
+// Tracking::map_out) to <dir>/NNNNNN.txt, "gid kp new u v depth X Y Z" per line; every new point of the run as an ASCII PLY.
 // stereo_kitti --decode-bgr in.(png|ppm|pgm) out.ppm: codec self-test of the colour decode (the PPM holds RGB, as the format says).
 #include <algorithm>
 #include <chrono>
@@ -153,6 +155,20 @@ int main(int argc, char** argv) {
     for (int j = i; j + take < argc; ++j) argv[j] = argv[j + take];
     argc -= take;
   }
+  // --write-map <dir>: each frame's map points and observations (Tracking::map_out) to <dir>/NNNNNN.txt, one record per line
+  // "gid kp new u v depth X Y Z" (%.9g: the floats read back exactly); --write-cloud <file.ply>: every record that is new in its
+  // frame - each map point once, where it was created - as an ASCII PLY vertex list.  Frame by frame and --pipelined, gray and --colour.
+  std::string map_dir, cloud_file;
+  for (int i = 1; i < argc;) {
+    const std::string a = argv[i];
+    int take = 0;
+    if (a == "--write-map" && i + 1 < argc) { map_dir = argv[i + 1]; take = 2; }
+    else if (a == "--write-cloud" && i + 1 < argc) { cloud_file = argv[i + 1]; take = 2; }
+    if (!take) { ++i; continue; }
+    for (int j = i; j + take < argc; ++j) argv[j] = argv[j + take];
+    argc -= take;
+  }
+  const bool map_out = !map_dir.empty() || !cloud_file.empty();
   bool pipelined = false;
   int per_call = 32;
   if (argc >= 5 && std::string(argv[1]) == "--pipelined") {
@@ -173,7 +189,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--pipelined] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--write-map dir] [--write-cloud file.ply] [--pipelined] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -204,6 +220,29 @@ int main(int argc, char** argv) {
   mpTracker->dynamic_lk_bgr = dynamic_lk_bgr;
   mpTracker->dynamic_dev = dynamic_dev;
   mpTracker->dynamic_dev_bgr = dynamic_dev_bgr;
+  mpTracker->map_out = map_out;
+  std::vector<svo_map_obs> cloud;
+  auto write_map = [&](int ni) {
+    const std::vector<svo_map_obs>& obs = mpTracker->Observations((size_t)ni);
+    for (const svo_map_obs& r : obs)
+      if (r.flags & SVO_MAP_NEW) cloud.push_back(r);
+    if (map_dir.empty()) return true;
+    FILE* o = fopen((map_dir + "/" + name("", ni, ".txt").substr(seq.size() + 2)).c_str(), "w");
+    if (!o) { std::cerr << "cannot write into " << map_dir << std::endl; return false; }
+    for (const svo_map_obs& r : obs)
+      fprintf(o, "%d %d %d %.9g %.9g %.9g %.9g %.9g %.9g\n", r.gid, (int)r.kp, (r.flags & SVO_MAP_NEW) ? 1 : 0, r.u, r.v, r.depth, r.X, r.Y, r.Z);
+    fclose(o);
+    return true;
+  };
+  auto write_cloud = [&]() {
+    if (cloud_file.empty()) return true;
+    FILE* o = fopen(cloud_file.c_str(), "w");
+    if (!o) { std::cerr << "cannot write " << cloud_file << std::endl; return false; }
+    fprintf(o, "ply\nformat ascii 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\nend_header\n", cloud.size());
+    for (const svo_map_obs& r : cloud) fprintf(o, "%.9g %.9g %.9g\n", r.X, r.Y, r.Z);
+    fclose(o);
+    return true;
+  };
   auto write_dynamic = [&](int ni, const std::vector<Point2f>& pts) {
     FILE* o = fopen((dynamic_dir + "/" + name("", ni, ".txt").substr(seq.size() + 2)).c_str(), "w");
     if (!o) { std::cerr << "cannot write into " << dynamic_dir << std::endl; return false; }
@@ -271,6 +310,9 @@ int main(int argc, char** argv) {
       for (int ni = 0; ni < nImages && !dynamic_dir.empty(); ++ni)
         if (!write_dynamic(ni, mpTracker->batch_dynamic[(size_t)ni])) return 1;
     }
+    for (int ni = 0; ni < nImages && map_out; ++ni)
+      if (!write_map(ni)) return 1;
+    if (!write_cloud()) return 1;
     const double total = std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t0).count();
     f.close(); f2.close();
     std::cout << std::endl << "trajectory saved!" << std::endl << "-------" << std::endl << std::endl;
@@ -296,7 +338,9 @@ int main(int argc, char** argv) {
     const auto t2 = std::chrono::steady_clock::now();
     vTimesTrack[ni] = (float)std::chrono::duration_cast<std::chrono::duration<double>>(t2 - t1).count();
     if (!dynamic_dir.empty() && !write_dynamic(ni, mpTracker->lastframe.DY_keypoints)) return 1;
+    if (map_out && !write_map(ni)) return 1;
   }
+  if (!write_cloud()) return 1;
   f.close(); f2.close();
   std::cout << std::endl << "trajectory saved!" << std::endl;
   std::sort(vTimesTrack.begin(), vTimesTrack.end());
