@@ -1501,7 +1501,7 @@ extern "C" void svo_elas_release(svo_ctx* ctx) {
   if (ctx->ev_elas_setup) { hipEventDestroy(ctx->ev_elas_setup); ctx->ev_elas_setup = nullptr; }
 }
 
-// Device-resident entry used by the tracker (svo_track.hip): images already in HBM, maps stay in HBM.
+// Device-resident entry used by the tracker (svo_track_entries.hip): images already in HBM, maps stay in HBM.
 int svo_elas_run_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitch, int W, int H,
                      const svo_elas_params* params, float** dD1, float** dD2, int* produced) {
   int rc = elas_check(ctx, W, H, pitch, *params);

@@ -325,6 +325,8 @@ int flush_set(svo_ctx* ctx, HostFeed* hf, int p) {
 // complete, staged ones are copied out).  include/svo.h promises all of it once the second following host-fed call has returned;
 // the work is two calls old, so the waits normally find it done.
 int reclaim_set(svo_ctx* ctx, HostFeed* hf, int p) {
+  // (a host-fed call begins: the tracker's staged lists and records that are two such calls old go out the same way, armed or not)
+  { const int rct = svo_track_host_out_call_begins(ctx); if (rct) return rct; }
   if (hf->used[p]) {
     for (int c = 0; c < hf->n_up[p]; ++c) SVO_HIP(ctx, hipEventSynchronize(hf->ev_up[p][c]));
     if (hf->done[p]) SVO_HIP(ctx, hipEventSynchronize(hf->done[p]));
@@ -339,8 +341,7 @@ int reclaim_set(svo_ctx* ctx, HostFeed* hf, int p) {
 // Everything the host-fed entries still owe the caller: records (and front-end outputs) that wait in pinned buffers are copied
 // into the arrays they were promised to.  Called by svo_sync, svo_track_reset, svo_destroy and before a set is reused.
 int svo_hostfeed_flush(svo_ctx* ctx) {
-  { const int rcd = svo_track_dyn_flush(ctx); if (rcd) return rcd; }   // (the dynamic-keypoint loop's lists, staged the same way)
-  { const int rcm = svo_track_map_flush(ctx); if (rcm) return rcm; }   // (svo_track_map_out's records, staged the same way)
+  { const int rct = svo_track_host_out_flush(ctx); if (rct) return rct; }   // (the dynamic-keypoint loop's lists and svo_track_map_out's records)
   HostFeed* hf = feed_of(ctx);
   if (!hf) return SVO_OK;
   for (int p = 0; p < 2; ++p) {

@@ -127,7 +127,7 @@ struct svo_ctx {
   uint8_t* h_stage = nullptr;      // pinned image staging of the host path: 2 x H x stage_pitch
   size_t pinned_bytes = 0;
 
-  // tracker state (svo_track.hip)
+  // tracker state (svo_track.hip and the svo_track_*.hip units around it)
   void* d_track = nullptr;      // n_seq TrackState records
   int n_seq = 0;
   // svo_track_multi_step_dev with svo_set_option("multi_pipeline", 1): the front end of step t + 1 runs beside the tail of
@@ -190,8 +190,8 @@ struct svo_ctx {
   void* msa_arenas = nullptr;   // MsaArenas: device buffers of svo_msa_solve and of the tracker's MSA mode
   void* sgbm = nullptr;         // SgbmArena (svo_sgbm.hip): cost / path volumes of svo_sgbm_* and of the tracker's SGBM mode
   void* lk = nullptr;           // LkArena (svo_lk.hip): pyramids, derivatives and point buffers of svo_lk_*
-  void* dyn = nullptr;          // DynState (svo_track.hip): the dynamic-keypoint loop inside the tracker, made by svo_track_dynamic
-  void* map = nullptr;          // MapState (svo_track.hip): svo_track_map_out's attachment and its staging, made by the first arming
+  void* dyn = nullptr;          // DynState (svo_track_dyn.hip): the dynamic-keypoint loop inside the tracker, made by svo_track_dynamic
+  void* map = nullptr;          // MapState (svo_track_map.hip): svo_track_map_out's attachment and its staging, made by the first arming
   float* d_dense = nullptr;     // dense maps of svo_track_batch_dev with depth_source 1: 2 x dense_cap x W*H
   int dense_cap = 0;
   svo_camera cam{};
@@ -276,6 +276,11 @@ int svo_launch_pose_opt(svo_ctx* ctx, const double* Xw, const double* obs, int n
 int svo_launch_pnp(svo_ctx* ctx, const double* Xw, const double* obs, int n, const double* K,
                    const double* Tfallback, const uint16_t* subset, void* hyp, double* T, uint8_t* mask,
                    svo_pnp_stats* stats);
+#define PNP_HYP 100        // cv::solvePnPRansac(..., iterationsCount = 100, ...) (reference src/pnpmatch.cc:227)
+struct PnpHyp {          // one RANSAC sample: EPnP pose of its five points and its consensus
+  double R[9], t[3];
+  int32_t cnt, ok;
+};
 size_t svo_pnp_hyp_bytes();
 int svo_launch_epnp5_probe(svo_ctx* ctx, const double* X5, const double* u5, const double* K, double* Rt, int reps);
 int svo_launch_epnp_gn_probe(svo_ctx* ctx, const double* L60, const double* rho6, const double* betas_in, double* betas_out);
@@ -299,8 +304,8 @@ struct MsaBfsRec { int32_t cpos, meta, ppos, node; };
 int svo_msa_tree_rec(const uint8_t* m_img3, const double* r_gra, const double* c_gra, int width, int height, MsaBfsRec* rec,
                      std::vector<int32_t>* level_ptr, int* maxw, int32_t* root);
 int svo_track_quiesce(svo_ctx* ctx, bool shard_too = true);   // waits for what overlapped tracker calls left in flight and may still read this context's arrays
-int svo_shard_quiesce(svo_ctx* ctx);   // svo_track.hip: the sharded tracker's part of that
-int svo_track_check_timeout(svo_ctx* ctx);   // svo_track.hip: sticky flag 4 in any sequence -> SVO_E_TIMEOUT (once per reset), fused pose launch off
+int svo_shard_quiesce(svo_ctx* ctx);   // svo_track_shard.hip: the sharded tracker's part of that
+int svo_track_check_timeout(svo_ctx* ctx);   // svo_track_debug.hip: sticky flag 4 in any sequence -> SVO_E_TIMEOUT (once per reset), fused pose launch off
 int svo_hostfeed_flush(svo_ctx* ctx);  // svo_hostfeed.hip: records / front-end outputs waiting in pinned buffers -> the caller's arrays
 void svo_hostfeed_release(svo_ctx* ctx);
 // svo_api.hip: a new stream (made by `make`) that runs side by side with every non-null stream of `others`, chosen by measuring
@@ -311,11 +316,11 @@ int svo_pick_stream(svo_ctx* ctx, const std::function<hipError_t(hipStream_t*)>&
                     int* attempts, int* percent, std::initializer_list<hipStream_t> holds_up = {}, std::initializer_list<hipStream_t> held_up_by = {});
 // a large grid in dispatch on `blocker` beside a chain of short kernels on `victim`: the chain's time in per cent of its time alone
 int svo_probe_block_percent(hipStream_t blocker, hipStream_t victim);
-int svo_track_fe_batch_stream(svo_ctx* ctx);   // svo_track.hip: creates ctx->stream_fe_batch (a stream that runs beside the tail's two chains)
+int svo_track_fe_batch_stream(svo_ctx* ctx);   // svo_track_entries.hip: creates ctx->stream_fe_batch (a stream that runs beside the tail's two chains)
 int svo_elas_batch_dev_hooked(svo_ctx* ctx, hipStream_t s, const uint8_t* d_L, const uint8_t* d_R, int stride, int W, int H, int B,
                               const svo_elas_params* params, float* d_D1, float* d_D2, int32_t* produced,
                               int (*hook)(void*, int, int), void* user);   // svo_elas.hip: svo_elas_batch_dev on stream `s`
-// svo_track.hip: svo_track_batch_dev / svo_track_sharded_dev for the host-fed entries (svo_hostfeed.hip), whose images arrive on a
+// svo_track_entries.hip / svo_track_shard.hip: svo_track_batch_dev / svo_track_sharded_dev for the host-fed entries (svo_hostfeed.hip), whose images arrive on a
 // copy stream: pair i of the call is resident in HBM after pair_ready[i] (context g's own pair i: pair_ready[g][i])
 // The colour (8UC3 BGR) pairs behind a call's gray ones (svo_track_batch_bgr_dev / _host): pair b at L / R + b * H * stride.
 // convert: the call writes the gray pairs itself from these, on the stream that reads them first (after waiting for `wait`);
@@ -332,7 +337,7 @@ struct SvoBgrSrc {
 int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
                         const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready,
                         const SvoBgrSrc* bgr = nullptr);
-// svo_track.hip: svo_track_frame once both gray images are in the context's staging slots 0 / 1 (d_bgrL / d_bgrR: the colour
+// svo_track_entries.hip: svo_track_frame once both gray images are in the context's staging slots 0 / 1 (d_bgrL / d_bgrR: the colour
 // pair in HBM for depth_source 2, `bgr_pitch` bytes per row; nullptr: MSA takes B = G = R copies of the gray)
 int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
                            const uint8_t* d_bgrR, int bgr_pitch);
@@ -353,7 +358,7 @@ extern "C" void svo_elas_release(svo_ctx* ctx);
 void svo_msa_release(svo_ctx* ctx);
 void svo_sgbm_release(svo_ctx* ctx);
 void svo_lk_release(svo_ctx* ctx);
-// svo_lk.hip: the LK machinery, for the tracker's dynamic-keypoint loop (svo_track.hip) as for svo_lk_* itself.  An arena holds the
+// svo_lk.hip: the LK machinery, for the tracker's dynamic-keypoint loop (svo_track_dyn.hip) as for svo_lk_* itself.  An arena holds the
 // pyramids and derivatives of a run of frames ("slots"), optionally their level-0 images, and the buffers of one track step.
 struct LkArena {
   uint8_t* img = nullptr;       // level-0 images the arena holds itself (svo_lk_track / svo_lk_track_bgr: the pair), rows cn W bytes apart
@@ -391,17 +396,18 @@ void lk_launch_track_seqs(hipStream_t s, LkArena* A, int cn, const uint8_t* img0
 // workgroup q = sequence q: everything q * (its row) further on, the counts arrays over the sequences (n_prev == nullptr: none)
 void lk_launch_compact_seqs(hipStream_t s, int nseq, const float* trk, const uint8_t* st, const int32_t* n_prev, const float* seeds,
                             const int32_t* n_seed, int max_seeds, int max_pts, float* list, int32_t* n_out, int32_t* dropped);
-// svo_track.hip: lists of the dynamic-keypoint loop that wait in pinned buffers -> the caller's host arrays (svo_hostfeed_flush)
-int svo_track_dyn_flush(svo_ctx* ctx);
-// svo_track.hip: svo_track_map_out's records that wait in pinned buffers -> the caller's host arrays (svo_hostfeed_flush)
-int svo_track_map_flush(svo_ctx* ctx);
-// svo_track.hip: SVO_E_INVALID with a message while svo_track_map_out is armed (the entries that do not deliver it); stays armed
+// svo_track_entries.hip: svo_track_dynamic_out's lists and svo_track_map_out's records that wait in pinned buffers -> the caller's
+// host arrays (the rule: svo_track_priv.h, HostStage).  All of them (svo_hostfeed_flush); those staged two or more host-fed calls
+// ago, when a host-fed call begins on the context (svo_hostfeed.hip, reclaim_set).  Not visible outside the library.
+__attribute__((visibility("hidden"))) int svo_track_host_out_flush(svo_ctx* ctx);
+__attribute__((visibility("hidden"))) int svo_track_host_out_call_begins(svo_ctx* ctx);
+// svo_track_map.hip: SVO_E_INVALID with a message while svo_track_map_out is armed (the entries that do not deliver it); stays armed
 int svo_track_map_refuse(svo_ctx* ctx, const char* who);
-// svo_track.hip: SVO_E_INVALID with a message while that loop is enabled (the entries that do not run it)
+// svo_track_dyn.hip: SVO_E_INVALID with a message while that loop is enabled (the entries that do not run it)
 int svo_track_dyn_refuse(svo_ctx* ctx, const char* who);
-// svo_track.hip: the same for the single-sequence entries while the loop in force was adopted by svo_track_multi_reset
+// svo_track_dyn.hip: the same for the single-sequence entries while the loop in force was adopted by svo_track_multi_reset
 int svo_track_dyn_refuse_single(svo_ctx* ctx, const char* who);
-// svo_track.hip: svo_track_multi_step_dev's work; `bgr` (svo_track_multi_step_bgr_dev): the step's colour pairs, whose gray this call
+// svo_track_entries.hip: svo_track_multi_step_dev's work; `bgr` (svo_track_multi_step_bgr_dev): the step's colour pairs, whose gray this call
 // writes to d_grayL / d_grayR on the stream its front end runs on - after bgr->wait, and bgr->done is recorded behind the front end
 int svo_track_multi_step_check(svo_ctx* ctx, const char* who, bool has_bgr);   // their refusals (loop adopted by svo_track_reset, depth_source, colour = 1 without colour)
 int svo_track_multi_step_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int n_seq,

@@ -479,7 +479,6 @@ struct LmShared {
   int done;
 };
 
-#define PNP_HYP 100        // cv::solvePnPRansac(..., iterationsCount = 100, ...) (reference src/pnpmatch.cc:227)
 #define PNP_MAXN 512       // correspondences per problem (one per keypoint at most)
 
 // LDS workspace of the pose-only LM
@@ -693,11 +692,6 @@ __device__ __forceinline__ void pose_opt_block(PoseLds& L, const double* __restr
 #include "svo_epnp_dev.h"
 #include "svo_epnp_exact_dev.h"
 #include "svo_epnp_ord_dev.h"
-
-struct PnpHyp {          // one RANSAC sample: EPnP pose of its five points and its consensus
-  double R[9], t[3];
-  int32_t cnt, ok;
-};
 
 // PnPRansacCallback::computeError for one point: projectPoints in double, rounded once to float, squared distance to
 // the float image point in float.  Inlier iff <= (float)(8 * 8).

@@ -41,6 +41,10 @@
 // (nearest last-frame descriptor of every keypoint) and k_tg_fmat (one wave: match filter, Hartley normalisation, normal
 // matrix, wave-parallel Jacobi, rank-2 projection; svo_fmat_dev.h).  Boxes arrive as HBM arrays in every mode
 // (svo_boxes_dev), nothing of a gated frame touches the host.
+//
+// This unit holds the kernels of both chains, their resources, tail_enqueue and the resets.  The entry points
+// (svo_track_entries.hip, svo_track_shard.hip), the two attachments (svo_track_dyn.hip, svo_track_map.hip) and the probes
+// (svo_track_debug.hip) are units of their own; svo_track_state.h and svo_track_priv.h hold what they share.
 #include <chrono>
 #include <cstddef>
 #include <initializer_list>
@@ -48,154 +52,12 @@
 #include <vector>
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 
-#include "svo_internal.h"
+#include "svo_track_priv.h"
 #include "svo_wave.h"
 #include "svo_gate.h"
 #include "svo_pose_dev.h"
 #include "svo_fmat_dev.h"
-
-#define TRK_MAXKP 512
-#define TRK_CAP 4096
-#define TRK_ROWS_MAX 3072        // live rows k_ti_lists can meet: 4 frames of local points + the last frame's, + slack
-#define TRK_LCAP 8               // packed entries (claimable columns) a pool row keeps; more -> the row is "dense"
-#define TRK_GPOS (1 << 20)       // map-point position table: ring over map-point ids
-#define TRK_DNC 24                // dense rows whose distance row is cached in LDS during a pass
-#define TRK_DENSE 0xFF           // ncand marker: more than `lcap` candidates, the row's distances are in D
-
-struct TrackPool {
-  alignas(16) uint32_t desc[TRK_CAP * 8];
-  int32_t create_id[TRK_CAP];
-  int32_t gid[TRK_CAP];          // map-point id = creation sequence number; positions live in gpos[gid % TRK_GPOS]
-  uint8_t bad[TRK_CAP];
-  uint8_t in_local[TRK_CAP];
-};
-
-// Samples of the fused pose launch whose completion the frame's workgroup waits for one by one: cv::solvePnPRansac's adaptive bound
-// ends within the first 8 samples on 96 % of the frames (a median of 4), and then the other 92 need not be waited for.
-#define TP_EARLY 8
-#define TP_FLAGS 16   // samples that announce themselves one by one (work->hyp_early)
-// What the index chain hands to the pose chain for one frame.
-// Written by k_ti_resolve with agent-scope (sc1) stores and published through `ready`, read by the pose kernels with agent-scope
-// loads after they have seen the tag: the pose chain does not wait on stream events for the index chain (see tp_wait_work).
-struct TrackWork {
-  int32_t ready;                 // = frame index + 1 once the record of that frame is complete (cleared by svo_track_reset)
-  int32_t frame_id, nkp, n_stereo, n_pass1, n_pass2, n_new, n_local, skip_match;
-  long long ts[8];               // diagnostics: s_memtime at begin / pass 1 / pass 2 / frame end / done, dense rows, late rows
-  long long rt[6];               // diagnostics: s_memrealtime (100 MHz, one clock for the chip) at k_ti_resolve start / end,
-                                 // k_tp_hyp start (its workgroup 0), k_tp_frame end, k_tp_frame start, and [5] a DURATION: fused
-                                 // launch, frame decided within the TP_EARLY awaited samples - from the latest of their announcement
-                                 // clocks (hyp_rt) to the LM's first build; 0 otherwise
-  int32_t diag[2];               // [0] rows of pass 1 | rounds << 16, [1] rows of pass 2 | rounds << 16
-  int32_t n_edges;               // 3D-2D correspondences of the frame (src/pnpmatch.cc:216-224), in keypoint order:
-  int32_t edge_gid[TRK_MAXKP];   //   id of the map point (CurrentFrame->MapPoints[j]->...) ...
-  int32_t edge_kp[TRK_MAXKP];    //   ... and the keypoint j it is matched to
-  int32_t new_gid[TRK_MAXKP];    // per keypoint: id of the map point created from it at the frame's end, or -1
-  // written by the pose chain (k_tp_frame), for svo_debug_track_frames: cv::solvePnPRansac's outcome and pose
-  int32_t pnp_best, pnp_iterations, pnp_inliers, pnp_ok;
-  double T_pnp[16];
-  int32_t hyp_done, pad_hyp;     // fused pose launch (k_tp_tail_ord): RANSAC samples of this frame that have stored their result
-  long long hyp_early[TP_FLAGS]; // ... and, for the first TP_FLAGS samples, ONE word once that sample's result is stored: frame id + 1 in
-                                 // the high half (ids only grow between two resets and a reset clears the records: a stale value never
-                                 // equals the current one), the sample's ok << 31 | consensus in the low half - whoever sees the
-                                 // announcement has the rule's inputs with it (tp_early_word)
-  long long hyp_rt[TP_EARLY];    // diagnostics: s_memrealtime of an awaited sample just before it announced itself (-> rt[5])
-};
-
-struct TrackState {
-  // ---- index chain -------------------------------------------------------------------------
-  int32_t frame_num, npool, lastN, cur;      // cur: active half of the pool ping-pong
-  int32_t next_gid, overflow, n_vetoed, n_boxes;
-  int32_t epnp_fallbacks, pad_counters[3];   // RANSAC samples of the default solver that took its sequential fallback (sticky count)
-  int32_t last_mp[TRK_MAXKP];
-  int32_t dbg_cur_mp[TRK_MAXKP];
-  svo_camera cam;
-  int32_t boxes[SVO_MAX_BOXES * 4];    // {left, right, top, bottom} of the current frame
-  double F[9];                         // fundamental matrix cur <- last (row-major)
-  float last_xy[TRK_MAXKP * 2];        // LastFrame.keypoints_l[i].pt
-  alignas(16) uint32_t last_desc[TRK_MAXKP * 8];   // LastFrame.f_descriptor
-  int32_t bf_idx[TRK_MAXKP], bf_dist[TRK_MAXKP], bf_min;
-  uint8_t bf_keep[TRK_MAXKP];
-  // ---- pose chain --------------------------------------------------------------------------
-  float lastTcw[16];
-  double Xw[TRK_MAXKP * 3], obs[TRK_MAXKP * 2], K[4], Tprior[16], T[16];
-  svo_lm_stats lm;
-  svo_pnp_stats pnp;
-  PnpHyp hyp[PNP_HYP];                 // the frame's RANSAC samples (k_tp_hyp)
-  long long pose_ts[16];               // diagnostics: s_memtime stamps of k_tp_hyp (0..7) and k_tp_frame (8..15)
-  // ---- large arrays (not cleared by a reset) -----------------------------------------------
-  TrackPool pool[2];
-  uint16_t rowmin[TRK_CAP];                // min over ALL current keypoints of the row's distances
-  uint8_t ncand[TRK_CAP];                  // packed entries of the row, or TRK_DENSE
-  uint32_t cand[(size_t)TRK_CAP * 2 * TRK_LCAP];   // packed entries, two words each (k_ti_lists), columns ascending
-  uint16_t D[(size_t)TRK_CAP * 512];       // full distance rows (written for every row that has an entry)
-  float gpos[(size_t)TRK_GPOS * 3];        // pose chain: world position of map point gid
-};
-
-// ---- block-wide exclusive scan (blockDim.x = 256 or 1024) -------------------------------------
-// wave64 inclusive scan on DPP (gfx9 row shifts + row broadcasts): six dependent VALU steps, no LDS crossbar
-__device__ __forceinline__ int tk_wave_incl_scan(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8  -> scan inside each row of 16
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
-  return v;
-}
-__device__ __forceinline__ int block_excl_scan(int v, int* sm /*[16], 16-byte aligned*/, int* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int incl = tk_wave_incl_scan(v);
-  const int nw = blockDim.x >> 6;
-  __syncthreads();
-  if (lane == 63) sm[wv] = incl;
-  __syncthreads();
-  const int4 a = reinterpret_cast<const int4*>(sm)[0], b = reinterpret_cast<const int4*>(sm)[1],
-             c = reinterpret_cast<const int4*>(sm)[2], d = reinterpret_cast<const int4*>(sm)[3];
-  const int t[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
-  int off = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 16; ++w) {
-    off += w < wv ? t[w] : 0;
-    tot += w < nw ? t[w] : 0;
-  }
-  *total = tot;
-  return off + incl - v;
-}
-
-__device__ __forceinline__ void tk_unproject(const svo_camera& cam, float u, float v, float z,
-                                             const float* Rwc, const float* twc, float* xyz) {
-  const float x = (u - cam.cx) * z * (1 / cam.fx);
-  const float y = (v - cam.cy) * z * (1 / cam.fy);
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const double acc = (double)Rwc[3 * r] * (double)x + (double)Rwc[3 * r + 1] * (double)y +
-                       (double)Rwc[3 * r + 2] * (double)z;
-    xyz[r] = (float)(acc + (double)twc[r]);
-  }
-}
-
-// ---- hand-over index chain -> pose chain without stream events -----------------------------------------------------------
-// The pose chain used to wait on one stream event per GROUP of frames (a wait costs ~3 us on the pose stream): whenever the
-// index chain's lead shrank below a group - runs of frames whose passes need 30-47 rounds - the pose chain of frames
-// g .. g + 3 stood still until frame g + 3 was matched (200-490 us per group, tools/gap_probe.py).  Now k_ti_resolve
-// publishes every frame's record itself: all of its fields go out with agent-scope (sc1) stores, every thread waits for its
-// own stores (s_waitcnt), and thread 0 then stores the frame's tag; the pose kernels are enqueued without any dependency on
-// the index stream, poll the tag with an agent-scope load and read the record with agent-scope loads.  No release / acquire
-// fence on either side: on gfx950 a release fence is buffer_wbl2 - a write-back of everything dirty in that XCD's L2, which
-// holds the pyramid data of the front end running beside the tail - and sc1 accesses reach the device-coherent level by
-// themselves.  The poll is bounded (~1 s): a lost hand-over sets the tracker's error flag instead of hanging the GPU.
-__device__ __forceinline__ int ld_agent(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ long long ld_agent(const long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(long long* p, long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#define TP_STORES_DONE() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-// work->hyp_early[k]: the frame's tag and the sample's outcome (ok << 31 | consensus) in one 8-byte word
-__device__ __forceinline__ long long tp_early_word(int frame_tag, unsigned ok_cnt) { return (long long)(((unsigned long long)(unsigned)frame_tag << 32) | ok_cnt); }
-__device__ __forceinline__ int tp_early_tag(long long w) { return (int)((unsigned long long)w >> 32); }
-__device__ __forceinline__ int tp_early_cnt(long long w) { return (int)((unsigned)w & 0x7fffffffu); }
-__device__ __forceinline__ int tp_early_ok(long long w) { return (int)(((unsigned)w >> 31) & 1u); }
 
 // ================================================================================================
 // Index chain 1/2: distances of every live pool row to the frame's keypoints -> sparse candidate lists
@@ -950,10 +812,6 @@ __global__ __launch_bounds__(64) void k_tg_fmat(TrackState* st, const svo_kp* kp
 // the pose chain: 122 against 117 us per frame in configs[4]).  blockIdx.y = frame of the group; the group's first frame must
 // not be the sequence's first (the caller starts groups at frame >= 1 of a call; frame 0 of a call keeps k_tg_bf / k_tg_fmat,
 // whose "last frame" is in the tracker state).  Results per frame in a GatePre record.
-struct GatePre {
-  int32_t bf_idx[TRK_MAXKP], bf_dist[TRK_MAXKP];
-  double F[9];
-};
 __global__ __launch_bounds__(256) void k_tg_bf_group(const uint32_t* desc, const int32_t* nkp_p, int kstride, const int32_t* nboxes,
                                                      GatePre* pre) {
   __shared__ uint32_t td[8 * TRK_MAXKP];
@@ -1564,69 +1422,10 @@ __global__ __launch_bounds__(TPF_NT) void k_tp_tail_ord(TrackState* st, TrackWor
   }
 }
 
-// ================================================================================================
-// The dynamic-keypoint loop inside the tracker (svo_track_dynamic): a frame's seeds
-// ================================================================================================
-// One workgroup behind the frame's k_ti_resolve on the index stream, one thread per keypoint.  The seeds the reference pushes to
-// DY_keypoints: Tracking::init (src/Tracking.cc:70-85, frame id 0) every keypoint strictly inside a box, then frame::createmappoint
-// (src/frame.cc:209-222) every keypoint strictly inside a box that has no map point after both matching passes - not in the
-// frame's correspondence list work->edge_kp[0 .. n_edges).  Both parts in keypoint order, the init part first, compacted by a
-// block-wide prefix sum; at frame 0 an inside keypoint appears in both.
-#define DYN_MAX_SEEDS (2 * TRK_MAXKP)
-__device__ __forceinline__ void td_seeds_body(const TrackWork* __restrict__ work, const svo_kp* __restrict__ kp,
-                                              const int32_t* __restrict__ boxes, const int32_t* __restrict__ nboxes,
-                                              float* __restrict__ seeds, int32_t* __restrict__ n_seed) {
-  __shared__ alignas(16) int sm[16];
-  __shared__ int sbox[SVO_MAX_BOXES * 4];
-  __shared__ uint8_t has_mp[TRK_MAXKP];
-  const int tid = threadIdx.x;
-  const int nkp = min(max(work->nkp, 0), TRK_MAXKP), n_edges = min(max(work->n_edges, 0), TRK_MAXKP);
-  const int n_boxes = (boxes && nboxes) ? min(max(*nboxes, 0), SVO_MAX_BOXES) : 0;
-  if (tid < 4 * n_boxes) sbox[tid] = boxes[tid];
-  has_mp[tid] = 0;
-  __syncthreads();
-  if (tid < n_edges) {
-    const int j = work->edge_kp[tid];
-    if (j >= 0 && j < TRK_MAXKP) has_mp[j] = 1;
-  }
-  __syncthreads();
-  bool inside = false;
-  float x = 0.f, y = 0.f;
-  if (tid < nkp) {
-    x = kp[tid].x; y = kp[tid].y;
-    for (int b = 0; b < n_boxes; ++b)
-      inside = inside || (x > (float)sbox[4 * b] && x < (float)sbox[4 * b + 1] && y > (float)sbox[4 * b + 2] && y < (float)sbox[4 * b + 3]);
-  }
-  const bool s_init = inside && work->frame_id == 0, s_create = inside && !has_mp[tid];
-  int n_init, n_create;
-  const int o_init = block_excl_scan(s_init ? 1 : 0, sm, &n_init);
-  const int o_create = n_init + block_excl_scan(s_create ? 1 : 0, sm, &n_create);
-  if (s_init) { seeds[2 * o_init] = x; seeds[2 * o_init + 1] = y; }
-  if (s_create) { seeds[2 * o_create] = x; seeds[2 * o_create + 1] = y; }   // (o_create < n_init + n_create <= 2 TRK_MAXKP)
-  if (tid == 0) *n_seed = n_init + n_create;
-}
-__global__ __launch_bounds__(TRK_MAXKP) void k_td_seeds(const TrackWork* __restrict__ work, const svo_kp* __restrict__ kp,
-                                                        const int32_t* __restrict__ boxes, const int32_t* __restrict__ nboxes,
-                                                        float* __restrict__ seeds, int32_t* __restrict__ n_seed) {
-  td_seeds_body(work, kp, boxes, nboxes, seeds, n_seed);
-}
-// Many sequences (svo_track_multi_step_dev): workgroup q = sequence q, behind the step's k_ti_resolve - its work record, keypoints
-// and boxes where the many-sequence kernels find them (q records, q * kstride keypoints, q * bstride boxes further on), seed list
-// q and seed count q.  A sequence without boxes (nboxes[q] == 0) writes count 0.
-__global__ __launch_bounds__(TRK_MAXKP) void k_td_seeds_seqs(const TrackWork* __restrict__ work, const svo_kp* __restrict__ kp, int kstride,
-                                                             const int32_t* __restrict__ boxes, const int32_t* __restrict__ nboxes,
-                                                             int bstride, float* __restrict__ seeds, int32_t* __restrict__ n_seed) {
-  const size_t q = blockIdx.x;
-  td_seeds_body(work + q, kp + q * kstride, boxes + q * bstride * 4, nboxes + q, seeds + q * 2 * DYN_MAX_SEEDS, n_seed + q);
-}
-
 // --------------------------------------------------------------------------------------------
 // Host side
 // --------------------------------------------------------------------------------------------
-static void shard_gather_free(svo_ctx* ctx);
-// The alternating front-end output sets (ms_out, tb_out): n sets of keypoints, descriptors and counts for `images` image slots and
-// depths - with `stereo_aux` also right x and SAD - for `pairs` pairs, K keypoints each.  A failed allocation leaves all n sets empty.
-static void fe_sets_free(SvoFeBufs* sets, int n) {
+void fe_sets_free(SvoFeBufs* sets, int n) {
   for (int q = 0; q < n; ++q) {
     SvoFeBufs& o = sets[q];
     if (o.kp) hipFree(o.kp);
@@ -1638,7 +1437,7 @@ static void fe_sets_free(SvoFeBufs* sets, int n) {
     o = SvoFeBufs{};
   }
 }
-static int fe_sets_alloc(SvoFeBufs* sets, int n, size_t images, size_t pairs, size_t K, bool stereo_aux) {
+int fe_sets_alloc(SvoFeBufs* sets, int n, size_t images, size_t pairs, size_t K, bool stereo_aux) {
   fe_sets_free(sets, n);
   for (int q = 0; q < n; ++q) {
     SvoFeBufs& o = sets[q];
@@ -1655,8 +1454,6 @@ static int fe_sets_alloc(SvoFeBufs* sets, int n, size_t images, size_t pairs, si
   }
   return SVO_OK;
 }
-static void dyn_release(svo_ctx* ctx);
-static void map_release(svo_ctx* ctx);
 void svo_track_release(svo_ctx* ctx) {
   shard_gather_free(ctx);
   dyn_release(ctx);
@@ -1695,69 +1492,15 @@ static int track_index_stream(svo_ctx* ctx) {
   return svo_pick_stream(ctx, [](hipStream_t* s) { return svo_stream_create(s, +1); }, {ctx->stream, ctx->stream_fe_batch}, &ctx->stream_idx,
                          &ctx->idx_probe_attempts, &ctx->idx_probe_spins, {}, {ctx->stream_fe_batch, ctx->stream_fe, ctx->stream_dense});
 }
-static void track_stream_diag(svo_ctx* ctx);
-// The batched tracker's front-end stream ("fe_cu_percent" of the CUs): side by side with both chains of the tail.
-int svo_track_fe_batch_stream(svo_ctx* ctx) {
-  if (ctx->stream_fe_batch) return SVO_OK;
-  const int dev = ctx->device, pct = ctx->opt_fe_cu_percent;
-  int attempts = 0, percent = 0;
-  const int rc = svo_pick_stream(ctx, [dev, pct](hipStream_t* s) { return pct < 100 ? svo_stream_create_masked(s, dev, pct) : svo_stream_create(s, -1); },
-                                 {ctx->stream, ctx->stream_idx}, &ctx->stream_fe_batch, &attempts, &percent,
-                                 {ctx->stream, ctx->stream_idx, ctx->stream_dense}, {ctx->stream_dense});   // (its grids wait for their eighth of the CUs: no chain, and not the dense stage, behind them)
-  if (rc == SVO_OK) { ctx->stream_diag_done = true; track_stream_diag(ctx); }
-  return rc;
-}
-
-// SVO_STREAM_DIAG=1: how long a grid of many small workgroups (the index chain's shape) takes on each of the tracker's streams, alone
-// and while front-end-like grids keep the front end's stream busy - printed once per context (docs/NEXT_ROUNDS.md, process states).
-__global__ void k_diag_spin(long long cycles) {
-  const long long t0 = clock64();
-  while (clock64() - t0 < cycles) __builtin_amdgcn_s_sleep(2);
-}
-static void track_stream_diag(svo_ctx* ctx) {
-  static const bool on = []() { const char* e = getenv("SVO_STREAM_DIAG"); return e && e[0] == '1'; }();
-  if (!on || !ctx->stream_idx || !ctx->stream_fe_batch) return;
-  hipStream_t ss[3] = {ctx->stream, ctx->stream_idx, ctx->stream_fe_batch};
-  const char* nm[3] = {"pose", "index", "front end"};
-  auto grid_us = [](hipStream_t q, int wgs, int threads, long long cyc) {
-    double best = 1e30;
-    for (int rep = 0; rep < 3; ++rep) {
-      hipStreamSynchronize(q);
-      const auto t0 = std::chrono::steady_clock::now();
-      hipLaunchKernelGGL(k_diag_spin, dim3(wgs), dim3(threads), 0, q, cyc);
-      hipStreamSynchronize(q);
-      best = std::min(best, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
-    }
-    return best;
-  };
-  for (int k = 0; k < 3; ++k) {
-    const double one = grid_us(ss[k], 1, 64, 4000), many = grid_us(ss[k], 3072, 64, 4000), big = grid_us(ss[k], 2048, 256, 40000);
-    double beside = 0;
-    if (k < 2) {
-      for (int i = 0; i < 4; ++i) hipLaunchKernelGGL(k_diag_spin, dim3(4096), dim3(256), 0, ss[2], 100000LL);
-      beside = grid_us(ss[k], 3072, 64, 4000);
-      hipStreamSynchronize(ss[2]);
-    }
-    fprintf(stderr, "[svo stream diag] ctx %p %-9s stream %p: 1 workgroup %.0f us, 3072 x 64 threads %.0f us, 2048 x 256 threads (18 us each) %.0f us, 3072 x 64 beside front-end grids %.0f us\n",
-            (void*)ctx, nm[k], (void*)ss[k], one, many, big, beside);
-  }
-  (void)hipGetLastError();
-}
-
 static size_t tail_lds_bytes() {
   static const size_t v = []() { const char* e = getenv("SVO_TAIL_LDS_KB"); const size_t kb = e ? (size_t)atoi(e) : 0; return std::max(sizeof(TpTailLds), kb << 10); }();
   return v;
 }
-// streams, events, work records and the kernels' LDS opt-ins for `frames` frames per call of `nseq` sequences
-static int track_resources(svo_ctx* ctx, int frames, int nseq) {
+int track_resources(svo_ctx* ctx, int frames, int nseq) {
   if (!ctx->stream_idx) { const int rcs = track_index_stream(ctx); if (rcs) return rcs; }
   if (!ctx->stream_diag_done) { ctx->stream_diag_done = true; track_stream_diag(ctx); }   // (SVO_STREAM_DIAG=1; once per context)
   if (!ctx->ev_frontend) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_frontend, hipEventDisableTiming));
-  while ((int)ctx->ev_frame.size() < frames) {
-    hipEvent_t e;
-    SVO_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ctx->ev_frame.push_back(e);
-  }
+  SVO_HIP(ctx, track_events_reserve(ctx->ev_frame, frames));
   const int need = std::max(frames, nseq);
   if (ctx->work_cap < need) {
     SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1792,430 +1535,6 @@ static int track_resources(svo_ctx* ctx, int frames, int nseq) {
   return ctx->track_lds_state > 0 ? SVO_OK : SVO_E_HIP;
 }
 
-// ---- the dynamic-keypoint loop inside the tracker (svo_track_dynamic) ------------------------------------------------------
-// list(f) = list(f - 1) tracked from left image f - 1 into left image f (k_lk_track) with the status-0 points erased, then the
-// frame's seeds (k_td_seeds) while the list has room (k_lk_compact) - svo_lk_chain_dev's loop, driven here frame by frame on the
-// INDEX stream: a group's seed kernels sit behind their k_ti_resolve; its track + compact steps - and, once per sub-batch of the
-// front end, the level-0 copies, pyramids and derivatives of that sub-batch's left images - behind the group's ev_frame record,
-// so the pose chain's wait is never behind LK work.  Everything of the loop is
-// ordered by that one stream; the pose stream joins it once, at the end of a call (what svo_sync and the calls' result copies
-// wait for then covers the lists).  The left images live in an arena of this state: a ring of slots in which slot `pos` is the
-// previous frame - a later call never reads an earlier call's image buffers.
-enum DynMode { DYN_NONE = 0, DYN_SINGLE, DYN_MULTI };   // which reset adopted the loop in force: svo_track_reset / svo_track_multi_reset
-struct DynOut { float* lists = nullptr; int32_t *counts = nullptr, *dropped = nullptr; };
-struct DynState {
-  svo_dyn_params next{};        // svo_track_dynamic's: adopted by the next reset
-  svo_dyn_params p{};           // in force
-  bool active = false;
-  DynMode mode = DYN_NONE;
-  int cn = 1, top = 0, cap = 0, slots = 0, pos = 0;   // cap: frames per call; slots of the arena, `pos` holds the previous left image
-  // many sequences (DYN_MULTI, see dyn_multi_step): cap = n_seq, the arena's 2 n_seq slots and the 2 n_seq lists are two halves that
-  // alternate by step - `half` holds the previous step's left images and lists; d_ints: counts of half 0, counts of half 1, dropped,
-  // seed counts, n_seq zeros (the seed counts of a step that cannot seed)
-  int half = 0;
-  bool in_step = false;
-  hipEvent_t ev_img = nullptr;  // behind a step's copy of its left images into the arena (index stream)
-  bool ev_img_valid = false;
-  int built_until = 0;          // frames of the tail call being enqueued whose images, pyramids and derivatives are in the arena (slots pos + 1 ..)
-  void* arena = nullptr;        // LkArena of its own (the context's serves svo_lk_*)
-  float *d_lists = nullptr, *d_seeds = nullptr;   // (cap + 1) lists, list 0 = the last one of the call before; cap seed lists
-  int32_t* d_ints = nullptr;    // cap + 1 counts, cap + 1 dropped, cap + 1 seed counts (the last one stays 0: a frame that cannot seed)
-  hipEvent_t ev_lk = nullptr;   // behind a call's last LK step (index stream)
-  bool ev_lk_valid = false;
-  DynOut out; bool attached = false;              // svo_track_dynamic_out, for the next call
-  // the call being enqueued
-  bool in_call = false, cur_on = false, cur_host = false, cur_direct = false;
-  DynOut cur; int cur_off = 0, cur_q = 0;
-  const uint8_t* src = nullptr; int src_stride = 0;   // its left images, cn channels: image i at src + i * H * src_stride
-  // lists for host arrays of the batched entries wait in pinned memory, two sets alternate between calls
-  float* h_lists[2] = {nullptr, nullptr}; int32_t* h_ints[2] = {nullptr, nullptr};
-  hipEvent_t ev_out[2] = {nullptr, nullptr};
-  DynOut pending[2]; int pending_n[2] = {0, 0}; int hparity = 0;
-  int32_t* counts() const { return d_ints; }
-  int32_t* dropped() const { return d_ints + cap + 1; }
-  int32_t* nseed() const { return d_ints + 2 * (cap + 1); }
-  // DYN_MULTI's layout of d_ints (5 cap entries): counts of list half h, dropped, seed counts, zeros
-  int32_t* m_counts(int h) const { return d_ints + (size_t)h * cap; }
-  int32_t* m_dropped() const { return d_ints + 2 * (size_t)cap; }
-  int32_t* m_nseed() const { return d_ints + 3 * (size_t)cap; }
-  int32_t* m_zeros() const { return d_ints + 4 * (size_t)cap; }
-};
-static DynState* dyn_of(svo_ctx* ctx) { return reinterpret_cast<DynState*>(ctx->dyn); }
-static bool dyn_active(const svo_ctx* ctx) { return ctx->dyn && reinterpret_cast<const DynState*>(ctx->dyn)->active; }
-static void dyn_free_buffers(DynState* D) {
-  lk_arena_free(&D->arena);
-  if (D->d_lists) hipFree(D->d_lists);
-  if (D->d_seeds) hipFree(D->d_seeds);
-  if (D->d_ints) hipFree(D->d_ints);
-  D->d_lists = D->d_seeds = nullptr; D->d_ints = nullptr;
-  for (int q = 0; q < 2; ++q) {
-    if (D->h_lists[q]) hipHostFree(D->h_lists[q]);
-    if (D->h_ints[q]) hipHostFree(D->h_ints[q]);
-    D->h_lists[q] = nullptr; D->h_ints[q] = nullptr; D->pending[q] = DynOut{}; D->pending_n[q] = 0;
-  }
-  D->cap = 0; D->slots = 0;
-}
-static void dyn_release(svo_ctx* ctx) {
-  DynState* D = dyn_of(ctx);
-  if (!D) return;
-  dyn_free_buffers(D);
-  if (D->ev_lk) hipEventDestroy(D->ev_lk);
-  if (D->ev_img) hipEventDestroy(D->ev_img);
-  for (hipEvent_t e : D->ev_out) if (e) hipEventDestroy(e);
-  delete D;
-  ctx->dyn = nullptr;
-}
-static int dyn_flush_set(svo_ctx* ctx, DynState* D, int q) {
-  if (!D->pending_n[q]) return SVO_OK;
-  SVO_HIP(ctx, hipEventSynchronize(D->ev_out[q]));
-  const size_t n = (size_t)D->pending_n[q], mp = (size_t)D->p.max_pts;
-  memcpy(D->pending[q].lists, D->h_lists[q], n * 2 * mp * sizeof(float));
-  memcpy(D->pending[q].counts, D->h_ints[q], n * sizeof(int32_t));
-  if (D->pending[q].dropped) memcpy(D->pending[q].dropped, D->h_ints[q] + D->cap, n * sizeof(int32_t));
-  D->pending_n[q] = 0;
-  return SVO_OK;
-}
-int svo_track_dyn_flush(svo_ctx* ctx) {
-  DynState* D = dyn_of(ctx);
-  if (!D) return SVO_OK;
-  for (int q = 0; q < 2; ++q) { const int rc = dyn_flush_set(ctx, D, q); if (rc) return rc; }
-  return SVO_OK;
-}
-// svo_track_reset (multi_nseq = 0) / svo_track_multi_reset (its n_seq), every stream idle: svo_track_dynamic's parameters come into
-// force for that kind of reset, the lists are empty.  Everything is sized here, once: one sequence - max_batch frames per call and
-// a ring of slots; many - the two halves of n_seq slots and lists
-static int dyn_adopt(svo_ctx* ctx, int multi_nseq) {
-  DynState* D = dyn_of(ctx);
-  if (!D) return SVO_OK;
-  D->attached = false; D->in_call = false; D->ev_lk_valid = false; D->pos = 0; D->hparity = 0;
-  D->in_step = false; D->ev_img_valid = false; D->half = 0;
-  if (!D->next.enable) {
-    if (D->active) dyn_free_buffers(D);
-    D->active = false; D->mode = DYN_NONE; D->p = D->next;
-    return SVO_OK;
-  }
-  const int W = ctx->g.W, H = ctx->g.H, cn = D->next.colour ? 3 : 1, top = lk_top_level(W, H, D->next.lk.maxLevel);
-  const DynMode mode = multi_nseq > 0 ? DYN_MULTI : DYN_SINGLE;
-  const bool many = mode == DYN_MULTI;
-  const int cap = many ? multi_nseq : std::max(ctx->max_batch, 1), slots = many ? 2 * cap : std::min(cap, 64) + 1;
-  const size_t n_ints = many ? 5 * (size_t)cap : 3 * (size_t)(cap + 1);
-  if (!D->active || mode != D->mode || cn != D->cn || top != D->top || D->next.max_pts != D->p.max_pts || cap != D->cap) {
-    dyn_free_buffers(D);
-    D->active = false; D->mode = DYN_NONE;
-    LkArena* A = nullptr;
-    const size_t mp = (size_t)D->next.max_pts;
-    int rc = lk_reserve_in(ctx, &D->arena, ctx->stream, W, H, cn, top, slots, many ? mp * cap : mp, slots, &A);
-    if (rc) { dyn_free_buffers(D); return rc; }
-    A->last = nullptr;   // (sized once: nothing ever grows it while work is in flight)
-    const size_t n_lists = many ? 2 * (size_t)cap : (size_t)(cap + 1);
-    if (hipMalloc(reinterpret_cast<void**>(&D->d_lists), n_lists * 2 * mp * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&D->d_seeds), (size_t)cap * 2 * DYN_MAX_SEEDS * sizeof(float)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&D->d_ints), n_ints * sizeof(int32_t)) != hipSuccess) {
-      (void)hipGetLastError();
-      dyn_free_buffers(D);
-      ctx->last_error = "svo_track_dynamic: device allocation failed";
-      return SVO_E_NOMEM;
-    }
-    D->cn = cn; D->top = top; D->cap = cap; D->slots = slots;
-    if (!D->ev_lk) SVO_HIP(ctx, hipEventCreateWithFlags(&D->ev_lk, hipEventDisableTiming));
-    if (!D->ev_img) SVO_HIP(ctx, hipEventCreateWithFlags(&D->ev_img, hipEventDisableTiming));
-    for (int q = 0; q < 2; ++q)
-      if (!D->ev_out[q]) SVO_HIP(ctx, hipEventCreateWithFlags(&D->ev_out[q], hipEventDisableTiming));
-  }
-  D->p = D->next;
-  SVO_HIP(ctx, hipMemsetAsync(D->d_ints, 0, n_ints * sizeof(int32_t), ctx->stream));   // (the caller waits for the stream)
-  D->active = true; D->mode = mode;
-  return SVO_OK;
-}
-// A tracker entry that runs the loop starts a call: its left images (cn channels, consecutive images H * stride bytes apart), and
-// where svo_track_dynamic_out's arrays live - `host`: host memory, `direct`: the entry synchronises before it returns
-static int dyn_begin(svo_ctx* ctx, const uint8_t* src, int stride, bool host, bool direct) {
-  DynState* D = dyn_of(ctx);
-  D->in_call = true; D->src = src; D->src_stride = stride; D->cur_off = 0; D->built_until = 0;
-  D->cur = D->out; D->cur_on = D->attached; D->cur_host = host; D->cur_direct = direct;
-  D->attached = false; D->out = DynOut{};
-  if (D->cur_on && host && !direct) {
-    const int q = D->hparity;
-    D->cur_q = q; D->hparity ^= 1;
-    const int rc = dyn_flush_set(ctx, D, q);   // (what the call two back left in this set)
-    if (rc) return rc;
-    if (!D->h_lists[q]) {
-      if (hipHostMalloc(reinterpret_cast<void**>(&D->h_lists[q]), (size_t)D->cap * 2 * D->p.max_pts * sizeof(float)) != hipSuccess ||
-          hipHostMalloc(reinterpret_cast<void**>(&D->h_ints[q]), 2 * (size_t)D->cap * sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->last_error = "svo_track_dynamic_out: out of pinned memory";
-        return SVO_E_NOMEM;
-      }
-    }
-  }
-  return SVO_OK;
-}
-static void dyn_end(svo_ctx* ctx) {
-  DynState* D = dyn_of(ctx);
-  D->in_call = false; D->cur_on = false; D->cur = DynOut{}; D->src = nullptr;
-}
-static bool dyn_can_seed(const DynState* D, int id) { return D->p.seed_frames < 0 || id < D->p.seed_frames; }
-// frames f0 .. f1 - 1 of the tail call being enqueued (`frames` in all), whose index kernels (and seed kernels) are on `s`: track +
-// compact frame by frame.  Images go into the arena, with their pyramids and derivatives, AHEAD of the steps: as far as the
-// stream has already waited for the call's images - to the end of the front end's sub-batch (the next non-null fe_events entry),
-// so that a sub-batch costs the index stream one set of launches, not one per group.  id0: frame 0 of the tail call counted
-// from the reset
-static int dyn_enqueue_group(svo_ctx* ctx, DynState* D, hipStream_t s, int f0, int f1, int id0, bool boxes, const hipEvent_t* fe_events,
-                             int frames) {
-  LkArena* A = static_cast<LkArena*>(D->arena);
-  const int W = ctx->g.W, H = ctx->g.H, cn = D->cn, mp = D->p.max_pts;
-  const size_t row = (size_t)cn * W, img = row * H;
-  size_t pyr_px, der_px;
-  lk_slot_px(W, H, D->top, &pyr_px, &der_px);
-  int f = f0;
-  while (f < f1) {
-    if (f >= D->built_until) {   // (every built frame has had its step: slot `pos` is frame f - 1)
-      int e = f1;
-      while (e < frames && !(fe_events && fe_events[e])) ++e;
-      const int n = std::min(e - f, D->slots - 1);
-      if (D->pos + n > D->slots - 1) {   // the ring is used up: the previous frame moves to slot 0
-        const size_t q = (size_t)D->pos;
-        SVO_HIP(ctx, hipMemcpyAsync(A->img, A->img + q * img, img, hipMemcpyDeviceToDevice, s));
-        if (pyr_px) SVO_HIP(ctx, hipMemcpyAsync(A->pyr, A->pyr + q * cn * pyr_px, cn * pyr_px, hipMemcpyDeviceToDevice, s));
-        SVO_HIP(ctx, hipMemcpyAsync(A->der, A->der + q * cn * der_px, cn * der_px * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        D->pos = 0;
-      }
-      const size_t first = (size_t)D->pos + 1;
-      SVO_HIP(ctx, hipMemcpy2DAsync(A->img + first * img, row, D->src + (size_t)(D->cur_off + f) * H * D->src_stride, D->src_stride, row,
-                                    (size_t)H * n, hipMemcpyDeviceToDevice, s));
-      LkArena V = *A;   // the slots from `first` on
-      V.pyr += first * cn * pyr_px; V.der += first * cn * der_px;
-      lk_build(s, &V, cn, A->img + first * img, (int)row, img, W, H, D->top, n, 0, n);
-      D->built_until = f + n;
-    }
-    for (const int stop = std::min(f1, D->built_until); f < stop; ++f) {
-      const int id = id0 + f;
-      const bool seeds = boxes && dyn_can_seed(D, id);
-      if (id > 0)
-        lk_launch_track(s, A, cn, A->img, (int)row, img, W, H, D->top, D->pos, 1, D->d_lists + (size_t)f * 2 * mp, D->counts() + f, 0, mp,
-                        A->next, A->status, nullptr);
-      lk_launch_compact(s, A->next, A->status, id > 0 ? D->counts() + f : nullptr, D->d_seeds + (size_t)f * 2 * DYN_MAX_SEEDS,
-                        D->nseed() + (seeds ? f : D->cap), DYN_MAX_SEEDS, mp, D->d_lists + (size_t)(f + 1) * 2 * mp, D->counts() + f + 1,
-                        D->dropped() + f + 1);
-      ++D->pos;
-    }
-  }
-  return SVO_OK;
-}
-// the end of a tail call of `frames` frames: its lists to the attached arrays, its last list to list 0, the pose stream joins
-static int dyn_finish(svo_ctx* ctx, DynState* D, hipStream_t s, hipStream_t pose, int frames) {
-  const size_t mp = (size_t)D->p.max_pts, off = (size_t)D->cur_off, n = (size_t)frames;
-  if (D->cur_on) {
-    const bool staged = D->cur_host && !D->cur_direct;
-    const int q = D->cur_q;
-    float* lists = staged ? D->h_lists[q] : D->cur.lists;
-    int32_t* counts = staged ? D->h_ints[q] : D->cur.counts;
-    int32_t* dropped = staged ? D->h_ints[q] + D->cap : D->cur.dropped;
-    const hipMemcpyKind kind = D->cur_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    SVO_HIP(ctx, hipMemcpyAsync(lists + off * 2 * mp, D->d_lists + 2 * mp, n * 2 * mp * sizeof(float), kind, s));
-    SVO_HIP(ctx, hipMemcpyAsync(counts + off, D->counts() + 1, n * sizeof(int32_t), kind, s));
-    if (dropped) SVO_HIP(ctx, hipMemcpyAsync(dropped + off, D->dropped() + 1, n * sizeof(int32_t), kind, s));
-    if (staged) {
-      SVO_HIP(ctx, hipEventRecord(D->ev_out[q], s));
-      D->pending[q] = D->cur; D->pending_n[q] = (int)(off + n);
-    }
-  }
-  SVO_HIP(ctx, hipMemcpyAsync(D->d_lists, D->d_lists + n * 2 * mp, 2 * mp * sizeof(float), hipMemcpyDeviceToDevice, s));
-  SVO_HIP(ctx, hipMemcpyAsync(D->counts(), D->counts() + n, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  D->cur_off += frames; D->built_until = 0;
-  SVO_HIP(ctx, hipEventRecord(D->ev_lk, s));
-  SVO_HIP(ctx, hipStreamWaitEvent(pose, D->ev_lk, 0));
-  D->ev_lk_valid = true;
-  return SVO_OK;
-}
-// the entries that have no such loop refuse while it is enabled
-int svo_track_dyn_refuse(svo_ctx* ctx, const char* who) {
-  if (!dyn_active(ctx)) return SVO_OK;
-  ctx->last_error = std::string(who) + ": the dynamic-keypoint loop is enabled on this context (svo_track_dynamic); this entry does not run it";
-  return SVO_E_INVALID;
-}
-// The loop's state belongs to the kind of reset that adopted it (svo_track_reset and svo_track_multi_reset(1) are otherwise the
-// same call): the entries of the other kind refuse in the same way
-int svo_track_dyn_refuse_single(svo_ctx* ctx, const char* who) {
-  if (!dyn_active(ctx) || dyn_of(ctx)->mode != DYN_MULTI) return SVO_OK;
-  ctx->last_error = std::string(who) + ": the dynamic-keypoint loop on this context was adopted by svo_track_multi_reset; only the many-sequence entries run it";
-  return SVO_E_INVALID;
-}
-static int dyn_refuse_multi(svo_ctx* ctx, const char* who) {
-  if (!dyn_active(ctx) || dyn_of(ctx)->mode == DYN_MULTI) return SVO_OK;
-  return svo_track_dyn_refuse(ctx, who);   // (adopted by svo_track_reset: today's refusal, today's words)
-}
-// One step of the many-sequence loop, on the index stream `s` behind the step's ev_frame record (the pose chain's wait is never
-// behind LK work): ONE 2-D copy of the n_seq left images into the arena half that is not the previous step's, one lk_build over
-// them (their derivatives serve the NEXT step, when they are the previous images), one track launch over the n_seq pairs
-// (previous half's slot q, this half's slot q) - none at id 0 -, one compact launch of n_seq workgroups.  Everything of the loop
-// is ordered by this one stream, so step t + 1's copy into the half step t's track launch read as "previous" cannot overtake it,
-// with or without "multi_pipeline".  `seeded`: the step's k_td_seeds_seqs ran (behind its k_ti_resolve).
-static int dyn_multi_step(svo_ctx* ctx, DynState* D, hipStream_t s, int id, bool seeded) {
-  LkArena* A = static_cast<LkArena*>(D->arena);
-  const int W = ctx->g.W, H = ctx->g.H, cn = D->cn, mp = D->p.max_pts, nseq = D->cap;
-  const size_t row = (size_t)cn * W, img = row * H;
-  size_t pyr_px, der_px;
-  lk_slot_px(W, H, D->top, &pyr_px, &der_px);
-  const int prev = D->half, cur = prev ^ 1;
-  const size_t first = (size_t)cur * nseq;
-  SVO_HIP(ctx, hipMemcpy2DAsync(A->img + first * img, row, D->src, D->src_stride, row, (size_t)H * nseq, hipMemcpyDeviceToDevice, s));
-  SVO_HIP(ctx, hipEventRecord(D->ev_img, s));   // (a colour step's gray staging may be written anew from here on)
-  D->ev_img_valid = true;
-  LkArena V = *A;   // this half's slots
-  V.pyr += first * cn * pyr_px; V.der += first * cn * der_px;
-  lk_build(s, &V, cn, A->img + first * img, (int)row, img, W, H, D->top, nseq, 0, nseq);
-  int32_t *n_prev = D->m_counts(prev), *n_cur = D->m_counts(cur), *dropped = D->m_dropped(), *n_seed = D->m_nseed(), *zeros = D->m_zeros();
-  float *l_prev = D->d_lists + (size_t)prev * nseq * 2 * mp, *l_cur = D->d_lists + (size_t)cur * nseq * 2 * mp;
-  if (id > 0)
-    lk_launch_track_seqs(s, A, cn, A->img, (int)row, img, W, H, D->top, prev * nseq, cur * nseq, nseq, l_prev, n_prev, mp, A->next, A->status);
-  lk_launch_compact_seqs(s, nseq, A->next, A->status, id > 0 ? n_prev : nullptr, D->d_seeds, seeded ? n_seed : zeros, DYN_MAX_SEEDS, mp, l_cur,
-                         n_cur, dropped);
-  if (D->cur_on) {   // svo_track_dynamic_out: sequence q's list at lists + q * 2 max_pts, counts[q], dropped[q]
-    SVO_HIP(ctx, hipMemcpyAsync(D->cur.lists, l_cur, (size_t)nseq * 2 * mp * sizeof(float), hipMemcpyDeviceToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(D->cur.counts, n_cur, (size_t)nseq * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    if (D->cur.dropped) SVO_HIP(ctx, hipMemcpyAsync(D->cur.dropped, dropped, (size_t)nseq * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  }
-  D->half = cur;
-  SVO_HIP(ctx, hipEventRecord(D->ev_lk, s));   // (the pose stream joins behind the step's pose kernels: tail_enqueue)
-  D->ev_lk_valid = true;
-  return SVO_OK;
-}
-
-// ---- each tracked frame's map points and observations (svo_track_map_out) ---------------------------------------------------
-// A one-shot attachment like svo_track_dynamic_out, without state of its own: ONE launch (k_tm_obs, at the end of this file) of one
-// workgroup per frame behind the call's last pose launch on the pose stream, which reads what the call left in HBM anyway - the
-// frames' work records (edge list, new_gid), the call's keypoint and depth arrays, the position table - and writes the records in
-// keypoint order.  On the pose stream, inside tail_enqueue: every event that lets a later call's index chain rewrite this half of
-// the work records or this front-end output set (ev_frontend at the next call's start, tb_done[p] / the callers' own events behind
-// tail_enqueue) is recorded on that stream after it.  Host destinations (svo_track_frame, the _host entries): the kernel writes
-// staging in HBM, a copy on the pose stream takes it to one of two pinned sets, and the flush hands each frame's counts[f]
-// records to the caller's array - at the entry's end (svo_track_frame has synchronised) or with the host-fed records (svo_hostfeed_flush).
-__global__ __launch_bounds__(TRK_MAXKP) void k_tm_obs(const TrackState* st, const TrackWork* work, const svo_kp* kp, const float* depth, int kstride, int tag0,
-                         int max_kp, svo_map_obs* obs, int32_t* counts);
-struct MapOut { svo_map_obs* obs = nullptr; int32_t* counts = nullptr; };
-struct MapState {
-  MapOut out; bool attached = false;        // svo_track_map_out, for the next call
-  // the call being enqueued
-  bool in_call = false, cur_host = false;
-  MapOut cur; int cur_off = 0, cur_q = 0;
-  // host destinations: staging in HBM for `cap` frames, two pinned sets that alternate between calls
-  int cap = 0;
-  svo_map_obs* d_obs = nullptr; int32_t* d_counts = nullptr;
-  svo_map_obs* h_obs[2] = {nullptr, nullptr}; int32_t* h_counts[2] = {nullptr, nullptr};
-  hipEvent_t ev_out[2] = {nullptr, nullptr};
-  MapOut pending[2]; int pending_n[2] = {0, 0}; int hparity = 0;
-};
-static MapState* map_of(svo_ctx* ctx) { return reinterpret_cast<MapState*>(ctx->map); }
-static void map_release(svo_ctx* ctx) {
-  MapState* M = map_of(ctx);
-  if (!M) return;
-  if (M->d_obs) hipFree(M->d_obs);
-  if (M->d_counts) hipFree(M->d_counts);
-  for (int q = 0; q < 2; ++q) {
-    if (M->h_obs[q]) hipHostFree(M->h_obs[q]);
-    if (M->h_counts[q]) hipHostFree(M->h_counts[q]);
-    if (M->ev_out[q]) hipEventDestroy(M->ev_out[q]);
-  }
-  delete M;
-  ctx->map = nullptr;
-}
-static int map_flush_set(svo_ctx* ctx, MapState* M, int q) {
-  if (!M->pending_n[q]) return SVO_OK;
-  SVO_HIP(ctx, hipEventSynchronize(M->ev_out[q]));
-  const size_t K = (size_t)ctx->max_kp;
-  for (int f = 0; f < M->pending_n[q]; ++f) {   // (a frame's records only: what lies behind them in the caller's array stays as it is)
-    const int n = std::min(std::max(M->h_counts[q][f], 0), ctx->max_kp);
-    M->pending[q].counts[f] = n;
-    memcpy(M->pending[q].obs + (size_t)f * K, M->h_obs[q] + (size_t)f * K, (size_t)n * sizeof(svo_map_obs));
-  }
-  M->pending_n[q] = 0;
-  return SVO_OK;
-}
-int svo_track_map_flush(svo_ctx* ctx) {
-  MapState* M = map_of(ctx);
-  if (!M) return SVO_OK;
-  for (int q = 0; q < 2; ++q) { const int rc = map_flush_set(ctx, M, q); if (rc) return rc; }
-  return SVO_OK;
-}
-// the entries that do not deliver it refuse while it is armed - and leave it armed
-int svo_track_map_refuse(svo_ctx* ctx, const char* who) {
-  if (!ctx->map || !map_of(ctx)->attached) return SVO_OK;
-  ctx->last_error = std::string(who) + ": svo_track_map_out is armed on this context; this entry does not deliver map observations";
-  return SVO_E_INVALID;
-}
-// A tracker entry that delivers the records starts a call; `host`: svo_track_map_out's arrays are host memory
-static int map_begin(svo_ctx* ctx, bool host) {
-  MapState* M = map_of(ctx);
-  if (!M || !M->attached) return SVO_OK;
-  M->cur = M->out; M->cur_host = host; M->cur_off = 0;
-  M->attached = false; M->out = MapOut{};
-  if (host) {
-    const int q = M->hparity;
-    M->cur_q = q; M->hparity ^= 1;
-    const int rc = map_flush_set(ctx, M, q);   // (what the call two back left in this set)
-    if (rc) return rc;
-    const size_t cap = (size_t)std::max(ctx->max_batch, 1), K = (size_t)ctx->max_kp;
-    bool ok = true;
-    if (!M->d_obs) {
-      ok = hipMalloc(reinterpret_cast<void**>(&M->d_obs), cap * K * sizeof(svo_map_obs)) == hipSuccess &&
-           hipMalloc(reinterpret_cast<void**>(&M->d_counts), cap * sizeof(int32_t)) == hipSuccess;
-      M->cap = (int)cap;
-    }
-    if (ok && !M->h_obs[q])
-      ok = hipHostMalloc(reinterpret_cast<void**>(&M->h_obs[q]), cap * K * sizeof(svo_map_obs)) == hipSuccess &&
-           hipHostMalloc(reinterpret_cast<void**>(&M->h_counts[q]), cap * sizeof(int32_t)) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      ctx->last_error = "svo_track_map_out: out of memory for the staging of host arrays";
-      return SVO_E_NOMEM;
-    }
-    if (!M->ev_out[q]) SVO_HIP(ctx, hipEventCreateWithFlags(&M->ev_out[q], hipEventDisableTiming));
-  }
-  M->in_call = true;
-  return SVO_OK;
-}
-// `direct`: the entry has synchronised the pose stream (svo_track_frame) - the caller's arrays are complete when it returns
-static int map_end(svo_ctx* ctx, bool direct, int rc) {
-  MapState* M = map_of(ctx);
-  if (!M || !M->in_call) return rc;
-  M->in_call = false; M->cur = MapOut{};
-  if (direct && M->cur_host) { const int rcf = map_flush_set(ctx, M, M->cur_q); if (rc == SVO_OK) rc = rcf; }
-  return rc;
-}
-// the end of a tail call of `frames` frames (tail_enqueue's arguments): the launch behind the call's last pose launch on `pose`
-static int map_enqueue(svo_ctx* ctx, MapState* M, hipStream_t pose, const TrackWork* work, const svo_kp* kp, const float* depth, int kstride,
-                       int frames, const int* row_of_frame) {
-  const size_t K = (size_t)ctx->max_kp, off = (size_t)M->cur_off;
-  if (M->cur_host && off + (size_t)frames > (size_t)M->cap) {
-    ctx->last_error = "svo_track_map_out: more frames than max_batch";
-    return SVO_E_CAPACITY;
-  }
-  svo_map_obs* obs = (M->cur_host ? M->d_obs : M->cur.obs) + off * K;
-  int32_t* counts = (M->cur_host ? M->d_counts : M->cur.counts) + off;
-  const TrackState* st = reinterpret_cast<const TrackState*>(ctx->d_track);
-  const int tag0 = ctx->track_frame + 1;   // k_ti_resolve's tag of the call's frame 0
-  {
-    SvoTimer t(ctx, "k_tm_obs", pose);
-    if (!row_of_frame) {
-      hipLaunchKernelGGL(k_tm_obs, dim3(frames), dim3(TRK_MAXKP), 0, pose, st, work, kp, depth, kstride, tag0, (int)K, obs, counts);
-    } else {   // (front-end rows that are not the frames' order: a launch per frame)
-      for (int f = 0; f < frames; ++f)
-        hipLaunchKernelGGL(k_tm_obs, dim3(1), dim3(TRK_MAXKP), 0, pose, st, work + f, kp + (size_t)row_of_frame[f] * kstride,
-                           depth + (size_t)row_of_frame[f] * kstride, kstride, tag0 + f, (int)K, obs + (size_t)f * K, counts + f);
-    }
-  }
-  if (M->cur_host) {
-    const int q = M->cur_q;
-    SVO_HIP(ctx, hipMemcpyAsync(M->h_obs[q] + off * K, M->d_obs + off * K, (size_t)frames * K * sizeof(svo_map_obs), hipMemcpyDeviceToHost, pose));
-    SVO_HIP(ctx, hipMemcpyAsync(M->h_counts[q] + off, M->d_counts + off, (size_t)frames * sizeof(int32_t), hipMemcpyDeviceToHost, pose));
-    SVO_HIP(ctx, hipEventRecord(M->ev_out[q], pose));
-    M->pending[q] = M->cur; M->pending_n[q] = (int)off + frames;
-  }
-  M->cur_off += frames;
-  return SVO_OK;
-}
-
 // The ordered tail for front-end results that are already in HBM (`kstride` keypoints per frame slot):
 //   nseq == 1: `frames` consecutive frames of the one sequence, record f into d_res[f];
 //   nseq  > 1: one frame of each of nseq sequences (frames == 1), sequence q from frame slot q into d_res[q].
@@ -2223,10 +1542,9 @@ static int map_enqueue(svo_ctx* ctx, MapState* M, hipStream_t pose, const TrackW
 // `fe_events` (may be null): fe_events[f] != nullptr is an event the index chain must wait for before frame f (its front-end
 // results are produced on another stream, in sub-batches).
 // `bx` (may be null): detection boxes in HBM - frame f's (nseq == 1) or sequence q's (nseq > 1) at bx->boxes + 4 * bx->stride * f.
-static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, const int32_t* nkp, const float* depth,
-                        int kstride, int frames, int nseq, svo_track_result* d_res, const svo_boxes_dev* bx,
-                        const hipEvent_t* fe_events = nullptr, const int* row_of_frame = nullptr, int work_half = 0,
-                        hipEvent_t idx_wait = nullptr, bool fe_elsewhere = false) {
+int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, const int32_t* nkp, const float* depth, int kstride, int frames,
+                 int nseq, svo_track_result* d_res, const svo_boxes_dev* bx, const hipEvent_t* fe_events, const int* row_of_frame,
+                 int work_half, hipEvent_t idx_wait, bool fe_elsewhere) {
   // work_half: which half of the TrackWork records this call uses (svo_track_batch_dev alternates, so that the index chain of
   // call c + 1 may start while the pose chain of call c still reads its records); idx_wait: what the index chain waits for
   // before it starts - by default everything the ctx stream holds (the front end of this call, the previous call's pose
@@ -2254,9 +1572,7 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
   // per-kernel HIP-event timing (svo_profile_enable) costs ~2.5 us per event pair on the host - more than a tail kernel's
   // launch; the tail is therefore SAMPLED: every 32nd frame of a call is timed (an event pair around a kernel also holds the chain up by ~5 us), the others run untimed
   const bool prof = ctx->profiling;
-  DynState* D = dyn_active(ctx) && dyn_of(ctx)->in_call && nseq == 1 ? dyn_of(ctx) : nullptr;   // the dynamic-keypoint loop runs with this call
-  DynState* DM = dyn_active(ctx) && dyn_of(ctx)->in_step && frames == 1 ? dyn_of(ctx) : nullptr;   // ... with this step of many sequences
-  const bool dm_seeds = DM && bx && dyn_can_seed(DM, ctx->track_frame);
+  const bool dyn = dyn_in_call(ctx);   // the dynamic-keypoint loop runs with this call (svo_track_dyn.hip)
   // frame f's front-end results sit in row f of the arrays unless the caller says otherwise (svo_track_sharded_dev)
   auto row = [&](int f) { return (size_t)(row_of_frame ? row_of_frame[f] : f); };
   // gated frames of ONE sequence whose front-end rows are consecutive: brute-force matches + F for groups of frames in one
@@ -2313,16 +1629,7 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
       hipLaunchKernelGGL(k_ti_resolve, dim3(1, ny), dim3(1024), sizeof(TiLds), s1, st, work + f, kpf, descf, nkpf, depf, kstride,
                          bxf, nbf, bstride, pre_f ? gpre[f].F : nullptr);
     }
-    if (D && bx && dyn_can_seed(D, ctx->track_frame + f)) {
-      SvoTimer t(ctx, "k_td_seeds", s1);
-      hipLaunchKernelGGL(k_td_seeds, dim3(1), dim3(TRK_MAXKP), 0, s1, work + f, kpf, bxf, nbf, D->d_seeds + (size_t)f * 2 * DYN_MAX_SEEDS,
-                         D->nseed() + f);
-    }
-    if (dm_seeds) {
-      SvoTimer t(ctx, "k_td_seeds_seqs", s1);
-      hipLaunchKernelGGL(k_td_seeds_seqs, dim3(ny), dim3(TRK_MAXKP), 0, s1, work + f, kpf, kstride, bxf, nbf, bstride, DM->d_seeds,
-                         DM->m_nseed());
-    }
+    if (dyn && bx) dyn_enqueue_seeds(ctx, s1, f, work + f, kpf, kstride, bxf, nbf, bstride);
   };
   // one sequence: the pose kernels find out by themselves when their frame's record is there (tp_wait_work) - no stream event
   // between the chains; tag of frame f = its index in the sequence + 1
@@ -2407,13 +1714,9 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
       cur0 = g0; cur1 = std::min(frames, g0 + gsize);
       for (int f = cur0; f < cur1; ++f) enqueue_index(f);
       if (!flagged) hipEventRecord(ctx->ev_frame[cur0], s1);
-      if (D) {   // (behind the group's record: the pose chain's wait is never behind LK work)
+      if (dyn) {   // (behind the group's record: the pose chain's wait is never behind LK work)
         ctx->profiling = false;
-        if ((rc = dyn_enqueue_group(ctx, D, s1, cur0, cur1, ctx->track_frame, bx != nullptr, fe_events, frames))) { ctx->profiling = prof; return rc; }
-      }
-      if (DM) {
-        ctx->profiling = false;
-        if ((rc = dyn_multi_step(ctx, DM, s1, ctx->track_frame, dm_seeds))) { ctx->profiling = prof; return rc; }
+        if ((rc = dyn_enqueue_group(ctx, s1, cur0, cur1, bx != nullptr, fe_events, frames))) { ctx->profiling = prof; return rc; }
       }
       g0 = cur1;
       ++ngroup;
@@ -2426,12 +1729,11 @@ static int tail_enqueue(svo_ctx* ctx, const svo_kp* kp, const uint8_t* desc8, co
     prev0 = cur0; prev1 = cur1;
   }
   ctx->profiling = prof;
-  if (D && (rc = dyn_finish(ctx, D, s1, s0, frames))) return rc;
+  // the pose stream joins the loop BEHIND the call's pose kernels (a step of many sequences: they run beside the step's LK work);
+  // what svo_sync, ms_tail_done and work ordered behind the context's stream wait for covers the lists and the image copy
+  if (dyn && (rc = dyn_finish(ctx, s1, s0, frames))) return rc;
   // svo_track_map_out: behind the call's last pose launch, and in front of whatever the callers record on the pose stream
-  if (ctx->map && map_of(ctx)->in_call && nseq == 1 && (rc = map_enqueue(ctx, map_of(ctx), s0, work, kp, depth, kstride, frames, row_of_frame))) return rc;
-  // many sequences: the pose stream joins the loop here, BEHIND the step's pose kernels, which therefore run beside the step's LK
-  // work; what svo_sync, ms_tail_done and work ordered behind the context's stream wait for covers the lists and the image copy
-  if (DM) SVO_HIP(ctx, hipStreamWaitEvent(s0, DM->ev_lk, 0));
+  if (map_in_call(ctx) && nseq == 1 && (rc = map_enqueue(ctx, s0, work, kp, depth, kstride, frames, row_of_frame))) return rc;
   if (bx && ctx->det_ready) {   // a detector feeds this context: its next call may overwrite these boxes once both chains read them
     for (int k = 0; k < 2; ++k)
       if (!ctx->det_read[k]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->det_read[k], hipEventDisableTiming));
@@ -2473,7 +1775,7 @@ static int track_reset_n(svo_ctx* ctx, const svo_camera* cam, int nseq, bool mul
     SVO_HIP(ctx, hipMemcpyAsync(&st->cam, cam, sizeof *cam, hipMemcpyHostToDevice, ctx->stream));
   }
   { const int rcd = dyn_adopt(ctx, multi ? nseq : 0); if (rcd) return rcd; }   // (svo_track_dynamic's parameters; the lists are empty again)
-  if (ctx->map) { MapState* M = map_of(ctx); M->attached = false; M->out = MapOut{}; M->in_call = false; }   // (svo_track_map_out is disarmed; its staged records were flushed above)
+  map_disarm(ctx);   // (svo_track_map_out; its staged records were flushed above)
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->cam = *cam;
   ctx->track_frame = 0;
@@ -2487,1131 +1789,4 @@ extern "C" int svo_track_multi_reset(svo_ctx* ctx, int n_seq, const svo_camera* 
   if (!ctx) return SVO_E_INVALID;
   if (n_seq < 1 || n_seq > ctx->max_batch) return SVO_E_CAPACITY;
   return track_reset_n(ctx, cam, n_seq, true);
-}
-
-// Depth source 1 (svo_set_option "depth_source"): the reference's live data flow - a dense disparity map
-// (src/Tracking.cc:226 `MB`, here the ELAS map D1) -> frame::disp2Depth (src/frame.cc:140-164: depth =
-// bf / disp wherever disp != 0, else -1) -> `depthimg.at<float>(y, x)` at the truncated keypoint position;
-// keypoints_r = x - disp unless disp == -1 (src/frame.cc:122-138).  D == nullptr: no map, no depth.
-// blockIdx.y = frame slot of a batch: map `map_stride` floats further on (0 floats: one frame), `produced` (may
-// be null) says whether that frame has a map at all.
-__global__ void k_tk_dense_depth(const svo_kp* kp, const int32_t* nkp, const float* D, int W, float bf,
-                                 float* uR, float* depth, int K, size_t map_stride, const int32_t* produced) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= K) return;
-  kp += (size_t)blockIdx.y * K; nkp += blockIdx.y; uR += (size_t)blockIdx.y * K; depth += (size_t)blockIdx.y * K;
-  if (D) D += (size_t)blockIdx.y * map_stride;
-  if (produced && !produced[blockIdx.y]) D = nullptr;
-  float u = -1.0f, z = -1.0f;
-  if (i < *nkp && D) {
-    const float disp = D[(size_t)(int)kp[i].y * W + (int)kp[i].x];
-    if (disp != -1.0f) u = kp[i].x - disp;
-    if (disp != 0.0f) z = bf / disp;
-  }
-  uR[i] = u; depth[i] = z;
-}
-
-// room for B frames' dense maps (two float maps and one flag per frame)
-static int dense_reserve(svo_ctx* ctx, int B) {
-  if (ctx->dense_cap >= B) return SVO_OK;
-  const size_t n = (size_t)ctx->g.W * ctx->g.H;
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->d_dense) hipFree(ctx->d_dense);
-  ctx->d_dense = nullptr; ctx->dense_cap = 0;
-  SVO_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->d_dense), (2 * n * sizeof(float) + sizeof(int32_t)) * (size_t)B));
-  ctx->dense_cap = B;
-  return SVO_OK;
-}
-
-extern "C" int svo_track_frame(svo_ctx* ctx, const uint8_t* grayL, int strideL,
-                               const uint8_t* grayR, int strideR, double timestamp,
-                               const int32_t* boxes, int n_boxes, svo_track_result* res) {
-  (void)timestamp;
-  if (!ctx || !grayL || !grayR || !res || strideL < ctx->g.W || strideR < ctx->g.W || n_boxes < 0 ||
-      n_boxes > SVO_MAX_BOXES || (n_boxes > 0 && !boxes))
-    return SVO_E_INVALID;
-  if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset first
-  { const int rcd = svo_track_dyn_refuse_single(ctx, "svo_track_frame"); if (rcd) return rcd; }
-  hipSetDevice(ctx->device);
-  { const int rcq = svo_track_quiesce(ctx); if (rcq) return rcq; }
-  int rc = svo_upload_image(ctx, grayL, strideL, 0);
-  if (rc) return rc;
-  if ((rc = svo_upload_image(ctx, grayR, strideR, 1))) return rc;
-  return svo_track_frame_staged(ctx, boxes, n_boxes, res, nullptr, nullptr, 0);
-}
-
-// svo_track_frame / svo_track_frame_bgr from the point where the pair's gray images are in staging slots 0 / 1
-static int track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
-                              const uint8_t* d_bgrR, int bgr_pitch);
-static int dyn_colour_needs_bgr(svo_ctx* ctx, const char* who) {
-  ctx->last_error = std::string(who) + ": svo_track_dynamic asked for LK on the colour frames (colour = 1), which a gray entry does not have";
-  return SVO_E_INVALID;
-}
-static int track_frame_staged_dyn(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
-                                  const uint8_t* d_bgrR, int bgr_pitch);
-int svo_track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
-                           const uint8_t* d_bgrR, int bgr_pitch) {
-  int rc = map_begin(ctx, true);   // (svo_track_map_out: host arrays, complete when the entry returns)
-  if (rc == SVO_OK) rc = track_frame_staged_dyn(ctx, boxes, n_boxes, res, d_bgrL, d_bgrR, bgr_pitch);
-  return map_end(ctx, true, rc);
-}
-static int track_frame_staged_dyn(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
-                                  const uint8_t* d_bgrR, int bgr_pitch) {
-  if (!dyn_active(ctx)) return track_frame_staged(ctx, boxes, n_boxes, res, d_bgrL, d_bgrR, bgr_pitch);
-  const bool colour = dyn_of(ctx)->p.colour != 0;
-  if (colour && !d_bgrL) return dyn_colour_needs_bgr(ctx, "svo_track_frame");
-  int rc = dyn_begin(ctx, colour ? d_bgrL : ctx->d_stage, colour ? bgr_pitch : ctx->stage_pitch, true, true);
-  if (rc == SVO_OK) rc = track_frame_staged(ctx, boxes, n_boxes, res, d_bgrL, d_bgrR, bgr_pitch);
-  dyn_end(ctx);
-  return rc;
-}
-static int track_frame_staged(svo_ctx* ctx, const int32_t* boxes, int n_boxes, svo_track_result* res, const uint8_t* d_bgrL,
-                              const uint8_t* d_bgrR, int bgr_pitch) {
-  const SvoGeom& g = ctx->g;
-  TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
-  uint8_t* dL = ctx->d_stage;
-  uint8_t* dR = ctx->d_stage + (size_t)g.H * ctx->stage_pitch;
-  int rc;
-  // the frame's boxes go to HBM with the images (pinned staging: the copies are asynchronous, the caller's array may be
-  // pageable); from there on a gated frame is device work only
-  int32_t* h_box = reinterpret_cast<int32_t*>(ctx->h_pinned + ctx->pinned_bytes - 4096);   // the buffer's last page: reserved for this (svo_msa.hip stays below it)
-  h_box[0] = n_boxes;
-  if (n_boxes > 0) memcpy(h_box + 4, boxes, 16 * (size_t)n_boxes);
-  SVO_HIP(ctx, hipMemcpyAsync(&st->n_boxes, h_box, 4, hipMemcpyHostToDevice, ctx->stream));
-  if (n_boxes > 0)
-    SVO_HIP(ctx, hipMemcpyAsync(st->boxes, h_box + 4, 16 * (size_t)n_boxes, hipMemcpyHostToDevice, ctx->stream));
-  const svo_boxes_dev bx{st->boxes, &st->n_boxes, SVO_MAX_BOXES};
-  const SvoFeBufs fb = svo_fe_own(ctx);
-  if (ctx->opt_depth_source == 1) {
-    if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 1))) return rc;   // left image only
-    svo_elas_params ep;
-    svo_elas_default_params(0, &ep);
-    float *dD1 = nullptr, *dD2 = nullptr;
-    int produced = 0;
-    if ((rc = svo_elas_run_dev(ctx, dL, dR, ctx->stage_pitch, g.W, g.H, &ep, &dD1, &dD2, &produced))) return rc;
-    SvoTimer t(ctx, "k_tk_dense_depth");
-    hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_kp,
-                       ctx->d_nkp, produced ? dD1 : nullptr, g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, (size_t)0,
-                       (const int32_t*)nullptr);
-  } else if (ctx->opt_depth_source == 2) {
-    // the reference's live configuration: frame::MB = MSA::solve(left, right, 48, 1) (src/Tracking.cc:225-228)
-    if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 1))) return rc;
-    if ((rc = dense_reserve(ctx, 1))) return rc;
-    // (colour entry: MSA gets the true colour pair, as in the reference; gray entry: B = G = R copies of the gray)
-    if ((rc = d_bgrL ? svo_msa_run_dev(ctx, d_bgrL, d_bgrR, bgr_pitch, g.W, g.H, 48, ctx->d_dense, true)
-                     : svo_msa_run_dev(ctx, dL, dR, ctx->stage_pitch, g.W, g.H, 48, ctx->d_dense)))
-      return rc;
-    SvoTimer t(ctx, "k_tk_dense_depth");
-    hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_kp,
-                       ctx->d_nkp, ctx->d_dense, g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, (size_t)0,
-                       (const int32_t*)nullptr);
-  } else if (ctx->opt_depth_source == 3) {
-    // the body of the reference's frame::ElasMatch (src/frame.cc:94-120): SGBM on the gray pair; invalid pixels are -1
-    if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 1))) return rc;
-    if ((rc = dense_reserve(ctx, 1))) return rc;
-    // (colour entry with "sgbm_colour": the cn = 3 solver on the BGR pair, as the reference calls it)
-    svo_sgbm_params sp;
-    if (d_bgrL && ctx->opt_sgbm_colour) {
-      svo_sgbm_default_params_bgr(g.H, &sp);
-      rc = svo_sgbm_run_bgr_dev(ctx, ctx->stream, d_bgrL, d_bgrR, bgr_pitch, (size_t)g.H * bgr_pitch, g.W, g.H, 1, &sp, ctx->opt_sgbm_mode, ctx->d_dense);
-    } else {
-      svo_sgbm_default_params(g.H, &sp);
-      rc = svo_sgbm_run_dev(ctx, ctx->stream, dL, dR, ctx->stage_pitch, (size_t)g.H * ctx->stage_pitch, g.W, g.H, 1, &sp, ctx->opt_sgbm_mode, ctx->d_dense);
-    }
-    if (rc) return rc;
-    SvoTimer t(ctx, "k_tk_dense_depth");
-    hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_kp,
-                       ctx->d_nkp, ctx->d_dense, g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, (size_t)0,
-                       (const int32_t*)nullptr);
-  } else {
-    if ((rc = svo_launch_orb(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, 2))) return rc;
-    if ((rc = svo_launch_stereo(ctx, ctx->stream, fb, dL, dR, ctx->stage_pitch, 1, &ctx->cam))) return rc;
-  }
-  svo_track_result* d_res = reinterpret_cast<svo_track_result*>(ctx->d_scratch);
-  rc = tail_enqueue(ctx, ctx->d_kp, ctx->d_desc, ctx->d_nkp, ctx->d_depth, ctx->max_kp, 1, 1, d_res, n_boxes > 0 ? &bx : nullptr);
-  if (rc) return rc;
-  SVO_HIP(ctx, hipMemcpyAsync(res, d_res, sizeof *res, hipMemcpyDeviceToHost, ctx->stream));
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->track_frame++;
-  if (res->n_pnp_inliers == -1) return svo_track_check_timeout(ctx);   // (the record is valid: the frame was tracked as a PnP failure)
-  return SVO_OK;
-}
-
-// Parity probe: what the dense depth sources handed the tail for frame `frame` of the last call (the context's own arrays)
-extern "C" int svo_debug_track_depths(svo_ctx* ctx, int frame, svo_kp* kp, float* depth, int32_t* n) {
-  if (!ctx || !kp || !depth || !n || frame < 0 || frame >= ctx->max_batch) return SVO_E_INVALID;
-  if (ctx->opt_depth_source == 0) { ctx->last_error = "svo_debug_track_depths: depth_source must be 1, 2 or 3"; return SVO_E_INVALID; }
-  hipSetDevice(ctx->device);
-  SVO_HIP(ctx, hipDeviceSynchronize());
-  const size_t K = ctx->max_kp;
-  SVO_HIP(ctx, hipMemcpy(n, ctx->d_nkp + frame, sizeof(int32_t), hipMemcpyDeviceToHost));
-  SVO_HIP(ctx, hipMemcpy(kp, ctx->d_kp + frame * K, K * sizeof(svo_kp), hipMemcpyDeviceToHost));
-  SVO_HIP(ctx, hipMemcpy(depth, ctx->d_depth + frame * K, K * sizeof(float), hipMemcpyDeviceToHost));
-  return SVO_OK;
-}
-
-// One time step of n_seq independent sequences: pair q is the next frame of sequence q.
-extern "C" int svo_track_multi_step_dev(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR,
-                                        int stride, int n_seq, const svo_boxes_dev* boxes, svo_track_result* d_results) {
-  if (!ctx || !d_grayL || !d_grayR || !d_results || stride < ctx->g.W) return SVO_E_INVALID;
-  if (!ctx->d_track || n_seq != ctx->n_seq) return SVO_E_INVALID;   // svo_track_multi_reset(n_seq) first
-  { const int rcc = svo_track_multi_step_check(ctx, "svo_track_multi_step_dev", false); if (rcc) return rcc; }
-  return svo_track_multi_step_fed(ctx, d_grayL, d_grayR, stride, n_seq, boxes, d_results, nullptr);
-}
-
-static int multi_step_enqueue(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int n_seq,
-                              const svo_boxes_dev* boxes, svo_track_result* d_results, const SvoBgrSrc* bgr);
-// what both many-sequence entries refuse before anything is allocated or enqueued
-int svo_track_multi_step_check(svo_ctx* ctx, const char* who, bool has_bgr) {
-  { const int rcd = dyn_refuse_multi(ctx, who); if (rcd) return rcd; }
-  { const int rcm = svo_track_map_refuse(ctx, who); if (rcm) return rcm; }
-  if (ctx->opt_depth_source != 0) {   // the many-sequence mode has the sparse matcher only
-    ctx->last_error = std::string(who) + ": depth_source must be 0";
-    return SVO_E_INVALID;
-  }
-  if (dyn_active(ctx) && dyn_of(ctx)->p.colour && !has_bgr) return dyn_colour_needs_bgr(ctx, who);
-  return SVO_OK;
-}
-// The step of the two many-sequence entries, which have checked their arguments and called svo_track_multi_step_check; with the
-// loop in force (adopted by svo_track_multi_reset) its images are the gray the front end reads, or - colour = 1 - the colour left frames
-int svo_track_multi_step_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int n_seq,
-                             const svo_boxes_dev* boxes, svo_track_result* d_results, const SvoBgrSrc* bgr) {
-  DynState* D = dyn_active(ctx) ? dyn_of(ctx) : nullptr;
-  if (D) {
-    D->in_step = true;
-    D->src = D->p.colour ? bgr->L : d_grayL; D->src_stride = D->p.colour ? bgr->stride : stride;
-    D->cur = D->out; D->cur_on = D->attached;   // (one-shot)
-    D->attached = false; D->out = DynOut{};
-  }
-  const int rc = multi_step_enqueue(ctx, d_grayL, d_grayR, stride, n_seq, boxes, d_results, bgr);
-  if (D) { D->in_step = false; D->cur_on = false; D->cur = DynOut{}; D->src = nullptr; }
-  return rc;
-}
-static int multi_step_enqueue(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int n_seq,
-                              const svo_boxes_dev* boxes, svo_track_result* d_results, const SvoBgrSrc* bgr) {
-  hipSetDevice(ctx->device);
-  { const int rcs = svo_shard_quiesce(ctx); if (rcs) return rcs; }   // (a sharded call of this context may still be in flight: staging sets, work records)
-  int rc;
-  // colour entry: the gray of the 2 n_seq images, on the stream the front end runs on, once the readers of the staging are done
-  // with it - the previous colour call's front end, and the copy the loop's previous step took of it (colour = 0)
-  auto bgr_convert = [&](hipStream_t s) -> int {
-    if (!bgr || !bgr->convert) return SVO_OK;
-    for (int k = 0; k < bgr->n_wait; ++k) SVO_HIP(ctx, hipStreamWaitEvent(s, bgr->wait[k], 0));
-    if (dyn_active(ctx) && !dyn_of(ctx)->p.colour && dyn_of(ctx)->ev_img_valid) SVO_HIP(ctx, hipStreamWaitEvent(s, dyn_of(ctx)->ev_img, 0));
-    const size_t gray_img = (size_t)ctx->g.H * stride, bgr_img = (size_t)ctx->g.H * bgr->stride;
-    svo_launch_bgr2gray(s, bgr->L, bgr->stride, bgr_img, const_cast<uint8_t*>(d_grayL), stride, gray_img, ctx->g.W, ctx->g.H, n_seq);
-    svo_launch_bgr2gray(s, bgr->R, bgr->stride, bgr_img, const_cast<uint8_t*>(d_grayR), stride, gray_img, ctx->g.W, ctx->g.H, n_seq);
-    return SVO_OK;
-  };
-  auto bgr_done = [&](hipStream_t s) -> int {
-    if (bgr && bgr->convert && bgr->done) SVO_HIP(ctx, hipEventRecord(bgr->done, s));
-    return SVO_OK;
-  };
-  if (ctx->opt_multi_pipeline) {
-    // Pipelined steps (svo_set_option("multi_pipeline", 1)): the front end is stateless, so step t + 1's may run while
-    // step t's tail is still busy - on its own stream, into the other of two private output sets.  Contract: between
-    // consecutive steps nothing else is enqueued on this context (svo_sync and reading results are fine).
-    if (ctx->ms_cap < n_seq) {
-      SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      if (ctx->stream_fe) SVO_HIP(ctx, hipStreamSynchronize(ctx->stream_fe));
-      ctx->ms_cap = 0;   // a failed allocation below leaves empty sets and no capacity behind, never freed memory
-      if ((rc = fe_sets_alloc(ctx->ms_out, 2, 2 * (size_t)n_seq, n_seq, ctx->max_kp, false))) return rc;
-      for (int p = 0; p < 2; ++p) {
-        if (!ctx->ms_fe_done[p]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->ms_fe_done[p], hipEventDisableTiming));
-        if (!ctx->ms_tail_done[p]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->ms_tail_done[p], hipEventDisableTiming));
-        ctx->ms_tail_recorded[p] = false;
-      }
-      ctx->ms_cap = n_seq;
-    }
-    if ((rc = track_resources(ctx, 1, n_seq))) return rc;   // streams and events exist from here on
-    if (!ctx->stream_fe) {   // (confining it to a share of the CUs only costs: 88 % -6 %, 75 % -8 %, 50 % -34 % with 64 sequences)
-      int attempts = 0, percent = 0;
-      const int rcp = svo_pick_stream(ctx, [](hipStream_t* q) { return svo_stream_create(q, -1); }, {ctx->stream, ctx->stream_idx}, &ctx->stream_fe,
-                                      &attempts, &percent, {ctx->stream, ctx->stream_idx}, {});
-      if (rcp) return rcp;
-    }
-    const int p = ctx->ms_parity;
-    if (ctx->ms_tail_recorded[p]) {
-      SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_fe, ctx->ms_tail_done[p], 0));   // the tail that read this set two steps ago
-    } else {
-      SVO_HIP(ctx, hipEventRecord(ctx->ev_frontend, ctx->stream));                  // first use: after whatever came before
-      SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_fe, ctx->ev_frontend, 0));
-    }
-    const SvoFeBufs fb = svo_fe_own(ctx).with_outputs(ctx->ms_out[p]);   // (right x and SAD: the context's own arrays)
-    if ((rc = bgr_convert(ctx->stream_fe))) return rc;
-    rc = svo_launch_orb(ctx, ctx->stream_fe, fb, d_grayL, d_grayR, stride, n_seq, 2 * n_seq);
-    if (rc == SVO_OK) rc = svo_launch_stereo(ctx, ctx->stream_fe, fb, d_grayL, d_grayR, stride, n_seq, &ctx->cam);
-    if (rc == SVO_OK) rc = bgr_done(ctx->stream_fe);
-    if (rc) return rc;
-    SVO_HIP(ctx, hipEventRecord(ctx->ms_fe_done[p], ctx->stream_fe));
-    SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ms_fe_done[p], 0));
-    if ((rc = tail_enqueue(ctx, fb.kp, fb.desc, fb.nkp, fb.depth, ctx->max_kp, 1, n_seq, d_results, boxes))) return rc;
-    SVO_HIP(ctx, hipEventRecord(ctx->ms_tail_done[p], ctx->stream));
-    ctx->ms_tail_recorded[p] = true;
-    ctx->ms_parity ^= 1;
-    ctx->track_frame++;
-    return SVO_OK;
-  }
-  const SvoFeBufs fb = svo_fe_own(ctx);
-  if ((rc = bgr_convert(ctx->stream))) return rc;
-  rc = svo_launch_orb(ctx, ctx->stream, fb, d_grayL, d_grayR, stride, n_seq, 2 * n_seq);
-  if (rc) return rc;
-  if ((rc = svo_launch_stereo(ctx, ctx->stream, fb, d_grayL, d_grayR, stride, n_seq, &ctx->cam))) return rc;
-  if ((rc = bgr_done(ctx->stream))) return rc;
-  if ((rc = tail_enqueue(ctx, ctx->d_kp, ctx->d_desc, ctx->d_nkp, ctx->d_depth, ctx->max_kp, 1, n_seq, d_results, boxes))) return rc;
-  ctx->track_frame++;
-  return SVO_OK;
-}
-
-static int track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
-                           const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr);
-static int track_batch_fed_dyn(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
-                               const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr);
-int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
-                        const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr) {
-  if (!ctx || !ctx->map) return track_batch_fed_dyn(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, pair_ready, bgr);
-  int rc = map_begin(ctx, pair_ready != nullptr);   // (svo_track_map_out: host arrays for the host-fed entries)
-  if (rc == SVO_OK) rc = track_batch_fed_dyn(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, pair_ready, bgr);
-  return map_end(ctx, false, rc);
-}
-static int track_batch_fed_dyn(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
-                               const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr) {
-  if (!ctx || !dyn_active(ctx)) return track_batch_fed(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, pair_ready, bgr);
-  const bool colour = dyn_of(ctx)->p.colour != 0;
-  if (colour && !bgr) return dyn_colour_needs_bgr(ctx, "svo_track_batch");
-  int rc = dyn_begin(ctx, colour ? bgr->L : d_grayL, colour ? bgr->stride : stride, pair_ready != nullptr, false);
-  if (rc == SVO_OK) rc = track_batch_fed(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, pair_ready, bgr);
-  dyn_end(ctx);
-  return rc;
-}
-static int track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR, int stride, int B,
-                           const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* pair_ready, const SvoBgrSrc* bgr) {
-  if (!ctx || !d_grayL || !d_grayR || !d_results || B < 1 || stride < ctx->g.W) return SVO_E_INVALID;
-  if (B > ctx->max_batch) return SVO_E_CAPACITY;
-  if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;
-  hipSetDevice(ctx->device);
-  { const int rcs = svo_shard_quiesce(ctx); if (rcs) return rcs; }   // (a sharded call of this context may still be in flight: staging sets, work records)
-  int rc;
-  // colour entries: the gray pairs f0 .. f0 + b - 1 are written here, on the stream that reads them first
-  const bool convert = bgr && bgr->convert;
-  const size_t gray_img = (size_t)ctx->g.H * stride, bgr_img = bgr ? (size_t)ctx->g.H * bgr->stride : 0;
-  auto bgr_wait = [&](hipStream_t s) -> int {   // the readers of the gray staging in the previous colour call
-    for (int k = 0; convert && k < bgr->n_wait; ++k) SVO_HIP(ctx, hipStreamWaitEvent(s, bgr->wait[k], 0));
-    // (the dynamic-keypoint loop of the previous call read the gray this call writes anew)
-    if (convert && dyn_active(ctx) && !dyn_of(ctx)->p.colour && dyn_of(ctx)->ev_lk_valid) SVO_HIP(ctx, hipStreamWaitEvent(s, dyn_of(ctx)->ev_lk, 0));
-    return SVO_OK;
-  };
-  auto bgr_convert = [&](hipStream_t s, int f0, int b) {
-    if (!convert) return;
-    svo_launch_bgr2gray(s, bgr->L + f0 * bgr_img, bgr->stride, bgr_img, const_cast<uint8_t*>(d_grayL) + f0 * gray_img, stride, gray_img,
-                        ctx->g.W, ctx->g.H, b);
-    svo_launch_bgr2gray(s, bgr->R + f0 * bgr_img, bgr->stride, bgr_img, const_cast<uint8_t*>(d_grayR) + f0 * gray_img, stride, gray_img,
-                        ctx->g.W, ctx->g.H, b);
-  };
-  if (ctx->opt_depth_source == 1 || ctx->opt_depth_source == 3) {
-    // (depth_source 3: the same pipeline with SGBM maps, which have no host phase - chunks of svo_sgbm_chunk() pairs, every pair
-    // produces a map)
-    // BASELINE configs[4] as a pipeline: the dense front end (ORB on the left images, ELAS maps, the reference's per-keypoint
-    // lookups - src/Tracking.cc:225-228, src/frame.cc:122-164) runs on a stream of its own; svo_elas_batch_dev moves the call's
-    // pairs through its GPU -> host -> GPU stages in chunks, and as soon as a chunk's last GPU phase is enqueued the hook
-    // below hangs that chunk's depth lookups behind it and enqueues the ordered tail of its frames on the tail's streams - the
-    // tail of chunk c runs while chunks c + 1 ... are still in the dense stage (whose host phases - support-point filter,
-    // Delaunay - block this thread, not the GPU).  Every chunk uses its own half of the work records, like consecutive calls
-    // of the sparse path.
-    const size_t n = (size_t)ctx->g.W * ctx->g.H, K = ctx->max_kp;
-    if ((rc = dense_reserve(ctx, B))) return rc;
-    if ((rc = track_resources(ctx, B, 1))) return rc;
-    if (!ctx->stream_dense) {   // the dense stage's stream: beside both chains of the tail
-      // (confined: a hardware queue of its own - which may still sit behind the dispatch pipe of one of the chains or of the front
-      // end's queue: picked by measurement either way)
-      const int dev = ctx->device, pct = ctx->opt_dense_cu_percent;
-      int attempts = 0, percent = 0;
-      const int rcp = svo_pick_stream(ctx, [dev, pct](hipStream_t* q) { return pct < 100 ? svo_stream_create_masked(q, dev, pct) : svo_stream_create(q, 0); },
-                                      {ctx->stream, ctx->stream_idx}, &ctx->stream_dense, &attempts, &percent,
-                                      {ctx->stream, ctx->stream_idx, ctx->stream_fe_batch}, {ctx->stream_fe_batch});
-      if (rcp) return rcp;
-    }
-    float* dD1 = ctx->d_dense;
-    float* dD2 = dD1 + n * (size_t)ctx->dense_cap;
-    int32_t* d_prod = reinterpret_cast<int32_t*>(dD2 + n * (size_t)ctx->dense_cap);
-    if (ctx->h_prod_cap < B) {
-      if (ctx->h_prod) { SVO_HIP(ctx, hipStreamSynchronize(ctx->stream_dense)); hipHostFree(ctx->h_prod); ctx->h_prod = nullptr; ctx->h_prod_cap = 0; }
-      if (hipHostMalloc(reinterpret_cast<void**>(&ctx->h_prod), sizeof(int32_t) * (size_t)B) != hipSuccess) { (void)hipGetLastError(); return SVO_E_NOMEM; }
-      ctx->h_prod_cap = B;
-    }
-    svo_elas_params ep;
-    svo_elas_default_params(0, &ep);
-    for (int q = 0; q < 2; ++q)
-      if (!ctx->tb_done[q]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->tb_done[q], hipEventDisableTiming));
-    // the dense stage writes the ctx's own result arrays and maps: everything the ctx stream holds (an earlier call's tail) first
-    SVO_HIP(ctx, hipEventRecord(ctx->ev_frontend, ctx->stream));
-    SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_dense, ctx->ev_frontend, 0));
-    struct Hook {
-      svo_ctx* ctx; const svo_boxes_dev* boxes; svo_track_result* d_results; float* dD1; int32_t* d_prod;
-      size_t n, K; int chunk;
-      static int run(void* u, int f0, int b) {
-        Hook& h = *static_cast<Hook*>(u);
-        svo_ctx* ctx = h.ctx;
-        hipStream_t sd = ctx->stream_dense;
-        while ((int)ctx->ev_sub.size() <= h.chunk) {
-          hipEvent_t e;
-          if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return SVO_E_HIP;
-          ctx->ev_sub.push_back(e);
-        }
-        if (hipMemcpyAsync(h.d_prod + f0, ctx->h_prod + f0, sizeof(int32_t) * (size_t)b, hipMemcpyHostToDevice, sd) != hipSuccess) return SVO_E_HIP;
-        const SvoFeBufs o = svo_fe_own(ctx).outputs_at(h.K, f0, f0);
-        hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256, b), dim3(256), 0, sd, o.kp, o.nkp,
-                           h.dD1 + h.n * f0, ctx->g.W, ctx->cam.bf, o.uR, o.depth, ctx->max_kp, h.n, h.d_prod + f0);
-        if (hipEventRecord(ctx->ev_sub[h.chunk], sd) != hipSuccess) return SVO_E_HIP;
-        const int p = ctx->tb_parity;
-        std::vector<hipEvent_t> wait(b, nullptr);
-        wait[0] = ctx->ev_sub[h.chunk];
-        svo_boxes_dev bj{nullptr, nullptr, 0};
-        if (h.boxes && h.boxes->boxes && h.boxes->n) bj = svo_boxes_dev{h.boxes->boxes + (size_t)f0 * h.boxes->stride * 4, h.boxes->n + f0, h.boxes->stride};
-        int rc = tail_enqueue(ctx, o.kp, o.desc, o.nkp, o.depth, ctx->max_kp, b, 1, h.d_results + f0, bj.boxes ? &bj : nullptr, wait.data(),
-                              nullptr, p, ctx->tb_used[p] ? ctx->tb_done[p] : ctx->ev_frontend, true);
-        if (rc == SVO_OK && hipEventRecord(ctx->tb_done[p], ctx->stream) != hipSuccess) rc = SVO_E_HIP;   // the pose chain is the last reader of this half
-        if (rc) return rc;
-        ctx->tb_used[p] = true;
-        ctx->tb_parity ^= 1;
-        ctx->track_frame += b;
-        ++h.chunk;
-        return SVO_OK;
-      }
-    } hook{ctx, boxes, d_results, dD1, d_prod, n, K, 0};
-    if (pair_ready) SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_dense, pair_ready[B - 1], 0));   // host-fed: the call's uploads
-    if ((rc = bgr_wait(ctx->stream_dense))) return rc;
-    bgr_convert(ctx->stream_dense, 0, B);   // (ELAS runs on the gray, like ORB: the reference never calls libelas)
-    rc = svo_launch_orb(ctx, ctx->stream_dense, svo_fe_own(ctx), d_grayL, d_grayR, stride, B, B);   // left images only
-    if (rc == SVO_OK && ctx->opt_depth_source == 3) {
-      // (colour entries with "sgbm_colour": the cn = 3 solver on the BGR pairs, in its own, smaller chunks)
-      const bool colour = bgr && ctx->opt_sgbm_colour;
-      svo_sgbm_params sp;
-      if (colour) svo_sgbm_default_params_bgr(ctx->g.H, &sp); else svo_sgbm_default_params(ctx->g.H, &sp);
-      for (int f0 = 0, step = colour ? svo_sgbm_chunk_bgr() : svo_sgbm_chunk(); f0 < B && rc == SVO_OK; f0 += step) {
-        const int b = std::min(step, B - f0);
-        for (int k = 0; k < b; ++k) ctx->h_prod[f0 + k] = 1;
-        rc = colour ? svo_sgbm_run_bgr_dev(ctx, ctx->stream_dense, bgr->L + f0 * bgr_img, bgr->R + f0 * bgr_img, bgr->stride, bgr_img,
-                                           ctx->g.W, ctx->g.H, b, &sp, ctx->opt_sgbm_mode, dD1 + n * f0)
-                    : svo_sgbm_run_dev(ctx, ctx->stream_dense, d_grayL + f0 * gray_img, d_grayR + f0 * gray_img, stride, gray_img, ctx->g.W,
-                              ctx->g.H, b, &sp, ctx->opt_sgbm_mode, dD1 + n * f0);
-        if (rc == SVO_OK) rc = Hook::run(&hook, f0, b);
-      }
-      return rc;
-    }
-    if (rc == SVO_OK)
-      rc = svo_elas_batch_dev_hooked(ctx, ctx->stream_dense, d_grayL, d_grayR, stride, ctx->g.W, ctx->g.H, B, &ep, dD1, dD2, ctx->h_prod,
-                                     &Hook::run, &hook);
-    return rc;
-  } else if (ctx->opt_depth_source == 2) {
-    // MSA maps, up to eight frames in flight (most of a solve is the host tree builds)
-    const size_t n = (size_t)ctx->g.W * ctx->g.H;
-    if ((rc = dense_reserve(ctx, B))) return rc;
-    if (pair_ready) SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, pair_ready[B - 1], 0));   // host-fed: the call's uploads
-    if ((rc = bgr_wait(ctx->stream))) return rc;
-    bgr_convert(ctx->stream, 0, B);
-    if ((rc = svo_launch_orb(ctx, ctx->stream, svo_fe_own(ctx), d_grayL, d_grayR, stride, B, B))) return rc;   // left images only
-    // (colour entries: MSA gets the true colour pairs, as in the reference; gray entries: B = G = R copies of the gray)
-    if ((rc = bgr ? svo_msa_run_many_dev(ctx, bgr->L, bgr->R, bgr->stride, bgr_img, ctx->g.W, ctx->g.H, 48, B, ctx->d_dense, true)
-                  : svo_msa_run_many_dev(ctx, d_grayL, d_grayR, stride, (size_t)ctx->g.H * stride, ctx->g.W, ctx->g.H, 48, B,
-                                         ctx->d_dense)))
-      return rc;
-    hipLaunchKernelGGL(k_tk_dense_depth, dim3((ctx->max_kp + 255) / 256, B), dim3(256), 0, ctx->stream, ctx->d_kp, ctx->d_nkp,
-                       ctx->d_dense, ctx->g.W, ctx->cam.bf, ctx->d_uR, ctx->d_depth, ctx->max_kp, n, (const int32_t*)nullptr);
-  } else {
-    // The front end runs in sub-batches on its own stream, so that only the first sub-batch stands in front of the
-    // ordered tail: while the tail works through sub-batch j, the front end of j + 1 runs beside it.  Sub-batch j writes the
-    // keypoints of its LEFT images to frame slots f0 .. f0 + b - 1 (what the tail reads); its right images use the slots
-    // behind them, which the next sub-batch's left images overwrite later on the same stream.
-    rc = track_resources(ctx, B, 1);
-    if (rc) return rc;
-    const int SUB = 32, nsub = (B + SUB - 1) / SUB;
-    // The front end of a batched call runs beside the ordered tail, and its kernels are large enough to fill every CU: the
-    // tail's small dependent kernels (100 single-wave RANSAC workgroups that want a CU's float64 pipe each) then queue for
-    // slots and run at a fraction of their speed - 7 us per frame on average (tools/option_sweep.py: 13.2 k frames/s with the
-    // front end on all CUs, 14.1 k on a quarter of them, 14.4 k on 32 CUs; stream priorities did not change that).  So the
-    // batched tracker's front-end stream is confined to a share of the compute units (default an eighth: four CUs of every XCD): the
-    // front end needs ~7 us per pair on the whole chip against the tail's ~70 us per frame - an eighth of the chip keeps up.
-    { const int rcf = svo_track_fe_batch_stream(ctx); if (rcf) return rcf; }
-    while ((int)ctx->ev_sub.size() < nsub) {
-      hipEvent_t e;
-      SVO_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      ctx->ev_sub.push_back(e);
-    }
-    // Output sets alternate between calls: this call's front end writes set p while the tail of the previous call still reads
-    // the other one - it only has to wait for the tail of the call BEFORE that (first use of a set: for whatever the ctx
-    // stream holds).  The front end's working set (pyramids, corner lists) is shared: stream_fe runs the calls' sub-batches
-    // one after the other anyway.
-    const int p = ctx->tb_parity;
-    if (p == 1 && !ctx->tb_out[1].kp && (rc = fe_sets_alloc(&ctx->tb_out[1], 1, ctx->max_images, ctx->max_batch, ctx->max_kp, true)))
-      return rc;
-    for (int q = 0; q < 2; ++q)
-      if (!ctx->tb_done[q]) SVO_HIP(ctx, hipEventCreateWithFlags(&ctx->tb_done[q], hipEventDisableTiming));
-    if (ctx->tb_used[p]) {
-      SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_fe_batch, ctx->tb_done[p], 0));
-    } else {
-      SVO_HIP(ctx, hipEventRecord(ctx->ev_frontend, ctx->stream));
-      SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_fe_batch, ctx->ev_frontend, 0));
-    }
-    std::vector<hipEvent_t> wait(B, nullptr);
-    const SvoFeBufs set = svo_fe_own(ctx).with_outputs(ctx->tb_out[p]);   // (set 0: tb_out[0] is empty, the context's own outputs)
-    const size_t K = ctx->max_kp, img = (size_t)ctx->g.H * stride;
-    hipStream_t fs = ctx->stream_fe_batch;
-    if ((rc = bgr_wait(fs))) return rc;
-    for (int j = 0; j < nsub && rc == SVO_OK; ++j) {
-      const int f0 = j * SUB, b = std::min(SUB, B - f0);
-      const SvoFeBufs fb = set.outputs_at(K, f0, f0);
-      if (pair_ready && hipStreamWaitEvent(fs, pair_ready[f0 + b - 1], 0) != hipSuccess) rc = SVO_E_HIP;   // host-fed: this sub-batch's uploads
-      if (rc) break;
-      bgr_convert(fs, f0, b);   // (colour entries: this sub-batch's gray, on the front end's share of the CUs)
-      rc = svo_launch_orb(ctx, fs, fb, d_grayL + f0 * img, d_grayR + f0 * img, stride, b, 2 * b);
-      if (rc == SVO_OK) rc = svo_launch_stereo(ctx, fs, fb, d_grayL + f0 * img, d_grayR + f0 * img, stride, b, &ctx->cam);
-      if (rc == SVO_OK && hipEventRecord(ctx->ev_sub[j], fs) != hipSuccess) rc = SVO_E_HIP;
-      wait[f0] = ctx->ev_sub[j];
-    }
-    if (rc) return rc;
-    // (the index chain: its inputs arrive through the sub-batch events; its half of the work records was last read by the pose
-    // chain of the call before the previous one - the same event the front end waited for)
-    if ((rc = tail_enqueue(ctx, set.kp, set.desc, set.nkp, set.depth, ctx->max_kp, B, 1, d_results, boxes, wait.data(), nullptr, p,
-                           ctx->tb_used[p] ? ctx->tb_done[p] : ctx->ev_frontend, true)))
-      return rc;
-    SVO_HIP(ctx, hipEventRecord(ctx->tb_done[p], ctx->stream));   // the pose chain is the last reader of this call's set
-    ctx->tb_used[p] = true;
-    ctx->tb_parity ^= 1;
-    ctx->track_frame += B;
-    return SVO_OK;
-  }
-  if ((rc = tail_enqueue(ctx, ctx->d_kp, ctx->d_desc, ctx->d_nkp, ctx->d_depth, ctx->max_kp, B, 1, d_results, boxes))) return rc;
-  ctx->track_frame += B;
-  return SVO_OK;
-}
-
-extern "C" int svo_dyn_default_params(svo_dyn_params* p) {
-  if (!p) return SVO_E_INVALID;
-  p->enable = 0;
-  p->colour = 0;
-  p->seed_frames = 2;
-  p->max_pts = 512;
-  return svo_lk_default_params(&p->lk);
-}
-
-// Checked on the host alone, in lk_check's order; in force from the next svo_track_reset on
-extern "C" int svo_track_dynamic(svo_ctx* ctx, const svo_dyn_params* p) {
-  if (!ctx || !p) return SVO_E_INVALID;
-  int rc = SVO_OK;
-  if (p->enable < 0 || p->enable > 1 || p->colour < 0 || p->colour > 1 || p->seed_frames < -1 || p->max_pts < 1) rc = SVO_E_INVALID;
-  if (rc == SVO_OK) rc = lk_check(&p->lk, ctx->g.W, ctx->g.H, p->max_pts, 1);
-  if (rc) {
-    ctx->last_error = rc == SVO_E_CAPACITY ? "svo_track_dynamic: image larger than 4096 x 4096 or more than 4096 points"
-                                           : "svo_track_dynamic: invalid argument or unsupported parameters";
-    return rc;
-  }
-  if (!ctx->dyn) {
-    if (!p->enable) return SVO_OK;   // (nothing to switch off)
-    ctx->dyn = new DynState();
-  }
-  dyn_of(ctx)->next = *p;
-  return SVO_OK;
-}
-
-extern "C" int svo_track_dynamic_out(svo_ctx* ctx, float* lists, int32_t* counts, int32_t* dropped) {
-  if (!ctx || !lists || !counts) return SVO_E_INVALID;
-  if (!dyn_active(ctx)) {
-    ctx->last_error = "svo_track_dynamic_out: the dynamic-keypoint loop is not enabled (svo_track_dynamic, then svo_track_reset or svo_track_multi_reset)";
-    return SVO_E_INVALID;
-  }
-  DynState* D = dyn_of(ctx);
-  D->out.lists = lists; D->out.counts = counts; D->out.dropped = dropped;
-  D->attached = true;
-  return SVO_OK;
-}
-
-extern "C" int svo_track_map_out(svo_ctx* ctx, svo_map_obs* obs, int32_t* counts) {
-  if (!ctx || !obs || !counts) return SVO_E_INVALID;   // (host only: no device is touched before this)
-  if (!ctx->d_track) {
-    ctx->last_error = "svo_track_map_out: svo_track_reset first";
-    return SVO_E_INVALID;
-  }
-  if ((reinterpret_cast<uintptr_t>(obs) & 15) || (reinterpret_cast<uintptr_t>(counts) & 3)) {
-    ctx->last_error = "svo_track_map_out: obs must be 16-byte aligned, counts 4-byte aligned";
-    return SVO_E_INVALID;
-  }
-  if (!ctx->map) ctx->map = new MapState();
-  MapState* M = map_of(ctx);
-  M->out.obs = obs; M->out.counts = counts;
-  M->attached = true;
-  return SVO_OK;
-}
-
-extern "C" int svo_track_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_grayR,
-                                   int stride, int B, const svo_boxes_dev* boxes, svo_track_result* d_results) {
-  if (ctx) { const int rcd = svo_track_dyn_refuse_single(ctx, "svo_track_batch_dev"); if (rcd) return rcd; }
-  return svo_track_batch_fed(ctx, d_grayL, d_grayR, stride, B, boxes, d_results, nullptr);
-}
-
-// The ordered tail alone, for front-end results produced elsewhere (another context, another GPU): frame f's keypoints
-// at d_kp + f * kp_stride, descriptors at d_desc + f * kp_stride * 32, count d_n[f], depths d_depth + f * kp_stride.
-extern "C" int svo_track_tail_dev(svo_ctx* ctx, const svo_kp* d_kp, const uint8_t* d_desc, const int32_t* d_n,
-                                  const float* d_depth, int kp_stride, int B, const svo_boxes_dev* boxes,
-                                  svo_track_result* d_results) {
-  if (!ctx || !d_kp || !d_desc || !d_n || !d_depth || !d_results || B < 1 || kp_stride < 1) return SVO_E_INVALID;
-  if (!ctx->d_track || ctx->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset first
-  { const int rcd = svo_track_dyn_refuse(ctx, "svo_track_tail_dev"); if (rcd) return rcd; }
-  hipSetDevice(ctx->device);
-  { const int rcs = svo_shard_quiesce(ctx); if (rcs) return rcs; }   // (a sharded call of this context may still be in flight: staging sets, work records)
-  int rc = map_begin(ctx, false);
-  if (rc == SVO_OK) rc = tail_enqueue(ctx, d_kp, d_desc, d_n, d_depth, kp_stride, B, 1, d_results, boxes);
-  if ((rc = map_end(ctx, false, rc))) return rc;
-  ctx->track_frame += B;
-  return SVO_OK;
-}
-
-// svo_sync's look at the sticky flags of the tracker's sequences (the stream is idle here): bit 4 = a wait inside the pose chain
-// ran into its bound (k_tp_tail_ord's frame part waiting for the samples of its own launch, or a kernel polling for a hand-over
-// record with "pose_flag").  The frame concerned was treated as a PnP failure (record: n_pnp_inliers = -1) - nothing stale was
-// consumed -; the context falls back to the two-launch pose chain, whose kernels never wait for each other, and says so (once
-// per svo_track_reset / svo_track_multi_reset, naming the sequences concerned when there are several).
-int svo_track_check_timeout(svo_ctx* ctx) {
-  if (!ctx->d_track || ctx->timeout_reported) return SVO_OK;
-  const TrackState* st = reinterpret_cast<const TrackState*>(ctx->d_track);
-  const int n = ctx->n_seq;
-  std::vector<int32_t> v((size_t)n, 0);
-  // (every sequence's flag in one strided copy: st[q].overflow, sizeof(TrackState) bytes apart)
-  SVO_HIP(ctx, hipMemcpy2DAsync(v.data(), sizeof(int32_t), &st->overflow, sizeof(TrackState), sizeof(int32_t), (size_t)n,
-                                hipMemcpyDeviceToHost, ctx->stream));
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::string seqs;
-  for (int q = 0; q < n; ++q)
-    if (v[(size_t)q] & 4) seqs += (seqs.empty() ? "" : ", ") + std::to_string(q);
-  if (seqs.empty()) return SVO_OK;
-  ctx->timeout_reported = true;
-  ctx->opt_tail_fused = 0;
-  ctx->opt_pose_flag = 0;
-  ctx->last_error = std::string("tracker: a wait inside the pose chain timed out (sticky flag 4") +
-                    (n > 1 ? "; sequence(s) " + seqs + " of " + std::to_string(n) : std::string()) +
-                    "): the frame was treated as a PnP failure (n_pnp_inliers = -1); "
-                    "the context now runs the two-launch pose chain (tail_fused = 0, pose_flag = 0)";
-  return SVO_E_TIMEOUT;
-}
-
-// Sticky flag of the tracker (0 = fine), a bit set (device side: atomicOr), OR-ed over the sequences.  1: a frame wanted more than
-// 4096 live map points or a map point outlived the position table (2^20 ids) - results after that are not the reference's.
-// 4: a bounded wait inside the pose chain timed out (above).
-extern "C" int svo_track_overflowed(svo_ctx* ctx, int32_t* flag) {
-  if (!ctx || !flag || !ctx->d_track) return SVO_E_INVALID;
-  TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  int32_t any = 0;
-  for (int q = 0; q < ctx->n_seq; ++q) {
-    int32_t v = 0;
-    SVO_HIP(ctx, svo_memcpy_sync(ctx, &v, &st[q].overflow, 4, hipMemcpyDeviceToHost));
-    any |= v;
-  }
-  *flag = any;
-  return SVO_OK;
-}
-
-// How the index chain's stream was chosen (svo_stream_burst, or track_index_stream with SVO_POOLED_QUEUES=1): out[0] = candidates
-// tried (0: probe switched off), out[1] = "two chains together / one alone" on the pose and the index stream in per cent
-// (~105 side by side, ~200: the two chains of the tail take turns instead of overlapping).
-extern "C" int svo_debug_stream_probe(svo_ctx* ctx, int32_t out[2]) {
-  if (!ctx || !out) return SVO_E_INVALID;
-  out[0] = ctx->idx_probe_attempts; out[1] = ctx->idx_probe_spins;
-  return SVO_OK;
-}
-
-// Do the front end's / the dense stage's queued grids hold the tail's two streams up?  (include/svo.h; svo_probe_block_percent)
-extern "C" int svo_debug_stream_pipes(svo_ctx* ctx, int32_t out[4]) {
-  if (!ctx || !out) return SVO_E_INVALID;
-  hipSetDevice(ctx->device);
-  { const int rcq = svo_track_quiesce(ctx, true); if (rcq) return rcq; }
-  hipStream_t fill[2] = {ctx->stream_fe_batch, ctx->stream_dense}, tail[2] = {ctx->stream, ctx->stream_idx};
-  for (int f = 0; f < 2; ++f)
-    for (int t = 0; t < 2; ++t)
-      out[2 * f + t] = fill[f] && tail[t] && fill[f] != tail[t] ? svo_probe_block_percent(fill[f], tail[t]) : -1;
-  return SVO_OK;
-}
-
-// How many RANSAC samples of the order-preserving EPnP (epnp_exact = 2) were handed to its sequential fallback since
-// svo_track_reset (a zero or repeated singular value, 25 Jacobi sweeps): same results, ~10x the time of the frame concerned.
-extern "C" int svo_track_epnp_fallbacks(svo_ctx* ctx, int64_t* count) {
-  if (!ctx || !count || !ctx->d_track) return SVO_E_INVALID;
-  TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  int64_t total = 0;
-  for (int q = 0; q < ctx->n_seq; ++q) {
-    int32_t v = 0;
-    SVO_HIP(ctx, svo_memcpy_sync(ctx, &v, &st[q].epnp_fallbacks, 4, hipMemcpyDeviceToHost));
-    total += v;
-  }
-  *count = total;
-  return SVO_OK;
-}
-
-extern "C" int svo_debug_track_matches(svo_ctx* ctx, int32_t* cur_mp) {
-  if (!ctx || !cur_mp || !ctx->d_track) return SVO_E_INVALID;
-  TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
-  SVO_HIP(ctx, hipMemcpyAsync(cur_mp, st->dbg_cur_mp, sizeof(int32_t) * ctx->max_kp,
-                              hipMemcpyDeviceToHost, ctx->stream));
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SVO_OK;
-}
-
-extern "C" int svo_debug_track_gate(svo_ctx* ctx, double F[9], int32_t* n_vetoed) {
-  if (!ctx || !ctx->d_track) return SVO_E_INVALID;
-  TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
-  if (F) SVO_HIP(ctx, hipMemcpyAsync(F, st->F, 72, hipMemcpyDeviceToHost, ctx->stream));
-  if (n_vetoed) SVO_HIP(ctx, hipMemcpyAsync(n_vetoed, &st->n_vetoed, 4, hipMemcpyDeviceToHost, ctx->stream));
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SVO_OK;
-}
-
-// Parity probe: map-point identities, RANSAC outcome and PnP pose of n frames of the last batched call (work slots first ..).
-extern "C" int svo_debug_track_frames(svo_ctx* ctx, int first, int n, svo_track_debug* out) {
-  if (!ctx || !out || !ctx->d_work || first < 0 || n < 1 || first + n > ctx->work_cap) return SVO_E_INVALID;
-  hipSetDevice(ctx->device);
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<TrackWork> w((size_t)n);
-  SVO_HIP(ctx, svo_memcpy_sync(ctx, w.data(), reinterpret_cast<TrackWork*>(ctx->d_work) + (size_t)ctx->work_last_half * ctx->work_cap + first,
-                         sizeof(TrackWork) * (size_t)n, hipMemcpyDeviceToHost));
-  for (int f = 0; f < n; ++f) {
-    const TrackWork& q = w[f];
-    svo_track_debug& o = out[f];
-    for (int j = 0; j < TRK_MAXKP; ++j) { o.match_gid[j] = -1; o.new_gid[j] = q.new_gid[j]; }
-    for (int e = 0; e < q.n_edges && e < TRK_MAXKP; ++e) o.match_gid[q.edge_kp[e]] = q.edge_gid[e];
-    o.frame_id = q.frame_id;
-    o.pnp_best = q.pnp_best; o.pnp_iterations = q.pnp_iterations; o.pnp_inliers = q.pnp_inliers; o.pnp_ok = q.pnp_ok;
-    o.active_rows[0] = q.diag[0] & 0xffff; o.active_rows[1] = q.diag[1] & 0xffff;
-    o.rounds[0] = q.diag[0] >> 16; o.rounds[1] = q.diag[1] >> 16;
-    o.resolve_us = (int32_t)((q.rt[1] - q.rt[0]) / 100);   // s_memrealtime: 100 MHz
-    for (int i = 0; i < 6; ++i) o.rt[i] = q.rt[i];
-    memcpy(o.T_pnp, q.T_pnp, sizeof o.T_pnp);
-  }
-  return SVO_OK;
-}
-
-// Diagnostics: s_memtime stamps (shader clock) of k_ti_resolve's phases for work slot `slot` of the last call:
-// begin, pass 1, pass 2, frame end, done.
-extern "C" int svo_debug_track_stamps(svo_ctx* ctx, int slot, int64_t ts[8]) {
-  if (!ctx || !ts || !ctx->d_work || slot < 0 || slot >= ctx->work_cap) return SVO_E_INVALID;
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  TrackWork* w = reinterpret_cast<TrackWork*>(ctx->d_work) + (size_t)ctx->work_last_half * ctx->work_cap + slot;
-  SVO_HIP(ctx, svo_memcpy_sync(ctx, ts, w->ts, sizeof(long long) * 8, hipMemcpyDeviceToHost));
-  return SVO_OK;
-}
-
-// Diagnostics: s_memrealtime stamps (100 MHz) of work slot `slot` of the last batched call: k_ti_resolve start / end,
-// k_tp_hyp start, k_tp_frame end - where the two chains of the tail wait for each other (tools/chain_times.py).
-extern "C" int svo_debug_track_realtime(svo_ctx* ctx, int slot, int64_t rt[4]) {
-  if (!ctx || !rt || !ctx->d_work || slot < 0 || slot >= ctx->work_cap) return SVO_E_INVALID;
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  TrackWork* w = reinterpret_cast<TrackWork*>(ctx->d_work) + (size_t)ctx->work_last_half * ctx->work_cap + slot;
-  SVO_HIP(ctx, svo_memcpy_sync(ctx, rt, w->rt, sizeof(long long) * 4, hipMemcpyDeviceToHost));   // (the first four stamps)
-  return SVO_OK;
-}
-
-// --------------------------------------------------------------------------------------------
-// ONE sequence over G GPUs in one process (BASELINE configs[3]): stereo pair k goes to context
-// k mod G - the stateless front end (ORB on both images + sparse stereo) shards by pair with nothing to exchange - and
-// the strict temporal chain (src/Tracking.cc:231-250) runs in frame order on context 0, which pulls every frame's
-// ~34 KB of keypoints / descriptors / depths from where they were produced (device-to-device copies on its own
-// stream, no collective, no host round trip).  d_grayL[g] / d_grayR[g]: the pairs of context g, on ITS device, in
-// order of increasing k (local index k / G).  B frames per call, records into d_results (on context 0's device).
-// Records are identical to svo_track_batch_dev on one context.  Does not synchronise.
-struct ShardGather {
-  // staging on the tail context's device: region g (frames g, g + G, ... of a call, `per` rows) holds what context g produced
-  svo_kp* kp = nullptr; uint8_t* desc = nullptr; int32_t* n = nullptr; float* depth = nullptr;
-  // TWO sets of staging rows (set p at row p * per * G): call c + 1 gathers into one while the tail of call c reads the other
-  int per = 0, G = 0;
-  std::vector<hipEvent_t> ev;         // front end (and staging copies) of context g finished; created ON context g's device
-  std::vector<int> ev_dev;            //   (an event is recorded on a stream of its own device only) - that device
-  hipEvent_t ev_prev = nullptr;       // what the tail context's stream held when the (first) call began
-  hipStream_t gs = nullptr;           // the gather's own stream on the tail context's device (not the pose chain's)
-  std::vector<hipEvent_t> ev_sub;     // sub-batch j of the latest call gathered (the index chain waits for it before the sub-batch's first frame)
-  hipEvent_t ev_gathered = nullptr;   // the latest call's gather finished: the contexts' result buffers / the bounce buffer are free again
-  hipEvent_t done[2] = {nullptr, nullptr};   // the pose chain finished with staging set / work half p
-  bool used[2] = {false, false};
-  int parity = 0;
-  std::vector<svo_ctx*> producers;    // contexts whose shard_wait points at ev_gathered
-  uint8_t* h_stage = nullptr;         // pinned bounce buffer for contexts whose device the tail's device cannot read directly
-  size_t h_bytes = 0;
-  std::vector<int> row_of_frame;
-};
-static std::vector<std::pair<svo_ctx*, ShardGather*>> g_gathers;   // per tail context, freed by svo_track_release
-static std::mutex g_gathers_mu;                                      // contexts may live on different host threads
-
-static ShardGather* shard_gather(svo_ctx* ctx) {
-  std::lock_guard<std::mutex> lock(g_gathers_mu);
-  for (auto& p : g_gathers)
-    if (p.first == ctx) return p.second;
-  g_gathers.emplace_back(ctx, new ShardGather());
-  return g_gathers.back().second;
-}
-static void shard_gather_buffers_free(ShardGather* g) {
-  if (g->kp) hipFree(g->kp);
-  if (g->desc) hipFree(g->desc);
-  if (g->n) hipFree(g->n);
-  if (g->depth) hipFree(g->depth);
-  g->kp = nullptr; g->desc = nullptr; g->n = nullptr; g->depth = nullptr;
-  g->per = 0; g->G = 0;
-}
-static void shard_gather_free(svo_ctx* ctx) {
-  std::lock_guard<std::mutex> lock(g_gathers_mu);
-  for (auto& pr : g_gathers) {   // a context that goes away is nobody's producer any more
-    auto& v = pr.second->producers;
-    v.erase(std::remove(v.begin(), v.end(), ctx), v.end());
-  }
-  ctx->shard_wait = nullptr;
-  for (size_t i = 0; i < g_gathers.size(); ++i)
-    if (g_gathers[i].first == ctx) {
-      ShardGather* g = g_gathers[i].second;
-      for (svo_ctx* pc : g->producers) if (pc->shard_wait == g->ev_gathered) pc->shard_wait = nullptr;
-      shard_gather_buffers_free(g);
-      for (hipEvent_t e : g->ev) hipEventDestroy(e);
-      if (g->ev_prev) hipEventDestroy(g->ev_prev);
-      if (g->ev_gathered) hipEventDestroy(g->ev_gathered);
-      for (hipEvent_t e : g->ev_sub) hipEventDestroy(e);
-      for (int q = 0; q < 2; ++q) if (g->done[q]) hipEventDestroy(g->done[q]);
-      if (g->gs) { hipStreamSynchronize(g->gs); hipStreamDestroy(g->gs); }
-      if (g->h_stage) hipHostFree(g->h_stage);
-      delete g;
-      g_gathers.erase(g_gathers.begin() + i);
-      return;
-    }
-}
-
-// What a sharded call left in flight and may still read of this context: as a producer, the gather of its result arrays (and of
-// the bounce buffer); as the tail context, the pose chains of the last two calls (staging sets, work records) - other entry
-// points of the context wait for them (svo_track_quiesce).
-int svo_shard_quiesce(svo_ctx* ctx) {
-  if (ctx->shard_wait) {
-    hipEvent_t e = ctx->shard_wait;
-    ctx->shard_wait = nullptr;
-    SVO_HIP(ctx, hipEventSynchronize(e));
-  }
-  ShardGather* sg = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(g_gathers_mu);
-    for (auto& pr : g_gathers)
-      if (pr.first == ctx) sg = pr.second;
-  }
-  if (sg)
-    for (int q = 0; q < 2; ++q)
-      if (sg->used[q] && sg->done[q]) SVO_HIP(ctx, hipEventSynchronize(sg->done[q]));
-  return SVO_OK;
-}
-
-int svo_track_sharded_fed(svo_ctx* const* ctxs, int G, const uint8_t* const* d_grayL, const uint8_t* const* d_grayR, int stride, int B,
-                          const svo_boxes_dev* boxes, svo_track_result* d_results, const hipEvent_t* const* pair_ready) {
-  if (!ctxs || G < 1 || !d_grayL || !d_grayR || B < 1 || !d_results) return SVO_E_INVALID;
-  svo_ctx* c0 = ctxs[0];
-  if (!c0 || !c0->d_track || c0->n_seq != 1) return SVO_E_INVALID;   // svo_track_reset(ctxs[0]) first
-  const int K = c0->max_kp;
-  for (int g = 0; g < G; ++g) {
-    if (!ctxs[g] || !d_grayL[g] || !d_grayR[g] || ctxs[g]->max_kp != K || ctxs[g]->g.W != c0->g.W || ctxs[g]->g.H != c0->g.H)
-      return SVO_E_INVALID;
-    if ((B - g + G - 1) / G > ctxs[g]->max_batch) return SVO_E_CAPACITY;
-  }
-  { const int rcd = svo_track_dyn_refuse(c0, "svo_track_sharded_dev"); if (rcd) return rcd; }
-  { const int rcm = svo_track_map_refuse(c0, "svo_track_sharded_dev"); if (rcm) return rcm; }
-  ShardGather* sg = shard_gather(c0);
-  SVO_HIP(c0, hipSetDevice(c0->device));
-  { const int rcf = svo_track_fe_batch_stream(c0); if (rcf) return rcf; }
-  if (!sg->gs) {   // the gather's copies feed the tail sub-batch by sub-batch: beside its chains, and never behind the front end's grids
-    int attempts = 0, percent = 0;
-    const int rcp = svo_pick_stream(c0, [](hipStream_t* q) { return svo_stream_create(q, 0); }, {c0->stream, c0->stream_idx, c0->stream_fe_batch},
-                                    &sg->gs, &attempts, &percent, {}, {c0->stream_fe_batch});
-    if (rcp) return rcp;
-  }
-  if (!sg->ev_gathered) SVO_HIP(c0, hipEventCreateWithFlags(&sg->ev_gathered, hipEventDisableTiming));
-  for (int q = 0; q < 2; ++q)
-    if (!sg->done[q]) SVO_HIP(c0, hipEventCreateWithFlags(&sg->done[q], hipEventDisableTiming));
-  const int per = (B + G - 1) / G;
-  const size_t wk = sizeof(svo_kp) * (size_t)K, wd = 32 * (size_t)K, wf = 4 * (size_t)K;
-  if (sg->per < per || sg->G < G) {
-    SVO_HIP(c0, hipStreamSynchronize(sg->gs));
-    if (c0->stream_idx) SVO_HIP(c0, hipStreamSynchronize(c0->stream_idx));
-    SVO_HIP(c0, hipStreamSynchronize(c0->stream));
-    shard_gather_buffers_free(sg);
-    const size_t rows = (size_t)per * G * 2;
-    if (hipMalloc(reinterpret_cast<void**>(&sg->kp), wk * rows) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&sg->desc), wd * rows) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&sg->n), 4 * rows) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&sg->depth), wf * rows) != hipSuccess) {
-      (void)hipGetLastError();
-      shard_gather_buffers_free(sg);
-      return SVO_E_NOMEM;
-    }
-    sg->per = per; sg->G = G;
-    sg->used[0] = sg->used[1] = false;
-  }
-  const int rper = sg->per;   // rows per region (may be larger than this call needs)
-  const int G0 = sg->G;       // regions per set
-  for (int g = 0; g < G; ++g) {
-    if (g < (int)sg->ev.size() && sg->ev_dev[g] == ctxs[g]->device) continue;
-    hipSetDevice(ctxs[g]->device);
-    hipEvent_t e;
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { hipSetDevice(c0->device); return SVO_E_HIP; }
-    if (g < (int)sg->ev.size()) { hipEventDestroy(sg->ev[g]); sg->ev[g] = e; sg->ev_dev[g] = ctxs[g]->device; }
-    else { sg->ev.push_back(e); sg->ev_dev.push_back(ctxs[g]->device); }
-  }
-  hipSetDevice(c0->device);
-  if (!sg->ev_prev) SVO_HIP(c0, hipEventCreateWithFlags(&sg->ev_prev, hipEventDisableTiming));
-  // How the tail's device reaches each producer's results: the same device, a direct peer read over xGMI (checked on every
-  // call - the contexts of a call may change), or a bounce through pinned host memory when the platform offers no peer access.
-  std::vector<int> direct(G, 1);
-  bool need_stage = false;
-  for (int g = 1; g < G; ++g) {
-    if (ctxs[g]->device == c0->device) continue;
-    int can = 0;
-    if (hipDeviceCanAccessPeer(&can, c0->device, ctxs[g]->device) != hipSuccess) { can = 0; (void)hipGetLastError(); }
-    if (can) {
-      const hipError_t e = hipDeviceEnablePeerAccess(ctxs[g]->device, 0);
-      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) can = 0;
-      (void)hipGetLastError();
-    }
-    direct[g] = can;
-    need_stage = need_stage || !can;
-  }
-  if (c0->opt_shard_force_staged) {   // test switch (SVO_SHARD_FORCE_STAGED at svo_create, or the option): the bounce path even where a direct read exists
-    for (int g = 1; g < G; ++g) direct[g] = 0;
-    need_stage = G > 1;
-  }
-  const size_t region_bytes = (wk + wd + wf + 4) * (size_t)rper;
-  if (need_stage && sg->h_bytes < region_bytes * G) {
-    SVO_HIP(c0, hipStreamSynchronize(sg->gs));
-    SVO_HIP(c0, hipStreamSynchronize(c0->stream));
-    if (sg->h_stage) hipHostFree(sg->h_stage);
-    sg->h_stage = nullptr; sg->h_bytes = 0;
-    if (hipHostMalloc(reinterpret_cast<void**>(&sg->h_stage), region_bytes * G, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); return SVO_E_NOMEM; }   // (portable: every producer's device copies into it)
-    sg->h_bytes = region_bytes * G;
-  }
-  // The pipeline over consecutive calls: the front ends of call c + 1 run while the tail of call c is in flight.  Nothing of a
-  // front end sits on the pose chain's stream: context g > 0 uses its own stream (its own GPU), context 0 its front-end
-  // stream (a share of the CUs, "fe_cu_percent", like svo_track_batch_dev); the gather runs on a stream of its own into the
-  // staging set the tail of call c does not read.  A front end waits only for the previous call's GATHER (the last reader of
-  // the context's result buffers and of the bounce buffer), the gather for the pose chain of call c - 1 (the last reader of
-  // its staging set), the index chain for the gather.
-  const int p = sg->parity;
-  const bool first_call = !(sg->used[0] || sg->used[1]);
-  if (first_call) SVO_HIP(c0, hipEventRecord(sg->ev_prev, c0->stream));   // after whatever the tail context's stream holds
-  // A front end on the TAIL's device (context 0's; in tests and one-GPU runs every context's) runs on the context's CU-confined
-  // front-end stream ("fe_cu_percent"), like svo_track_batch_dev's: on all CUs at the main stream's high priority it took the
-  // tail's CUs (measured with two contexts on one GPU: 5.4 k frames/s against 8.1 k).  Every context works through its pairs in
-  // sub-batches (its left images' results end up contiguous, row i = its pair i; a sub-batch's right images use the slots
-  // behind it, which the next sub-batch overwrites - as in svo_track_batch_dev), so that the tail can start on the first
-  // sub-batch while the rest of the call's front end still runs.
-  // sub-batch j of every context: its pairs sub_off[j] .. sub_off[j + 1]; 8, 8, 16, then 32 at a time - the tail of a call that
-  // finds the chip idle starts after 8 pairs per context instead of 32 (the confined stream takes ~50 us per pair)
-  std::vector<int> sub_off(1, 0);
-  while (sub_off.back() < per) {
-    const int j = (int)sub_off.size() - 1;
-    sub_off.push_back(std::min(per, sub_off.back() + (j < 2 ? 8 : j == 2 ? 16 : 32)));
-  }
-  const int nsub = (int)sub_off.size() - 1;
-  std::vector<char> confined(G, 0);
-  for (int g = 0; g < G; ++g) {
-    svo_ctx* c = ctxs[g];
-    hipSetDevice(c->device);
-    while ((int)c->ev_sub.size() < nsub) {
-      hipEvent_t e;
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { hipSetDevice(c0->device); return SVO_E_HIP; }
-      c->ev_sub.push_back(e);
-    }
-    if (c->device == c0->device) confined[g] = 1;   // ... on context 0's front-end stream, one context after the other: two
-    // confined streams kept that share of the CUs busy without a gap, and the RANSAC workgroups the dispatcher places there
-    // waited for room (pose chain 111 -> 147 us per frame with two contexts on one GPU)
-  }
-  hipSetDevice(c0->device);
-  while ((int)sg->ev_sub.size() < nsub) {
-    hipEvent_t e;
-    SVO_HIP(c0, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    sg->ev_sub.push_back(e);
-  }
-  const size_t img = (size_t)c0->g.H * stride;
-  int rc = SVO_OK;
-  // sub-batch by sub-batch, every context's share of it (contexts on the tail's device share ONE stream: all of context 0's
-  // sub-batches in front of context 1's first would hold the tail up for the whole of context 0's front end)
-  std::vector<hipStream_t> fsv(G, nullptr);
-  for (int g = 0; g < G && rc == SVO_OK; ++g) {
-    svo_ctx* c = ctxs[g];
-    if ((B - g + G - 1) / G <= 0) continue;
-    hipSetDevice(c->device);
-    { const int rcq = svo_track_quiesce(c, false); if (rcq) { hipSetDevice(c0->device); return rcq; } }   // (a batched call of this context may still read its result arrays; its own earlier calls are ordered by the stream waits below)
-    fsv[g] = confined[g] ? c0->stream_fe_batch : c->stream;
-    bool waited = false;   // (contexts that share a stream: one wait is enough)
-    for (int q = 0; q < g; ++q) waited = waited || fsv[q] == fsv[g];
-    if (!waited && hipStreamWaitEvent(fsv[g], first_call ? sg->ev_prev : sg->ev_gathered, 0) != hipSuccess) rc = SVO_E_HIP;
-  }
-  for (int j = 0; j < nsub && rc == SVO_OK; ++j) {
-    for (int g = 0; g < G && rc == SVO_OK; ++g) {
-      const int nb = (B - g + G - 1) / G;
-      const int f0 = sub_off[j], b = std::min(sub_off[j + 1], nb) - f0;
-      if (b <= 0) continue;
-      svo_ctx* c = ctxs[g];
-      hipStream_t fs = fsv[g];
-      hipSetDevice(c->device);
-      const SvoFeBufs fb = svo_fe_own(c).outputs_at(K, f0, f0);
-      if (pair_ready && hipStreamWaitEvent(fs, pair_ready[g][f0 + b - 1], 0) != hipSuccess) rc = SVO_E_HIP;   // host-fed: this sub-batch's uploads (context g's copy stream, its device)
-      if (rc == SVO_OK) rc = svo_launch_orb(c, fs, fb, d_grayL[g] + f0 * img, d_grayR[g] + f0 * img, stride, b, 2 * b);
-      if (rc == SVO_OK) rc = svo_launch_stereo(c, fs, fb, d_grayL[g] + f0 * img, d_grayR[g] + f0 * img, stride, b, &c0->cam);
-      if (rc == SVO_OK && !direct[g]) {
-        // bounce, first half: this sub-batch's results into the context's region of the pinned buffer, on its own stream
-        uint8_t* h = sg->h_stage + region_bytes * g;
-        if (hipMemcpyAsync(h + wk * f0, fb.kp, wk * b, hipMemcpyDeviceToHost, fs) != hipSuccess ||
-            hipMemcpyAsync(h + wk * rper + wd * f0, fb.desc, wd * b, hipMemcpyDeviceToHost, fs) != hipSuccess ||
-            hipMemcpyAsync(h + (wk + wd) * rper + wf * f0, fb.depth, wf * b, hipMemcpyDeviceToHost, fs) != hipSuccess ||
-            hipMemcpyAsync(h + (wk + wd + wf) * rper + 4 * (size_t)f0, fb.nkp, 4 * (size_t)b, hipMemcpyDeviceToHost, fs) != hipSuccess)
-          rc = SVO_E_HIP;
-      }
-      if (rc == SVO_OK && hipEventRecord(c->ev_sub[j], fs) != hipSuccess) rc = SVO_E_HIP;
-    }
-  }
-  hipSetDevice(c0->device);
-  if (rc) { if (rc == SVO_E_HIP) c0->last_error = std::string("svo_track_sharded_dev: ") + hipGetErrorString(hipGetLastError()); return rc; }
-  // gather on its own stream, sub-batch by sub-batch: rows of region g of staging set p <- context g's results
-  const size_t set0 = (size_t)p * rper * G0;
-  if (sg->used[p]) SVO_HIP(c0, hipStreamWaitEvent(sg->gs, sg->done[p], 0));
-  std::vector<hipEvent_t> wait(B, nullptr);
-  for (int j = 0; j < nsub; ++j) {
-    bool any = false;
-    for (int g = 0; g < G; ++g) {
-      const int nb = (B - g + G - 1) / G;
-      const int f0 = sub_off[j], b = std::min(sub_off[j + 1], nb) - f0;
-      if (b <= 0) continue;
-      any = true;
-      svo_ctx* c = ctxs[g];
-      SVO_HIP(c0, hipStreamWaitEvent(sg->gs, c->ev_sub[j], 0));
-      const size_t r0 = set0 + (size_t)g * rper + f0;
-      if (!direct[g]) {
-        const uint8_t* h = sg->h_stage + region_bytes * g;
-        SVO_HIP(c0, hipMemcpyAsync(sg->kp + r0 * K, h + wk * f0, wk * b, hipMemcpyHostToDevice, sg->gs));
-        SVO_HIP(c0, hipMemcpyAsync(sg->desc + r0 * wd, h + wk * rper + wd * f0, wd * b, hipMemcpyHostToDevice, sg->gs));
-        SVO_HIP(c0, hipMemcpyAsync(sg->depth + r0 * K, h + (wk + wd) * rper + wf * f0, wf * b, hipMemcpyHostToDevice, sg->gs));
-        SVO_HIP(c0, hipMemcpyAsync(sg->n + r0, h + (wk + wd + wf) * rper + 4 * (size_t)f0, 4 * (size_t)b, hipMemcpyHostToDevice, sg->gs));
-        continue;
-      }
-      const bool same = c->device == c0->device;
-      auto pull = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        return same ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, sg->gs)
-                    : hipMemcpyPeerAsync(dst, c0->device, src, c->device, bytes, sg->gs);
-      };
-      SVO_HIP(c0, pull(sg->kp + r0 * K, c->d_kp + (size_t)f0 * K, wk * b));
-      SVO_HIP(c0, pull(sg->desc + r0 * wd, c->d_desc + (size_t)f0 * wd, wd * b));
-      SVO_HIP(c0, pull(sg->depth + r0 * K, c->d_depth + (size_t)f0 * K, wf * b));
-      SVO_HIP(c0, pull(sg->n + r0, c->d_nkp + f0, 4 * (size_t)b));
-    }
-    if (!any) break;
-    SVO_HIP(c0, hipEventRecord(sg->ev_sub[j], sg->gs));
-    if (sub_off[j] * G < B) wait[(size_t)sub_off[j] * G] = sg->ev_sub[j];   // frames sub_off[j] G .. of the call need sub-batch j of every context
-  }
-  SVO_HIP(c0, hipEventRecord(sg->ev_gathered, sg->gs));
-  // the ordered tail reads frame k = g + G i from row g * rper + i of set p; its index chain starts when the gather is done
-  // (which came after the pose chain that last read this set and this half of the work records)
-  sg->row_of_frame.resize(B);
-  for (int k = 0; k < B; ++k) sg->row_of_frame[k] = (int)set0 + (k % G) * rper + k / G;
-  rc = tail_enqueue(c0, sg->kp, sg->desc, sg->n, sg->depth, K, B, 1, d_results, boxes, wait.data(), sg->row_of_frame.data(), p,
-                    nullptr, true);
-  if (rc) return rc;
-  SVO_HIP(c0, hipEventRecord(sg->done[p], c0->stream));   // the pose chain is the last reader of this set
-  for (int g = 0; g < G; ++g) {
-    ctxs[g]->shard_wait = sg->ev_gathered;
-    if (std::find(sg->producers.begin(), sg->producers.end(), ctxs[g]) == sg->producers.end()) sg->producers.push_back(ctxs[g]);
-  }
-  sg->used[p] = true;
-  sg->parity ^= 1;
-  c0->track_frame += B;
-  return SVO_OK;
-}
-
-extern "C" int svo_track_sharded_dev(svo_ctx* const* ctxs, int G, const uint8_t* const* d_grayL, const uint8_t* const* d_grayR,
-                                     int stride, int B, const svo_boxes_dev* boxes, svo_track_result* d_results) {
-  return svo_track_sharded_fed(ctxs, G, d_grayL, d_grayR, stride, B, boxes, d_results, nullptr);
-}
-
-// Parity probe: cv::solvePnPRansac's outcome for the frame just tracked (winning sample, consensus, samples visited)
-// and the pose it handed to PoseOptimization (before the CV_32F rounding), row-major 4x4.
-extern "C" int svo_debug_track_pnp(svo_ctx* ctx, svo_pnp_stats* stats, double T_pnp[16]) {
-  if (!ctx || !ctx->d_track) return SVO_E_INVALID;
-  TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (stats) SVO_HIP(ctx, svo_memcpy_sync(ctx, stats, &st->pnp, sizeof *stats, hipMemcpyDeviceToHost));
-  if (T_pnp) {
-    PnpHyp h;
-    svo_pnp_stats s;
-    SVO_HIP(ctx, svo_memcpy_sync(ctx, &s, &st->pnp, sizeof s, hipMemcpyDeviceToHost));
-    if (s.best_hypothesis < 0) return SVO_E_INVALID;
-    SVO_HIP(ctx, svo_memcpy_sync(ctx, &h, &st->hyp[s.best_hypothesis], sizeof h, hipMemcpyDeviceToHost));
-    for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) T_pnp[4 * r + c] = h.R[3 * r + c]; T_pnp[4 * r + 3] = h.t[r]; }
-    T_pnp[12] = 0; T_pnp[13] = 0; T_pnp[14] = 0; T_pnp[15] = 1;
-  }
-  return SVO_OK;
-}
-
-// Diagnostics: s_memtime stamps of the pose chain for the frame just tracked: [0] k_tp_hyp start, [1] correspondences
-// gathered, [2] EPnP start, [3] EPnP done, [4] consensus counted; [8] k_tp_frame start, [9] RANSAC rule applied,
-// [10] PoseOptimization done, [11] record written.
-extern "C" int svo_debug_track_pose_stamps(svo_ctx* ctx, int64_t ts[16]) {
-  if (!ctx || !ts || !ctx->d_track) return SVO_E_INVALID;
-  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  TrackState* st = reinterpret_cast<TrackState*>(ctx->d_track);
-  SVO_HIP(ctx, svo_memcpy_sync(ctx, ts, st->pose_ts, sizeof(long long) * 16, hipMemcpyDeviceToHost));
-  return SVO_OK;
-}
-
-// ================================================================================================
-// svo_track_map_out: a call's map points and observations, frame by frame (host side: map_enqueue)
-// ================================================================================================
-// Workgroup f = frame f of the call, thread j = keypoint j.  Behind the call's last pose launch on the pose stream: every frame's
-// pose launch has finished, so its record was published (the pose kernels waited for the tag) and the position table holds every
-// point the call created.  The record is read the way the pose kernels read it - the index chain wrote it on another stream with
-// agent-scope stores, and the XCDs' L2s are not coherent for plain loads: the tag first, then agent-scope loads; a record whose tag
-// is not the frame's (a lost hand-over: the pose chain treated the frame as a PnP failure) gives count 0, never stale records.
-// "matched" comes from the frame's correspondence list (edge_kp is ascending), "created" from new_gid - exactly one per keypoint -;
-// a block-wide prefix sum puts the records in keypoint order, two 16-byte stores each.  Defined last in this file: no existing
-// kernel's place in the code object moves (k_tp_tail_ord's Jacobi loop is sensitive to its fetch alignment).
-__global__ __launch_bounds__(TRK_MAXKP) void k_tm_obs(const TrackState* __restrict__ st, const TrackWork* __restrict__ work,
-                                                      const svo_kp* __restrict__ kp, const float* __restrict__ depth, int kstride,
-                                                      int tag0, int max_kp, svo_map_obs* __restrict__ obs, int32_t* __restrict__ counts) {
-  static_assert(sizeof(svo_map_obs) == 32, "svo_map_obs: two 16-byte stores");
-  __shared__ alignas(16) int sm[16];
-  __shared__ int mgid[TRK_MAXKP];
-  const int f = blockIdx.x, tid = threadIdx.x;
-  work += f; kp += (size_t)f * kstride; depth += (size_t)f * kstride; obs += (size_t)f * max_kp;
-  const bool have = ld_agent(&work->ready) == tag0 + f;
-  // (keypoints and depths were written with plain stores by front-end kernels on other streams: as in tp_wait_work)
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  const int nkp = have ? min(max(ld_agent(&work->nkp), 0), min(TRK_MAXKP, kstride)) : 0;
-  const int n_edges = have ? min(max(ld_agent(&work->n_edges), 0), TRK_MAXKP) : 0;
-  const int id = ld_agent(&work->frame_id);
-  mgid[tid] = -1;
-  __syncthreads();
-  if (tid < n_edges) {
-    const int j = ld_agent(&work->edge_kp[tid]);
-    if (j >= 0 && j < TRK_MAXKP) mgid[j] = ld_agent(&work->edge_gid[tid]);
-  }
-  __syncthreads();
-  int gid = -1;
-  uint32_t flags = 0;
-  if (tid < nkp) {
-    gid = mgid[tid];
-    if (gid >= 0) {
-      flags = id == 0 ? (uint32_t)SVO_MAP_NEW : 0u;   // Tracking::init's points
-    } else {
-      gid = ld_agent(&work->new_gid[tid]);            // frame::createmappoint's
-      flags = (uint32_t)SVO_MAP_NEW;
-    }
-  }
-  int total;
-  const int pos = block_excl_scan(gid >= 0 ? 1 : 0, sm, &total);
-  if (gid >= 0 && pos < max_kp) {
-    const svo_kp k = kp[tid];
-    const float* gp = st->gpos + 3 * (size_t)(gid & (TRK_GPOS - 1));
-    uint4 a, b;
-    a.x = (uint32_t)gid; a.y = (uint32_t)tid | (flags << 16); a.z = __float_as_uint(k.x); a.w = __float_as_uint(k.y);
-    b.x = __float_as_uint(depth[tid]); b.y = __float_as_uint(gp[0]); b.z = __float_as_uint(gp[1]); b.w = __float_as_uint(gp[2]);
-    uint4* dst = reinterpret_cast<uint4*>(obs + pos);
-    dst[0] = a; dst[1] = b;
-  }
-  if (tid == 0) counts[f] = min(total, max_kp);
 }

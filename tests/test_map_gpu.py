@@ -276,6 +276,86 @@ def test_frame_entry_and_host_fed(pkg, fx):
     assert res.tobytes() == rec_off
 
 
+def dyn_params(pkg):
+    p = pkg.dyn_default_params()
+    p.enable, p.max_pts = 1, 512
+    return p
+
+
+def dyn_want(fx):
+    """the loop's lists, counts and dropped counts of the six frames (numpy), from the _dev entry without the map attachment - the
+    run test_with_the_dynamic_loop takes them from; made once"""
+    if "dyn" not in fx._want:
+        torch = fx.torch
+        d = (torch.zeros((N, 512, 2), dtype=torch.float32, device="cuda"), torch.zeros(N, dtype=torch.int32, device="cuda"),
+             torch.full((N,), -7, dtype=torch.int32, device="cuda"))
+        ctx = fx.new_ctx(dyn=dyn_params(fx.pkg))
+        run_dev(fx, ctx, splits=(2, 4), arm=(False, False), dyn_out=d)
+        ctx.close()
+        fx._want["dyn"] = tuple(a.cpu().numpy() for a in d)
+        assert fx._want["dyn"][1][N - 1] > 0
+    return fx._want["dyn"]
+
+
+def host_fed_three_calls(pkg, fx, armed_calls):
+    """svo_track_batch_host in calls of 2, 2 and 2 frames on a context with the dynamic-keypoint loop (max_pts 512); both
+    svo_track_map_out and svo_track_dynamic_out armed with host arrays on the calls of `armed_calls`.  Checked when the third call
+    has returned and BEFORE any svo_sync - the first call's two frames are with the caller (include/svo.h: "once the second
+    following host-fed call has returned"), complete and byte for byte, and nothing was written for a call that was not armed -
+    and again after svo_sync, all six frames and the result records."""
+    want, rec_off, _, _ = fx.want()
+    wl, wc, wd = dyn_want(fx)
+    ctx = fx.new_ctx(dyn=dyn_params(pkg))
+    raw = np.full(N * K * 32 + 80, GUARD, np.uint8)
+    obs = raw[(-raw.ctypes.data) % 16:][:N * K * 32 + 64]
+    counts = np.full(N + 4, -1, np.int32)
+    lists = np.full(N * 512 * 8 + 64, GUARD, np.uint8)
+    cnt = np.full(N + 4, -1, np.int32); drp = np.full(N + 4, -7, np.int32)
+    res = np.zeros(N, pkg.TRACK_DTYPE)
+    aL, aR = np.ascontiguousarray(fx.L), np.ascontiguousarray(fx.R)
+    armed = [c in armed_calls for c in range(3) for _ in range(2)]
+
+    def check_frames(frames):
+        """frames 0 .. frames - 1 as delivered (or, not armed, untouched); every frame behind them untouched if its call was not armed"""
+        check(obs[:frames * K * 32], counts[:frames], want, range(frames), armed=armed[:frames], extra=0)
+        for k in range(N):
+            mine = lists[k * 512 * 8:(k + 1) * 512 * 8]
+            if not armed[k]:
+                assert (obs[k * K * 32:(k + 1) * K * 32] == GUARD).all() and counts[k] == -1, k
+                assert (mine == GUARD).all() and cnt[k] == -1 and drp[k] == -7, k
+            elif k < frames:
+                assert cnt[k] == wc[k] and drp[k] == wd[k], (k, cnt[k], wc[k], drp[k], wd[k])
+                assert mine[:cnt[k] * 8].tobytes() == wl[k, :wc[k]].tobytes(), k
+        assert (obs[N * K * 32:] == GUARD).all() and (lists[N * 512 * 8:] == GUARD).all()
+        assert (counts[N:] == -1).all() and (cnt[N:] == -1).all() and (drp[N:] == -7).all()
+
+    for c in range(3):
+        f0 = 2 * c
+        if c in armed_calls:
+            ctx.track_map_out(obs[f0 * K * 32:], counts[f0:])
+            ctx.track_dynamic_out(lists[f0 * 512 * 8:], cnt[f0:], drp[f0:])
+        ctx.track_batch_host(aL[f0:].ctypes.data, aR[f0:].ctypes.data, W, 2, res[f0:], boxes=pkg.boxes_host(fx.hb[f0:f0 + 2], fx.hn[f0:f0 + 2]))
+    check_frames(2)     # (no svo_sync yet)
+    ctx.sync()
+    ctx.close()
+    check_frames(N)
+    assert res.tobytes() == rec_off
+
+
+@pytest.mark.gpu
+def test_host_fed_set_reuse(pkg, fx):
+    """both attachments armed on each of three host-fed calls: the third call stages in the pinned set of the first, whose two
+    frames reach the caller's arrays first - before any svo_sync"""
+    host_fed_three_calls(pkg, fx, armed_calls=(0, 1, 2))
+
+
+@pytest.mark.gpu
+def test_host_fed_armed_once(pkg, fx):
+    """both attachments armed on the first of three host-fed calls only: its two frames are with the caller when the third call
+    has returned, before any svo_sync, though no later armed call reuses the pinned set; the other calls' arrays stay untouched"""
+    host_fed_three_calls(pkg, fx, armed_calls=(0,))
+
+
 def tail_call(fx, ctx, f0, b, obs, counts, res, arm=True):
     if arm:
         ctx.track_map_out(obs.data_ptr() + f0 * K * 32, counts.data_ptr() + 4 * f0)
