@@ -420,6 +420,30 @@ int svo_debug_epnp5(svo_ctx* ctx, const double Xw5[15], const double uv5[10], co
 int svo_debug_epnp_gn(svo_ctx* ctx, const double L[60], const double rho[6], const double betas_in[12],
                       double betas_out[12]);
 
+/* Parity probe of RANSACPointSetRegistrator::run's sequential rule - which sample wins, how many are visited - in every copy
+ * the library holds of it: the plain rule of svo_pnp_ransac and the tracker's variants that work from precomputed pow / log
+ * terms, on the first m samples only, or report the iteration bound after m samples.  Two modes:
+ *   SVO_PNP_RULE_TABLE  count = the number of points n (5 .. 512); cnt, ok, n unused (NULL).  For every consensus g = 5 .. n:
+ *                       out_f64[g] = log(1 - (g / n)^5) as tabulated per frame (1.0: "denominator below DBL_MIN", the bound is 0),
+ *                       out_i32[g] = rint(log(0.01) / that), out_i32[n + 1 + g] = RANSACUpdateNumIters(0.99, (n - g) / n, 5, 100);
+ *                       entries below g = 5 are 0; out_f64[n + 1] = log(0.01).  out_f64: n + 2 doubles, out_i32: 2 (n + 1) ints.
+ *   SVO_PNP_RULE_CASES  count cases (1 .. 4096), one thread each: cnt / ok = count x 100 (each sample's consensus and whether
+ *                       it gave a model), n = count point numbers (5 .. 512); out_f64 unused.  out_i32: SVO_PNP_RULE_W ints per case:
+ *                       {best, good, iters} of the plain rule; the same from precomputed terms; then for m = 0 .. 100
+ *                       {samples visited within the first m or m + 1, the same from the walk that also yields the winner, its
+ *                       winner, its consensus (-2 where the walk did not end within m), the iteration bound after m samples}. */
+#define SVO_PNP_RULE_TABLE 0
+#define SVO_PNP_RULE_CASES 1
+#define SVO_PNP_RULE_W (6 + 5 * 101)
+int svo_debug_pnp_rule(svo_ctx* ctx, int mode, int count, const int32_t* cnt, const int32_t* ok, const int32_t* n,
+                       double* out_f64, int32_t* out_i32);
+
+/* Parity probe of a RANSAC sample's consensus count: one wavefront counts the inliers of the model (R row-major, t) over the
+ * n (1 .. 512) correspondences exactly as every sample of svo_pnp_ransac does (projection in double, rounded once to float,
+ * squared distance in float <= 64).  flags: n bytes, 1 = inlier. */
+int svo_debug_pnp_consensus(svo_ctx* ctx, const double* Xw, const double* obs, int n, const double K[4], const double R[9],
+                            const double t[3], int32_t* count, uint8_t* flags);
+
 /* ---- a-5: Optimizer::PoseOptimization (src/Optimizer.cc:15-86) -------------- */
 /* Pose-only Levenberg-Marquardt exactly as g2o runs it for this graph: one SE3
  * vertex, n unary EdgeSE3ProjectXYZOnlyPose edges, information I2, Huber

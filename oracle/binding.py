@@ -213,6 +213,34 @@ def pose_opt(Xw, obs, K, T, trace_cap=128):
     return T.reshape(4, 4), st, trace[:nt].copy()
 
 
+def pose_counts():
+    """Branch counters of the last pose_opt call (orc_pose_last_counts): se3_exp with theta < 1e-5 / series / libm, quat_from_R with
+    trace > 0 / largest diagonal 0 / 1 / 2, quaternions flipped for q.w < 0."""
+    return np.array((C.c_int32 * 8).in_dll(lib(), "orc_pose_last_counts"), np.int32)
+
+
+def ransac_update_num_iters(ep, max_iters, p=0.99, model_points=5):
+    """RANSACUpdateNumIters(p, ep, modelPoints, maxIters) as orc_solvepnp_ransac calls it."""
+    f = lib().orc_ransac_update_num_iters
+    f.argtypes = [C.c_double, C.c_double, C.c_int, C.c_int]; f.restype = C.c_int
+    return f(float(p), float(ep), int(model_points), int(max_iters))
+
+
+def ransac_update_num_iters_batch(ep, max_iters):
+    """the same (p = 0.99, modelPoints = 5) on arrays, broadcast against each other"""
+    ep, mi = np.broadcast_arrays(np.asarray(ep, np.float64), np.asarray(max_iters, np.int32))
+    ep = np.ascontiguousarray(ep); mi = np.ascontiguousarray(mi); out = np.zeros(ep.shape, np.int32)
+    lib().orc_ransac_update_num_iters_batch(_p(ep), _p(mi), int(ep.size), _p(out))
+    return out
+
+
+def ransac_log_denom_batch(ep):
+    """log(1 - (1 - ep)^5) as RANSACUpdateNumIters computes it (-inf where ep == 0)"""
+    ep = np.ascontiguousarray(ep, np.float64); out = np.zeros(ep.shape)
+    lib().orc_ransac_log_denom_batch(_p(ep), int(ep.size), _p(out))
+    return out
+
+
 def pnp_ransac(Xw, obs, K, T_fallback, rng_state=0, refine=0):
     """cv::solvePnPRansac(..., false, 100, 8.0, 0.99) restated; rng_state 0 = OpenCV's (uint64)-1."""
     Xw = np.ascontiguousarray(Xw, np.float64); obs = np.ascontiguousarray(obs, np.float64)

@@ -567,7 +567,22 @@ static int find_inliers(const double* Xw, const double* obs, int n, const double
   return good;
 }
 
+/* RANSACUpdateNumIters (ptsetreg.cpp), exported for the tests of the device's copies of the rule */
+int orc_ransac_update_num_iters(double p, double ep, int modelPoints, int maxIters);
+void orc_ransac_update_num_iters_batch(const double* ep, const int32_t* maxIters, int count, int32_t* out) {
+  for (int i = 0; i < count; ++i) out[i] = orc_ransac_update_num_iters(0.99, ep[i], 5, maxIters[i]);
+}
+/* log(1 - (1 - ep)^5), the denominator RANSACUpdateNumIters(., ep, 5, .) divides by, as it computes it (tests: how far the device's is) */
+void orc_ransac_log_denom_batch(const double* ep, int count, double* out) {
+  for (int i = 0; i < count; ++i) {
+    double e = ep[i] > 0. ? ep[i] : 0.; e = e < 1. ? e : 1.;
+    out[i] = log(1. - pow(1. - e, 5));
+  }
+}
 static int ransac_update_num_iters(double p, double ep, int modelPoints, int maxIters) {
+  return orc_ransac_update_num_iters(p, ep, modelPoints, maxIters);
+}
+int orc_ransac_update_num_iters(double p, double ep, int modelPoints, int maxIters) {
   p = p > 0. ? p : 0.; p = p < 1. ? p : 1.;
   ep = ep > 0. ? ep : 0.; ep = ep < 1. ? ep : 1.;
   double num = 1. - p > DBL_MIN ? 1. - p : DBL_MIN;
@@ -650,8 +665,10 @@ int orc_solvepnp_ransac(const double* Xw, const double* obs, int n, const double
       }
       orc_epnp5(X5, u5, K, R, t);                   /* runKernel: solvePnP(..., SOLVEPNP_EPNP), then Rodrigues(R, rvec) */
       rodrigues_to_vector(R, rvec);
-      if (!(isfinite(rvec[0]) && isfinite(rvec[1]) && isfinite(rvec[2]) && isfinite(t[0]) && isfinite(t[1]) && isfinite(t[2])))
+      if (!(isfinite(rvec[0]) && isfinite(rvec[1]) && isfinite(rvec[2]) && isfinite(t[0]) && isfinite(t[1]) && isfinite(t[2]))) {
+        if (n == modelPoints) break;                /* run(): count == modelPoints is ONE runKernel call, no loop */
         continue;
+      }
       if (n == modelPoints) {                       /* run(): count == modelPoints -> the model, mask all ones */
         memset(bestMask, 1, (size_t)n);
         memcpy(best_r, rvec, sizeof best_r); memcpy(best_t, t, sizeof best_t);

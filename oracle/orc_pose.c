@@ -35,10 +35,17 @@
 
 typedef struct { double q[4]; /* x y z w */ double t[3]; } se3_t;
 
+/* Branch counters of the last orc_pose_opt call (tests: which paths a fixture case walks; tools/make_lm_edge_cases.py).
+ *   [0..2] se3_exp calls with theta < 1e-5 / on the fixed series / on libm's sin and cos (theta >= 0.5: not bit-guaranteed)
+ *   [3..6] quat_from_R calls with trace > 0 / largest diagonal 0 / 1 / 2
+ *   [7]    normalize_rotation calls that met q.w < 0 and flipped the quaternion */
+int32_t orc_pose_last_counts[8];
+
 /* Eigen Quaternion(Matrix3) - quaternionbase_assign_impl<Other,3,3>. */
 static void quat_from_R(const double m[9], double q[4]) {
   double t = m[0] + m[4] + m[8];
   if (t > 0.0) {
+    ++orc_pose_last_counts[3];
     t = sqrt(t + 1.0);
     q[3] = 0.5 * t;
     t = 0.5 / t;
@@ -49,6 +56,7 @@ static void quat_from_R(const double m[9], double q[4]) {
     int i = 0;
     if (m[4] > m[0]) i = 1;
     if (m[8] > m[4 * i]) i = 2;
+    ++orc_pose_last_counts[4 + i];
     int j = (i + 1) % 3, k = (j + 1) % 3;
     t = sqrt(m[4 * i] - m[4 * j] - m[4 * k] + 1.0);
     q[i] = 0.5 * t;
@@ -60,7 +68,10 @@ static void quat_from_R(const double m[9], double q[4]) {
 }
 /* se3quat.h:280-285 */
 static void normalize_rotation(se3_t* s) {
-  if (s->q[3] < 0) for (int i = 0; i < 4; ++i) s->q[i] *= -1;
+  if (s->q[3] < 0) {
+    ++orc_pose_last_counts[7];
+    for (int i = 0; i < 4; ++i) s->q[i] *= -1;
+  }
   double n = sqrt(s->q[0] * s->q[0] + s->q[1] * s->q[1] + s->q[2] * s->q[2] + s->q[3] * s->q[3]);
   for (int i = 0; i < 4; ++i) s->q[i] /= n;
 }
@@ -161,6 +172,7 @@ static void se3_exp(const double u[6], se3_t* out) {
   const double Om[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
   double Om2[9], R[9], V[9];
   mat3_mul(Om, Om, Om2);
+  ++orc_pose_last_counts[theta < 0.00001 ? 0 : (theta < 0.5 ? 1 : 2)];
   if (theta < 0.00001) {
     for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + Om[i] + Om2[i];
     memcpy(V, R, sizeof R);
@@ -297,6 +309,7 @@ int orc_pose_opt(const double* Xw, const double* obs, int n, const double K[4], 
                  orc_lm_stats* stats, double* trace, int trace_cap) {
   const double delta = (double)(float)sqrt(5.991); /* const float deltaMono, Optimizer.cc:38 */
   se3_t est;
+  memset(orc_pose_last_counts, 0, sizeof orc_pose_last_counts);
   se3_from_T(T, &est);
   double lambda = -1., ni = 2.;
   int nBad = 0, ntrace = 0, iters = 0, trials_total = 0, terminated = 0;

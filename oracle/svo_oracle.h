@@ -97,6 +97,9 @@ void orc_se3_exp_matrix(const double upd[6], double T[16]);
 void orc_se3_update(const double upd[6], double T[16]);
 int orc_pose_opt(const double* Xw, const double* obs, int n, const double K[4], double T[16],
                  orc_lm_stats* stats, double* trace, int trace_cap);
+/* branch counters of the last orc_pose_opt call: se3_exp per regime (theta < 1e-5, series, libm), quat_from_R per branch (trace > 0,
+ * largest diagonal 0 / 1 / 2), quaternions flipped for q.w < 0 (orc_pose.c) */
+extern int32_t orc_pose_last_counts[8];
 /* cv::solvePnPRansac(..., false, 100, 8.0, 0.99, inliers) restated (orc_pnp_cv.c).  T_fallback: the pose reported when
  * OpenCV returns false; rng_state 0 = (uint64)-1, what RANSACPointSetRegistrator::run seeds its cv::RNG with. */
 int orc_pnp_ransac(const double* Xw, const double* obs, int n, const double K[4],
@@ -104,6 +107,11 @@ int orc_pnp_ransac(const double* Xw, const double* obs, int n, const double K[4]
                    orc_pnp_stats* stats);
 int orc_solvepnp_ransac(const double* Xw, const double* obs, int n, const double K[4], const double T_fallback[16],
                         uint64_t rng_state, int refine, double T[16], uint8_t* inlier_mask, orc_pnp_stats* stats);
+/* RANSACUpdateNumIters(p, ep, modelPoints, maxIters): the iteration bound of RANSACPointSetRegistrator::run */
+int orc_ransac_update_num_iters(double p, double ep, int modelPoints, int maxIters);
+/* the same for p = 0.99, modelPoints = 5 on arrays (the tests' exhaustive tables) */
+void orc_ransac_update_num_iters_batch(const double* ep, const int32_t* maxIters, int count, int32_t* out);
+void orc_ransac_log_denom_batch(const double* ep, int count, double* out);   /* log(1 - (1 - ep)^5) as that function computes it */
 /* epnp::compute_pose on five correspondences: R (row-major 3x3), t */
 void orc_epnp5(const double Xw5[15], const double uv5[10], const double K[4], double R_out[9], double t_out[3]);
 

@@ -52,7 +52,7 @@ ABI_SYMBOLS = [
     "svo_debug_fast_corners", "svo_stereo_frame", "svo_stereo_frame_ex", "svo_disp2depth",
     "svo_unproject", "svo_descriptor_distance", "svo_hamming_argmin", "svo_match_greedy",
     "svo_match_greedy_gated",
-    "svo_bf_match", "svo_pnp_ransac", "svo_debug_epnp5", "svo_debug_epnp_gn", "svo_pose_opt", "svo_track_reset", "svo_track_frame",
+    "svo_bf_match", "svo_pnp_ransac", "svo_debug_epnp5", "svo_debug_epnp_gn", "svo_debug_pnp_rule", "svo_debug_pnp_consensus", "svo_pose_opt", "svo_track_reset", "svo_track_frame",
     "svo_debug_track_matches", "svo_debug_track_gate", "svo_debug_track_pnp", "svo_debug_track_frames", "svo_fundamental_8point",
     "svo_frontend_batch_dev", "svo_track_batch_dev", "svo_profile_enable", "svo_profile_reset",
     "svo_profile_get",
@@ -70,6 +70,8 @@ ABI_SYMBOLS = [
     "svo_dyn_default_params", "svo_track_dynamic", "svo_track_dynamic_out", "svo_track_multi_step_bgr_dev",
     "svo_debug_stereo_match", "svo_track_map_out",
 ]
+
+PNP_RULE_W = 6 + 5 * 101   # SVO_PNP_RULE_W (include/svo.h)
 
 # svo_create_ex flags (include/svo.h)
 CREATE_POOLED_STREAMS = 1
@@ -390,6 +392,36 @@ class Svo:
         betas = np.ascontiguousarray(betas, np.float64).reshape(12); out = np.zeros(12)
         self._chk(self.lib.svo_debug_epnp_gn(self.h, _p(L), _p(rho), _p(betas), _p(out)))
         return out.reshape(3, 4)
+
+    def debug_pnp_rule_table(self, n):
+        """svo_debug_pnp_rule, table mode: for g = 0 .. n (zeros below 5) the tabulated ld = log(1 - (g / n)^5) (1.0: bound 0), r =
+        rint(log(0.01) / ld) and RANSACUpdateNumIters(0.99, (n - g) / n, 5, 100); and log(0.01) as the device spells it."""
+        d = np.zeros(n + 2); i = np.zeros(2 * (n + 1), np.int32)
+        self._chk(self.lib.svo_debug_pnp_rule(self.h, 0, int(n), None, None, None, _p(d), _p(i)))
+        return d[:n + 1].copy(), i[:n + 1].copy(), i[n + 1:].copy(), float(d[n + 1])
+
+    def debug_pnp_rule(self, cnt, ok, n):
+        """svo_debug_pnp_rule, rule mode: cnt / ok B x 100, n B -> dict of the copies' results (see include/svo.h); per_m: B x 101 x 5
+        {pre_bound, pre_early, early best, early good, bound_after}."""
+        cnt = np.ascontiguousarray(cnt, np.int32).reshape(-1, 100); ok = np.ascontiguousarray(ok, np.int32).reshape(-1, 100)
+        n = np.ascontiguousarray(n, np.int32).reshape(-1)
+        B = len(n)
+        if len(cnt) != B or len(ok) != B:
+            raise SvoError("debug_pnp_rule: cnt, ok and n must hold one row per case")
+        out = np.zeros((B, PNP_RULE_W), np.int32)
+        self._chk(self.lib.svo_debug_pnp_rule(self.h, 1, B, _p(cnt), _p(ok), _p(n), None, _p(out)))
+        return {"select": out[:, 0:3].copy(), "select_pre": out[:, 3:6].copy(), "per_m": out[:, 6:].reshape(B, 101, 5).copy()}
+
+    def debug_pnp_consensus(self, Xw, obs, K, R, t):
+        """svo_debug_pnp_consensus: one wave's inlier count of the model (R, t) over the n correspondences, and the per-point flags."""
+        Xw = np.ascontiguousarray(Xw, np.float64).reshape(-1, 3); obs = np.ascontiguousarray(obs, np.float64).reshape(-1, 2)
+        K = np.ascontiguousarray(K, np.float64); R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        if len(obs) != len(Xw):
+            raise SvoError("debug_pnp_consensus: one observation per point")
+        cnt = np.zeros(1, np.int32); flags = np.zeros(max(len(Xw), 1), np.uint8)
+        self._chk(self.lib.svo_debug_pnp_consensus(self.h, _p(Xw), _p(obs), len(Xw), _p(K), _p(R), _p(t), _p(cnt), _p(flags)))
+        return int(cnt[0]), flags[:len(Xw)]
 
     # ---- Optimizer::PoseOptimization ------------------------------------------------------
     def pose_opt(self, Xw, obs, K, T):

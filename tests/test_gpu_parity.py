@@ -323,7 +323,8 @@ def test_pose_opt_zero_edges_keeps_pose(svo_small):
 # bit-identical on all 4,541 frames of tests/test_full_length.py).
 # (The statistical solver, mode 0, orders its linear algebra differently: tolerances in test_epnp5_candidates_against_oracle.)
 PNP_TOL = 1e-9
-@pytest.mark.parametrize("seed,n,outliers", [(7, 500, 0.2), (12, 60, 0.2), (21, 200, 0.5), (33, 300, 0.0), (5, 9, 0.0)])
+@pytest.mark.parametrize("seed,n,outliers", [(7, 500, 0.2), (12, 60, 0.2), (21, 200, 0.5), (33, 300, 0.0), (5, 9, 0.0),
+                                             (76, 6, 0.2), (43, 7, 0.2)])     # (n = 6, 7: the redraw loop of svo_pnp_subsets at small n; 16 / 41 samples visited)
 def test_pnp_ransac_against_oracle(svo_small, orc, seed, n, outliers):
     Xw, obs, K, T_true = util.pose_problem(seed, n=n, outlier_frac=outliers)
     T0 = np.eye(4)
@@ -424,7 +425,8 @@ def test_epnp5_exact_mode_equals_oracle_candidate_by_candidate(pkg, orc):
     print("epnp_exact worst |delta| =", worst)
 
 
-@pytest.mark.parametrize("seed,n,outliers", [(7, 500, 0.2), (12, 60, 0.2), (21, 200, 0.5), (33, 300, 0.0), (5, 9, 0.0), (13, 5, 0.0)])
+@pytest.mark.parametrize("seed,n,outliers", [(7, 500, 0.2), (12, 60, 0.2), (21, 200, 0.5), (33, 300, 0.0), (5, 9, 0.0), (13, 5, 0.0),
+                                             (76, 6, 0.2), (43, 7, 0.2)])
 def test_pnp_ransac_exact_mode_equals_oracle(pkg, orc, seed, n, outliers):
     """cv::solvePnPRansac in the bit-comparable mode: the discrete outcome AND the pose (to 1e-9) are the oracle's."""
     Xw, obs, K, T_true = util.pose_problem(seed, n=n, outlier_frac=outliers)
