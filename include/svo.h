@@ -1128,6 +1128,57 @@ int svo_det_sync(svo_det* det);
  * network input, 3 x height x width).  Synchronises. */
 int svo_det_debug_tensor(svo_det* det, int layer, int frame, float* host_out);
 
+/* ---- stereo rectification on the device (ABI-8 additions; no existing entry changed) ---------------------------------------
+ * Every other entry of this header starts from a RECTIFIED pair.  These entries make one from a raw pair and the calibration
+ * an ORB-SLAM2 settings file carries (LEFT.K / .D / .R / .P and RIGHT.*, or the flat Camera.fx .. Camera.p2 keys):
+ * cv::initUndistortRectifyMap(K, D, R, P, size, CV_32FC1) once per object, then cv::remap(INTER_LINEAR, BORDER_CONSTANT 0)
+ * per image, 8-bit, 1 channel or 3 interleaved channels.  The arithmetic, operation by operation, is DESIGN.md section 8
+ * "Rectification" (restated from OpenCV 3.2; parity with OpenCV itself is not pinned - the tests compare with a numpy restatement).
+ *   K = (fx, fy, cx, cy); D = (k1, k2, p1, p2, k3); R = 3 x 3 row-major; P = (fx', fy', cx', cy'), the entries (0,0), (1,1),
+ *   (0,2), (1,2) of the 3 x 4 projection.  Sizes: widths 8 .. 8192, heights 1 .. 8192; source and destination may differ.
+ * Out of scope: computing R and P from extrinsics (cv::stereoRectify); fisheye, rational (k4..k6), thin-prism and tilted
+ * models; 16-bit images; interpolations other than bilinear; rectification inside the host-fed entries
+ * (svo_track_batch_host, svo_track_sharded_*): rectify into device buffers and call the device-resident ones. */
+typedef struct svo_rect_cam { double K[4], D[5], R[9], P[4]; } svo_rect_cam;
+typedef struct svo_rect svo_rect;
+
+/* Builds both cameras' maps on HIP device `device` (float64, one lane per destination row: the running sums along a row are
+ * part of the contract) and keeps them in HBM.  SVO_E_INVALID before any device is touched: a NULL pointer, a width outside
+ * 8 .. 8192 or a height outside 1 .. 8192, a non-finite calibration value, det(Ar R) == 0 (or not finite).
+ * svo_rect_last_error(NULL) says which. */
+int svo_rect_create(int device, int src_w, int src_h, int dst_w, int dst_h, const svo_rect_cam* left,
+                    const svo_rect_cam* right, svo_rect** out);
+int svo_rect_destroy(svo_rect* rect);
+/* Text of the last failure of `rect`; with rect = NULL, of the calling thread's last svo_rect_create. */
+const char* svo_rect_last_error(const svo_rect* rect);
+/* The rectified pair's camera for svo_track_reset and the front end: fx', fy', cx', cy' of the LEFT P (as float), bf as given
+ * (0 where the caller has none). */
+int svo_rect_camera(const svo_rect* rect, double bf_or_0, svo_camera* cam);
+/* One raw pair, host to host: L / R rows `src_stride` bytes apart (>= cn * src_w), cn = 1 or 3, outL / outR rows
+ * `dst_stride` bytes apart (>= cn * dst_w; bytes of a row beyond cn * dst_w are not written).  Synchronises. */
+int svo_rect_process(svo_rect* rect, const uint8_t* L, const uint8_t* R, int src_stride, int cn, uint8_t* outL,
+                     uint8_t* outR, int dst_stride);
+/* B raw pairs resident in HBM (pair b at d_L / d_R + b * src_h * src_stride) -> B rectified pairs (pair b at d_outL / d_outR
+ * + b * dst_h * dst_stride: the layout svo_track_batch_dev, svo_track_batch_bgr_dev, svo_track_multi_step[_bgr]_dev and
+ * svo_frontend_batch_dev take), one launch for both sides (in chunks where B exceeds the grid's limit; B >= 1, no cap).
+ * Does not synchronise: the rectifier runs on a stream of its own (svo_rect_stream).
+ * consumer (may be NULL, same device): that context's NEXT call of one of the five entries above waits ON THE DEVICE for
+ * these outputs before it reads a pixel - no host synchronisation in between.  A context never named here enqueues exactly
+ * what it did before.
+ * The other direction has no hidden wait: the outputs (and the inputs) of a call may be rewritten once the consumer's call
+ * that read them is done - after svo_sync(consumer), or behind an event the caller records on svo_stream(consumer) after
+ * that call and makes svo_rect_stream wait for (the rule svo_track_multi_step_dev states for its images).  A caller that
+ * alternates between two output sets and synchronises the consumer once per two calls satisfies it. */
+int svo_rect_batch_dev(svo_rect* rect, const uint8_t* d_L, const uint8_t* d_R, int src_stride, int cn, int B,
+                       uint8_t* d_outL, uint8_t* d_outR, int dst_stride, svo_ctx* consumer);
+/* Wait for the rectifier's work in flight; its stream (a hipStream_t). */
+int svo_rect_sync(svo_rect* rect);
+void* svo_rect_stream(svo_rect* rect);
+/* Parity probe, side 0 = left, 1 = right; any output may be NULL: the inverse matrix iR (host float64), the float32 maps
+ * (dst_h x dst_w each) and the fixed-point coordinates the remap kernel works from, sxsy[2 (i dst_w + j)] = sx, [.. + 1] =
+ * sy (ix = sx >> 5, a = sx & 31); a pixel that is "outside" by its map value has sx = sy = INT32_MIN.  Synchronises. */
+int svo_rect_debug_maps(svo_rect* rect, int side, double iR[9], float* mapx, float* mapy, int32_t* sxsy);
+
 #ifdef __cplusplus
 }
 #endif

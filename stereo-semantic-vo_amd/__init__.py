@@ -69,6 +69,8 @@ ABI_SYMBOLS = [
     "svo_lk_track_bgr", "svo_lk_batch_bgr_dev", "svo_lk_chain_bgr_dev", "svo_lk_debug_level_bgr",
     "svo_dyn_default_params", "svo_track_dynamic", "svo_track_dynamic_out", "svo_track_multi_step_bgr_dev",
     "svo_debug_stereo_match", "svo_track_map_out",
+    "svo_rect_create", "svo_rect_destroy", "svo_rect_last_error", "svo_rect_camera", "svo_rect_process", "svo_rect_batch_dev",
+    "svo_rect_sync", "svo_rect_stream", "svo_rect_debug_maps",
 ]
 
 PNP_RULE_W = 6 + 5 * 101   # SVO_PNP_RULE_W (include/svo.h)
@@ -1087,3 +1089,187 @@ class Detector:
         self._chk(self.lib.svo_det_debug_tensor(self.h, int(layer), int(frame), out.ctypes.data_as(C.c_void_p)),
                   "svo_det_debug_tensor")
         return out
+
+
+# ---- stereo rectification (svo_rect_* in include/svo.h; the contract: DESIGN.md section 8 "Rectification") ----------------------------------
+class RectCam(C.Structure):
+    """svo_rect_cam: K = (fx, fy, cx, cy), D = (k1, k2, p1, p2, k3), R 3 x 3 row-major, P = (fx', fy', cx', cy')."""
+    _fields_ = [("K", C.c_double * 4), ("D", C.c_double * 5), ("R", C.c_double * 9), ("P", C.c_double * 4)]
+
+
+def rect_cam(K, D, R=None, P=None):
+    """A RectCam from sequences; R defaults to the identity, P to K (one undistorted camera)."""
+    K = [float(v) for v in K]
+    D = [float(v) for v in D] + [0.0] * (5 - len(D))
+    R = np.eye(3) if R is None else np.asarray(R, np.float64).reshape(3, 3)
+    P = K if P is None else [float(v) for v in P]
+    return RectCam((C.c_double * 4)(*K), (C.c_double * 5)(*D[:5]), (C.c_double * 9)(*R.ravel()), (C.c_double * 4)(*P))
+
+
+def _settings_entries(path):
+    """The scalars and !!opencv-matrix blocks of an OpenCV FileStorage YAML file, as ORB-SLAM2's settings files use it
+    (`key: value` lines; a matrix is rows / cols / dt / data, where `data: [...]` may span lines)."""
+    import re
+    txt = open(path).read()
+    txt = re.sub(r"^%YAML.*$", "", txt, flags=re.M)
+    txt = re.sub(r"#.*$", "", txt, flags=re.M)
+    mats, scalars = {}, {}
+    pat = re.compile(r"^([A-Za-z_][\w.]*)\s*:\s*!!opencv-matrix\s*$((?:\n[ \t]+.*|\n[ \t]*)*)", re.M)
+    for m in pat.finditer(txt):
+        body = m.group(2)
+        rows = re.search(r"\brows\s*:\s*(\d+)", body)
+        cols = re.search(r"\bcols\s*:\s*(\d+)", body)
+        data = re.search(r"\bdata\s*:\s*\[(.*?)\]", body, re.S)
+        if not (rows and cols and data):
+            raise SvoError("%s: matrix %s needs rows, cols and data: [...]" % (path, m.group(1)))
+        vals = [float(v) for v in data.group(1).replace("\n", " ").split(",") if v.strip()]
+        if len(vals) != int(rows.group(1)) * int(cols.group(1)):
+            raise SvoError("%s: matrix %s holds %d values, rows x cols = %d" %
+                           (path, m.group(1), len(vals), int(rows.group(1)) * int(cols.group(1))))
+        mats[m.group(1)] = np.array(vals, np.float64).reshape(int(rows.group(1)), int(cols.group(1)))
+    txt = pat.sub("", txt)
+    for m in re.finditer(r"^([A-Za-z_][\w.]*)\s*:\s*(\S+)\s*$", txt, re.M):
+        scalars[m.group(1)] = m.group(2).strip('"')
+    return scalars, mats
+
+
+def load_rect_settings(path):
+    """The rectification an ORB-SLAM2 settings file describes: dict(left, right (RectCam), src_w, src_h, dst_w, dst_h, bf).
+    LEFT.K / LEFT.D / LEFT.R / LEFT.P and RIGHT.* (EuRoC style; sizes from LEFT.width / LEFT.height, else Camera.width /
+    Camera.height) win; otherwise the flat keys Camera.fx, fy, cx, cy, k1, k2, p1, p2 and an optional Camera.k3 are one
+    camera model for both sides with R = I and P = K.  Raises SvoError naming the missing key."""
+    sc, mats = _settings_entries(path)
+
+    def num(key, default=None):
+        if key not in sc:
+            if default is None:
+                raise SvoError("%s: key %s is missing" % (path, key))
+            return default
+        return float(sc[key])
+
+    cams = {}
+    if any(k.startswith(("LEFT.", "RIGHT.")) for k in mats):
+        for side in ("LEFT", "RIGHT"):
+            need = {}
+            for part, shape in (("K", 9), ("D", None), ("R", 9), ("P", 12)):
+                key = "%s.%s" % (side, part)
+                if key not in mats:
+                    raise SvoError("%s: key %s is missing" % (path, key))
+                need[part] = mats[key].ravel()
+                if shape is not None and need[part].size != shape:
+                    raise SvoError("%s: %s must hold %d values" % (path, key, shape))
+            if not 4 <= need["D"].size <= 5:
+                raise SvoError("%s: %s.D must hold 4 or 5 values (k1, k2, p1, p2[, k3])" % (path, side))
+            K, P = need["K"], need["P"]
+            cams[side] = rect_cam((K[0], K[4], K[2], K[5]), list(need["D"]), need["R"], (P[0], P[5], P[2], P[6]))
+        w = int(num("LEFT.width", num("Camera.width", -1.0)))
+        h = int(num("LEFT.height", num("Camera.height", -1.0)))
+    else:
+        K = [num("Camera." + k) for k in ("fx", "fy", "cx", "cy")]
+        D = [num("Camera." + k) for k in ("k1", "k2", "p1", "p2")] + [num("Camera.k3", 0.0)]
+        cams["LEFT"] = rect_cam(K, D)
+        cams["RIGHT"] = rect_cam(K, D)
+        w, h = int(num("Camera.width", -1.0)), int(num("Camera.height", -1.0))
+    if w < 0 or h < 0:
+        raise SvoError("%s: no image size (LEFT.width / LEFT.height or Camera.width / Camera.height)" % path)
+    return dict(left=cams["LEFT"], right=cams["RIGHT"], src_w=w, src_h=h, dst_w=w, dst_h=h, bf=num("Camera.bf", 0.0))
+
+
+class Rectifier:
+    """Undistort + rectify raw stereo pairs on one GPU (wraps svo_rect): cv::initUndistortRectifyMap once, cv::remap
+    (bilinear, constant 0 border) per 8-bit image, gray or BGR."""
+
+    def __init__(self, src_w, src_h, left, right, dst_w=None, dst_h=None, device=0):
+        self.lib = lib = load_library()
+        lib.svo_rect_last_error.restype = C.c_char_p
+        lib.svo_rect_last_error.argtypes = [C.c_void_p]
+        lib.svo_rect_create.argtypes = [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        lib.svo_rect_destroy.argtypes = [C.c_void_p]
+        lib.svo_rect_camera.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        lib.svo_rect_process.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        lib.svo_rect_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_int, C.c_void_p]
+        lib.svo_rect_sync.argtypes = [C.c_void_p]
+        lib.svo_rect_stream.restype = C.c_void_p
+        lib.svo_rect_stream.argtypes = [C.c_void_p]
+        lib.svo_rect_debug_maps.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        self.src_w, self.src_h = int(src_w), int(src_h)
+        self.dst_w = self.src_w if dst_w is None else int(dst_w)
+        self.dst_h = self.src_h if dst_h is None else int(dst_h)
+        h = C.c_void_p()
+        rc = lib.svo_rect_create(int(device), self.src_w, self.src_h, self.dst_w, self.dst_h,
+                                 None if left is None else C.addressof(left), None if right is None else C.addressof(right),
+                                 C.byref(h))
+        if rc != 0:
+            raise SvoError("svo_rect_create: %s: %s" % (lib.svo_strerror(rc).decode(), lib.svo_rect_last_error(None).decode()))
+        self.h = h
+        self._keep = (left, right)
+
+    @classmethod
+    def from_settings(cls, path, device=0):
+        s = load_rect_settings(path)
+        r = cls(s["src_w"], s["src_h"], s["left"], s["right"], s["dst_w"], s["dst_h"], device=device)
+        r.bf = s["bf"]
+        return r
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.svo_rect_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise SvoError("%s: %s: %s" % (what, self.lib.svo_strerror(rc).decode(), self.lib.svo_rect_last_error(self.h).decode()))
+
+    def camera(self, bf=0.0):
+        """The rectified pair's Camera (the left P's fx', fy', cx', cy'; bf as given)."""
+        cam = Camera()
+        self._chk(self.lib.svo_rect_camera(self.h, float(bf), C.addressof(cam)), "svo_rect_camera")
+        return cam
+
+    def process(self, L, R, out_stride=None):
+        """One raw pair (H x W gray or H x W x 3 BGR numpy arrays, any row stride) -> the rectified pair.  out_stride: bytes
+        per row of the returned arrays' buffers (default tight); bytes beyond a row's pixels keep the value 0xA5."""
+        def rows_ok(a):   # rows may be further apart than their pixels (a view of a padded buffer); pixels must be packed
+            return a.dtype == np.uint8 and a.strides[1:] == ((1,) if a.ndim == 2 else (a.shape[2], 1)) and a.strides[0] > 0
+        if not (rows_ok(L) and rows_ok(R) and L.strides == R.strides):
+            L, R = _u8(L), _u8(R)
+        cn = 1 if L.ndim == 2 else L.shape[2]
+        st = cn * self.dst_w if out_stride is None else int(out_stride)
+        oL = np.full((self.dst_h, max(st, 1)), 0xA5, np.uint8)
+        oR = np.full((self.dst_h, max(st, 1)), 0xA5, np.uint8)
+        self._chk(self.lib.svo_rect_process(self.h, _p(L), _p(R), L.strides[0], cn, _p(oL), _p(oR), st), "svo_rect_process")
+        if out_stride is not None:
+            return oL, oR
+        shape = (self.dst_h, self.dst_w) if cn == 1 else (self.dst_h, self.dst_w, 3)
+        return oL.reshape(shape), oR.reshape(shape)
+
+    def batch_dev(self, d_L, d_R, src_stride, cn, B, d_outL, d_outR, dst_stride, consumer=None):
+        """svo_rect_batch_dev on device memory: torch uint8 tensors, or device pointers as ints.  consumer: an Svo whose next
+        device-resident tracking / front-end call waits on the device for these images.  Does not synchronise."""
+        ptr = [int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t) for t in (d_L, d_R, d_outL, d_outR)]
+        self._chk(self.lib.svo_rect_batch_dev(self.h, C.c_void_p(ptr[0]), C.c_void_p(ptr[1]), int(src_stride), int(cn), int(B),
+                                              C.c_void_p(ptr[2]), C.c_void_p(ptr[3]), int(dst_stride),
+                                              None if consumer is None else consumer.h), "svo_rect_batch_dev")
+
+    def sync(self):
+        self._chk(self.lib.svo_rect_sync(self.h), "svo_rect_sync")
+
+    @property
+    def stream(self):
+        return self.lib.svo_rect_stream(self.h)
+
+    def maps(self, side=0):
+        """(iR (9,) float64, mapx, mapy (dst_h x dst_w float32), sxsy (dst_h x dst_w x 2 int32)) of side 0 = left, 1 = right."""
+        iR = np.zeros(9, np.float64)
+        mx = np.zeros((self.dst_h, self.dst_w), np.float32)
+        my = np.zeros((self.dst_h, self.dst_w), np.float32)
+        s = np.zeros((self.dst_h, self.dst_w, 2), np.int32)
+        self._chk(self.lib.svo_rect_debug_maps(self.h, int(side), _p(iR), _p(mx), _p(my), _p(s)), "svo_rect_debug_maps")
+        return iR, mx, my, s

@@ -330,6 +330,7 @@ extern "C" void svo_destroy(svo_ctx* ctx) {
   for (void* p : ptrs)
     if (p) hipFree(p);
   if (ctx->det_ready) hipEventDestroy(ctx->det_ready);
+  if (ctx->rect_ready) hipEventDestroy(ctx->rect_ready);
   for (hipEvent_t e : ctx->det_read)
     if (e) hipEventDestroy(e);
   if (ctx->h_pinned) hipHostFree(ctx->h_pinned);
@@ -969,6 +970,7 @@ extern "C" int svo_frontend_batch_dev(svo_ctx* ctx, const uint8_t* d_grayL, cons
   if (B > ctx->max_batch) return SVO_E_CAPACITY;
   hipSetDevice(ctx->device);
   { const int rcq = svo_track_quiesce(ctx); if (rcq) return rcq; }   // (a batched tracker call's tail may still read the result arrays)
+  SVO_HIP(ctx, svo_rect_gate(ctx, ctx->stream));   // (images of svo_rect_batch_dev(consumer = ctx): the other slices' streams fork from this one below)
   // Slices of the batch side by side on their own streams: the kernels of the chain are a mix of arithmetic-bound ones (k_fast: the
   // vector ALUs 88 % busy) and latency-bound ones (k_select, k_stereo_*, the small pyramid levels: a few waves per CU
   // waiting on memory) - side by side they fill each other's gaps.  With the per-kernel timers on (svo_profile_enable)

@@ -152,6 +152,8 @@ struct svo_ctx {
   bool det_pending = false;         // the next tail_enqueue waits for det_ready on both tail streams, then clears this
   hipEvent_t det_read[2] = {nullptr, nullptr};   // recorded on both tail streams behind a call that read boxes while det_ready exists;
   bool det_read_valid = false;                    // the next svo_det_batch_dev(consumer = this ctx) waits for them before it writes
+  hipEvent_t rect_ready = nullptr;  // svo_rect_batch_dev(consumer = this ctx): recorded on the rectifier's stream behind its images
+  bool rect_pending = false;        // the next entry that reads caller images makes its first reading stream wait for it (svo_rect_gate)
   hipEvent_t shard_wait = nullptr;   // borrowed: the gather event of the sharded tracker call that last read this context's result arrays
   void* d_gate_pre = nullptr;   // GatePre records (brute-force matches + F solved ahead of the index chain), like d_work
   int idx_probe_attempts = -1;  // how many candidate streams the index chain's stream was chosen from (-1: not chosen yet, 0: probe off)
@@ -238,6 +240,15 @@ static inline hipError_t svo_memcpy_sync(svo_ctx* ctx, void* dst, const void* sr
   hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   return e;
+}
+
+// Images handed over by svo_rect_batch_dev(consumer = ctx) (svo_rect.hip): `s` is the stream on which the entry that calls this
+// reads its caller's images FIRST - every other stream that reads them in that entry is ordered behind `s` from there on (the list,
+// entry by entry: DESIGN.md section 8 "Rectification").  A context never named as a consumer enqueues nothing here.
+static inline hipError_t svo_rect_gate(svo_ctx* ctx, hipStream_t s) {
+  if (!ctx->rect_pending) return hipSuccess;
+  ctx->rect_pending = false;
+  return hipStreamWaitEvent(s, ctx->rect_ready, 0);
 }
 
 static inline SvoFeBufs svo_fe_own(const svo_ctx* ctx) {

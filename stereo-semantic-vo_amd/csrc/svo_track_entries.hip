@@ -280,6 +280,7 @@ int svo_track_multi_step_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t
   { const int rcs = svo_shard_quiesce(ctx); if (rcs) return rcs; }   // (a sharded call of this context may still be in flight: staging sets, work records)
   // the step's front end on stream `s` into `fb`: the colour entry's gray of the 2 n_seq images first, ORB, sparse stereo
   auto front_end = [&](hipStream_t s, const SvoFeBufs& fb) -> int {
+    SVO_HIP(ctx, svo_rect_gate(ctx, s));   // (images of svo_rect_batch_dev(consumer = ctx): the tail reads them behind this front end)
     int rcf = bgr_to_gray(ctx, s, bgr, d_grayL, d_grayR, stride, 0, n_seq, true);
     if (rcf == SVO_OK) rcf = svo_launch_orb(ctx, s, fb, d_grayL, d_grayR, stride, n_seq, 2 * n_seq);
     if (rcf == SVO_OK) rcf = svo_launch_stereo(ctx, s, fb, d_grayL, d_grayR, stride, n_seq, &ctx->cam);
@@ -381,6 +382,7 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
     svo_elas_default_params(0, &ep);
     if ((rc = tb_done_events(ctx))) return rc;
     // the dense stage writes the ctx's own result arrays and maps: everything the ctx stream holds (an earlier call's tail) first
+    SVO_HIP(ctx, svo_rect_gate(ctx, ctx->stream));   // (and a rectifier's images: the dense stage's streams fork from here)
     SVO_HIP(ctx, hipEventRecord(ctx->ev_frontend, ctx->stream));
     SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream_dense, ctx->ev_frontend, 0));
     struct Hook {
@@ -440,6 +442,7 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
     const size_t n = (size_t)ctx->g.W * ctx->g.H;
     if ((rc = dense_reserve(ctx, B))) return rc;
     if (pair_ready) SVO_HIP(ctx, hipStreamWaitEvent(ctx->stream, pair_ready[B - 1], 0));   // host-fed: the call's uploads
+    SVO_HIP(ctx, svo_rect_gate(ctx, ctx->stream));
     if ((rc = bgr_to_gray(ctx, ctx->stream, bgr, d_grayL, d_grayR, stride, 0, B, true))) return rc;
     if ((rc = svo_launch_orb(ctx, ctx->stream, svo_fe_own(ctx), d_grayL, d_grayR, stride, B, B))) return rc;   // left images only
     // (colour entries: MSA gets the true colour pairs, as in the reference; gray entries: B = G = R copies of the gray)
@@ -483,6 +486,7 @@ int svo_track_batch_fed(svo_ctx* ctx, const uint8_t* d_grayL, const uint8_t* d_g
     const SvoFeBufs set = svo_fe_own(ctx).with_outputs(ctx->tb_out[p]);   // (set 0: tb_out[0] is empty, the context's own outputs)
     const size_t K = ctx->max_kp, img = (size_t)ctx->g.H * stride;
     hipStream_t fs = ctx->stream_fe_batch;
+    SVO_HIP(ctx, svo_rect_gate(ctx, fs));   // (images of svo_rect_batch_dev(consumer = ctx): both chains read them behind the sub-batch events)
     for (int j = 0; j < nsub && rc == SVO_OK; ++j) {
       const int f0 = j * SUB, b = std::min(SUB, B - f0);
       const SvoFeBufs fb = set.outputs_at(K, f0, f0);

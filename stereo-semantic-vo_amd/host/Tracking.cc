@@ -5,9 +5,12 @@
 #include <sstream>
 #include <stdexcept>
 
+#include <hip/hip_runtime_api.h>
+
 #include "Optimizer.h"
 #include "convert.h"
 #include "pnpmatch.h"
+#include "rect_settings.h"
 
 using namespace svo_host;
 
@@ -46,7 +49,95 @@ Tracking::Tracking(const svo_camera& cam, int w, int h, int dev) : device(dev), 
   width = w; height = h;
   Velocity = eye4();
 }
+// TrackBatch behind the rectifier: the call's raw pairs, two sets of rectified pairs and boxes that alternate between calls (set p
+// is rewritten behind read_done[p], recorded on the tracker's stream after the call that read it), one result array per call
+struct Tracking::RectBatch {
+  uint8_t* raw = nullptr; size_t raw_cap = 0;
+  uint8_t* out[2] = {nullptr, nullptr}; size_t out_cap[2] = {0, 0};
+  int32_t* boxes[2] = {nullptr, nullptr}; size_t box_cap[2] = {0, 0};
+  hipEvent_t read_done[2] = {nullptr, nullptr};
+  bool used[2] = {false, false};
+  int parity = 0;
+  struct Call { svo_track_result* d; size_t first; int n; };
+  std::vector<Call> calls;
+};
+
+void Tracking::LoadRectification(const std::string& strSettingPath) {
+  RectSettings s;
+  std::string err;
+  if (!read_rect_yaml(strSettingPath, s, err)) throw std::runtime_error("LoadRectification: " + strSettingPath + ": " + err);
+  if (s.width != width || s.height != height) throw std::runtime_error("LoadRectification: the calibration's image size is not the tracker's");
+  if (rect) svo_rect_destroy(rect);
+  rect = nullptr;
+  if (svo_rect_create(device, width, height, width, height, &s.left, &s.right, &rect) != SVO_OK)
+    throw std::runtime_error(std::string("svo_rect_create: ") + svo_rect_last_error(nullptr));
+  svo_rect_camera(rect, K.bf, &K);   // (bf: the value the constructor read)
+  bf = K.bf;
+}
+
+static void hip_check(hipError_t e, const char* what) {
+  if (e != hipSuccess) throw std::runtime_error(std::string("TrackBatch (rectified): ") + what + ": " + hipGetErrorString(e));
+}
+template <typename T>
+static void grow(T*& p, size_t& cap, size_t need) {   // (the caller has made sure nothing in flight uses p)
+  if (need <= cap) return;
+  if (p) (void)hipFree(p);
+  p = nullptr; cap = 0;
+  hip_check(hipMalloc(reinterpret_cast<void**>(&p), need * sizeof(T)), "hipMalloc");
+  cap = need;
+}
+
+void Tracking::TrackBatchRectified(const uint8_t* L, const uint8_t* R, int stride, int n, const int32_t* flat, const int32_t* cnt, int most,
+                                   bool bgr, size_t first) {
+  if (!rect_batch) {
+    rect_batch = new RectBatch();
+    for (hipEvent_t& e : rect_batch->read_done) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+  }
+  RectBatch& B = *rect_batch;
+  hipStream_t rs = static_cast<hipStream_t>(svo_rect_stream(rect));
+  const size_t row = (size_t)(bgr ? 3 : 1) * width, side = (size_t)n * height * row;
+  const int p = B.parity;
+  // the rectifier's stream: behind the tracker call that read set p two calls ago, then this call's uploads
+  if (B.used[p]) hip_check(hipStreamWaitEvent(rs, B.read_done[p], 0), "hipStreamWaitEvent");
+  if (2 * side > B.raw_cap || 2 * side > B.out_cap[p] || (size_t)n * (most * 4 + 1) > B.box_cap[p]) {
+    hip_check(hipStreamSynchronize(rs), "hipStreamSynchronize");
+    grow(B.raw, B.raw_cap, 2 * side);
+    grow(B.out[p], B.out_cap[p], 2 * side);
+    grow(B.boxes[p], B.box_cap[p], (size_t)n * (most * 4 + 1));
+  }
+  hip_check(hipMemcpy2DAsync(B.raw, row, L, stride, row, (size_t)n * height, hipMemcpyHostToDevice, rs), "upload");
+  hip_check(hipMemcpy2DAsync(B.raw + side, row, R, stride, row, (size_t)n * height, hipMemcpyHostToDevice, rs), "upload");
+  if (most > 0) {
+    hip_check(hipMemcpyAsync(B.boxes[p], flat, (size_t)n * most * 4 * sizeof(int32_t), hipMemcpyHostToDevice, rs), "upload");
+    hip_check(hipMemcpyAsync(B.boxes[p] + (size_t)n * most * 4, cnt, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, rs), "upload");
+  }
+  hip_check(hipStreamSynchronize(rs), "hipStreamSynchronize");   // (the caller refills its buffers when this returns)
+  svo_track_result* d_res = nullptr;
+  hip_check(hipMalloc(reinterpret_cast<void**>(&d_res), (size_t)n * sizeof(svo_track_result)), "hipMalloc");
+  B.calls.push_back({d_res, first, n});
+  if (svo_rect_batch_dev(rect, B.raw, B.raw + side, (int)row, bgr ? 3 : 1, n, B.out[p], B.out[p] + side, (int)row, ctx_batch) != SVO_OK)
+    throw std::runtime_error(std::string("svo_rect_batch_dev: ") + svo_rect_last_error(rect));
+  const svo_boxes_dev bd{B.boxes[p], B.boxes[p] + (size_t)n * most * 4, most};
+  const int rc = (bgr ? svo_track_batch_bgr_dev : svo_track_batch_dev)(ctx_batch, B.out[p], B.out[p] + side, (int)row, n, most > 0 ? &bd : nullptr, d_res);
+  if (rc != SVO_OK) throw std::runtime_error(std::string(bgr ? "svo_track_batch_bgr_dev: " : "svo_track_batch_dev: ") + svo_last_error(ctx_batch));
+  hip_check(hipEventRecord(B.read_done[p], static_cast<hipStream_t>(svo_stream(ctx_batch))), "hipEventRecord");
+  B.used[p] = true;
+  B.parity ^= 1;
+}
+
 Tracking::~Tracking() {
+  if (rect_batch) {
+    if (ctx_batch) svo_sync(ctx_batch);
+    for (auto& c : rect_batch->calls) (void)hipFree(c.d);
+    for (int p = 0; p < 2; ++p) {
+      if (rect_batch->out[p]) (void)hipFree(rect_batch->out[p]);
+      if (rect_batch->boxes[p]) (void)hipFree(rect_batch->boxes[p]);
+      if (rect_batch->read_done[p]) (void)hipEventDestroy(rect_batch->read_done[p]);
+    }
+    if (rect_batch->raw) (void)hipFree(rect_batch->raw);
+    delete rect_batch;
+  }
+  if (rect) svo_rect_destroy(rect);
   if (ctx_batch) svo_destroy(ctx_batch);
   if (ctx_map) svo_destroy(ctx_map);
   svo_destroy(ctx);
@@ -87,6 +178,12 @@ void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n,
       for (int j = 0; j < 4; ++j) flat[((size_t)k * most + b) * 4 + j] = detection_box[k][b][j];
   }
   const svo_boxes_host bx{flat.data(), cnt.data(), std::max(most, 1)};
+  if (rect) {   // raw pairs: rectified on the device, then the device-resident entry
+    if (dynamic_dev || dynamic_dev_bgr || map_out) throw std::runtime_error("TrackBatch: dynamic_dev / map_out are not available behind LoadRectification");
+    TrackBatchRectified(L, R, stride, n, flat.data(), cnt.data(), most, bgr, first);
+    frame_num += n;
+    return;
+  }
   if (dynamic_dev || dynamic_dev_bgr) {
     if (dynamic_dev_bgr && !bgr) throw std::runtime_error("Tracking::dynamic_dev_bgr needs TrackBatch(bgr = true)");
     batch_dyn_calls.emplace_back(new DynCall());
@@ -112,6 +209,15 @@ void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n,
 void Tracking::FinishBatches(std::ofstream& f, std::ofstream& f2) {
   if (!ctx_batch) return;
   if (svo_sync(ctx_batch) != SVO_OK) throw std::runtime_error(std::string("FinishBatches: ") + svo_last_error(ctx_batch));
+  if (rect_batch) {   // the rectified calls' records are in device memory
+    hipStream_t rs = static_cast<hipStream_t>(svo_rect_stream(rect));
+    for (auto& c : rect_batch->calls) {
+      hip_check(hipMemcpyAsync(batch_results.data() + c.first, c.d, (size_t)c.n * sizeof(svo_track_result), hipMemcpyDeviceToHost, rs), "download");
+      hip_check(hipStreamSynchronize(rs), "hipStreamSynchronize");
+      (void)hipFree(c.d);
+    }
+    rect_batch->calls.clear();
+  }
   for (const auto& c : batch_dyn_calls)   // (complete now: the lists of every batched frame, in order)
     for (size_t k = 0; k < c->counts.size(); ++k) {
       const Point2f* p = reinterpret_cast<const Point2f*>(c->lists.data() + k * 2 * (size_t)dynamic_max_pts);
@@ -226,14 +332,32 @@ void Tracking::SaveTrajectoryAndDraw(std::ofstream& f, std::ofstream& f2) {
 
 void Tracking::Track(const GrayImage& imLeft, const GrayImage& imRight, double timestamp, std::ofstream& f,
                      std::ofstream& f2, const std::vector<std::vector<int>>& detection_box) {
+  if (rect) {   // a raw pair: rectified first (svo_rect_process)
+    if (imLeft.cols != width || imLeft.rows != height || imRight.cols != width || imRight.rows != height) throw std::runtime_error("Track: image size is not the calibration's");
+    GrayImage rL, rR;
+    rL.cols = rR.cols = width; rL.rows = rR.rows = height;
+    rL.data.resize((size_t)width * height); rR.data.resize(rL.data.size());
+    if (svo_rect_process(rect, imLeft.ptr(), imRight.ptr(), width, 1, rL.data.data(), rR.data.data(), width) != SVO_OK)
+      throw std::runtime_error(std::string("svo_rect_process: ") + svo_rect_last_error(rect));
+    TrackImages(rL, rR, nullptr, nullptr, timestamp, f, f2, detection_box);
+    return;
+  }
   TrackImages(imLeft, imRight, nullptr, nullptr, timestamp, f, f2, detection_box);
 }
 
 void Tracking::Track(const BgrImage& imLeft, const BgrImage& imRight, double timestamp, std::ofstream& f,
                      std::ofstream& f2, const std::vector<std::vector<int>>& detection_box) {
+  BgrImage rL, rR;
+  if (rect) {   // a raw colour pair: rectified first, all three channels (svo_rect_process, cn = 3)
+    if (imLeft.cols != width || imLeft.rows != height || imRight.cols != width || imRight.rows != height) throw std::runtime_error("Track: image size is not the calibration's");
+    rL.cols = rR.cols = width; rL.rows = rR.rows = height;
+    rL.data.resize((size_t)3 * width * height); rR.data.resize(rL.data.size());
+    if (svo_rect_process(rect, imLeft.ptr(), imRight.ptr(), 3 * width, 3, rL.data.data(), rR.data.data(), 3 * width) != SVO_OK)
+      throw std::runtime_error(std::string("svo_rect_process: ") + svo_rect_last_error(rect));
+  }
   // cv::ORB's own reduction (COLOR_BGR2GRAY, src/frame.cc:75-79), on the device
   GrayImage gL, gR;
-  const BgrImage* in[2] = {&imLeft, &imRight};
+  const BgrImage* in[2] = {rect ? &rL : &imLeft, rect ? &rR : &imRight};
   GrayImage* out[2] = {&gL, &gR};
   for (int s = 0; s < 2; ++s) {
     out[s]->cols = in[s]->cols; out[s]->rows = in[s]->rows;
@@ -241,7 +365,7 @@ void Tracking::Track(const BgrImage& imLeft, const BgrImage& imRight, double tim
     if (svo_bgr_to_gray(ctx, in[s]->ptr(), in[s]->cols, in[s]->rows, in[s]->step(), out[s]->data.data(), in[s]->cols) != SVO_OK)
       throw std::runtime_error(std::string("svo_bgr_to_gray: ") + svo_last_error(ctx));
   }
-  TrackImages(gL, gR, &imLeft, &imRight, timestamp, f, f2, detection_box);
+  TrackImages(gL, gR, in[0], in[1], timestamp, f, f2, detection_box);
 }
 
 void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, const BgrImage* colLeft, const BgrImage* colRight,

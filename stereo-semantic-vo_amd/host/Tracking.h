@@ -47,6 +47,14 @@ class Tracking {
   bool map_out = false;
   const std::vector<svo_map_obs>& Observations(size_t frame_id) const;
   const svo_map_obs* ObservationOf(size_t frame_id, int kp) const;
+  // Raw (unrectified) input: reads LEFT.K / .D / .R / .P and RIGHT.* - or the flat Camera.k1 / k2 / p1 / p2 [/ k3] keys - of the
+  // settings file (rect_settings.h), builds the maps on the device (svo_rect_create; the images' size is the context's) and
+  // makes the left P's fx', fy', cx', cy' the tracker's camera (bf as the file has it).  From then on Track() rectifies every
+  // pair first (svo_rect_process, gray or colour) and TrackBatch() does it on the device: the call's raw pairs go to device
+  // buffers of its own, svo_rect_batch_dev(.., consumer = ctx_batch) writes one of two output sets and svo_track_batch_dev /
+  // svo_track_batch_bgr_dev follows with no host synchronisation in between (not with dynamic_dev or map_out, whose arrays
+  // belong to the host-fed entries).  Call it before the first frame.
+  void LoadRectification(const std::string& strSettingPath);
   Tracking(const svo_camera& cam, int width, int height, int device = 0);
   ~Tracking();
   void init();                                                          // src/Tracking.cc:42-97
@@ -73,6 +81,8 @@ class Tracking {
  private:
   void MapFrame(const svo_host::GrayImage& imLeft, const svo_host::GrayImage& imRight, const svo_host::BgrImage* colLeft,
                 const svo_host::BgrImage* colRight, double timestamp, const std::vector<std::vector<int>>& detection_box);
+  void TrackBatchRectified(const uint8_t* L, const uint8_t* R, int stride, int n, const int32_t* flat, const int32_t* cnt, int most,
+                           bool bgr, size_t first);
   void TrackImages(const svo_host::GrayImage& imLeft, const svo_host::GrayImage& imRight, const svo_host::BgrImage* colLeft,
                    const svo_host::BgrImage* colRight, double timestamp, std::ofstream& f, std::ofstream& f2,
                    const std::vector<std::vector<int>>& detection_box);
@@ -85,6 +95,9 @@ class Tracking {
   std::vector<double> batch_timestamps;
   struct DynCall { std::vector<float> lists; std::vector<int32_t> counts, dropped; };   // one TrackBatch()'s svo_track_dynamic_out arrays
   std::vector<std::unique_ptr<DynCall>> batch_dyn_calls;                               // (complete after svo_sync: FinishBatches collects them)
+  svo_rect* rect = nullptr;               // LoadRectification
+  struct RectBatch;                       // TrackBatch's device buffers behind the rectifier (Tracking.cc)
+  RectBatch* rect_batch = nullptr;
   svo_ctx* ctx_map = nullptr;             // Track() with map_out: the device-resident tracker beside the classes (max_batch = 1)
   std::vector<std::vector<svo_map_obs>> observations;   // per tracked frame
   struct MapCall { std::vector<svo_map_obs> obs; std::vector<int32_t> counts; };       // one TrackBatch()'s svo_track_map_out arrays

@@ -21,6 +21,10 @@
 // --dynamic-lk-bgr (implies --dynamic-lk; needs --colour): the same loop on the colour left images, svo_lk_track_bgr.
 // --write-map <dir> / --write-cloud <file.ply> (any mode): each frame's map points and observations (svo_track_map_out,
 // Tracking::map_out) to <dir>/NNNNNN.txt, "gid kp new u v depth X Y Z" per line; every new point of the run as an ASCII PLY.
+// --rectify <settings.yaml> (any mode, gray and --colour): the sequence's images are RAW; the file's LEFT.* / RIGHT.* blocks (or its
+// flat Camera.k1 .. p2 keys) are the calibration, Tracking::LoadRectification.  Frame by frame every pair goes through
+// svo_rect_process first; --pipelined rectifies on the device in front of the device-resident tracker (not with --dynamic-dev /
+// --write-map / --write-cloud).  It may be the settings file itself.
 // stereo_kitti --decode-bgr in.(png|ppm|pgm) out.ppm: codec self-test of the colour decode (the PPM holds RGB, as the format says).
 #include <algorithm>
 #include <chrono>
@@ -169,6 +173,14 @@ int main(int argc, char** argv) {
     argc -= take;
   }
   const bool map_out = !map_dir.empty() || !cloud_file.empty();
+  std::string rectify;   // --rectify <settings.yaml>
+  for (int i = 1; i + 1 < argc; ++i)
+    if (std::string(argv[i]) == "--rectify") {
+      rectify = argv[i + 1];
+      for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+      argc -= 2;
+      break;
+    }
   bool pipelined = false;
   int per_call = 32;
   if (argc >= 5 && std::string(argv[1]) == "--pipelined") {
@@ -188,8 +200,12 @@ int main(int argc, char** argv) {
     std::cerr << "--write-dynamic needs --dynamic-lk or, with --pipelined, --dynamic-dev" << std::endl;
     return 1;
   }
+  if (!rectify.empty() && pipelined && (dynamic_dev || map_out)) {
+    std::cerr << "--rectify with --pipelined: not with --dynamic-dev / --dynamic-dev-bgr / --write-map / --write-cloud" << std::endl;
+    return 1;
+  }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--write-map dir] [--write-cloud file.ply] [--pipelined] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--rectify settings.yaml] [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--write-map dir] [--write-cloud file.ply] [--pipelined] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -221,6 +237,14 @@ int main(int argc, char** argv) {
   mpTracker->dynamic_dev = dynamic_dev;
   mpTracker->dynamic_dev_bgr = dynamic_dev_bgr;
   mpTracker->map_out = map_out;
+  if (!rectify.empty()) {
+    try {
+      mpTracker->LoadRectification(rectify);
+    } catch (const std::exception& e) {
+      std::cerr << e.what() << std::endl;
+      return 1;
+    }
+  }
   std::vector<svo_map_obs> cloud;
   auto write_map = [&](int ni) {
     const std::vector<svo_map_obs>& obs = mpTracker->Observations((size_t)ni);
