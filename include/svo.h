@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_track_map_out, svo_map_obs (each tracked frame's map points and observations
+#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_ba_* (windowed bundle adjustment on the device over the map records; see
+                              "windowed bundle adjustment" below); no existing entry changed.
+                              8, backward-compatible addition: svo_track_map_out, svo_map_obs (each tracked frame's map points and observations
                               in HBM; see "the map behind a tracked frame" below); no existing entry changed.
                               8, backward-compatible addition: svo_debug_stereo_match (the sparse stereo matcher on the caller's keypoints, a
                               parity probe; see there); no existing entry changed.
@@ -1178,6 +1180,68 @@ void* svo_rect_stream(svo_rect* rect);
  * (dst_h x dst_w each) and the fixed-point coordinates the remap kernel works from, sxsy[2 (i dst_w + j)] = sx, [.. + 1] =
  * sy (ix = sx >> 5, a = sx & 31); a pixel that is "outside" by its map value has sx = sy = INT32_MIN.  Synchronises. */
 int svo_rect_debug_maps(svo_rect* rect, int side, double iR[9], float* mapx, float* mapy, int32_t* sxsy);
+
+/* ---- windowed bundle adjustment over the map records (backward-compatible addition; no existing entry changed) --------------
+ * What ORB-SLAM2 calls local bundle adjustment, over the records svo_track_map_out leaves in HBM: the last `window` poses and
+ * the points they share, refined together - g2o's EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ edges, BlockSolver's Schur
+ * complement, its Levenberg-Marquardt.  The contract, operation by operation: DESIGN.md section 8 "Windowed bundle adjustment";
+ * the numpy twin: tests/ba_ref.py.  Nothing feeds back into the tracker.
+ * Out of scope: chained windows (a window's fixed frames taking the previous window's result: one call per window does that),
+ * outlier-removal rounds, per-octave information, marginalisation priors, the many-sequence and sharded tracker entries. */
+enum { SVO_BA_OK = 0, SVO_BA_EMPTY = 1 };   /* svo_ba_stats.status; empty: no point with two edges, the input poses are returned */
+typedef struct svo_ba_params {
+  int32_t window;        /* frames of a window, 2 .. 8 */
+  int32_t n_fixed;       /* the first n_fixed frames keep their poses, 1 .. window - 1 */
+  int32_t iterations;    /* LM iterations, 1 .. 20 */
+  int32_t stereo;        /* 1: a record with depth > 0 is a stereo edge (u, v, u - bf / depth); 0: every edge is mono */
+  double huber_mono, huber_stereo;   /* Huber delta per edge type; <= 0: no robust kernel */
+  double lambda_init;    /* > 0: the LM's first lambda (g2o's userLambdaInit); otherwise 1e-5 x the largest diagonal entry */
+} svo_ba_params;
+/* window 8, n_fixed 1, iterations 10, stereo 1, (double)(float)sqrt(5.991) and (double)(float)sqrt(7.815), lambda_init 0 */
+int svo_ba_default_params(svo_ba_params* p);
+
+typedef struct svo_ba_stats {
+  int32_t status, n_points, n_edges, n_edges_stereo, iterations, trials_total;
+  double chi2_initial, chi2_final, lambda_final;
+} svo_ba_stats;
+typedef struct svo_ba_point {   /* 32 bytes */
+  int32_t gid, n_obs;    /* the map point and the number of its edges in the window */
+  double X, Y, Z;        /* refined world position */
+} svo_ba_point;
+typedef struct svo_ba svo_ba;
+
+/* An adjuster for windows of up to 8 frames x max_kp records (1 .. 4096) and up to max_windows windows a call, with a stream
+ * and scratch of its own (about 2.6 KB per record of a window).  Touches no device: the stream and the scratch, whose size is
+ * fixed here, come with the first call that needs them (SVO_E_NODEVICE / SVO_E_NOMEM are answered there), so the argument checks
+ * of every entry answer on a machine without a GPU.  svo_ba_last_error(NULL): the calling thread's last failure without an object. */
+int svo_ba_create(int device, int max_kp, int max_windows, svo_ba** out);
+void svo_ba_destroy(svo_ba* ba);
+int svo_ba_sync(svo_ba* ba);
+void* svo_ba_stream(svo_ba* ba);
+const char* svo_ba_last_error(const svo_ba* ba);
+
+/* n_windows windows over frames resident in HBM; window w covers frames first + w * step .. + window - 1.  Frame f's records
+ * are d_obs + f * obs_stride (obs_stride <= max_kp records a frame; d_counts[f] of them count, a count above obs_stride is
+ * clamped on the device), its float32 4 x 4 Tcw stands at the start of element f of d_Tcw, elements pose_stride_bytes apart
+ * (64 for bare poses; an array of svo_track_result fits with sizeof(svo_track_result)).
+ * Outputs: d_Tcw_out n_windows x window x 16 float64 (a fixed frame, a free frame without edges and every frame of an empty
+ * window: the input pose widened); d_points (may be NULL) n_windows x (window * max_kp / 2) records, the first n_points of
+ * a window written, by ascending gid; d_stats one record per window.
+ * Does not synchronise.  producer (may be NULL, same device): the adjuster's stream waits ON THE DEVICE for an event recorded
+ * on svo_stream(producer), so the windows run behind the tracker call that writes the records and poses; the producer waits
+ * for nothing and nothing else is enqueued on its streams.  Windows are independent problems: a window's outputs do not depend
+ * on n_windows, on its index or on the other windows, and are the same bytes on every run.
+ * SVO_E_INVALID before a device is touched (svo_ba_last_error names the argument): a NULL pointer, window outside 2 .. 8,
+ * n_fixed outside 1 .. window - 1, iterations outside 1 .. 20, a non-finite parameter or camera value, fx or fy <= 0,
+ * obs_stride outside 1 .. max_kp, n_windows outside 1 .. max_windows, first < 0, step < 1, d_obs not 16-byte aligned, a pose
+ * stride below 64 or not a multiple of 4. */
+int svo_ba_windows_dev(svo_ba* ba, const svo_camera* cam, const svo_ba_params* params, const svo_map_obs* d_obs,
+                       const int32_t* d_counts, int obs_stride, const void* d_Tcw, int pose_stride_bytes, int first, int n_windows,
+                       int step, double* d_Tcw_out, svo_ba_point* d_points, svo_ba_stats* d_stats, svo_ctx* producer);
+/* One window, host to host: obs window x obs_stride records, counts window, Tcw window x 16 float32; points (may be NULL
+ * together with n_points) holds window * max_kp / 2 records.  Synchronises. */
+int svo_ba_window(svo_ba* ba, const svo_camera* cam, const svo_ba_params* params, const svo_map_obs* obs, const int32_t* counts,
+                  int obs_stride, const float* Tcw, double* Tcw_out, svo_ba_point* points, int32_t* n_points, svo_ba_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,13 @@ MAP_OBS_DTYPE = np.dtype([("gid", "<i4"), ("kp", "<i2"), ("flags", "<u2"), ("u",
                           ("X", "<f4"), ("Y", "<f4"), ("Z", "<f4")])
 MAP_NEW = 1   # svo_map_obs.flags: the point exists since this frame
 
+# svo_ba_stats / svo_ba_point (include/svo.h): a window's statistics and refined points (svo_ba_windows_dev, svo_ba_window)
+BA_STATS_DTYPE = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("n_edges", "<i4"), ("n_edges_stereo", "<i4"),
+                           ("iterations", "<i4"), ("trials_total", "<i4"), ("chi2_initial", "<f8"), ("chi2_final", "<f8"),
+                           ("lambda_final", "<f8")])
+BA_POINT_DTYPE = np.dtype([("gid", "<i4"), ("n_obs", "<i4"), ("X", "<f8"), ("Y", "<f8"), ("Z", "<f8")])
+BA_OK, BA_EMPTY = 0, 1   # svo_ba_stats.status
+
 # Every symbol include/svo.h declares (checked by tests/test_abi.py without a GPU).
 ABI_SYMBOLS = [
     "svo_abi_version", "svo_strerror", "svo_last_error", "svo_create", "svo_destroy", "svo_sync",
@@ -71,6 +78,8 @@ ABI_SYMBOLS = [
     "svo_debug_stereo_match", "svo_track_map_out",
     "svo_rect_create", "svo_rect_destroy", "svo_rect_last_error", "svo_rect_camera", "svo_rect_process", "svo_rect_batch_dev",
     "svo_rect_sync", "svo_rect_stream", "svo_rect_debug_maps",
+    "svo_ba_default_params", "svo_ba_create", "svo_ba_destroy", "svo_ba_sync", "svo_ba_stream", "svo_ba_last_error",
+    "svo_ba_windows_dev", "svo_ba_window",
 ]
 
 PNP_RULE_W = 6 + 5 * 101   # SVO_PNP_RULE_W (include/svo.h)
@@ -1273,3 +1282,100 @@ class Rectifier:
         s = np.zeros((self.dst_h, self.dst_w, 2), np.int32)
         self._chk(self.lib.svo_rect_debug_maps(self.h, int(side), _p(iR), _p(mx), _p(my), _p(s)), "svo_rect_debug_maps")
         return iR, mx, my, s
+
+
+# ---- windowed bundle adjustment (svo_ba_* in include/svo.h; the contract: DESIGN.md section 8 "Windowed bundle adjustment") ------------------
+class BaParams(C.Structure):
+    """svo_ba_params; BaParams.default() is svo_ba_default_params, keyword arguments replace single fields."""
+    _fields_ = [("window", C.c_int32), ("n_fixed", C.c_int32), ("iterations", C.c_int32), ("stereo", C.c_int32),
+                ("huber_mono", C.c_double), ("huber_stereo", C.c_double), ("lambda_init", C.c_double)]
+
+    @classmethod
+    def default(cls, **kw):
+        p = cls()
+        rc = load_library().svo_ba_default_params(C.byref(p))
+        if rc != 0:
+            raise SvoError("svo_ba_default_params failed (%d)" % rc)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("BaParams has no field %r" % k)
+            setattr(p, k, v)
+        return p
+
+
+def _dptr(t):
+    if t is None:
+        return None
+    return C.c_void_p(int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t))
+
+
+class BundleAdjuster:
+    """Windowed bundle adjustment on one GPU (wraps svo_ba): the last `window` poses and the points they share, from the records
+    Svo.track_map_out leaves.  An object with a stream and scratch of its own; creating it touches no device."""
+
+    def __init__(self, max_kp, max_windows=1, device=0):
+        self.lib = lib = load_library()
+        lib.svo_ba_last_error.restype = C.c_char_p
+        lib.svo_ba_last_error.argtypes = [C.c_void_p]
+        lib.svo_ba_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        lib.svo_ba_destroy.argtypes = [C.c_void_p]
+        lib.svo_ba_destroy.restype = None
+        lib.svo_ba_sync.argtypes = [C.c_void_p]
+        lib.svo_ba_stream.restype = C.c_void_p
+        lib.svo_ba_stream.argtypes = [C.c_void_p]
+        lib.svo_ba_windows_dev.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4
+        lib.svo_ba_window.argtypes = [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 5
+        self.max_kp, self.max_windows = int(max_kp), int(max_windows)
+        h = C.c_void_p()
+        rc = lib.svo_ba_create(int(device), self.max_kp, self.max_windows, C.byref(h))
+        if rc != 0:
+            raise SvoError("svo_ba_create: %s: %s" % (lib.svo_strerror(rc).decode(), lib.svo_ba_last_error(None).decode()))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.svo_ba_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise SvoError("%s: %s: %s" % (what, self.lib.svo_strerror(rc).decode(), self.lib.svo_ba_last_error(self.h).decode()))
+
+    def windows_dev(self, cam, params, d_obs, d_counts, obs_stride, d_Tcw, pose_stride_bytes, first, n_windows, step, d_Tcw_out,
+                    d_points, d_stats, producer=None):
+        """svo_ba_windows_dev on device memory (torch tensors or device pointers as ints; d_points may be None).  producer: the
+        Svo whose tracker call writes the records - the windows run behind it on the device.  Does not synchronise."""
+        self._chk(self.lib.svo_ba_windows_dev(self.h, C.addressof(cam), C.addressof(params), _dptr(d_obs), _dptr(d_counts),
+                                              int(obs_stride), _dptr(d_Tcw), int(pose_stride_bytes), int(first), int(n_windows),
+                                              int(step), _dptr(d_Tcw_out), _dptr(d_points), _dptr(d_stats),
+                                              None if producer is None else producer.h), "svo_ba_windows_dev")
+
+    def window(self, cam, params, obs, counts, Tcw):
+        """One window, host to host: obs (window, obs_stride) MAP_OBS_DTYPE, counts (window,), Tcw (window, 4, 4) ->
+        (Tcw (window, 4, 4) float64, points (n_points,) BA_POINT_DTYPE, stats (BA_STATS_DTYPE scalar))."""
+        W = int(params.window)
+        obs = np.ascontiguousarray(obs, MAP_OBS_DTYPE)
+        if obs.ndim != 2 or obs.shape[0] != W:
+            raise ValueError("obs must be (window, obs_stride)")
+        counts = np.ascontiguousarray(counts, np.int32)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(W, 16)
+        out = np.zeros((W, 4, 4), np.float64)
+        pts = np.zeros(max(W * self.max_kp // 2, 1), BA_POINT_DTYPE)
+        n = C.c_int32(0)
+        st = np.zeros(1, BA_STATS_DTYPE)
+        self._chk(self.lib.svo_ba_window(self.h, C.addressof(cam), C.addressof(params), _p(obs), _p(counts), int(obs.shape[1]), _p(T),
+                                         _p(out), _p(pts), C.addressof(n), _p(st)), "svo_ba_window")
+        return out, pts[:n.value].copy(), st[0]
+
+    def sync(self):
+        self._chk(self.lib.svo_ba_sync(self.h), "svo_ba_sync")
+
+    @property
+    def stream(self):
+        return self.lib.svo_ba_stream(self.h)

@@ -138,6 +138,7 @@ Tracking::~Tracking() {
     delete rect_batch;
   }
   if (rect) svo_rect_destroy(rect);
+  if (ba) svo_ba_destroy(ba);
   if (ctx_batch) svo_destroy(ctx_batch);
   if (ctx_map) svo_destroy(ctx_map);
   svo_destroy(ctx);
@@ -243,6 +244,30 @@ void Tracking::FinishBatches(std::ofstream& f, std::ofstream& f2) {
 const std::vector<svo_map_obs>& Tracking::Observations(size_t frame_id) const {
   if (frame_id >= observations.size()) throw std::runtime_error("Tracking::Observations: no such frame (map_out set? FinishBatches() called?)");
   return observations[frame_id];
+}
+Tracking::LocalBAResult Tracking::LocalBA(size_t first_frame, const svo_ba_params& params) {
+  const int W = params.window;
+  if (W < 2 || W > 8) throw std::runtime_error("Tracking::LocalBA: window must be 2 .. 8");
+  if (first_frame + (size_t)W > observations.size() || first_frame + (size_t)W > batch_results.size())
+    throw std::runtime_error("Tracking::LocalBA: no such frames (map_out set? TrackBatch() and FinishBatches() called?)");
+  if (!ba && svo_ba_create(device, 500, 1, &ba) != SVO_OK) throw std::runtime_error(std::string("Tracking::LocalBA: ") + svo_ba_last_error(nullptr));
+  std::vector<svo_map_obs> obs((size_t)W * 500, svo_map_obs{});
+  std::vector<int32_t> counts((size_t)W, 0);
+  std::vector<float> T((size_t)W * 16);
+  for (int f = 0; f < W; ++f) {
+    const std::vector<svo_map_obs>& o = observations[first_frame + f];
+    std::copy(o.begin(), o.end(), obs.begin() + (size_t)f * 500);
+    counts[f] = (int32_t)o.size();
+    std::copy(batch_results[first_frame + f].Tcw, batch_results[first_frame + f].Tcw + 16, T.begin() + (size_t)f * 16);
+  }
+  LocalBAResult r;
+  r.Tcw.assign((size_t)W * 16, 0.0);
+  r.points.assign((size_t)W * 250, svo_ba_point{});
+  int32_t n = 0;
+  if (svo_ba_window(ba, &K, &params, obs.data(), counts.data(), 500, T.data(), r.Tcw.data(), r.points.data(), &n, &r.stats) != SVO_OK)
+    throw std::runtime_error(std::string("Tracking::LocalBA: ") + svo_ba_last_error(ba));
+  r.points.resize((size_t)n);
+  return r;
 }
 const svo_map_obs* Tracking::ObservationOf(size_t frame_id, int kp) const {
   const std::vector<svo_map_obs>& o = Observations(frame_id);   // (ascending kp)

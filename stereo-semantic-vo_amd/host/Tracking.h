@@ -47,6 +47,11 @@ class Tracking {
   bool map_out = false;
   const std::vector<svo_map_obs>& Observations(size_t frame_id) const;
   const svo_map_obs* ObservationOf(size_t frame_id, int kp) const;
+  // Windowed bundle adjustment (svo_ba_window) over what map_out keeps for TrackBatch(): frames first_frame .. first_frame +
+  // params.window - 1, their records (Observations) and their tracked poses (batch_results), after FinishBatches().  Returns
+  // the window's refined poses (Tcw, window x 16 float64) and points; nothing feeds back into the tracker.
+  struct LocalBAResult { std::vector<double> Tcw; std::vector<svo_ba_point> points; svo_ba_stats stats; };
+  LocalBAResult LocalBA(size_t first_frame, const svo_ba_params& params);
   // Raw (unrectified) input: reads LEFT.K / .D / .R / .P and RIGHT.* - or the flat Camera.k1 / k2 / p1 / p2 [/ k3] keys - of the
   // settings file (rect_settings.h), builds the maps on the device (svo_rect_create; the images' size is the context's) and
   // makes the left P's fx', fy', cx', cy' the tracker's camera (bf as the file has it).  From then on Track() rectifies every
@@ -96,6 +101,7 @@ class Tracking {
   struct DynCall { std::vector<float> lists; std::vector<int32_t> counts, dropped; };   // one TrackBatch()'s svo_track_dynamic_out arrays
   std::vector<std::unique_ptr<DynCall>> batch_dyn_calls;                               // (complete after svo_sync: FinishBatches collects them)
   svo_rect* rect = nullptr;               // LoadRectification
+  svo_ba* ba = nullptr;                   // LocalBA's adjuster (500 records a frame, one window), made on first use
   struct RectBatch;                       // TrackBatch's device buffers behind the rectifier (Tracking.cc)
   RectBatch* rect_batch = nullptr;
   svo_ctx* ctx_map = nullptr;             // Track() with map_out: the device-resident tracker beside the classes (max_batch = 1)

@@ -162,11 +162,17 @@ int main(int argc, char** argv) {
   // --write-map <dir>: each frame's map points and observations (Tracking::map_out) to <dir>/NNNNNN.txt, one record per line
   // "gid kp new u v depth X Y Z" (%.9g: the floats read back exactly); --write-cloud <file.ply>: every record that is new in its
   // frame - each map point once, where it was created - as an ASCII PLY vertex list.  Frame by frame and --pipelined, gray and --colour.
+  // --local-ba W [--ba-step S] [--ba-fixed F] (with --pipelined and --write-map): windowed bundle adjustment over the tracked
+  // sequence (Tracking::LocalBA, svo_ba_window), one <dir>/ba_%06d.txt per window.
   std::string map_dir, cloud_file;
+  int ba_window = 0, ba_step = 0, ba_fixed = 1;
   for (int i = 1; i < argc;) {
     const std::string a = argv[i];
     int take = 0;
     if (a == "--write-map" && i + 1 < argc) { map_dir = argv[i + 1]; take = 2; }
+    else if (a == "--local-ba" && i + 1 < argc) { ba_window = atoi(argv[i + 1]); take = 2; }
+    else if (a == "--ba-step" && i + 1 < argc) { ba_step = atoi(argv[i + 1]); take = 2; }
+    else if (a == "--ba-fixed" && i + 1 < argc) { ba_fixed = atoi(argv[i + 1]); take = 2; }
     else if (a == "--write-cloud" && i + 1 < argc) { cloud_file = argv[i + 1]; take = 2; }
     if (!take) { ++i; continue; }
     for (int j = i; j + take < argc; ++j) argv[j] = argv[j + take];
@@ -204,8 +210,14 @@ int main(int argc, char** argv) {
     std::cerr << "--rectify with --pipelined: not with --dynamic-dev / --dynamic-dev-bgr / --write-map / --write-cloud" << std::endl;
     return 1;
   }
+  if (ba_window && (!pipelined || map_dir.empty())) { std::cerr << "--local-ba needs --pipelined and --write-map" << std::endl; return 1; }
+  if (ba_window && !ba_step) ba_step = ba_window;
+  if (ba_window && (ba_window < 2 || ba_window > 8 || ba_fixed < 1 || ba_fixed >= ba_window || ba_step < 1)) {
+    std::cerr << "--local-ba W: 2 .. 8; --ba-fixed F: 1 .. W - 1; --ba-step S: >= 1" << std::endl;
+    return 1;
+  }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--rectify settings.yaml] [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--write-map dir] [--write-cloud file.ply] [--pipelined] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--rectify settings.yaml] [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--write-map dir] [--write-cloud file.ply] [--pipelined] [--local-ba W [--ba-step S] [--ba-fixed F]] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -256,6 +268,39 @@ int main(int argc, char** argv) {
     for (const svo_map_obs& r : obs)
       fprintf(o, "%d %d %d %.9g %.9g %.9g %.9g %.9g %.9g\n", r.gid, (int)r.kp, (r.flags & SVO_MAP_NEW) ? 1 : 0, r.u, r.v, r.depth, r.X, r.Y, r.Z);
     fclose(o);
+    return true;
+  };
+  // --local-ba W: windows of W frames every --ba-step frames (default W), the first --ba-fixed (default 1) fixed, over the
+  // tracked sequence (Tracking::LocalBA); window k -> <map dir>/ba_%06d.txt: the refined poses of its frames as KITTI rows
+  // (Twc, 12 numbers), then "# first_frame status n_points n_edges n_edges_stereo iterations trials chi2_initial chi2_final lambda_final"
+  auto write_local_ba = [&]() {
+    svo_ba_params bp;
+    svo_ba_default_params(&bp);
+    bp.window = ba_window; bp.n_fixed = ba_fixed;
+    int k = 0;
+    for (int f0 = 0; f0 + ba_window <= nImages; f0 += ba_step, ++k) {
+      Tracking::LocalBAResult r;
+      try {
+        r = mpTracker->LocalBA((size_t)f0, bp);
+      } catch (const std::exception& e) {
+        std::cerr << e.what() << std::endl;
+        return false;
+      }
+      char nm[32];
+      snprintf(nm, sizeof nm, "/ba_%06d.txt", k);
+      FILE* o = fopen((map_dir + nm).c_str(), "w");
+      if (!o) { std::cerr << "cannot write into " << map_dir << std::endl; return false; }
+      for (int f = 0; f < ba_window; ++f) {
+        const double* T = r.Tcw.data() + 16 * f;
+        for (int i = 0; i < 3; ++i) {     // Twc = [R^T | -R^T t]
+          const double t = -(T[i] * T[3] + T[4 + i] * T[7] + T[8 + i] * T[11]);
+          fprintf(o, "%.17g %.17g %.17g %.17g%s", T[i], T[4 + i], T[8 + i], t, i == 2 ? "\n" : " ");
+        }
+      }
+      fprintf(o, "# %d %d %d %d %d %d %d %.17g %.17g %.17g\n", f0, r.stats.status, r.stats.n_points, r.stats.n_edges, r.stats.n_edges_stereo,
+              r.stats.iterations, r.stats.trials_total, r.stats.chi2_initial, r.stats.chi2_final, r.stats.lambda_final);
+      fclose(o);
+    }
     return true;
   };
   auto write_cloud = [&]() {
@@ -337,6 +382,7 @@ int main(int argc, char** argv) {
     for (int ni = 0; ni < nImages && map_out; ++ni)
       if (!write_map(ni)) return 1;
     if (!write_cloud()) return 1;
+    if (ba_window && !write_local_ba()) return 1;
     const double total = std::chrono::duration_cast<std::chrono::duration<double>>(std::chrono::steady_clock::now() - t0).count();
     f.close(); f2.close();
     std::cout << std::endl << "trajectory saved!" << std::endl << "-------" << std::endl << std::endl;
