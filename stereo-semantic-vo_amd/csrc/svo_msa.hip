@@ -1,4 +1,6 @@
-// svo_msa.hip - stages of the reference's MSA dense stereo built so far.
+// svo_msa.hip - the reference's MSA dense stereo: its device stages one by one, and
+// MSA::solve end to end for C >= 1 pairs (msa_chunk_device).  The host-side graph stages that produce the aggregation
+// tree (build, Tarjan arborescence, region Kruskal, BFS orders; MSA.cpp:152-926) are in svo_msa_graph.hip.
 //
 //  svo_ctmf : Thirdparty/MB/ctmf.h:7 `ctmf(src, dst, width, height, src_step, dst_step, r, channels, memsize)`,
 //             the constant-time median filter MSA runs on the colour images (r = 1, 3 channels,
@@ -21,11 +23,10 @@
 //             per (node, disparity); the children are added in the order the reference's adjacency chain yields
 //             them, each `+=` rounded to float as there.
 //  svo_msa_wta / svo_msa_lrcheck : `MSA::WTA` (:992-1006, first minimum + 5x5 ctmf) and `MSA::LRcheck` (:1027-1105).
-// Not built: the host-side graph stages that produce the tree (build, Tarjan arborescence, region Kruskal, BFS
-// orders; MSA.cpp:152-926) and therefore MSA::solve as a whole.
 #include <math.h>
 
 #include <algorithm>
+#include <functional>
 #include <stdio.h>
 #include <string.h>
 #include <atomic>
@@ -105,60 +106,43 @@ __global__ void k_msa_cost_right(const float* costL, int n, int m, int disp, flo
   costR[idx] = costL[(size_t)(t + dd) * disp + dd];
 }
 
-// leaves -> root: nodes of one level, all their children are final
-__global__ void k_msa_dp_up(const int32_t* nodes, int cnt, int D, const int32_t* child_ptr, const int32_t* child,
-                            const uint8_t* child_c, const double* Exp, float* up) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= cnt * D) return;
-  const int u = nodes[idx / D], d = idx % D;
-  float acc = up[(size_t)u * D + d];
-  for (int e = child_ptr[u]; e < child_ptr[u + 1]; ++e)
-    acc = (float)((double)acc + Exp[child_c[e]] * (double)up[(size_t)child[e] * D + d]);
-  up[(size_t)u * D + d] = acc;
-}
-// root -> leaves: nodes of one level, their parent is final
-__global__ void k_msa_dp_down(const int32_t* nodes, int cnt, int D, const int32_t* parent, const uint8_t* parent_c,
-                              const double* Exp, const float* up, float* A) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= cnt * D) return;
-  const int v = nodes[idx / D], d = idx % D, u = parent[v];
-  if (u < 0) { A[(size_t)v * D + d] = up[(size_t)v * D + d]; return; }
-  const double w = Exp[parent_c[v]];
-  A[(size_t)v * D + d] = (float)(w * (double)A[(size_t)u * D + d] + (1 - w * w) * (double)up[(size_t)v * D + d]);
-}
-// The same two sweeps for several frames at once (blockIdx.y = frame): the level sweep of one frame is a chain of
-// ~2000 tiny dependent launches, so a batch shares them - level l of every frame in one launch.
-struct MsaTreeTab {   // one tree on the device
-  const int32_t *nodes, *level_ptr, *child_ptr, *child, *parent;
+// One tree on the device and the volumes of one aggregation over it (blockIdx.y of every TreeDp kernel picks the tree).
+// (MsaBfsRec - first child's position | weight to parent + (children << 8) | parent's position | pixel - is declared in
+// svo_internal.h: the host-side tree builder writes the records itself)
+struct MsaTab {
+  const MsaBfsRec* rec;        // the tree by level-order position (k_msa_dp_bfs)
+  const int32_t* level_ptr; int32_t levels, N;
+  const float* cost;           // [pixel][D] in
+  float* up;                   // work: [D][position] (k_msa_dp_bfs), [pixel][D] (level launches)
+  float* A;                    // [pixel][D] out
+  const int32_t *nodes, *child_ptr, *child, *parent;   // the tree by pixel: the level launches only
   const uint8_t *child_c, *parent_c;
-  int32_t levels;
 };
-__global__ void k_msa_dp_up_many(const MsaTreeTab* tabs, int l, int D, const double* Exp, float* up_slab, size_t V) {
-  const MsaTreeTab t = tabs[blockIdx.y];
+// TreeDp with one launch per level: level l of every tree in one launch (a tree with fewer levels sits it out).
+// leaves -> root: all children of the level's nodes are final
+__global__ void k_msa_dp_up_many(const MsaTab* tabs, int l, int D, const double* Exp) {
+  const MsaTab t = tabs[blockIdx.y];
   if (l >= t.levels) return;
   const int beg = t.level_ptr[l], cnt = t.level_ptr[l + 1] - beg;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= cnt * D) return;
-  float* up = up_slab + (size_t)blockIdx.y * V;
   const int u = t.nodes[beg + idx / D], d = idx % D;
-  float acc = up[(size_t)u * D + d];
+  float acc = t.cost[(size_t)u * D + d];
   for (int e = t.child_ptr[u]; e < t.child_ptr[u + 1]; ++e)
-    acc = (float)((double)acc + Exp[t.child_c[e]] * (double)up[(size_t)t.child[e] * D + d]);
-  up[(size_t)u * D + d] = acc;
+    acc = (float)((double)acc + Exp[t.child_c[e]] * (double)t.up[(size_t)t.child[e] * D + d]);
+  t.up[(size_t)u * D + d] = acc;
 }
-__global__ void k_msa_dp_down_many(const MsaTreeTab* tabs, int l, int D, const double* Exp, const float* up_slab, float* A_slab,
-                                   size_t V) {
-  const MsaTreeTab t = tabs[blockIdx.y];
+// root -> leaves: the parents of the level's nodes are final
+__global__ void k_msa_dp_down_many(const MsaTab* tabs, int l, int D, const double* Exp) {
+  const MsaTab t = tabs[blockIdx.y];
   if (l >= t.levels) return;
   const int beg = t.level_ptr[l], cnt = t.level_ptr[l + 1] - beg;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= cnt * D) return;
-  const float* up = up_slab + (size_t)blockIdx.y * V;
-  float* A = A_slab + (size_t)blockIdx.y * V;
   const int v = t.nodes[beg + idx / D], d = idx % D, u = t.parent[v];
-  if (u < 0) { A[(size_t)v * D + d] = up[(size_t)v * D + d]; return; }
+  if (u < 0) { t.A[(size_t)v * D + d] = t.up[(size_t)v * D + d]; return; }
   const double w = Exp[t.parent_c[v]];
-  A[(size_t)v * D + d] = (float)(w * (double)A[(size_t)u * D + d] + (1 - w * w) * (double)up[(size_t)v * D + d]);
+  t.A[(size_t)v * D + d] = (float)(w * (double)t.A[(size_t)u * D + d] + (1 - w * w) * (double)t.up[(size_t)v * D + d]);
 }
 
 // ---- TreeDp as ONE launch per aggregation -------------------------------------------------------------------------
@@ -168,25 +152,17 @@ __global__ void k_msa_dp_down_many(const MsaTreeTab* tabs, int l, int D, const d
 // position g in level order (children of a node are consecutive there, MsaBfsRec::cpos), the per-disparity values live in
 // a transposed slab upT[d][g] (coalesced), and the values of the level just finished - all the next level needs -
 // stay in LDS: a level costs one LDS round trip and a barrier, the HBM reads of the next level's own terms are issued a
-// level ahead.  Arithmetic and its order are those of k_msa_dp_up / k_msa_dp_down (the child's weighted term
+// level ahead.  Arithmetic and its order are those of k_msa_dp_up_many / k_msa_dp_down_many (the child's weighted term
 // Exp[c] * (double)up[child] is formed by the child, added by the parent in child order).
-// (MsaBfsRec - first child's position | weight to parent + (children << 8) | parent's position | pixel - is declared in svo_internal.h:
-// the host-side tree builder writes the records itself)
-struct MsaBfsTab {   // one tree and the volumes of one aggregation over it
-  const MsaBfsRec* rec; const int32_t* level_ptr; int32_t levels, N;
-  const float* cost;   // [pixel][D] in
-  float* upT;          // [D][position] work
-  float* A;            // [pixel][D] out
-};
 
 // upT[d][g] = cost[node(g)][d]  (64 positions x D disparities per workgroup, transposed through LDS)
-__global__ __launch_bounds__(256) void k_msa_bfs_gather(const MsaBfsTab* tabs, int D) {
+__global__ __launch_bounds__(256) void k_msa_bfs_gather(const MsaTab* tabs, int D) {
   extern __shared__ float msa_tile[];   // 64 x (D + 1)
-  const MsaBfsTab t = tabs[blockIdx.y];
+  const MsaTab t = tabs[blockIdx.y];
   const int g0 = blockIdx.x * 64;
   if (g0 >= t.N) return;
   const float* cost = t.cost;
-  float* upT = t.upT;
+  float* upT = t.up;
   for (int idx = threadIdx.x; idx < 64 * D; idx += 256) {
     const int gi = idx / D, d = idx - gi * D;
     if (g0 + gi < t.N) msa_tile[gi * (D + 1) + d] = cost[(size_t)t.rec[g0 + gi].node * D + d];
@@ -199,9 +175,9 @@ __global__ __launch_bounds__(256) void k_msa_bfs_gather(const MsaBfsTab* tabs, i
 }
 
 template <int T>
-__global__ __launch_bounds__(T) void k_msa_dp_bfs(const MsaBfsTab* tabs, int D, const double* Exp, int maxw, int maxl) {
+__global__ __launch_bounds__(T) void k_msa_dp_bfs(const MsaTab* tabs, int D, const double* Exp, int maxw, int maxl) {
   extern __shared__ double msa_lds[];   // Exp[256] | two level buffers of maxw doubles | level_ptr (maxl + 2 ints)
-  const MsaBfsTab t = tabs[blockIdx.y];
+  const MsaTab t = tabs[blockIdx.y];
   const int d = blockIdx.x, tid = threadIdx.x, L = t.levels;
   double* E = msa_lds;
   double* cur = msa_lds + 256;
@@ -210,7 +186,7 @@ __global__ __launch_bounds__(T) void k_msa_dp_bfs(const MsaBfsTab* tabs, int D, 
   for (int i = tid; i < 256; i += T) E[i] = Exp[i];
   for (int i = tid; i <= L; i += T) lp[i] = t.level_ptr[i];
   __syncthreads();
-  float* up = t.upT + (size_t)d * t.N;
+  float* up = t.up + (size_t)d * t.N;
   float* A = t.A;
   const MsaBfsRec* rec = t.rec;
   MsaBfsRec r_n = {0, 0, -1, 0};
@@ -293,16 +269,17 @@ struct DevBuf {   // device allocations of one solve; reset() hands the same buf
   }
 };
 
-// the buffers of svo_msa_solve / the tracker's MSA mode live as long as the ctx (index 0: the ctx stream; 1..: the
-// streams of svo_msa_run_many_dev) - a solve allocates ~0.5 GB at KITTI size and hipFree synchronises the device
-struct MsaHostStore;   // host-side buffers of the batched solve (kept for the same reason: page faults)
-struct MsaArenas { std::vector<DevBuf*> a; std::mutex m; MsaHostStore* host[2] = {nullptr, nullptr}; };
-DevBuf& msa_arena(svo_ctx* ctx, int idx) {
+// the buffers of svo_msa_solve / the tracker's MSA mode live as long as the ctx (index 0: the ctx stream; 1, 2: the
+// lanes of svo_msa_run_many_dev) - a solve allocates ~0.55 GB per pair at KITTI size and hipFree synchronises the device
+struct MsaHostStore;   // host-side buffers of a solve (kept for the same reason: page faults)
+struct MsaArena { DevBuf dev, io; MsaHostStore* host = nullptr; };   // dev: the solver's buffers; io: svo_msa_solve's uploaded pair and output
+struct MsaArenas { std::vector<MsaArena*> a; std::mutex m; };
+MsaArena& msa_arena(svo_ctx* ctx, int idx) {
   if (!ctx->msa_arenas) ctx->msa_arenas = new MsaArenas();
   MsaArenas* A = static_cast<MsaArenas*>(ctx->msa_arenas);
   std::lock_guard<std::mutex> lock(A->m);
-  while ((int)A->a.size() <= idx) A->a.push_back(new DevBuf());
-  A->a[idx]->reset();
+  while ((int)A->a.size() <= idx) A->a.push_back(new MsaArena());
+  A->a[idx]->dev.reset(); A->a[idx]->io.reset();
   return *A->a[idx];
 }
 
@@ -332,22 +309,61 @@ static bool msa_bfs_records(int N, const int32_t* nodes, const std::vector<int32
   return ok && cpos == N;
 }
 
-// k_msa_dp_bfs applicable?  (levels fit its LDS buffers, opt-in above 64 KB granted; SVO_MSA_LEVEL_LAUNCHES forces the old path)
+static bool msa_level_launches() { return getenv("SVO_MSA_LEVEL_LAUNCHES") != nullptr; }   // read per call: a test may set and clear it
+
+// How one chunk's aggregations run: as k_msa_dp_bfs (every tree in level order, the levels fit its LDS buffers, opt-in above
+// 64 KB granted) or as one launch per level (otherwise, or when SVO_MSA_LEVEL_LAUNCHES asks for it).
 constexpr int kMsaDpThreads = 512;
-static size_t msa_dp_bfs_lds(int maxw, int maxl) { return sizeof(double) * (256 + 2 * (size_t)maxw) + sizeof(int) * ((size_t)maxl + 2); }
-static bool msa_dp_bfs_ok(svo_ctx* ctx, int D, int maxw, int maxl) {
-  const size_t lds = msa_dp_bfs_lds(maxw, maxl);
-  if (getenv("SVO_MSA_LEVEL_LAUNCHES") || lds > 150 * 1024 || (size_t)64 * (D + 1) * sizeof(float) > 64 * 1024) return false;
-  if (ctx->msa_lds_state == 0)
-    ctx->msa_lds_state = hipFuncSetAttribute(reinterpret_cast<const void*>(k_msa_dp_bfs<kMsaDpThreads>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess ? 1 : -1;
-  return ctx->msa_lds_state > 0 || lds <= 64 * 1024;
+struct MsaDpPlan {
+  bool bfs = true;
+  int maxw = 0;             // widest level of any tree
+  std::vector<int> width;   // widest level l over the trees: the grid of that level's launch
+  void add(const std::vector<int32_t>& level_ptr, bool bfs_ok) {
+    bfs = bfs && bfs_ok;
+    if (width.size() + 1 < level_ptr.size()) width.resize(level_ptr.size() - 1, 0);
+    for (size_t l = 0; l + 1 < level_ptr.size(); ++l) {
+      width[l] = std::max(width[l], level_ptr[l + 1] - level_ptr[l]);
+      maxw = std::max(maxw, width[l]);
+    }
+  }
+  size_t lds() const { return sizeof(double) * (256 + 2 * (size_t)maxw) + sizeof(int) * (width.size() + 2); }
+  void decide(svo_ctx* ctx, int D) {
+    if (msa_level_launches() || lds() > 150 * 1024 || (size_t)64 * (D + 1) * sizeof(float) > 64 * 1024) { bfs = false; return; }
+    if (ctx->msa_lds_state == 0)
+      ctx->msa_lds_state = hipFuncSetAttribute(reinterpret_cast<const void*>(k_msa_dp_bfs<kMsaDpThreads>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess ? 1 : -1;
+    bfs = bfs && (ctx->msa_lds_state > 0 || lds() <= 64 * 1024);
+  }
+};
+// One aggregation (both sweeps) of the trees tabs[0 .. ntrees): two launches, or two per level
+static void msa_aggregate(hipStream_t s, const MsaTab* d_tabs, int ntrees, int N, int D, const double* d_Exp, const MsaDpPlan& p) {
+  const int L = (int)p.width.size();
+  if (p.bfs) {
+    hipLaunchKernelGGL(k_msa_bfs_gather, dim3((unsigned)((N + 63) / 64), ntrees), dim3(256), (size_t)64 * (D + 1) * sizeof(float), s, d_tabs, D);
+    hipLaunchKernelGGL(k_msa_dp_bfs<kMsaDpThreads>, dim3(D, ntrees), dim3(kMsaDpThreads), p.lds(), s, d_tabs, D, d_Exp, p.maxw, L);
+    return;
+  }
+  auto grid = [&](int l) { return dim3((unsigned)(((size_t)p.width[l] * D + 255) / 256), ntrees); };
+  for (int l = L - 1; l >= 0; --l) hipLaunchKernelGGL(k_msa_dp_up_many, grid(l), dim3(256), 0, s, d_tabs, l, D, d_Exp);
+  for (int l = 0; l < L; ++l) hipLaunchKernelGGL(k_msa_dp_down_many, grid(l), dim3(256), 0, s, d_tabs, l, D, d_Exp);
 }
-// One aggregation (both sweeps) of `ntrees` trees: two launches
-static void msa_dp_bfs_launch(hipStream_t s, const MsaBfsTab* d_tabs, int ntrees, int N, int D, const double* d_Exp, int maxw, int maxl) {
-  hipLaunchKernelGGL(k_msa_bfs_gather, dim3((unsigned)((N + 63) / 64), ntrees), dim3(256), (size_t)64 * (D + 1) * sizeof(float), s, d_tabs, D);
-  hipLaunchKernelGGL(k_msa_dp_bfs<kMsaDpThreads>, dim3(D, ntrees), dim3(kMsaDpThreads), msa_dp_bfs_lds(maxw, maxl), s, d_tabs, D, d_Exp,
-                     maxw, maxl);
+// The by-pixel arrays of one tree for the level launches: device copies from `buf`, pointers into `tab`
+static int msa_upload_by_pixel(svo_ctx* ctx, hipStream_t s, DevBuf& buf, int N, const int32_t* nodes, const int32_t* child_ptr,
+                               const int32_t* child, const uint8_t* child_c, const int32_t* parent, const uint8_t* parent_c, MsaTab& tab) {
+  int32_t* d_int[4] = {buf.get<int32_t>(N), buf.get<int32_t>(N + 1), buf.get<int32_t>(N), buf.get<int32_t>(N)};
+  uint8_t* d_byte[2] = {buf.get<uint8_t>(N), buf.get<uint8_t>(N)};
+  if (!d_int[0] || !d_int[1] || !d_int[2] || !d_int[3] || !d_byte[0] || !d_byte[1]) { ctx->last_error = "svo_msa: hipMalloc"; return SVO_E_NOMEM; }
+  SVO_HIP(ctx, hipMemcpyAsync(d_int[0], nodes, (size_t)N * 4, hipMemcpyHostToDevice, s));
+  SVO_HIP(ctx, hipMemcpyAsync(d_int[1], child_ptr, ((size_t)N + 1) * 4, hipMemcpyHostToDevice, s));
+  if (N > 1) {
+    SVO_HIP(ctx, hipMemcpyAsync(d_int[2], child, ((size_t)N - 1) * 4, hipMemcpyHostToDevice, s));
+    SVO_HIP(ctx, hipMemcpyAsync(d_byte[0], child_c, (size_t)N - 1, hipMemcpyHostToDevice, s));
+  }
+  SVO_HIP(ctx, hipMemcpyAsync(d_int[3], parent, (size_t)N * 4, hipMemcpyHostToDevice, s));
+  SVO_HIP(ctx, hipMemcpyAsync(d_byte[1], parent_c, (size_t)N, hipMemcpyHostToDevice, s));
+  tab.nodes = d_int[0]; tab.child_ptr = d_int[1]; tab.child = d_int[2]; tab.parent = d_int[3];
+  tab.child_c = d_byte[0]; tab.parent_c = d_byte[1];
+  return SVO_OK;
 }
 
 extern "C" int svo_msa_tree_dp(svo_ctx* ctx, const float* cost, int N, int D, const int32_t* seq, const int32_t* child_ptr,
@@ -382,68 +398,32 @@ extern "C" int svo_msa_tree_dp(svo_ctx* ctx, const float* cost, int N, int D, co
   }
   double Exp[256];
   for (int i = 0; i <= 255; ++i) Exp[i] = exp(-i * 1.0 / o / 255);   // MSA::setExp, MSA.cpp:1126-1130
+  std::vector<MsaBfsRec> rec;
+  std::vector<int32_t> pos;
+  int maxw = 0;
+  MsaDpPlan plan;
+  plan.add(level_ptr, msa_bfs_records(N, nodes.data(), level_ptr, child_ptr, child, parent.data(), parent_c.data(), pos, rec, &maxw));
   SVO_HIP(ctx, hipSetDevice(ctx->device));
+  plan.decide(ctx, D);
   DevBuf buf;
   const size_t V = (size_t)N * D;
-  float* d_up = buf.get<float>(V); float* d_A = buf.get<float>(V);
-  {
-    // both sweeps in one launch (k_msa_dp_bfs) whenever the tree's levels fit its LDS buffers
-    std::vector<MsaBfsRec> rec;
-    std::vector<int32_t> pos;
-    int maxw = 0;
-    if (msa_bfs_records(N, nodes.data(), level_ptr, child_ptr, child, parent.data(), parent_c.data(), pos, rec, &maxw) &&
-        msa_dp_bfs_ok(ctx, D, maxw, max_depth + 1)) {
-      float* d_cost = buf.get<float>(V);
-      MsaBfsRec* d_rec = buf.get<MsaBfsRec>(N);
-      int32_t* d_lp = buf.get<int32_t>(level_ptr.size());
-      MsaBfsTab* d_tab = buf.get<MsaBfsTab>(1);
-      double* d_E = buf.get<double>(256);
-      if (!d_up || !d_A || !d_cost || !d_rec || !d_lp || !d_tab || !d_E) { ctx->last_error = "svo_msa_tree_dp: hipMalloc"; return SVO_E_NOMEM; }
-      hipStream_t s = ctx->stream;
-      const MsaBfsTab tab{d_rec, d_lp, max_depth + 1, N, d_cost, d_up, d_A};
-      SVO_HIP(ctx, hipMemcpyAsync(d_cost, cost, V * sizeof(float), hipMemcpyHostToDevice, s));
-      SVO_HIP(ctx, hipMemcpyAsync(d_rec, rec.data(), (size_t)N * sizeof(MsaBfsRec), hipMemcpyHostToDevice, s));
-      SVO_HIP(ctx, hipMemcpyAsync(d_lp, level_ptr.data(), level_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-      SVO_HIP(ctx, hipMemcpyAsync(d_tab, &tab, sizeof tab, hipMemcpyHostToDevice, s));
-      SVO_HIP(ctx, hipMemcpyAsync(d_E, Exp, sizeof Exp, hipMemcpyHostToDevice, s));
-      {
-        SvoTimer t(ctx, "k_msa_tree_dp");
-        msa_dp_bfs_launch(s, d_tab, 1, N, D, d_E, maxw, max_depth + 1);
-      }
-      SVO_HIP(ctx, hipMemcpyAsync(costA, d_A, V * sizeof(float), hipMemcpyDeviceToHost, s));
-      SVO_HIP(ctx, hipStreamSynchronize(s));
-      SVO_HIP(ctx, hipGetLastError());
-      return SVO_OK;
-    }
-  }
-  int32_t* d_nodes = buf.get<int32_t>(N); int32_t* d_cptr = buf.get<int32_t>(N + 1); int32_t* d_child = buf.get<int32_t>(N);
-  int32_t* d_parent = buf.get<int32_t>(N);
-  uint8_t* d_cc = buf.get<uint8_t>(N); uint8_t* d_pc = buf.get<uint8_t>(N);
-  double* d_Exp = buf.get<double>(256);
-  if (!d_up || !d_A || !d_nodes || !d_cptr || !d_child || !d_parent || !d_cc || !d_pc || !d_Exp) { ctx->last_error = "svo_msa_tree_dp: hipMalloc"; return SVO_E_NOMEM; }
+  float* d_cost = buf.get<float>(V); float* d_up = buf.get<float>(V); float* d_A = buf.get<float>(V);
+  MsaBfsRec* d_rec = buf.get<MsaBfsRec>(N);
+  int32_t* d_lp = buf.get<int32_t>(level_ptr.size());
+  MsaTab* d_tab = buf.get<MsaTab>(1);
+  double* d_E = buf.get<double>(256);
+  if (!d_cost || !d_up || !d_A || !d_rec || !d_lp || !d_tab || !d_E) { ctx->last_error = "svo_msa_tree_dp: hipMalloc"; return SVO_E_NOMEM; }
   hipStream_t s = ctx->stream;
-  SVO_HIP(ctx, hipMemcpyAsync(d_up, cost, V * sizeof(float), hipMemcpyHostToDevice, s));
-  SVO_HIP(ctx, hipMemcpyAsync(d_nodes, nodes.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  SVO_HIP(ctx, hipMemcpyAsync(d_cptr, child_ptr, (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  if (N > 1) {
-    SVO_HIP(ctx, hipMemcpyAsync(d_child, child, (N - 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(d_cc, child_c, (N - 1), hipMemcpyHostToDevice, s));
-  }
-  SVO_HIP(ctx, hipMemcpyAsync(d_parent, parent.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  SVO_HIP(ctx, hipMemcpyAsync(d_pc, parent_c.data(), N, hipMemcpyHostToDevice, s));
-  SVO_HIP(ctx, hipMemcpyAsync(d_Exp, Exp, sizeof Exp, hipMemcpyHostToDevice, s));
+  MsaTab tab{d_rec, d_lp, max_depth + 1, N, d_cost, d_up, d_A, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (plan.bfs) SVO_HIP(ctx, hipMemcpyAsync(d_rec, rec.data(), (size_t)N * sizeof(MsaBfsRec), hipMemcpyHostToDevice, s));
+  else if (const int rc = msa_upload_by_pixel(ctx, s, buf, N, nodes.data(), child_ptr, child, child_c, parent.data(), parent_c.data(), tab)) return rc;
+  SVO_HIP(ctx, hipMemcpyAsync(d_cost, cost, V * sizeof(float), hipMemcpyHostToDevice, s));
+  SVO_HIP(ctx, hipMemcpyAsync(d_lp, level_ptr.data(), level_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  SVO_HIP(ctx, hipMemcpyAsync(d_tab, &tab, sizeof tab, hipMemcpyHostToDevice, s));
+  SVO_HIP(ctx, hipMemcpyAsync(d_E, Exp, sizeof Exp, hipMemcpyHostToDevice, s));
   {
     SvoTimer t(ctx, "k_msa_tree_dp");
-    for (int l = max_depth; l >= 0; --l) {
-      const int cnt = level_ptr[l + 1] - level_ptr[l];
-      hipLaunchKernelGGL(k_msa_dp_up, dim3((unsigned)(((size_t)cnt * D + 255) / 256)), dim3(256), 0, s, d_nodes + level_ptr[l], cnt, D,
-                         d_cptr, d_child, d_cc, d_Exp, d_up);
-    }
-    for (int l = 0; l <= max_depth; ++l) {
-      const int cnt = level_ptr[l + 1] - level_ptr[l];
-      hipLaunchKernelGGL(k_msa_dp_down, dim3((unsigned)(((size_t)cnt * D + 255) / 256)), dim3(256), 0, s, d_nodes + level_ptr[l], cnt, D,
-                         d_parent, d_pc, d_Exp, d_up, d_A);
-    }
+    msa_aggregate(s, d_tab, 1, N, D, d_E, plan);
   }
   SVO_HIP(ctx, hipMemcpyAsync(costA, d_A, V * sizeof(float), hipMemcpyDeviceToHost, s));
   SVO_HIP(ctx, hipStreamSynchronize(s));
@@ -592,10 +572,7 @@ extern "C" int svo_ctmf(svo_ctx* ctx, const uint8_t* src, uint8_t* dst, int widt
   return rc;
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// MSA::solve (MSA.cpp:1132-1169) end to end: everything per pixel / per node on the GPU and resident there
-// (the four cost volumes never leave HBM), the two aggregation trees on two host threads in between.
-// ------------------------------------------------------------------------------------------------------------
+// ---- MSA::solve: what the chunk solver below needs besides the stages above ------------------------------------
 namespace {
 
 __global__ void k_msa_scale(const uint8_t* d, int n, int scale, uint8_t* out) {
@@ -658,8 +635,7 @@ struct HostTree {                       // what svo_msa_tree returns, plus what 
   // exist only on the fallback path (SVO_MSA_LEVEL_LAUNCHES, or a node with more than 255 children).
   void build(const uint8_t* med3, const double* r_gra, const double* c_gra, int m, int n) {
     const int N = n * m;
-    static const bool level_launches = getenv("SVO_MSA_LEVEL_LAUNCHES") != nullptr;
-    if (!level_launches) {
+    if (!msa_level_launches()) {
       rec.resize(N);
       rc = svo_msa_tree_rec(med3, r_gra, c_gra, m, n, rec.data(), &level_ptr, &maxw, &root);
       if (rc == SVO_OK) { bfs_ok = true; full_ = false; have_csr_ = false; return; }
@@ -716,237 +692,196 @@ struct HostTree {                       // what svo_msa_tree returns, plus what 
   std::vector<uint8_t> pc_;
 };
 
-struct DevTree { int32_t *nodes, *child_ptr, *child, *parent; uint8_t *child_c, *parent_c; };
-struct MsaHostStore {
-  std::vector<HostTree> tree;
-  std::vector<std::vector<uint8_t>> med;
-  std::vector<std::vector<double>> gra;
+struct MsaHostStore {   // what a solve downloads, builds and uploads; the next solve on the same arena uses the buffers again
+  std::vector<HostTree> tree;               // 2b: left image of pair b, 2b + 1: right image
+  std::vector<std::vector<uint8_t>> med;    // their median images
+  std::vector<std::vector<double>> gra;     // per pair: r_graL c_graL r_graR c_graR
+  std::vector<MsaTab> tabs;                 // [side * C + b]
+  double Exp[512];                          // the weights of the first two aggregations | of the refinement
 };
+
+__global__ void k_msa_gray_to_bgr(const uint8_t* gray, int stride, int m, int n, uint8_t* bgr) {
+  const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+  if (j >= m) return;
+  const uint8_t v = gray[(size_t)i * stride + j];
+  uint8_t* o = bgr + ((size_t)i * m + j) * 3;
+  o[0] = v; o[1] = v; o[2] = v;
+}
+__global__ void k_msa_to_float(const uint8_t* d, int n, float* out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = (float)d[i];
+}
 
 }  // namespace
 
-// img3[side]: packed BGR images on the device (3 * m bytes per row); d_out: n * m bytes on the device.
-static int msa_solve_device(svo_ctx* ctx, hipStream_t s, DevBuf& buf, uint8_t* const img3[2], int n, int m, int d, int scale,
-                            uint8_t* d_out) {
+// MSA's input image in its tight 8UC3 layout: B = G = R copies of a gray image on the device (what a grayscale file read as
+// colour gives), or a pitched copy of a colour image on the device (the colour entries, main.cpp:160-161)
+static hipError_t msa_load_img3(hipStream_t st, const uint8_t* src, int pitch, bool bgr, int m, int n, uint8_t* img3) {
+  if (bgr) return hipMemcpy2DAsync(img3, 3 * (size_t)m, src, pitch, 3 * (size_t)m, n, hipMemcpyDeviceToDevice, st);
+  hipLaunchKernelGGL(k_msa_gray_to_bgr, dim3((m + 255) / 256, n), dim3(256), 0, st, src, pitch, m, n, img3);
+  return hipSuccess;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// MSA::solve (MSA.cpp:1132-1169) for C >= 1 pairs together, on stream `s` with the buffers of arena `ar`: everything per
+// pixel / per node on the GPU and resident there (the cost volumes never leave HBM), the 2C aggregation trees on host
+// threads in between, then every stage of the aggregation once for the whole chunk - the sweeps of all trees in one
+// launch (one per level on the fallback path), the per-pixel stages over the maps stacked into one tall image.
+// Pair b: rows `pitch` bytes apart at dL / dR + b * frame_stride, gray or (bgr) 8UC3.  The C disparity maps (uint8, n x m
+// each) are left in the arena; `emit` enqueues whatever turns them into the caller's output before the final wait.
+// With two lanes alternating over the chunks (svo_msa_run_many_dev), host_phase is held over the tree builders and
+// gpu_phase from the tree upload to the end, so that the trees of one chunk grow while the GPU aggregates the previous
+// one and initialises the next.
+// ------------------------------------------------------------------------------------------------------------
+static int msa_chunk_device(svo_ctx* ctx, hipStream_t s, MsaArena& ar, const uint8_t* dL, const uint8_t* dR, int pitch,
+                            size_t frame_stride, bool bgr, int m, int n, int d, int C, std::mutex* host_phase, std::mutex* gpu_phase,
+                            const std::function<void(const uint8_t*)>& emit) {
+  const bool dbg = getenv("SVO_MSA_DEBUG") != nullptr;
   auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](const char* name) {   // wall-clock profile entries of the host-visible stages
+  auto mark = [&](const char* name) {   // wall clock of a host-visible stage: a profile entry, a line under SVO_MSA_DEBUG
+    { HostTimer t(ctx, name); t.t0 = t_last; }
     const auto now = std::chrono::steady_clock::now();
-    if (ctx->profiling) {
-      const double ms = std::chrono::duration<double, std::milli>(now - t_last).count();
-      bool found = false;
-      for (auto& e : ctx->prof)
-        if (e.name == name) { e.total_ms += ms; e.launches += 1; found = true; break; }
-      if (!found) { SvoProfileEntry e; e.name = name; e.total_ms = ms; e.launches = 1; ctx->prof.push_back(e); }
-    }
+    if (dbg) fprintf(stderr, "[msa x%d] %-30s %8.2f ms\n", C, name, std::chrono::duration<double, std::milli>(now - t_last).count());
     t_last = now;
   };
-  const int D = d + 1;
+  const int D = d + 1, T2 = 2 * C;
   const size_t N = (size_t)n * m, V = N * D;
-  double* g = buf.get<double>(6 * N);                 // graL graR r_graL c_graL r_graR c_graR
-  float* cost[2] = {buf.get<float>(V), buf.get<float>(V)};   // costL, costR
-  float* d_up = buf.get<float>(V); float* d_A = buf.get<float>(V);
+  DevBuf& buf = ar.dev;
+  uint8_t* img3[2] = {buf.get<uint8_t>(3 * N), buf.get<uint8_t>(3 * N)};   // one pair as tight 8UC3, when the caller's is not
   uint8_t* med3[2] = {buf.get<uint8_t>(3 * N), buf.get<uint8_t>(3 * N)};
   uint8_t* gray = buf.get<uint8_t>(N);
-  uint8_t* d_disp[2] = {buf.get<uint8_t>(N), buf.get<uint8_t>(N)};   // d0 (left), d1 (right)
-  uint8_t* d_raw = buf.get<uint8_t>(N); uint8_t* d_mask = buf.get<uint8_t>(N);
-  double* d_Exp = buf.get<double>(256);
-  DevTree dt[2];
-  for (int s2 = 0; s2 < 2; ++s2) {
-    dt[s2].nodes = buf.get<int32_t>(N); dt[s2].child_ptr = buf.get<int32_t>(N + 1); dt[s2].child = buf.get<int32_t>(N);
-    dt[s2].parent = buf.get<int32_t>(N); dt[s2].child_c = buf.get<uint8_t>(N); dt[s2].parent_c = buf.get<uint8_t>(N);
-  }
-  MsaBfsRec* d_rec[2] = {buf.get<MsaBfsRec>(N), buf.get<MsaBfsRec>(N)};     // the trees in level order (k_msa_dp_bfs)
-  int32_t* d_lp[2] = {buf.get<int32_t>(N + 1), buf.get<int32_t>(N + 1)};
-  MsaBfsTab* d_tabs = buf.get<MsaBfsTab>(2);
-  double* d_Exp2 = buf.get<double>(256);
-  float* d_up1 = buf.get<float>(V); float* d_A1 = buf.get<float>(V); uint8_t* d_raw1 = buf.get<uint8_t>(N);   // second work volume
-  if (!g || !cost[0] || !cost[1] || !d_up || !d_A || !med3[0] || !med3[1] || !gray || !d_disp[0] || !d_disp[1] || !d_raw ||
-      !d_mask || !d_Exp || !dt[1].parent_c || !d_rec[0] || !d_rec[1] || !d_lp[0] || !d_lp[1] || !d_tabs || !d_Exp2 ||
-      !d_up1 || !d_A1 || !d_raw1) {
+  double* g = buf.get<double>(6 * N);                                      // graL graR r_graL c_graL r_graR c_graR
+  float* cost = buf.get<float>(V * T2);                                    // [side * C + b][pixel][disparity]: costL, costR
+  float* d_up = buf.get<float>(V * T2); float* d_A = buf.get<float>(V * T2);   // the aggregations' work and result volumes, same index
+  uint8_t* d_disp = buf.get<uint8_t>(N * T2); uint8_t* d_raw = buf.get<uint8_t>(N * T2);
+  uint8_t* d_mask = buf.get<uint8_t>(N * C);
+  double* d_Exp = buf.get<double>(512);
+  MsaBfsRec* d_rec = buf.get<MsaBfsRec>(N * T2);
+  int32_t* d_lp = buf.get<int32_t>((N + 1) * T2);
+  MsaTab* d_tabs = buf.get<MsaTab>(T2);
+  if (!img3[0] || !img3[1] || !med3[0] || !med3[1] || !gray || !g || !cost || !d_up || !d_A || !d_disp || !d_raw || !d_mask ||
+      !d_Exp || !d_rec || !d_lp || !d_tabs) {
     ctx->last_error = "svo_msa_solve: hipMalloc";
     return SVO_E_NOMEM;
   }
+  if (!ar.host) ar.host = new MsaHostStore();
+  MsaHostStore& hs = *ar.host;
+  if ((int)hs.tree.size() < T2) { hs.tree.resize(T2); hs.med.resize(T2); }
+  if ((int)hs.gra.size() < C) hs.gra.resize(C);
+  for (int k = 0; k < T2; ++k) hs.med[k].resize(3 * N);
+  for (int b = 0; b < C; ++b) hs.gra[b].resize(4 * N);
+  hs.tabs.resize(T2);
   mark("host_msa_alloc");
   const dim3 px((m + 255) / 256, n);
   const unsigned nbN = (unsigned)((N + 255) / 256), nbV = (unsigned)((V + 255) / 256);
 
-  // 1. MSA::init on the device
-  {
-    SvoTimer t(ctx, "k_msa_init");
-    for (int side = 0; side < 2; ++side) {
-      hipLaunchKernelGGL(k_msa_gray, dim3(nbN), dim3(256), 0, s, img3[side], (int)N, gray);
-      hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 1, 127.5, g + side * N);
+  // 1. MSA::init per pair; the median images and their gradients go to the host for the tree builders
+  const bool in_place = bgr && pitch == 3 * m;
+  for (int b = 0; b < C; ++b) {
+    const uint8_t* im[2] = {dL + b * frame_stride, dR + b * frame_stride};
+    for (int side = 0; side < 2 && !in_place; ++side) {
+      SVO_HIP(ctx, msa_load_img3(s, im[side], pitch, bgr, m, n, img3[side]));
+      im[side] = img3[side];
     }
-    hipLaunchKernelGGL(k_msa_cost, dim3(nbV), dim3(256), 0, s, img3[0], img3[1], g, g + N, n, m, D, cost[0]);
-    hipLaunchKernelGGL(k_msa_cost_right, dim3(nbV), dim3(256), 0, s, cost[0], n, m, D, cost[1]);
-    for (int side = 0; side < 2; ++side) {
-      hipLaunchKernelGGL(k_ctmf<1>, dim3((3 * m + 255) / 256, n), dim3(256), 0, s, img3[side], med3[side], m, n, 3 * m, 3 * m, 3);
-      hipLaunchKernelGGL(k_msa_gray, dim3(nbN), dim3(256), 0, s, med3[side], (int)N, gray);
-      hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 1, 0.0, g + (2 + 2 * side) * N);
-      hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 0, 0.0, g + (3 + 2 * side) * N);
+    float* cL = cost + (size_t)b * V;
+    float* cR = cost + (size_t)(C + b) * V;
+    {
+      SvoTimer t(ctx, "k_msa_init", s);
+      for (int side = 0; side < 2; ++side) {
+        hipLaunchKernelGGL(k_msa_gray, dim3(nbN), dim3(256), 0, s, im[side], (int)N, gray);
+        hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 1, 127.5, g + side * N);
+      }
+      hipLaunchKernelGGL(k_msa_cost, dim3(nbV), dim3(256), 0, s, im[0], im[1], g, g + N, n, m, D, cL);
+      hipLaunchKernelGGL(k_msa_cost_right, dim3(nbV), dim3(256), 0, s, cL, n, m, D, cR);
+      for (int side = 0; side < 2; ++side) {
+        hipLaunchKernelGGL(k_ctmf<1>, dim3((3 * m + 255) / 256, n), dim3(256), 0, s, im[side], med3[side], m, n, 3 * m, 3 * m, 3);
+        hipLaunchKernelGGL(k_msa_gray, dim3(nbN), dim3(256), 0, s, med3[side], (int)N, gray);
+        hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 1, 0.0, g + (2 + 2 * side) * N);
+        hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 0, 0.0, g + (3 + 2 * side) * N);
+      }
     }
+    for (int side = 0; side < 2; ++side) SVO_HIP(ctx, hipMemcpyAsync(hs.med[2 * b + side].data(), med3[side], 3 * N, hipMemcpyDeviceToHost, s));
+    SVO_HIP(ctx, hipMemcpyAsync(hs.gra[b].data(), g + 2 * N, 4 * N * sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  std::vector<uint8_t> h_med[2] = {std::vector<uint8_t>(3 * N), std::vector<uint8_t>(3 * N)};
-  std::vector<double> h_gra(4 * N);
-  for (int side = 0; side < 2; ++side) SVO_HIP(ctx, hipMemcpyAsync(h_med[side].data(), med3[side], 3 * N, hipMemcpyDeviceToHost, s));
-  SVO_HIP(ctx, hipMemcpyAsync(h_gra.data(), g + 2 * N, 4 * N * sizeof(double), hipMemcpyDeviceToHost, s));
   SVO_HIP(ctx, hipStreamSynchronize(s));
   mark("host_msa_init_and_download");
 
-  // 2. the two aggregation trees, one host thread each (the reference builds them one after the other)
-  HostTree tree[2];
-  auto grow = [&](int side) {
-    HostTree& t = tree[side];
-    t.build(h_med[side].data(), h_gra.data() + 2 * side * N, h_gra.data() + (2 * side + 1) * N, m, n);
-  };
+  // 2. the 2C trees, on as many host threads as are sensible (the reference builds a pair's two one after the other).  A
+  // lane's init kernels and downloads - its own arena - have run while the other lane built its trees.
+  std::unique_lock<std::mutex> host_lock;
+  if (host_phase) host_lock = std::unique_lock<std::mutex>(*host_phase);
+  std::vector<HostTree>& tree = hs.tree;
   {
-    std::thread right(grow, 1);
-    grow(0);
-    right.join();
+    std::atomic<int> next(0);
+    auto work = [&]() {
+      for (int k = next.fetch_add(1); k < T2; k = next.fetch_add(1)) {
+        const double* gra = hs.gra[k >> 1].data() + 2 * (k & 1) * N;
+        tree[k].build(hs.med[k].data(), gra, gra + N, m, n);
+      }
+    };
+    const int T = std::max(1, std::min(std::min(T2, 32), 2 * svo_host_cpus()));   // (measured on a 16-CPU quota: 32 builders 58 frames/s, 16: 51, 64: 36)
+    std::vector<std::thread> pool;
+    for (int t = 1; t < T; ++t) pool.emplace_back(work);
+    work();
+    for (auto& th : pool) th.join();
   }
   mark("host_msa_trees");
-  for (int side = 0; side < 2; ++side)
-    if (tree[side].rc) { ctx->last_error = "svo_msa_solve: tree construction failed"; return tree[side].rc; }
-  // one launch per aggregation (k_msa_dp_bfs) when the widest level fits its LDS buffers - always, on real images
-  int maxw = 0, maxl = 0;
-  for (int side = 0; side < 2; ++side) { maxw = std::max(maxw, tree[side].maxw); maxl = std::max(maxl, (int)tree[side].level_ptr.size() - 1); }
-  const bool bfs = tree[0].bfs_ok && tree[1].bfs_ok && msa_dp_bfs_ok(ctx, D, maxw, maxl);
-  MsaBfsTab h_tabs[2];
-  for (int side = 0; side < 2; ++side) {
-    const HostTree& t = tree[side];
-    if (bfs) {
-      SVO_HIP(ctx, hipMemcpyAsync(d_rec[side], t.rec.data(), N * sizeof(MsaBfsRec), hipMemcpyHostToDevice, s));
-      SVO_HIP(ctx, hipMemcpyAsync(d_lp[side], t.level_ptr.data(), t.level_ptr.size() * 4, hipMemcpyHostToDevice, s));
-      h_tabs[side] = MsaBfsTab{d_rec[side], d_lp[side], (int32_t)t.level_ptr.size() - 1, (int32_t)N, cost[side], side ? d_up1 : d_up,
-                               side ? d_A1 : d_A};
+  for (int k = 0; k < T2; ++k)
+    if (tree[k].rc) { ctx->last_error = "svo_msa_solve: tree construction failed"; return tree[k].rc; }
+  if (host_lock.owns_lock()) host_lock.unlock();
+  std::unique_lock<std::mutex> gpu_lock;
+  if (gpu_phase) gpu_lock = std::unique_lock<std::mutex>(*gpu_phase);
+
+  // 3. trees to the device, tabs[side * C + b]: in level order, or by pixel when some tree of the chunk needs the level launches
+  MsaDpPlan plan;
+  for (int k = 0; k < T2; ++k) plan.add(tree[k].level_ptr, tree[k].bfs_ok);
+  plan.decide(ctx, D);
+  for (int k = 0; k < T2; ++k) {
+    HostTree& t = tree[k];
+    if (!plan.bfs) t.need_full((int)N);   // (rewrites level_ptr, to the same values: before its copy is enqueued)
+    const size_t i = (size_t)(k & 1) * C + (k >> 1);
+    const int levels = (int)t.level_ptr.size() - 1;
+    MsaTab& tab = hs.tabs[i];
+    tab = MsaTab{d_rec + i * N, d_lp + i * (N + 1), levels, (int32_t)N, cost + i * V, d_up + i * V, d_A + i * V,
+                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    SVO_HIP(ctx, hipMemcpyAsync(d_lp + i * (N + 1), t.level_ptr.data(), (size_t)(levels + 1) * 4, hipMemcpyHostToDevice, s));
+    if (plan.bfs) {
+      SVO_HIP(ctx, hipMemcpyAsync(d_rec + i * N, t.rec.data(), N * sizeof(MsaBfsRec), hipMemcpyHostToDevice, s));
       continue;
     }
-    tree[side].need_full((int)N);
-    SVO_HIP(ctx, hipMemcpyAsync(dt[side].nodes, t.nodes.data(), N * 4, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(dt[side].child_ptr, t.child_ptr.data(), (N + 1) * 4, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(dt[side].child, t.child.data(), (N - 1) * 4, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(dt[side].parent, t.parent.data(), N * 4, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(dt[side].child_c, t.child_c.data(), N - 1, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(dt[side].parent_c, t.parent_c.data(), N, hipMemcpyHostToDevice, s));
+    if (const int rc = msa_upload_by_pixel(ctx, s, buf, (int)N, t.nodes.data(), t.child_ptr.data(), t.child.data(), t.child_c.data(),
+                                           t.parent.data(), t.parent_c.data(), tab)) return rc;
   }
-  if (bfs) SVO_HIP(ctx, hipMemcpyAsync(d_tabs, h_tabs, sizeof h_tabs, hipMemcpyHostToDevice, s));
+  SVO_HIP(ctx, hipMemcpyAsync(d_tabs, hs.tabs.data(), sizeof(MsaTab) * T2, hipMemcpyHostToDevice, s));
+  for (int i = 0; i <= 255; ++i) { hs.Exp[i] = exp(-i * 1.0 / 0.1 / 255); hs.Exp[256 + i] = exp(-i * 1.0 / (0.1 / 2) / 255); }
+  SVO_HIP(ctx, hipMemcpyAsync(d_Exp, hs.Exp, sizeof hs.Exp, hipMemcpyHostToDevice, s));
 
-  // 3. TreeDp + WTA per image, L/R check, TreeDp + WTA again with the sharper weights
-  double Exp[2][256];
-  for (int i = 0; i <= 255; ++i) { Exp[0][i] = exp(-i * 1.0 / 0.1 / 255); Exp[1][i] = exp(-i * 1.0 / (0.1 / 2) / 255); }
-  auto aggregate = [&](int side, const float* c, const double* E, uint8_t* out_disp) -> int {
-    const HostTree& t = tree[side];
-    const int levels = (int)t.level_ptr.size() - 1;
-    SVO_HIP(ctx, hipMemcpyAsync(d_Exp, E, 256 * sizeof(double), hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(d_up, c, V * sizeof(float), hipMemcpyDeviceToDevice, s));
-    {
-      SvoTimer tm(ctx, "k_msa_tree_dp");
-      for (int l = levels - 1; l >= 0; --l) {
-        const int cnt = t.level_ptr[l + 1] - t.level_ptr[l];
-        hipLaunchKernelGGL(k_msa_dp_up, dim3((unsigned)(((size_t)cnt * D + 255) / 256)), dim3(256), 0, s, dt[side].nodes + t.level_ptr[l],
-                           cnt, D, dt[side].child_ptr, dt[side].child, dt[side].child_c, d_Exp, d_up);
-      }
-      for (int l = 0; l < levels; ++l) {
-        const int cnt = t.level_ptr[l + 1] - t.level_ptr[l];
-        hipLaunchKernelGGL(k_msa_dp_down, dim3((unsigned)(((size_t)cnt * D + 255) / 256)), dim3(256), 0, s, dt[side].nodes + t.level_ptr[l],
-                           cnt, D, dt[side].parent, dt[side].parent_c, d_Exp, d_up, d_A);
-      }
-    }
-    SvoTimer tm(ctx, "k_msa_wta");
-    hipLaunchKernelGGL(k_msa_argmin, dim3(nbN), dim3(256), 0, s, d_A, (int)N, D, d_raw);
-    hipLaunchKernelGGL(k_ctmf<2>, dim3((m + 255) / 256, n), dim3(256), 0, s, d_raw, out_disp, m, n, m, m, 1);
-    return SVO_OK;
+  // 4. TreeDp + WTA for the right and the left images (one launch: they are independent until the L/R check), the L/R
+  // check, TreeDp + WTA again over the left trees with the sharper weights and the checked costs
+  auto wta = [&](int maps) {   // first minimum + 5x5 median of the maps [0, maps)
+    SvoTimer tm(ctx, "k_msa_wta", s);
+    hipLaunchKernelGGL(k_msa_argmin, dim3((unsigned)((N * maps + 255) / 256)), dim3(256), 0, s, d_A, (int)(N * maps), D, d_raw);
+    for (int k = 0; k < maps; ++k)
+      hipLaunchKernelGGL(k_ctmf<2>, px, dim3(256), 0, s, d_raw + (size_t)k * N, d_disp + (size_t)k * N, m, n, m, m, 1);
   };
-  int rc;
-  if (bfs) {
-    // the two first aggregations (right image as base, left image as base) in ONE launch pair, the refinement in another
-    SVO_HIP(ctx, hipMemcpyAsync(d_Exp, Exp[0], 256 * sizeof(double), hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(d_Exp2, Exp[1], 256 * sizeof(double), hipMemcpyHostToDevice, s));
-    {
-      SvoTimer tm(ctx, "k_msa_tree_dp");
-      msa_dp_bfs_launch(s, d_tabs, 2, (int)N, D, d_Exp, maxw, maxl);
-    }
-    {
-      SvoTimer tm(ctx, "k_msa_wta");
-      hipLaunchKernelGGL(k_msa_argmin, dim3(nbN), dim3(256), 0, s, d_A1, (int)N, D, d_raw1);
-      hipLaunchKernelGGL(k_ctmf<2>, dim3((m + 255) / 256, n), dim3(256), 0, s, d_raw1, d_disp[1], m, n, m, m, 1);
-      hipLaunchKernelGGL(k_msa_argmin, dim3(nbN), dim3(256), 0, s, d_A, (int)N, D, d_raw);
-      hipLaunchKernelGGL(k_ctmf<2>, dim3((m + 255) / 256, n), dim3(256), 0, s, d_raw, d_disp[0], m, n, m, m, 1);
-    }
-    {
-      SvoTimer tm(ctx, "k_msa_lrcheck");
-      hipLaunchKernelGGL(k_msa_lrcheck, dim3(nbV), dim3(256), 0, s, d_disp[0], d_disp[1], n, m, D, cost[0], d_mask);
-    }
-    {
-      SvoTimer tm(ctx, "k_msa_tree_dp");
-      msa_dp_bfs_launch(s, d_tabs, 1, (int)N, D, d_Exp2, maxw, maxl);   // refine: left tree, sharper weights, checked costs
-    }
-    {
-      SvoTimer tm(ctx, "k_msa_wta");
-      hipLaunchKernelGGL(k_msa_argmin, dim3(nbN), dim3(256), 0, s, d_A, (int)N, D, d_raw);
-      hipLaunchKernelGGL(k_ctmf<2>, dim3((m + 255) / 256, n), dim3(256), 0, s, d_raw, d_disp[0], m, n, m, m, 1);
-    }
-  } else {
-  // (levels too wide for k_msa_dp_bfs: one launch per level)
-  // The first two aggregations (right image as base image, left image as base image) are independent until the L/R
-  // check: their level sweeps - two chains of ~2 x 1000 small dependent launches - run side by side on two streams, with
-  // their own work volumes, instead of one after the other.
   {
-    if (!ctx->stream_fe) SVO_HIP(ctx, svo_stream_create(&ctx->stream_fe, -1));
-    hipStream_t s2 = ctx->stream_fe;
-    hipEvent_t e0, e1;
-    SVO_HIP(ctx, hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-    SVO_HIP(ctx, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-    SVO_HIP(ctx, hipMemcpyAsync(d_Exp, Exp[0], 256 * sizeof(double), hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(d_up, cost[0], V * sizeof(float), hipMemcpyDeviceToDevice, s));
-    SVO_HIP(ctx, hipEventRecord(e0, s));
-    SVO_HIP(ctx, hipStreamWaitEvent(s2, e0, 0));
-    SVO_HIP(ctx, hipMemcpyAsync(d_up1, cost[1], V * sizeof(float), hipMemcpyDeviceToDevice, s2));
-    const int lv[2] = {(int)tree[0].level_ptr.size() - 1, (int)tree[1].level_ptr.size() - 1};
-    float* ups[2] = {d_up, d_up1}; float* As[2] = {d_A, d_A1};
-    hipStream_t st2[2] = {s, s2};
-    {
-      SvoTimer tm(ctx, "k_msa_tree_dp");
-      const int lmax = std::max(lv[0], lv[1]);
-      for (int l = lmax - 1; l >= 0; --l)
-        for (int side = 0; side < 2; ++side) {
-          if (l >= lv[side]) continue;
-          const HostTree& t = tree[side];
-          const int cnt = t.level_ptr[l + 1] - t.level_ptr[l];
-          hipLaunchKernelGGL(k_msa_dp_up, dim3((unsigned)(((size_t)cnt * D + 255) / 256)), dim3(256), 0, st2[side],
-                             dt[side].nodes + t.level_ptr[l], cnt, D, dt[side].child_ptr, dt[side].child, dt[side].child_c, d_Exp, ups[side]);
-        }
-      for (int l = 0; l < lmax; ++l)
-        for (int side = 0; side < 2; ++side) {
-          if (l >= lv[side]) continue;
-          const HostTree& t = tree[side];
-          const int cnt = t.level_ptr[l + 1] - t.level_ptr[l];
-          hipLaunchKernelGGL(k_msa_dp_down, dim3((unsigned)(((size_t)cnt * D + 255) / 256)), dim3(256), 0, st2[side],
-                             dt[side].nodes + t.level_ptr[l], cnt, D, dt[side].parent, dt[side].parent_c, d_Exp, ups[side], As[side]);
-        }
-    }
-    {
-      SvoTimer tm(ctx, "k_msa_wta");
-      hipLaunchKernelGGL(k_msa_argmin, dim3(nbN), dim3(256), 0, s2, d_A1, (int)N, D, d_raw1);
-      hipLaunchKernelGGL(k_ctmf<2>, dim3((m + 255) / 256, n), dim3(256), 0, s2, d_raw1, d_disp[1], m, n, m, m, 1);
-      hipLaunchKernelGGL(k_msa_argmin, dim3(nbN), dim3(256), 0, s, d_A, (int)N, D, d_raw);
-      hipLaunchKernelGGL(k_ctmf<2>, dim3((m + 255) / 256, n), dim3(256), 0, s, d_raw, d_disp[0], m, n, m, m, 1);
-    }
-    SVO_HIP(ctx, hipEventRecord(e1, s2));
-    SVO_HIP(ctx, hipStreamWaitEvent(s, e1, 0));
-    hipEventDestroy(e0); hipEventDestroy(e1);   // destruction is deferred until the recorded work has completed
-    (void)rc;
+    SvoTimer tm(ctx, "k_msa_tree_dp", s);
+    msa_aggregate(s, d_tabs, T2, (int)N, D, d_Exp, plan);
+  }
+  wta(T2);
+  {
+    SvoTimer tm(ctx, "k_msa_lrcheck", s);   // the C maps as one tall image: the check only looks along a row
+    hipLaunchKernelGGL(k_msa_lrcheck, dim3((unsigned)((V * C + 255) / 256)), dim3(256), 0, s, d_disp, d_disp + N * C, n * C, m, D, cost, d_mask);
   }
   {
-    SvoTimer tm(ctx, "k_msa_lrcheck");
-    hipLaunchKernelGGL(k_msa_lrcheck, dim3(nbV), dim3(256), 0, s, d_disp[0], d_disp[1], n, m, D, cost[0], d_mask);
+    SvoTimer tm(ctx, "k_msa_tree_dp", s);
+    msa_aggregate(s, d_tabs, C, (int)N, D, d_Exp + 256, plan);
   }
-  if ((rc = aggregate(0, cost[0], Exp[1], d_disp[0]))) return rc;   // refine
-  }
-  hipLaunchKernelGGL(k_msa_scale, dim3(nbN), dim3(256), 0, s, d_disp[0], (int)N, scale, d_out);
+  wta(C);
+  emit(d_disp);
   mark("host_msa_enqueue_aggregation");
   SVO_HIP(ctx, hipStreamSynchronize(s));
-  mark("host_msa_wait_aggregation");   // Exp[][] and the trees are read by copies until here
+  mark("host_msa_wait_aggregation");
   SVO_HIP(ctx, hipGetLastError());
   return SVO_OK;
 }
@@ -962,9 +897,9 @@ extern "C" int svo_msa_solve(svo_ctx* ctx, const uint8_t* bgrL, const uint8_t* b
   }
   SVO_HIP(ctx, hipSetDevice(ctx->device));
   const size_t N = (size_t)n * m;
-  DevBuf& buf = msa_arena(ctx, 0);
-  uint8_t* img3[2] = {buf.get<uint8_t>(3 * N), buf.get<uint8_t>(3 * N)};
-  uint8_t* d_out = buf.get<uint8_t>(N);
+  MsaArena& ar = msa_arena(ctx, 0);
+  uint8_t* img3[2] = {ar.io.get<uint8_t>(3 * N), ar.io.get<uint8_t>(3 * N)};
+  uint8_t* d_out = ar.io.get<uint8_t>(N);
   if (!img3[0] || !img3[1] || !d_out) { ctx->last_error = "svo_msa_solve: hipMalloc"; return SVO_E_NOMEM; }
   hipStream_t s = ctx->stream;
   if (ctx->h_pinned && 6 * N + 4096 <= ctx->pinned_bytes) {   // (the buffer's last page belongs to svo_track_frame's boxes)
@@ -979,238 +914,28 @@ extern "C" int svo_msa_solve(svo_ctx* ctx, const uint8_t* bgrL, const uint8_t* b
     SVO_HIP(ctx, hipMemcpy2DAsync(img3[0], 3 * (size_t)m, bgrL, step, 3 * (size_t)m, n, hipMemcpyHostToDevice, s));
     SVO_HIP(ctx, hipMemcpy2DAsync(img3[1], 3 * (size_t)m, bgrR, step, 3 * (size_t)m, n, hipMemcpyHostToDevice, s));
   }
-  const int rc = msa_solve_device(ctx, s, buf, img3, n, m, d, scale, d_out);
+  const int rc = msa_chunk_device(ctx, s, ar, img3[0], img3[1], 3 * m, 0, true, m, n, d, 1, nullptr, nullptr, [&](const uint8_t* maps) {
+    hipLaunchKernelGGL(k_msa_scale, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, maps, (int)N, scale, d_out);
+  });
   if (rc) return rc;
   SVO_HIP(ctx, svo_memcpy_sync(ctx, disparity, d_out, N, hipMemcpyDeviceToHost));
   return SVO_OK;
 }
 
-namespace {
-__global__ void k_msa_gray_to_bgr(const uint8_t* gray, int stride, int m, int n, uint8_t* bgr) {
-  const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
-  if (j >= m) return;
-  const uint8_t v = gray[(size_t)i * stride + j];
-  uint8_t* o = bgr + ((size_t)i * m + j) * 3;
-  o[0] = v; o[1] = v; o[2] = v;
-}
-__global__ void k_msa_to_float(const uint8_t* d, int n, float* out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = (float)d[i];
-}
-}  // namespace
-
-// MSA's input image in its tight 8UC3 layout: B = G = R copies of a gray image on the device (what a grayscale file read as
-// colour gives), or a pitched copy of a colour image on the device (the colour entries, main.cpp:160-161)
-static hipError_t msa_load_img3(hipStream_t st, const uint8_t* src, int pitch, bool bgr, int m, int n, uint8_t* img3) {
-  if (bgr) return hipMemcpy2DAsync(img3, 3 * (size_t)m, src, pitch, 3 * (size_t)m, n, hipMemcpyDeviceToDevice, st);
-  hipLaunchKernelGGL(k_msa_gray_to_bgr, dim3((m + 255) / 256, n), dim3(256), 0, st, src, pitch, m, n, img3);
-  return hipSuccess;
-}
-
-// frame::MB (src/frame.cc:82-91) for the tracker's dense-depth mode: gray or colour images already on the device, disparity
-// as CV_32F like `disp_img.convertTo(disp_32f, CV_32F, 1)`.
-static int msa_run_on_stream(svo_ctx* ctx, hipStream_t st, int arena, const uint8_t* dL, const uint8_t* dR, int pitch, int W,
-                             int H, int d, float* d_disp, bool bgr) {
-  if (H < 5 || W < 5 || d < 0 || d > 255) return SVO_E_INVALID;
-  const size_t N = (size_t)W * H;
-  DevBuf& buf = msa_arena(ctx, arena);
-  uint8_t* img3[2] = {buf.get<uint8_t>(3 * N), buf.get<uint8_t>(3 * N)};
-  uint8_t* d_out = buf.get<uint8_t>(N);
-  if (!img3[0] || !img3[1] || !d_out) { ctx->last_error = "svo_msa_run_dev: hipMalloc"; return SVO_E_NOMEM; }
-  SVO_HIP(ctx, msa_load_img3(st, dL, pitch, bgr, W, H, img3[0]));
-  SVO_HIP(ctx, msa_load_img3(st, dR, pitch, bgr, W, H, img3[1]));
-  const int rc = msa_solve_device(ctx, st, buf, img3, H, W, d, 1, d_out);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_msa_to_float, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, d_out, (int)N, d_disp);
-  SVO_HIP(ctx, hipStreamSynchronize(st));   // the arena is handed out again by the next solve
-  return SVO_OK;
+// frame::MB (src/frame.cc:82-91) for the tracker's dense-depth mode: C gray or colour pairs already on the device, the
+// disparities as CV_32F like `disp_img.convertTo(disp_32f, CV_32F, 1)` at d_disp
+static int msa_float_chunk(svo_ctx* ctx, hipStream_t s, int arena, const uint8_t* dL, const uint8_t* dR, int pitch, size_t frame_stride,
+                           int W, int H, int d, int C, float* d_disp, std::mutex* host_phase, std::mutex* gpu_phase, bool bgr) {
+  const size_t NC = (size_t)W * H * C;
+  return msa_chunk_device(ctx, s, msa_arena(ctx, arena), dL, dR, pitch, frame_stride, bgr, W, H, d, C, host_phase, gpu_phase,
+                          [&](const uint8_t* maps) {
+    hipLaunchKernelGGL(k_msa_to_float, dim3((unsigned)((NC + 255) / 256)), dim3(256), 0, s, maps, (int)NC, d_disp);
+  });
 }
 
 int svo_msa_run_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int pitch, int W, int H, int d, float* d_disp, bool bgr) {
-  return msa_run_on_stream(ctx, ctx->stream, 0, dL, dR, pitch, W, H, d, d_disp, bgr);
-}
-
-// MSA::solve for C frames together (gray frames on the device, float maps out): init per frame, all 2C trees on host
-// threads, then every stage of the aggregation once for the whole chunk - the level sweeps as one launch per level for
-// all frames, the per-pixel stages over the C maps stacked into one tall image.
-// `lane` (0 / 1) selects the device arena and host store; with two lanes alternating over the chunks, host_phase is held
-// over the tree builders and gpu_phase from the tree upload to the end, so that the trees of one chunk grow while the GPU
-// aggregates the previous one and initialises the next.
-static int msa_many_device(svo_ctx* ctx, hipStream_t s, const uint8_t* dL, const uint8_t* dR, int pitch, size_t frame_stride,
-                           int m, int n, int d, int C, float* d_disp_out, int lane, std::mutex* host_phase,
-                           std::mutex* gpu_phase, bool bgr) {
-  const bool dbg = getenv("SVO_MSA_DEBUG") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](const char* what) {
-    const auto now = std::chrono::steady_clock::now();
-    if (dbg) fprintf(stderr, "[msa x%d] %-28s %8.2f ms\n", C, what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
-  const int D = d + 1;
-  const size_t N = (size_t)n * m, V = N * D;
-  std::unique_lock<std::mutex> host_lock;   // taken for the tree builders only (below): a lane's init kernels and downloads - its own
-  // arena, its own host store - run while the other lane builds its trees
-  DevBuf& buf = msa_arena(ctx, 1 + lane);
-  uint8_t* img3[2] = {buf.get<uint8_t>(3 * N), buf.get<uint8_t>(3 * N)};
-  uint8_t* med3[2] = {buf.get<uint8_t>(3 * N), buf.get<uint8_t>(3 * N)};
-  uint8_t* gray = buf.get<uint8_t>(N);
-  double* g = buf.get<double>(6 * N);
-  float* cost[2] = {buf.get<float>(V * C), buf.get<float>(V * C)};   // [side][frame][pixel][disparity]
-  float* d_up = buf.get<float>(V * C); float* d_A = buf.get<float>(V * C);
-  uint8_t* d_disp[2] = {buf.get<uint8_t>(N * C), buf.get<uint8_t>(N * C)};
-  uint8_t* d_raw = buf.get<uint8_t>(N * C); uint8_t* d_mask = buf.get<uint8_t>(N * C);
-  double* d_Exp = buf.get<double>(512);
-  int32_t* d_int = buf.get<int32_t>((size_t)2 * C * (5 * N + 4));     // nodes, level_ptr, child_ptr, child, parent per tree
-  uint8_t* d_byte = buf.get<uint8_t>((size_t)2 * C * 2 * N);          // child_c, parent_c per tree
-  MsaTreeTab* d_tabs = buf.get<MsaTreeTab>((size_t)2 * C);
-  MsaBfsRec* d_rec = buf.get<MsaBfsRec>((size_t)2 * C * N);           // the trees in level order (k_msa_dp_bfs)
-  MsaBfsTab* d_btabs = buf.get<MsaBfsTab>((size_t)2 * C);
-  if (!d_rec || !d_btabs) { ctx->last_error = "svo_msa (batched): hipMalloc"; return SVO_E_NOMEM; }
-  if (!img3[0] || !img3[1] || !med3[0] || !med3[1] || !gray || !g || !cost[0] || !cost[1] || !d_up || !d_A || !d_disp[0] ||
-      !d_disp[1] || !d_raw || !d_mask || !d_Exp || !d_int || !d_byte || !d_tabs) {
-    ctx->last_error = "svo_msa (batched): hipMalloc";
-    return SVO_E_NOMEM;
-  }
-  mark("device buffers");
-  const dim3 px((m + 255) / 256, n);
-  const unsigned nbN = (unsigned)((N + 255) / 256), nbV = (unsigned)((V + 255) / 256);
-  // 1. MSA::init per frame; the median images and their gradients go to the host for the tree builders
-  MsaArenas* arenas = static_cast<MsaArenas*>(ctx->msa_arenas);
-  if (!arenas->host[lane]) arenas->host[lane] = new MsaHostStore();
-  MsaHostStore& hs = *arenas->host[lane];
-  if ((int)hs.tree.size() < 2 * C) { hs.tree.resize(2 * C); hs.med.resize(2 * C); }
-  if ((int)hs.gra.size() < C) hs.gra.resize(C);
-  for (int k = 0; k < 2 * C; ++k) hs.med[k].resize(3 * N);
-  for (int b = 0; b < C; ++b) hs.gra[b].resize(4 * N);
-  std::vector<std::vector<uint8_t>>& h_med = hs.med;
-  std::vector<std::vector<double>>& h_gra = hs.gra;
-  mark("host buffers");
-  for (int b = 0; b < C; ++b) {
-    SVO_HIP(ctx, msa_load_img3(s, dL + b * frame_stride, pitch, bgr, m, n, img3[0]));
-    SVO_HIP(ctx, msa_load_img3(s, dR + b * frame_stride, pitch, bgr, m, n, img3[1]));
-    for (int side = 0; side < 2; ++side) {
-      hipLaunchKernelGGL(k_msa_gray, dim3(nbN), dim3(256), 0, s, img3[side], (int)N, gray);
-      hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 1, 127.5, g + side * N);
-    }
-    hipLaunchKernelGGL(k_msa_cost, dim3(nbV), dim3(256), 0, s, img3[0], img3[1], g, g + N, n, m, D, cost[0] + (size_t)b * V);
-    hipLaunchKernelGGL(k_msa_cost_right, dim3(nbV), dim3(256), 0, s, cost[0] + (size_t)b * V, n, m, D, cost[1] + (size_t)b * V);
-    for (int side = 0; side < 2; ++side) {
-      hipLaunchKernelGGL(k_ctmf<1>, dim3((3 * m + 255) / 256, n), dim3(256), 0, s, img3[side], med3[side], m, n, 3 * m, 3 * m, 3);
-      hipLaunchKernelGGL(k_msa_gray, dim3(nbN), dim3(256), 0, s, med3[side], (int)N, gray);
-      hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 1, 0.0, g + (2 + 2 * side) * N);
-      hipLaunchKernelGGL(k_msa_gradient, px, dim3(256), 0, s, gray, n, m, 0, 0.0, g + (3 + 2 * side) * N);
-      SVO_HIP(ctx, hipMemcpyAsync(h_med[2 * b + side].data(), med3[side], 3 * N, hipMemcpyDeviceToHost, s));
-    }
-    SVO_HIP(ctx, hipMemcpyAsync(h_gra[b].data(), g + 2 * N, 4 * N * sizeof(double), hipMemcpyDeviceToHost, s));
-  }
-  SVO_HIP(ctx, hipStreamSynchronize(s));
-  mark("init + download");
-  if (host_phase) host_lock = std::unique_lock<std::mutex>(*host_phase);
-  // 2. the 2C trees, on as many host threads as are sensible (tree 2b: left image of frame b, 2b + 1: right)
-  std::vector<HostTree>& tree = hs.tree;
-  std::atomic<long long> dbg_tree_us{0}, dbg_levels_us{0};
-  {
-    std::atomic<int> next(0);
-    auto work = [&]() {
-      for (int k = next.fetch_add(1); k < 2 * C; k = next.fetch_add(1)) {
-        HostTree& t = tree[k];
-        const int b = k >> 1, side = k & 1;
-        const auto ta = std::chrono::steady_clock::now();
-        t.build(h_med[k].data(), h_gra[b].data() + 2 * side * N, h_gra[b].data() + (2 * side + 1) * N, m, n);
-        const auto tb = std::chrono::steady_clock::now();
-        if (dbg) { dbg_tree_us += (long long)std::chrono::duration<double, std::micro>(tb - ta).count(); dbg_levels_us += (long long)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tb).count(); }
-      }
-    };
-    const int T = std::max(1, std::min(std::min(2 * C, 32), 2 * svo_host_cpus()));   // (measured on a 16-CPU quota: 32 builders 58 frames/s, 16: 51, 64: 36)
-    std::vector<std::thread> pool;
-    for (int t = 1; t < T; ++t) pool.emplace_back(work);
-    work();
-    for (auto& th : pool) th.join();
-  }
-  mark("trees");
-  if (dbg) fprintf(stderr, "[msa x%d]   per tree (thread time): svo_msa_tree %.1f ms, level records %.1f ms\n", C, dbg_tree_us / 1e3 / (2 * C), dbg_levels_us / 1e3 / (2 * C));
-  for (int k = 0; k < 2 * C; ++k)
-    if (tree[k].rc) { ctx->last_error = "svo_msa (batched): tree construction failed"; return tree[k].rc; }
-  if (host_lock.owns_lock()) host_lock.unlock();
-  std::unique_lock<std::mutex> gpu_lock;
-  if (gpu_phase) gpu_lock = std::unique_lock<std::mutex>(*gpu_phase);
-  // 3. trees to the device: tabs[side * C + b]
-  std::vector<MsaTreeTab> h_tabs(2 * C);
-  std::vector<MsaBfsTab> h_btabs(2 * C);
-  int Lmax[2] = {0, 0};
-  int maxw = 0, maxl = 0;
-  bool bfs = true;
-  for (int k = 0; k < 2 * C; ++k) { bfs = bfs && tree[k].bfs_ok; maxw = std::max(maxw, tree[k].maxw); maxl = std::max(maxl, (int)tree[k].level_ptr.size() - 1); }
-  bfs = bfs && msa_dp_bfs_ok(ctx, D, maxw, maxl);
-  for (int k = 0; k < 2 * C; ++k) {
-    const HostTree& t = tree[k];
-    const int b = k >> 1, side = k & 1;
-    int32_t* ip = d_int + (size_t)k * (5 * N + 4);
-    uint8_t* bp = d_byte + (size_t)k * 2 * N;
-    const int levels = (int)t.level_ptr.size() - 1;
-    SVO_HIP(ctx, hipMemcpyAsync(ip + N, t.level_ptr.data(), (size_t)(levels + 1) * 4, hipMemcpyHostToDevice, s));
-    Lmax[side] = std::max(Lmax[side], levels);
-    if (bfs) {
-      SVO_HIP(ctx, hipMemcpyAsync(d_rec + (size_t)k * N, t.rec.data(), N * sizeof(MsaBfsRec), hipMemcpyHostToDevice, s));
-      h_btabs[side * C + b] = MsaBfsTab{d_rec + (size_t)k * N, ip + N, levels, (int32_t)N, cost[side] + (size_t)b * V, d_up + (size_t)b * V,
-                                        d_A + (size_t)b * V};
-      continue;
-    }
-    tree[k].need_full((int)N);
-    SVO_HIP(ctx, hipMemcpyAsync(ip, t.nodes.data(), N * 4, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(ip + 2 * N + 2, t.child_ptr.data(), (N + 1) * 4, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(ip + 3 * N + 3, t.child.data(), (N - 1) * 4, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(ip + 4 * N + 3, t.parent.data(), N * 4, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(bp, t.child_c.data(), N - 1, hipMemcpyHostToDevice, s));
-    SVO_HIP(ctx, hipMemcpyAsync(bp + N, t.parent_c.data(), N, hipMemcpyHostToDevice, s));
-    h_tabs[side * C + b] = MsaTreeTab{ip, ip + N, ip + 2 * N + 2, ip + 3 * N + 3, ip + 4 * N + 3, bp, bp + N, levels};
-  }
-  if (bfs) SVO_HIP(ctx, hipMemcpyAsync(d_btabs, h_btabs.data(), sizeof(MsaBfsTab) * 2 * C, hipMemcpyHostToDevice, s));
-  SVO_HIP(ctx, hipMemcpyAsync(d_tabs, h_tabs.data(), sizeof(MsaTreeTab) * 2 * C, hipMemcpyHostToDevice, s));
-  double Exp[512];
-  for (int i = 0; i <= 255; ++i) { Exp[i] = exp(-i * 1.0 / 0.1 / 255); Exp[256 + i] = exp(-i * 1.0 / (0.1 / 2) / 255); }
-  SVO_HIP(ctx, hipMemcpyAsync(d_Exp, Exp, sizeof Exp, hipMemcpyHostToDevice, s));
-  mark("tree upload (enqueue)");
-  // widest level over the frames, per level and side: the grid of that level's launch
-  std::vector<int> width[2];
-  for (int side = 0; side < 2; ++side) {
-    width[side].assign(Lmax[side], 0);
-    for (int b = 0; b < C; ++b) {
-      const HostTree& t = tree[2 * b + side];
-      for (int l = 0; l + 1 < (int)t.level_ptr.size(); ++l) width[side][l] = std::max(width[side][l], t.level_ptr[l + 1] - t.level_ptr[l]);
-    }
-  }
-  // 4. TreeDp + WTA for the right images, the left images, L/R check, TreeDp + WTA again with the sharper weights
-  auto aggregate = [&](int side, const float* c, const double* E, uint8_t* out_disp) -> int {
-    const MsaTreeTab* tabs = d_tabs + side * C;
-    if (bfs) {
-      msa_dp_bfs_launch(s, d_btabs + side * C, C, (int)N, D, E, maxw, maxl);   // reads the costs from where they are
-    } else {
-    SVO_HIP(ctx, hipMemcpyAsync(d_up, c, V * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-    for (int l = Lmax[side] - 1; l >= 0; --l)
-      hipLaunchKernelGGL(k_msa_dp_up_many, dim3((unsigned)(((size_t)width[side][l] * D + 255) / 256), C), dim3(256), 0, s, tabs, l, D, E,
-                         d_up, V);
-    for (int l = 0; l < Lmax[side]; ++l)
-      hipLaunchKernelGGL(k_msa_dp_down_many, dim3((unsigned)(((size_t)width[side][l] * D + 255) / 256), C), dim3(256), 0, s, tabs, l, D,
-                         E, d_up, d_A, V);
-    }
-    hipLaunchKernelGGL(k_msa_argmin, dim3((unsigned)((N * C + 255) / 256)), dim3(256), 0, s, d_A, (int)(N * C), D, d_raw);
-    for (int b = 0; b < C; ++b)
-      hipLaunchKernelGGL(k_ctmf<2>, dim3((m + 255) / 256, n), dim3(256), 0, s, d_raw + (size_t)b * N, out_disp + (size_t)b * N, m, n, m, m, 1);
-    return SVO_OK;
-  };
-  int rc;
-  if ((rc = aggregate(1, cost[1], d_Exp, d_disp[1]))) return rc;
-  if ((rc = aggregate(0, cost[0], d_Exp, d_disp[0]))) return rc;
-  hipLaunchKernelGGL(k_msa_lrcheck, dim3((unsigned)((V * C + 255) / 256)), dim3(256), 0, s, d_disp[0], d_disp[1], n * C, m, D, cost[0],
-                     d_mask);   // the C maps as one tall image: the check only looks along a row
-  if ((rc = aggregate(0, cost[0], d_Exp + 256, d_disp[0]))) return rc;
-  hipLaunchKernelGGL(k_msa_to_float, dim3((unsigned)((N * C + 255) / 256)), dim3(256), 0, s, d_disp[0], (int)(N * C), d_disp_out);
-  mark("aggregation (enqueue)");
-  SVO_HIP(ctx, hipStreamSynchronize(s));
-  mark("aggregation (wait)");   // host trees and tables are read by copies until here
-  SVO_HIP(ctx, hipGetLastError());
-  return SVO_OK;
+  if (H < 5 || W < 5 || d < 0 || d > 255) return SVO_E_INVALID;
+  return msa_float_chunk(ctx, ctx->stream, 0, dL, dR, pitch, 0, W, H, d, 1, d_disp, nullptr, nullptr, bgr);
 }
 
 // B frames (frame b at dL + b * frame_stride bytes, map b at d_disp + b * W * H floats), solved in chunks that share
@@ -1225,10 +950,10 @@ int svo_msa_run_many_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int
     }
     return SVO_OK;
   }
-  // chunks of up to 16 frames: ~0.4 GB of HBM per frame at KITTI size (four cost volumes)
+  // chunks of up to 16 frames: ~0.55 GB of HBM per frame at KITTI size (six cost-sized volumes: two costs, and a work and a
+  // result volume for each of the two aggregations that share a launch)
   const int nchunk = (B + 15) / 16;
-  if (nchunk == 1)
-    return msa_many_device(ctx, ctx->stream, dL, dR, pitch, frame_stride, W, H, d, B, d_disp, 0, nullptr, nullptr, bgr);
+  if (nchunk == 1) return msa_float_chunk(ctx, ctx->stream, 1, dL, dR, pitch, frame_stride, W, H, d, B, d_disp, nullptr, nullptr, bgr);
   // two lanes (threads, streams, arenas) take the chunks alternately
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));   // whatever produced the frames
   std::mutex host_phase, gpu_phase;
@@ -1239,8 +964,8 @@ int svo_msa_run_many_dev(svo_ctx* ctx, const uint8_t* dL, const uint8_t* dR, int
     if (hipSetDevice(ctx->device) != hipSuccess) { rcs[t] = SVO_E_HIP; return; }
     for (int c = t; c < nchunk; c += 2) {
       const int b0 = 16 * c, C = std::min(16, B - b0);
-      const int rc = msa_many_device(ctx, st[t], dL + b0 * frame_stride, dR + b0 * frame_stride, pitch, frame_stride, W, H, d, C,
-                                     d_disp + b0 * N, t, &host_phase, &gpu_phase, bgr);
+      const int rc = msa_float_chunk(ctx, st[t], 1 + t, dL + b0 * frame_stride, dR + b0 * frame_stride, pitch, frame_stride, W, H, d, C,
+                                     d_disp + b0 * N, &host_phase, &gpu_phase, bgr);
       if (rc) { rcs[t] = rc; return; }
     }
   };
@@ -1268,9 +993,7 @@ extern "C" int svo_msa_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t
 void svo_msa_release(svo_ctx* ctx) {
   if (!ctx || !ctx->msa_arenas) return;
   MsaArenas* A = static_cast<MsaArenas*>(ctx->msa_arenas);
-  for (DevBuf* b : A->a) delete b;
-  delete A->host[0];
-  delete A->host[1];
+  for (MsaArena* a : A->a) { delete a->host; delete a; }
   delete A;
   ctx->msa_arenas = nullptr;
 }

@@ -3,6 +3,7 @@
 CPU: the compiled reference equals the plain definition (true median, window clamped to the image).
 GPU: svo_ctmf through the C-ABI equals the compiled reference, bit for bit, at the radii / channel counts
 MSA uses (MSA.cpp:58-59: r = 1 on 3 channels; MSA.cpp:1006: r = 2 on 1 channel) and others."""
+import functools
 import os
 
 import numpy as np
@@ -258,18 +259,27 @@ def test_oracle_solve_recovers_a_known_shift():
     assert np.array_equal(ob.msa_solve(L, R, 16, 3), (d * 3).astype(np.uint8))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("W,H,d,shift", [(120, 64, 16, 7), (200, 120, 48, 11), (321, 97, 31, 0), (1241, 376, 48, 0)])
-def test_gpu_solve_equals_oracle(pkg, W, H, d, shift):
-    """svo_msa_solve (GPU stages + host trees, volumes resident in HBM) is bit-identical to orc_msa_solve."""
+@functools.lru_cache(maxsize=None)
+def solve_case(W, H, d, shift):
+    """A pair and the oracle's map for it (computed once, shared by the tests that compare against it)."""
     if W > 1000:      # the full KITTI frame (the urban fixture is exactly that big): trees ~1000 levels deep
         gl, gr = util.urban_pair(W, H, 0, 0)
         L = np.ascontiguousarray(np.repeat(gl[:, :, None], 3, 2)); R = np.ascontiguousarray(np.repeat(gr[:, :, None], 3, 2))
     else:
         L, R = shifted_colour_pair(W, H, shift) if shift else colour_pair(W, H)
+    r = ob.msa_solve(L, R, d, 1)
+    for a in (L, R, r):
+        a.setflags(write=False)
+    return L, R, r
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H,d,shift", [(120, 64, 16, 7), (200, 120, 48, 11), (321, 97, 31, 0), (1241, 376, 48, 0)])
+def test_gpu_solve_equals_oracle(pkg, W, H, d, shift):
+    """svo_msa_solve (GPU stages + host trees, volumes resident in HBM) is bit-identical to orc_msa_solve."""
+    L, R, r = solve_case(W, H, d, shift)
     s = pkg.Svo(640, 240)
     g = s.msa_solve(L, R, d, 1)
-    r = ob.msa_solve(L, R, d, 1)
     assert np.array_equal(g, r), int((g != r).sum())
     if shift:
         assert (g[:, 3 * shift:] == shift).mean() > 0.95
@@ -286,26 +296,103 @@ def test_gpu_solve_equals_oracle(pkg, W, H, d, shift):
 def test_gpu_batch_equals_single_solves(pkg, B):
     """svo_msa_batch_dev (frames solved together: shared level sweeps, stacked per-pixel stages) == svo_msa_solve per
     frame on the B = G = R colour images, for frames of different content (different tree depths in one chunk)."""
-    import torch
-    W, H, d = 200, 120, 32
-    dev = torch.device("cuda", 0)
-    pitch = 256
-    Ls, Rs = [], []
-    for b in range(B):
-        L, R = util.urban_pair(W, H, 100 + 45 * b, 40 + 10 * b)
-        Ls.append(L); Rs.append(R)
-    Ls[3] = np.full((H, W), 80, np.uint8); Rs[3] = np.full((H, W), 80, np.uint8)     # a flat frame: a very different tree
-    dL = torch.zeros((B, H, pitch), dtype=torch.uint8, device=dev); dR = torch.zeros_like(dL)
-    dL[:, :, :W] = torch.from_numpy(np.stack(Ls)).to(dev); dR[:, :, :W] = torch.from_numpy(np.stack(Rs)).to(dev)
-    out = torch.zeros((B, H, W), dtype=torch.float32, device=dev)
-    torch.cuda.synchronize()
     s = pkg.Svo(640, 240)
-    s.msa_batch_dev(dL.data_ptr(), dR.data_ptr(), pitch, W, H, B, out.data_ptr(), d)
-    got = out.cpu().numpy()
-    g2c = lambda g: np.ascontiguousarray(np.repeat(g[:, :, None], 3, 2))
+    got, dL, dR, out = batch_maps(s, B)
     for b in range(B):
-        want = s.msa_solve(g2c(Ls[b]), g2c(Rs[b]), d, 1).astype(np.float32)
-        assert np.array_equal(got[b], want), b
+        assert np.array_equal(got[b], single_map(s, b)), b
     with pytest.raises(pkg.SvoError):
-        s.msa_batch_dev(dL.data_ptr(), dR.data_ptr(), W - 1, W, H, B, out.data_ptr(), d)
+        s.msa_batch_dev(dL.data_ptr(), dR.data_ptr(), BATCH_W - 1, BATCH_W, BATCH_H, B, out.data_ptr(), BATCH_D)
     s.close()
+
+
+BATCH_W, BATCH_H, BATCH_D, BATCH_PITCH = 200, 120, 32, 256
+
+
+@functools.lru_cache(maxsize=None)
+def batch_frame(b):
+    """Gray pair b of the batch tests; pair 3 is flat: a very different tree."""
+    if b == 3:
+        return (np.full((BATCH_H, BATCH_W), 80, np.uint8),) * 2
+    return util.urban_pair(BATCH_W, BATCH_H, 100 + 45 * b, 40 + 10 * b)
+
+
+def batch_maps(s, B):
+    """svo_msa_batch_dev over the pairs 0 .. B - 1 in pitched device memory: the B float maps (and the device tensors)."""
+    import torch
+    dev = torch.device("cuda", 0)
+    dL = torch.zeros((B, BATCH_H, BATCH_PITCH), dtype=torch.uint8, device=dev); dR = torch.zeros_like(dL)
+    dL[:, :, :BATCH_W] = torch.from_numpy(np.stack([batch_frame(b)[0] for b in range(B)])).to(dev)
+    dR[:, :, :BATCH_W] = torch.from_numpy(np.stack([batch_frame(b)[1] for b in range(B)])).to(dev)
+    out = torch.zeros((B, BATCH_H, BATCH_W), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    s.msa_batch_dev(dL.data_ptr(), dR.data_ptr(), BATCH_PITCH, BATCH_W, BATCH_H, B, out.data_ptr(), BATCH_D)
+    return out.cpu().numpy(), dL, dR, out
+
+
+_SINGLE_MAPS = {}
+
+
+def single_map(s, b):
+    """svo_msa_solve on pair b as a B = G = R colour image (solved once per pair, on the default path)."""
+    assert "SVO_MSA_LEVEL_LAUNCHES" not in os.environ
+    if b not in _SINGLE_MAPS:
+        g2c = lambda g: np.ascontiguousarray(np.repeat(g[:, :, None], 3, 2))
+        L, R = batch_frame(b)
+        _SINGLE_MAPS[b] = s.msa_solve(g2c(L), g2c(R), BATCH_D, 1).astype(np.float32)
+    return _SINGLE_MAPS[b]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 17])       # one pair; 16 + 1: the second lane solves a chunk of one beside a full one
+def test_gpu_chunk_of_one_equals_single_solve(pkg, B):
+    s = pkg.Svo(640, 240)
+    got = batch_maps(s, B)[0]
+    for b in range(B):
+        assert np.array_equal(got[b], single_map(s, b)), b
+    s.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H,d,shift", [(120, 64, 16, 7), (321, 97, 31, 0)])
+def test_gpu_solve_level_launch_path_equals_oracle(pkg, monkeypatch, W, H, d, shift):
+    """The whole solve with TreeDp forced onto one launch per level (the path of a tree whose widest level overflows LDS or
+    that has a node with more than 255 children): bit-identical to orc_msa_solve; the same context without the variable -
+    back on k_msa_dp_bfs, same arena, same host trees - gives the same bytes."""
+    L, R, r = solve_case(W, H, d, shift)
+    s = pkg.Svo(640, 240)
+    monkeypatch.setenv("SVO_MSA_LEVEL_LAUNCHES", "1")
+    g = s.msa_solve(L, R, d, 1)
+    assert np.array_equal(g, r), int((g != r).sum())
+    monkeypatch.delenv("SVO_MSA_LEVEL_LAUNCHES")
+    assert s.msa_solve(L, R, d, 1).tobytes() == g.tobytes()
+    s.close()
+
+
+@pytest.mark.gpu
+def test_gpu_batch_level_launch_path_equals_single_solves(pkg, monkeypatch):
+    """A chunk of five on the level launches: level l of all ten trees in one launch.  The flat pair's trees have a very
+    different depth, so a tree sitting out a level (l >= levels) and the per-level grid width are on the path."""
+    s = pkg.Svo(640, 240)
+    monkeypatch.setenv("SVO_MSA_LEVEL_LAUNCHES", "1")
+    got = batch_maps(s, 5)[0]
+    monkeypatch.delenv("SVO_MSA_LEVEL_LAUNCHES")
+    for b in range(5):
+        assert np.array_equal(got[b], single_map(s, b)), b
+    s.close()
+
+
+@pytest.mark.gpu
+def test_gpu_solve_profile_names(pkg):
+    """One profiled svo_msa_solve: the four device timers (two aggregation launches - both first aggregations share one - and
+    two WTA rounds) and the wall-clock entries of the host-visible stages, once each."""
+    L, R, _ = solve_case(120, 64, 16, 7)
+    s = pkg.Svo(640, 240)
+    s.msa_solve(L, R, 16, 1)
+    s.profile_enable(True); s.profile_reset(); s.msa_solve(L, R, 16, 1); s.profile_enable(False)
+    prof = s.profile()
+    s.close()
+    assert {k: v[1] for k, v in prof.items() if k.startswith("k_msa")} == {"k_msa_init": 1, "k_msa_tree_dp": 2, "k_msa_wta": 2, "k_msa_lrcheck": 1}
+    assert {k: v[1] for k, v in prof.items() if k.startswith("host_msa")} == {
+        "host_msa_alloc": 1, "host_msa_init_and_download": 1, "host_msa_trees": 1, "host_msa_enqueue_aggregation": 1,
+        "host_msa_wait_aggregation": 1}
+    assert all(v[0] >= 0 for v in prof.values())
