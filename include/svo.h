@@ -422,6 +422,13 @@ int svo_debug_epnp5(svo_ctx* ctx, const double Xw5[15], const double uv5[10], co
 int svo_debug_epnp_gn(svo_ctx* ctx, const double L[60], const double rho[6], const double betas_in[12],
                       double betas_out[12]);
 
+/* Parity probe: the 12 x 12 one-sided Jacobi sweeps of that solve alone (JacobiSVDImpl_ on temp_a = (M^T M)^T, without the sort), as
+ * ONE wave runs them.  At 12 x 12 row-major.  rows_out: 12 rows of 16 doubles - the rotated row scaled by 1 / W in columns 0 .. 11,
+ * W = sqrt(sum_k At[i][k]^2) in column 15.  steps: steps of the wave's schedule the loop ran (prologue + one period per sweep).
+ * flag: 1 = it ran out of sweeps (25); the solver then redoes the sweeps in full IEEE arithmetic, as it does when a W leaves
+ * [2^-100, 2^100] - inside that range the rows are JacobiSVDImpl_'s bit for bit. */
+int svo_debug_jacobi12(svo_ctx* ctx, const double At[144], double rows_out[12 * 16], int32_t* steps, int32_t* flag);
+
 /* Parity probe of RANSACPointSetRegistrator::run's sequential rule - which sample wins, how many are visited - in every copy
  * the library holds of it: the plain rule of svo_pnp_ransac and the tracker's variants that work from precomputed pow / log
  * terms, on the first m samples only, or report the iteration bound after m samples.  Two modes:

@@ -59,7 +59,7 @@ ABI_SYMBOLS = [
     "svo_debug_fast_corners", "svo_stereo_frame", "svo_stereo_frame_ex", "svo_disp2depth",
     "svo_unproject", "svo_descriptor_distance", "svo_hamming_argmin", "svo_match_greedy",
     "svo_match_greedy_gated",
-    "svo_bf_match", "svo_pnp_ransac", "svo_debug_epnp5", "svo_debug_epnp_gn", "svo_debug_pnp_rule", "svo_debug_pnp_consensus", "svo_pose_opt", "svo_track_reset", "svo_track_frame",
+    "svo_bf_match", "svo_pnp_ransac", "svo_debug_epnp5", "svo_debug_epnp_gn", "svo_debug_jacobi12", "svo_debug_pnp_rule", "svo_debug_pnp_consensus", "svo_pose_opt", "svo_track_reset", "svo_track_frame",
     "svo_debug_track_matches", "svo_debug_track_gate", "svo_debug_track_pnp", "svo_debug_track_frames", "svo_fundamental_8point",
     "svo_frontend_batch_dev", "svo_track_batch_dev", "svo_profile_enable", "svo_profile_reset",
     "svo_profile_get",
@@ -403,6 +403,15 @@ class Svo:
         betas = np.ascontiguousarray(betas, np.float64).reshape(12); out = np.zeros(12)
         self._chk(self.lib.svo_debug_epnp_gn(self.h, _p(L), _p(rho), _p(betas), _p(out)))
         return out.reshape(3, 4)
+
+    def debug_jacobi12(self, At):
+        """svo_debug_jacobi12: the 12 x 12 step loop of the order-preserving EPnP alone, one wave -> (rows 12 x 12 scaled by 1 / W, W[12],
+        steps, flag)."""
+        At = np.ascontiguousarray(At, np.float64).reshape(144); rows = np.zeros(12 * 16)
+        steps, flag = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.svo_debug_jacobi12(self.h, _p(At), _p(rows), C.byref(steps), C.byref(flag)))
+        rows = rows.reshape(12, 16)
+        return rows[:, :12].copy(), rows[:, 15].copy(), int(steps.value), int(flag.value)
 
     def debug_pnp_rule_table(self, n):
         """svo_debug_pnp_rule, table mode: for g = 0 .. n (zeros below 5) the tabulated ld = log(1 - (g / n)^5) (1.0: bound 0), r =

@@ -349,9 +349,17 @@ EO_FN unsigned long long jacobi_rows(Lds& S, int n, int base, int lane) {
     [base] "v"(base), [act] "v"(act), [pm] "v"(pm), [mk] "v"(mk), [eps] "v"(eps), [eps2hi] "v"(eps2hi), [eps2lo] "v"(eps2lo),   \
     [amine] "v"(amine), [axch] "v"(axch)                                                                                          \
   : EO_JACOBI_ASM_CLOBBERS
-  // M = 12 (one problem on rows 0..11): the schedule is unrolled in the block, which only reads the lane's table entries of the period
+  // M = 12 (one problem on rows 0..11): the schedule is unrolled in the block, which only reads the lane's table entries of the period;
+  // -DEO_JACOBI12_PREV builds the block with the step body in its former instruction order (same operations, same bits) from
+  // svo_epnp_ord_asm_prev.h - not a committed file: `make -C tools prev_header` writes it (gen_jacobi_asm.py --prev)
+#ifdef EO_JACOBI12_PREV
+#include "svo_epnp_ord_asm_prev.h"
+#define EO_JACOBI_ASM_12_BLOCK EO_JACOBI_ASM_12_PREV
+#else
+#define EO_JACOBI_ASM_12_BLOCK EO_JACOBI_ASM_12
+#endif
   if (M == 12)
-    asm volatile(EO_JACOBI_ASM_12
+    asm volatile(EO_JACOBI_ASM_12_BLOCK
                  : [x0] "+v"(x0), [x1] "+v"(x1), [x2] "+v"(x2), [chg] "+v"(chg), [flag] "+v"(flag)
                  : [tper] "v"(twrap), [lane] "v"(lane), [base] "v"(base), [act] "v"(act), [pm] "v"(pm), [eps] "v"(eps),
                    [eps2hi] "v"(eps2hi), [eps2lo] "v"(eps2lo), [amine] "v"(amine), [axch] "v"(axch)
@@ -368,6 +376,15 @@ EO_FN unsigned long long jacobi_rows(Lds& S, int n, int base, int lane) {
                  : EO_JACOBI_ASM_CLOBBERS);
   }
 #undef EO_JACOBI_OPERANDS
+#undef EO_JACOBI_ASM_12_BLOCK
+#ifdef EO_JACOBI12_STEPS   // diagnostics (svo_pnp_probe.hip defines it, nobody else): the steps the M = 12 block ran - the prologue and one period
+  if (M == 12) {           // per sweep, the last of which (one behind the last that rotated a row) rotates nothing; 25 sweeps at the most
+    unsigned any = chg;
+    for (int o = 32; o; o >>= 1) any |= __shfl_xor(any, o);
+    const int sw = any ? 33 - __clz(any) : 1;
+    nst = EO_TAB12_PROLOGUE + (EO_TAB12_STEPS - EO_TAB12_PROLOGUE) * (sw < 25 ? sw : 25);
+  }
+#endif
 #ifdef EO_PROFILE
   if (M == 3) {               // sweeps the loop ran: the block's counter, or (table-driven) one more than the last sweep a row rotated in (25 at the most)
     const int sw = regs3 ? (int)chg : (33 - __clz(chg) < 25 ? 33 - __clz(chg) : 25);

@@ -1,6 +1,8 @@
-// svo_pnp_probe.hip - parity probes of RANSAC's stopping rule and consensus count (svo_debug_pnp_rule, svo_debug_pnp_consensus):
+// svo_pnp_probe.hip - parity probes of RANSAC's stopping rule and consensus count (svo_debug_pnp_rule, svo_debug_pnp_consensus)
+// and of the 12 x 12 step loop of the order-preserving EPnP (svo_debug_jacobi12):
 // kernels that call the device functions of svo_pose_dev.h exactly as svo_pose.hip's and the tracker's kernels do, their launchers
 // and C entries.  A translation unit of its own: nothing the library runs outside the tests is compiled differently for it.
+#define EO_JACOBI12_STEPS 1      // jacobi_rows<12> of THIS translation unit leaves its step count in S.sweeps
 #include "svo_pose_dev.h"
 
 // Table mode: what the tracker tabulates per frame - pnp_update_terms(g, n) for every consensus g = 5 .. n -, the plain
@@ -65,6 +67,27 @@ __global__ __launch_bounds__(64) void k_pnp_consensus_probe(const double* __rest
   }
   cnt = wave_sum_i32_dpp(cnt);
   if (lane == 0) *count = cnt;
+}
+// The 12 x 12 step loop alone, ONE wave: the matrix goes into S.jr as solve5_wave's load_mtm leaves M^T M there (row b of At = row
+// b of S.jr, everything else zero), jacobi_rows<12> runs on it as in a RANSAC sample.  rows: the 12 rows of S.jr afterwards (16
+// doubles each: rotated, scaled by 1 / W, W in column 15); out_i: {steps, the step loop ran out of sweeps}.
+__global__ __launch_bounds__(64) void k_jacobi12_probe(const double* __restrict__ At, double* __restrict__ rows, int* __restrict__ out_i) {
+  __shared__ epnp_ord::Lds S;
+  const int lane = threadIdx.x, r16 = lane & 15;
+  for (int e = lane; e < 16 * 16; e += 64) S.jr[e] = 0.0;
+  if (lane == 0) { S.flag = 0; S.why = 0; S.sweeps = 0; }
+  epnp_ord::load_tables(S, lane);
+  EO_SYNC();
+  for (int e = lane; e < 144; e += 64) S.jr[(e / 12) * 16 + e % 12] = At[e];
+  EO_SYNC();
+  const unsigned long long ex = epnp_ord::jacobi_rows<12>(S, r16 < 12 ? 12 : 0, r16 < 12 ? 0 : r16, lane);
+  for (int e = lane; e < 12 * 16; e += 64) rows[e] = S.jr[e];
+  if (lane == 0) { out_i[0] = S.sweeps; out_i[1] = ex != 0 ? 1 : 0; }
+}
+static int svo_launch_jacobi12_probe(svo_ctx* ctx, const double* At, double* rows, int* out_i) {
+  hipLaunchKernelGGL(k_jacobi12_probe, dim3(1), dim3(64), 0, ctx->stream, At, rows, out_i);
+  SVO_HIP(ctx, hipGetLastError());
+  return SVO_OK;
 }
 static int svo_launch_pnp_rule_table(svo_ctx* ctx, int n, double* out_d, int* out_i) {
   hipLaunchKernelGGL(k_pnp_rule_table, dim3(1), dim3(64), 0, ctx->stream, n, out_d, out_i);
@@ -148,5 +171,21 @@ extern "C" int svo_debug_pnp_consensus(svo_ctx* ctx, const double* Xw, const dou
   if (rc) return rc;
   D2H(count, dCnt, 4); D2H(flags, dF, n);
   SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SVO_OK;
+}
+
+extern "C" int svo_debug_jacobi12(svo_ctx* ctx, const double At[144], double rows_out[12 * 16], int32_t* steps, int32_t* flag) {
+  if (!ctx || !At || !rows_out || !steps || !flag) return SVO_E_INVALID;
+  hipSetDevice(ctx->device);
+  Bump bm{ctx};
+  double* dA = bm.take<double>(144); double* dR = bm.take<double>(12 * 16); int* dI = bm.take<int>(2);
+  if (!bm.ok()) return SVO_E_CAPACITY;
+  H2D(dA, At, 8 * 144);
+  int rc = svo_launch_jacobi12_probe(ctx, dA, dR, dI);
+  if (rc) return rc;
+  int32_t hi[2] = {0, 0};
+  D2H(rows_out, dR, 8 * 12 * 16); D2H(hi, dI, 8);
+  SVO_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *steps = hi[0]; *flag = hi[1];
   return SVO_OK;
 }

@@ -20,8 +20,10 @@ Three layouts:
     with ONE backward branch.  Before the first step the block reads the lane's PER table entries of the period from LDS and
     turns them into two registers per slot (partner row's address; sign | relative sweep); VALID of a copy is a 16-bit constant
     of that copy & ACT; the sweep bookkeeping and the exit test are emitted only in the copy that closes a sweep (the period's
-    last), where the base bit U_BB is doubled.  No table read, no walk, no decode and no closing test per step.  pair_test,
-    decide, the rotation, the commit and the write-back are the same instruction sequences as in the table-driven layout.
+    last), where the base bit U_BB is doubled.  No table read, no walk, no decode and no closing test per step.  The commit and
+    the write-back are the same instruction sequences as in the table-driven layout; the sums, the decision and the rotation are
+    the same operations in an order that follows the step's dependent chain (pair_test12 / decide_rotate12 below).  The block
+    with pair_test, decide and rotation in the table-driven layout's order stays as EO_JACOBI_ASM_12_PREV (--prev; -DEO_JACOBI12_PREV).
 
   M = 3, rows in registers (program3r, EO_JACOBI_ASM_3R): three-row problems only - what every caller of jacobi_rows<3> passes.  Each
     lane holds columns g and 4 + g of all three rows of its problem, so a step needs no partner row from LDS: three copies of the
@@ -436,7 +438,105 @@ def decode12(u, t):
     ]
 
 
-def program12():
+# ---- M = 12: the step body rescheduled around its dependent chain ---------------------------------------------------------
+# A step is one dependent chain (sums -> decision -> two divisions and two square roots -> row update) and is bound by that chain,
+# not by issue - and the chain has no idle issue slots to speak of: every instruction woven into it cost its own issue time when
+# measured.  So the functions below emit the SAME floating-point operations on the same operands as pair_test / decide / rotation -
+# no operation on a committed value is added, removed, reordered within a sum or rounded differently - in an order that takes work
+# the chain does not need out of its way, WITHOUT adding instructions to the rotating path.  Three items (ITEMS12; each can be
+# left out for measurements: JACOBI12_ITEMS=, =1, =12 ...; figures in docs/NEXT_ROUNDS.md):
+#   1  the lane's own-row sum WW = sum x[k]^2 needs nothing from the partner: its three DMFMAs run in front of the wait for the
+#      partner's row, in the shadow of the LDS round trip, and six DMFMAs instead of nine follow the wait.
+#   2  2p, beta = WW - WP, the |2p| > |beta| select and the first reciprocal of the rotation need P, WW and WP only: they are
+#      issued speculatively between decide()'s instructions, and decide()'s scalar mask logic and both branches sit behind the
+#      reciprocal and its first refinement steps, whose latency they would otherwise wait out.  2p goes to a register of its own
+#      (P2X): the undecided path still reads |P|.  The select's lane mask is CL (free between two sweep closings), the exact
+#      threshold's nsqrt keeps Y / H / RR / D to itself (the prefix uses RCP / ERR / HI / LO / BETA / P2X).  Where no lane rotates
+#      the prefix is dropped; lanes outside ROT compute garbage (rcp(0), 0/0) that reaches no committed register: commit, chg and
+#      the write-back go by ROT as before.
+#   3  c and s are R1 and R2 or R2 and R1 by the sign of beta, which is known from the start: the compare takes the wait state
+#      behind the last division's reciprocal (an s_nop before) instead of standing, with two wait states of its own, between the
+#      division and the row update.
+ITEMS12 = frozenset(int(c) for c in os.environ.get("JACOBI12_ITEMS", "123"))
+P2X = CC                             # 2p of the speculative prefix (CC / SS are written behind the last division)
+
+
+def pair_test12(items):
+    if 1 not in items:
+        return pair_test(12, wait=0)
+    wa, wb, p = pair(WW), pair(WP), pair(P)
+    regs = ((T0, U0, V0, X0, Q0), (T1, U1, V1, X1, Q1), (T2, U2, V2, X2, P2))
+    out = ["v_mul_f64 %s, %s, %s" % (pair(u), pair(x), pair(x)) for t, u, w, x, y in regs]
+    out += [mfma(wa, pair(U0), "0"), "s_nop 3", mfma(wa, pair(U1), wa), "s_nop 3", mfma(wa, pair(U2), wa)]
+    out.append("s_waitcnt lgkmcnt(0)")             # the partner's row (requested at the end of the previous step)
+    for t, u, w, x, y in regs:
+        out += ["v_mul_f64 %s, %s, %s" % (pair(t), pair(x), pair(y)), "v_mul_f64 %s, %s, %s" % (pair(w), pair(y), pair(y))]
+    for q, (t, u, w, x, y) in enumerate(regs):
+        c = (lambda r: "0") if q == 0 else (lambda r: r)
+        if q:
+            out.append("s_nop 2")
+        out += [mfma(wb, pair(w), c(wb)), mfma(p, pair(t), c(p))]
+    out.append("s_nop 4")     # 6 wait states between a chain's last DMFMA and the VALU read of its sum (WP first, P two instructions on)
+    return out
+
+
+def decide_rotate12(tag, items):
+    """From the sums to the rotated row N0..N2 (rotating lanes: ROT; SCC clear at L_skip_<tag>: nobody rotates)."""
+    p2 = P2X if 2 in items else P
+    hi, lo = "|%s|" % pair(HI), "|%s|" % pair(LO)
+    nd1 = ndiv(pair(QQ), lo, hi)
+
+    def prefix(mask, e64):
+        cm = (lambda d, f, t_: "v_cndmask_b32_e64 %s, %s, %s, %s" % (v(d), v(f), v(t_), mask)) if e64 else \
+             (lambda d, f, t_: "v_cndmask_b32 %s, %s, %s, vcc" % (v(d), v(f), v(t_)))
+        return [
+            "v_add_f64 %s, %s, %s" % (pair(p2), pair(P), pair(P)),
+            "v_add_f64 %s, %s, -%s" % (pair(BETA), pair(WW), pair(WP)),
+            "v_xor_b32 %s, %s, %s" % (v(BETA + 1), v(BETA + 1), v(U_SGN)),
+            "v_cmp_gt_f64 %s, |%s|, |%s|" % (mask, pair(p2), pair(BETA)),
+        ], [cm(HI, BETA, p2), cm(HI + 1, BETA + 1, p2 + 1), cm(LO, p2, BETA), cm(LO + 1, p2 + 1, BETA + 1)]
+
+    if 2 in items:
+        (a2p, abeta, axor, acmp), sel = prefix(CL, True)
+        d = decide(tag)
+        k = d.index("s_cbranch_scc0 L_decided_%s%%=" % tag)
+        dm, dcmp1, dcmp2, dsor, dsandn = d[0:4], d[4], d[5], d[6], d[7]
+        assert k == 8 and d[-1].startswith("s_and_b64 %s" % ROT)
+        o = [abeta, dm[0], a2p, dm[1], axor, dm[2], acmp, dm[3], dcmp1, dcmp2] + sel
+        # (the two scalar instructions are the wait state behind the reciprocal)
+        o += [nd1[0], dsor, dsandn, nd1[2], d[k]] + d[k + 1:-1] + [d[-1], nd1[3], "s_cbranch_scc0 L_skip_%s%%=" % tag] + nd1[4:]
+    else:
+        (a2p, abeta, axor, acmp), sel = prefix("vcc", False)
+        o = decide(tag) + ["s_cbranch_scc0 L_skip_%s%%=" % tag, a2p, abeta, axor, acmp, "s_nop 1"] + sel + nd1
+    o += ["v_mul_f64 %s, %s, %s" % (pair(TA), pair(QQ), pair(QQ)), "v_add_f64 %s, %s, 1.0" % (pair(TA), pair(TA))]
+    o += nsqrt(pair(TB), pair(TA))
+    o += ["v_mul_f64 %s, %s, %s" % (pair(GAM), hi, pair(TB)),
+          "v_add_f64 %s, %s, |%s|" % (pair(TA), pair(GAM), pair(BETA)),
+          "v_add_f64 %s, %s, %s" % (pair(TC), pair(GAM), pair(GAM))]
+    o += ndiv(pair(QQ), pair(TA), pair(TC))
+    o += nsqrt(pair(R1), pair(QQ))
+    o += ["v_mul_f64 %s, %s, %s" % (pair(TA), pair(GAM), pair(R1)), "v_add_f64 %s, %s, %s" % (pair(TA), pair(TA), pair(TA))]
+    last = ndiv(pair(R2), pair(p2), pair(TA))
+    sign = "v_cmp_gt_f64 vcc, 0, %s" % pair(BETA)
+    if 3 in items:
+        assert last[1] == "s_nop 0"
+        last[1] = sign
+        o += last
+    else:
+        o += last + [sign, "s_nop 1"]
+    o += ["v_cndmask_b32 %s, %s, %s, vcc" % (v(SS), v(R2), v(R1)), "v_cndmask_b32 %s, %s, %s, vcc" % (v(SS + 1), v(R2 + 1), v(R1 + 1)),
+          "v_cndmask_b32 %s, %s, %s, vcc" % (v(CC), v(R1), v(R2)), "v_cndmask_b32 %s, %s, %s, vcc" % (v(CC + 1), v(R1 + 1), v(R2 + 1)),
+          "v_xor_b32 %s, %s, %s" % (v(SS + 1), v(SS + 1), v(U_SGN))]
+    rows = ((N0, X0, Q0, T0), (N1, X1, Q1, T1), (N2, X2, P2, T2))
+    for n_, x_, q_, t_ in rows:
+        o += ["v_mul_f64 %s, %s, %s" % (pair(n_), pair(CC), pair(x_)), "v_mul_f64 %s, %s, %s" % (pair(t_), pair(SS), pair(q_))]
+    o += ["v_add_f64 %s, %s, %s" % (pair(n_), pair(n_), pair(t_)) for n_, x_, q_, t_ in rows]
+    return o
+
+
+def program12(prev=False, items=None):
+    """prev: the block as it was before the step body was rescheduled (EO_JACOBI_ASM_12_PREV, built with -DEO_JACOBI12_PREV)."""
+    items = ITEMS12 if items is None else frozenset(items)
     u = Unrolled()
     u.check()
     o = []
@@ -474,11 +574,16 @@ def program12():
             for _ in range(LOOP_NOPS):
                 a("s_nop 0")
             a("L_loop_%=:")
-        o += pair_test(12, wait=0)
-        o += decide("%d_" % t)
-        a("s_cbranch_scc0 L_skip_%d_%%=" % t)
-        a("v_and_b32 %s, 0x80000000, %s" % (v(U_SGN), v(k)))
-        o += rotation(U_SGN)
+        if prev:
+            o += pair_test(12, wait=0)
+            o += decide("%d_" % t)
+            a("s_cbranch_scc0 L_skip_%d_%%=" % t)
+            a("v_and_b32 %s, 0x80000000, %s" % (v(U_SGN), v(k)))
+            o += rotation(U_SGN)
+        else:
+            a("v_and_b32 %s, 0x80000000, %s" % (v(U_SGN), v(k)))
+            o += pair_test12(items)
+            o += decide_rotate12("%d_" % t, items)
         o += commit()
         if t >= u.pro:
             a("v_lshlrev_b32 %s, %s, %s" % (v(U_TMP), v(k), v(U_BB)))      # 1 << (base + the pair's relative sweep)
@@ -614,25 +719,30 @@ def program3r():
     return [l.replace('%%[', '%[') for l in o]
 
 
-def main():
-    print("// generated by tools/gen_jacobi_asm.py - do not edit")
-    print("// The step loop of jacobi_rows (svo_epnp_ord_dev.h) for M = 12, 6, 3 columns of A, and for M = 3 with the rows in registers (3R); registers v140..v255, s60..s71.")
-    for M in (12, 6, 3):
-        lines = program12() if M == 12 else program(M)
-        print("#define EO_JACOBI_ASM_%d \\" % M)
-        for i, l in enumerate(lines):
-            end = " \\" if i + 1 < len(lines) else ""
-            print('  "%s\\n\\t"%s' % (l, end))
-        print("")
-    lines = program3r()
-    print("#define EO_JACOBI_ASM_3R \\")
+def emit(name, lines):
+    print("#define EO_JACOBI_ASM_%s \\" % name)
     for i, l in enumerate(lines):
         end = " \\" if i + 1 < len(lines) else ""
         print('  "%s\\n\\t"%s' % (l, end))
     print("")
+
+
+def main(prev=False):
+    """The committed header; prev: csrc/svo_epnp_ord_asm_prev.h instead - the former M = 12 block alone, under the name
+    EO_JACOBI_ASM_12_PREV (a build product: tools/Makefile writes it for the -DEO_JACOBI12_PREV builds)."""
+    print("// generated by tools/gen_jacobi_asm.py - do not edit")
+    if prev:
+        print("// The M = 12 step loop of jacobi_rows with the step body in its former instruction order (-DEO_JACOBI12_PREV).")
+        emit("12_PREV", program12(prev=True))
+        return
+    print("// The step loop of jacobi_rows (svo_epnp_ord_dev.h) for M = 12, 6, 3 columns of A, and for M = 3 with the rows in registers (3R); registers v140..v255, s60..s71.")
+    for M in (12, 6, 3):
+        emit(str(M), program12() if M == 12 else program(M))
+    emit("3R", program3r())
     clob = ", ".join('"v%d"' % i for i in range(140, 256)) + ", " + ", ".join('"s%d"' % i for i in range(60, 72)) + ', "vcc", "scc", "memory"'
     print("#define EO_JACOBI_ASM_CLOBBERS " + clob)
 
 
 if __name__ == "__main__":
-    main()
+    import sys
+    main(prev="--prev" in sys.argv[1:])
