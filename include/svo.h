@@ -429,9 +429,9 @@ int svo_debug_epnp_gn(svo_ctx* ctx, const double L[60], const double rho[6], con
  * [2^-100, 2^100] - inside that range the rows are JacobiSVDImpl_'s bit for bit. */
 int svo_debug_jacobi12(svo_ctx* ctx, const double At[144], double rows_out[12 * 16], int32_t* steps, int32_t* flag);
 
-/* Parity probe of RANSACPointSetRegistrator::run's sequential rule - which sample wins, how many are visited - in every copy
- * the library holds of it: the plain rule of svo_pnp_ransac and the tracker's variants that work from precomputed pow / log
- * terms, on the first m samples only, or report the iteration bound after m samples.  Two modes:
+/* Parity probe of RANSACPointSetRegistrator::run's sequential rule - which sample wins, how many are visited - in every form
+ * the library runs its one walker in: the plain rule of svo_pnp_ransac and the tracker's variants that work from precomputed pow /
+ * log terms, on the first m samples only, or report the iteration bound after m samples.  Two modes:
  *   SVO_PNP_RULE_TABLE  count = the number of points n (5 .. 512); cnt, ok, n unused (NULL).  For every consensus g = 5 .. n:
  *                       out_f64[g] = log(1 - (g / n)^5) as tabulated per frame (1.0: "denominator below DBL_MIN", the bound is 0),
  *                       out_i32[g] = rint(log(0.01) / that), out_i32[n + 1 + g] = RANSACUpdateNumIters(0.99, (n - g) / n, 5, 100);

@@ -421,7 +421,7 @@ class Svo:
         return d[:n + 1].copy(), i[:n + 1].copy(), i[n + 1:].copy(), float(d[n + 1])
 
     def debug_pnp_rule(self, cnt, ok, n):
-        """svo_debug_pnp_rule, rule mode: cnt / ok B x 100, n B -> dict of the copies' results (see include/svo.h); per_m: B x 101 x 5
+        """svo_debug_pnp_rule, rule mode: cnt / ok B x 100, n B -> dict of the instantiations' results (see include/svo.h); per_m: B x 101 x 5
         {pre_bound, pre_early, early best, early good, bound_after}."""
         cnt = np.ascontiguousarray(cnt, np.int32).reshape(-1, 100); ok = np.ascontiguousarray(ok, np.int32).reshape(-1, 100)
         n = np.ascontiguousarray(n, np.int32).reshape(-1)

@@ -6,7 +6,7 @@
 #include "svo_pose_dev.h"
 
 // Table mode: what the tracker tabulates per frame - pnp_update_terms(g, n) for every consensus g = 5 .. n -, the plain
-// pnp_update_iters(ep, 100) beside it, and log(0.01) as the rule's copies spell it.  out_d[g] = ld (g = 0 .. n; 0 below 5),
+// pnp_update_iters(ep, 100) beside it, and log(0.01) as the rule spells it (pnp_log_1mp).  out_d[g] = ld (g = 0 .. n; 0 below 5),
 // out_d[n + 1] = log(0.01); out_i[g] = r, out_i[n + 1 + g] = pnp_update_iters.
 __global__ __launch_bounds__(64) void k_pnp_rule_table(int n, double* out_d, int* out_i) {
   for (int g = threadIdx.x; g <= n; g += 64) {
@@ -17,12 +17,13 @@ __global__ __launch_bounds__(64) void k_pnp_rule_table(int n, double* out_d, int
     }
     out_d[g] = ld; out_i[g] = r; out_i[n + 1 + g] = it;
   }
-  if (threadIdx.x == 0) out_d[n + 1] = log(fmax(1. - 0.99, 2.2250738585072014e-308));
+  if (threadIdx.x == 0) out_d[n + 1] = pnp_log_1mp();
 }
-// Rule mode: one thread per case (cnt[100], ok[100], n): every copy of the sequential rule on the same samples.  Per case
-// SVO_PNP_RULE_W ints: pnp_select's {best, good, iters}; pnp_select_pre's, with the terms made per sample as the tracker's tail
-// makes them; then for m = 0 .. 100 {pnp_select_pre_bound, pnp_select_pre_early, its best, its good (-2: not written),
-// pnp_bound_after}.
+// Rule mode: one thread per case (cnt[100], ok[100], n): every instantiation of the one walker (pnp_walk) on the same samples.  Per
+// case SVO_PNP_RULE_W ints: pnp_select's {best, good, iters}; pnp_select_pre's, with the terms made per sample as the tracker's tail
+// makes them; then for m = 0 .. 100 the walk over the prepared terms cut at m, as the fused tail runs it with m = TP_EARLY -
+// {visited, visited again (the column a separate copy of the loop once filled), best, good (-2: cut, nothing decided)} - and
+// pnp_bound_after(m).
 __global__ __launch_bounds__(64) void k_pnp_rule_cases(const int* __restrict__ cnt_all, const int* __restrict__ ok_all,
                                                        const int* __restrict__ n_all, int ncases, int* out_all) {
   const int c = blockIdx.x * 64 + threadIdx.x;
@@ -42,15 +43,15 @@ __global__ __launch_bounds__(64) void k_pnp_rule_cases(const int* __restrict__ c
   out[3] = pnp_select_pre(cnt, ok, ld, r, n, &good, &iters); out[4] = good; out[5] = iters;
   for (int m = 0; m <= PNP_HYP; ++m) {
     int* o = out + 6 + 5 * m;
-    int best = -2; good = -2;
-    o[0] = pnp_select_pre_bound(cnt, ok, ld, r, n, m);
-    o[1] = pnp_select_pre_early(cnt, ok, ld, r, n, m, &best, &good);
-    o[2] = best; o[3] = good;
+    const PnpWalk w = pnp_walk<true>(cnt, ok, ld, r, n, m);
+    const bool ended = w.visited <= m;
+    o[0] = w.visited; o[1] = w.visited;
+    o[2] = ended ? w.best : -2; o[3] = ended ? w.good : -2;
     o[4] = pnp_bound_after(cnt, ok, n, m);
   }
 }
-// The consensus of one model over n points by ONE wave, as the three pnp_hyp_* kernels count it: lane l takes the points
-// l, l + 64, ..., pnp_inlier on each, wave_sum_i32_dpp over the lanes.  Rt: R row-major, then t.
+// The consensus of one model over n points by ONE wave: pnp_consensus_wave, the function the three pnp_hyp_* kernels count with,
+// here with its per-point flags.  Rt: R row-major, then t.
 __global__ __launch_bounds__(64) void k_pnp_consensus_probe(const double* __restrict__ Xw, const double* __restrict__ uv, int n,
                                                             const double* __restrict__ Kp, const double* __restrict__ Rt,
                                                             int* count, uint8_t* flags) {
@@ -59,13 +60,7 @@ __global__ __launch_bounds__(64) void k_pnp_consensus_probe(const double* __rest
   double R[9], t[3];
   for (int i = 0; i < 9; ++i) R[i] = Rt[i];
   for (int i = 0; i < 3; ++i) t[i] = Rt[9 + i];
-  int cnt = 0;
-  for (int e = lane; e < n; e += 64) {
-    const int in = pnp_inlier(R, t, Xw + 3 * e, uv + 2 * e, K) ? 1 : 0;
-    flags[e] = (uint8_t)in;
-    cnt += in;
-  }
-  cnt = wave_sum_i32_dpp(cnt);
+  const int cnt = pnp_consensus_wave(R, t, Xw, uv, n, K, flags);
   if (lane == 0) *count = cnt;
 }
 // The 12 x 12 step loop alone, ONE wave: the matrix goes into S.jr as solve5_wave's load_mtm leaves M^T M there (row b of At = row

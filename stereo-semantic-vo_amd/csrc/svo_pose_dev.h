@@ -4,9 +4,13 @@
 //   pose_opt_block   <- Optimizer::PoseOptimization (reference src/Optimizer.cc:15-86) as g2o executes it: one SE3
 //                       vertex, n unary reprojection edges, Huber delta=(double)(float)sqrt(5.991), Levenberg-
 //                       Marquardt x10 (Thirdparty/g2o/g2o/core/optimization_algorithm_levenberg.cpp:61-164).
-//   pnp_ransac_block <- the cv::solvePnPRansac call of pnpmatch::poseEstimationPnP (src/pnpmatch.cc:212-247).
+//   pnp_hyp_* / pnp_walk <- the cv::solvePnPRansac call of pnpmatch::poseEstimationPnP (src/pnpmatch.cc:212-247), each piece
+//                       stated once: a sample's solve in its three modes (pnp_hyp_block, pnp_hyp_exact_wave, pnp_hyp_ord_wave)
+//                       with ONE tail - pnp_consensus_wave, pnp_hyp_store -, and RANSACPointSetRegistrator::run's rule as ONE
+//                       walker, pnp_walk<PREPARED>(.., m), behind pnp_select, pnp_select_pre, pnp_bound_after and the fused
+//                       tail's early decision.
 //
-// Both are called by ALL 256 threads of a workgroup (they contain barriers).  Per-edge residuals / Jacobians live in
+// pose_opt_block is called by ALL 256 threads of a workgroup (it contains barriers).  Per-edge residuals / Jacobians live in
 // registers; the 6x6 J^T W J, J^T W e and chi2 are reduced on f64 MFMA (or wave shuffles + one LDS hop); lane 0 runs
 // the scalar LM logic (LDLT, exp map, lambda schedule) so every accept/reject branch is taken in float64 exactly once.
 #pragma once
@@ -707,6 +711,43 @@ __device__ __forceinline__ bool pnp_inlier(const double* R, const double* t, con
   return err <= 64.0f;
 }
 
+// A sample's consensus, counted by ONE wave (all 64 lanes call): lane l takes the points l, l + 64, ..., pnp_inlier on each, the
+// lanes' counts summed.  A failed sample is passed n = 0.  flags (the probe svo_debug_pnp_consensus only): one byte per point.
+__device__ __forceinline__ int pnp_consensus_wave(const double* R, const double* t, const double* Xw, const double* uv, int n,
+                                                  const double* K, uint8_t* flags = nullptr) {
+  int cnt = 0;
+  for (int e = threadIdx.x & 63; e < n; e += 64) {
+    const int in = pnp_inlier(R, t, Xw + 3 * e, uv + 2 * e, K) ? 1 : 0;
+    if (flags) flags[e] = (uint8_t)in;
+    cnt += in;
+  }
+  return wave_sum_i32_dpp(cnt);
+}
+// ... and its record out[k], stored by lane 0.  AGENT_OUT: the result is read by ANOTHER workgroup of the same launch - stored with
+// agent-scope (sc1) stores in the order R, t, cnt, ok, which reach the device-coherent level by themselves (no release fence: see
+// tp_wait_work in svo_track.hip).  word: ok << 31 | consensus, for the caller's announcement.
+template <bool AGENT_OUT>
+__device__ __forceinline__ void pnp_hyp_store(PnpHyp* out, int k, const double* R, const double* t, int cnt, bool ok, unsigned* word = nullptr) {
+  if ((threadIdx.x & 63) != 0) return;
+  if (word) *word = (ok ? 0x80000000u : 0u) | (unsigned)cnt;
+  if (AGENT_OUT) {
+    PnpHyp* o = out + k;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) __hip_atomic_store(reinterpret_cast<long long*>(&o->R[i]), __builtin_bit_cast(long long, R[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) __hip_atomic_store(reinterpret_cast<long long*>(&o->t[i]), __builtin_bit_cast(long long, t[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&o->cnt, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&o->ok, ok ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    PnpHyp h;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) h.R[i] = R[i];
+    h.t[0] = t[0]; h.t[1] = t[1]; h.t[2] = t[2];
+    h.cnt = cnt; h.ok = ok ? 1 : 0;
+    out[k] = h;
+  }
+}
+
 // Hypotheses hyp_base .. hyp_base + (waves of the block) - 1, one wave each.  Xw / uv: the n correspondences in LDS (or
 // anywhere), subset: the 100 x 5 sample indices cv::RNG((uint64)-1) yields for this n (svo_pnp_subsets).
 __device__ __forceinline__ void pnp_hyp_block(EpnpWaveLds* ws, const double* Xw, const double* uv, int n, const double* K,
@@ -721,18 +762,7 @@ __device__ __forceinline__ void pnp_hyp_block(EpnpWaveLds* ws, const double* Xw,
   }
   double R[9], t[3];
   const bool ok = epnp5_wave(ws[wv], K, R, t);
-  int cnt = 0;
-  if (ok)
-    for (int e = lane; e < n; e += 64) cnt += pnp_inlier(R, t, Xw + 3 * e, uv + 2 * e, K) ? 1 : 0;
-  cnt = wave_sum_i32_dpp(cnt);
-  if (lane == 0) {
-    PnpHyp h;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) h.R[i] = R[i];
-    h.t[0] = t[0]; h.t[1] = t[1]; h.t[2] = t[2];
-    h.cnt = cnt; h.ok = ok ? 1 : 0;
-    out[k] = h;
-  }
+  pnp_hyp_store<false>(out, k, R, t, pnp_consensus_wave(R, t, Xw, uv, ok ? n : 0, K), ok);
 }
 
 // The same samples in the parity mode (svo_set_option "epnp_exact"): ONE sample per wave - lane 0 walks the sequential
@@ -761,26 +791,14 @@ __device__ __forceinline__ void pnp_hyp_exact_wave(PnpExactLds& S, const double*
 #pragma unroll
   for (int i = 0; i < 3; ++i) t[i] = S.t[i];
   const bool ok = S.ok != 0;
-  int cnt = 0;
-  if (ok)
-    for (int e = lane; e < n; e += 64) cnt += pnp_inlier(R, t, Xw + 3 * e, uv + 2 * e, K) ? 1 : 0;
-  cnt = wave_sum_i32_dpp(cnt);
-  if (lane == 0) {
-    PnpHyp h;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) h.R[i] = R[i];
-    h.t[0] = t[0]; h.t[1] = t[1]; h.t[2] = t[2];
-    h.cnt = cnt; h.ok = ok ? 1 : 0;
-    out[k] = h;
-  }
+  pnp_hyp_store<false>(out, k, R, t, pnp_consensus_wave(R, t, Xw, uv, ok ? n : 0, K), ok);
 }
 
 // The same samples in the order-preserving wave mode (svo_set_option "epnp_exact" = 2, the default): ONE sample per wave,
 // OpenCV's operations spread over the wavefront with their rounding kept (svo_epnp_ord_dev.h), bit-identical to the
 // sequential restatement; then the wave counts the sample's consensus.  Called by all 64 lanes of the wave that owns sample k.
 struct PnpOrdLds { epnp_ord::Lds S; epnp_exact::Work W; };
-// AGENT_OUT: the result is read by ANOTHER workgroup of the same launch - stored with agent-scope (sc1) stores, which reach the
-// device-coherent level by themselves (no release fence: see tp_wait_work in svo_track.hip).
+// AGENT_OUT: see pnp_hyp_store.
 template <bool AGENT_OUT = false>
 __device__ __forceinline__ void pnp_hyp_ord_wave(PnpOrdLds& L, const double* Xw, const double* uv, int n, const double* K,
                                                  const uint16_t* subset, PnpHyp* out, int k, bool force_seq = false,
@@ -794,54 +812,20 @@ __device__ __forceinline__ void pnp_hyp_ord_wave(PnpOrdLds& L, const double* Xw,
   }
   double R[9], t[3];
   const bool ok = epnp_ord::solve5_wave(L.S, L.W, K, R, t, nullptr, force_seq);
-  int cnt = 0;
-  if (ok)
-    for (int e = lane; e < n; e += 64) cnt += pnp_inlier(R, t, Xw + 3 * e, uv + 2 * e, K) ? 1 : 0;
-  cnt = wave_sum_i32_dpp(cnt);
-  if (lane == 0) {
-    if (word) *word = (ok ? 0x80000000u : 0u) | (unsigned)cnt;
-    if (AGENT_OUT) {
-      PnpHyp* o = out + k;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) __hip_atomic_store(reinterpret_cast<long long*>(&o->R[i]), __builtin_bit_cast(long long, R[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) __hip_atomic_store(reinterpret_cast<long long*>(&o->t[i]), __builtin_bit_cast(long long, t[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&o->cnt, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&o->ok, ok ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      PnpHyp h;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) h.R[i] = R[i];
-      h.t[0] = t[0]; h.t[1] = t[1]; h.t[2] = t[2];
-      h.cnt = cnt; h.ok = ok ? 1 : 0;
-      out[k] = h;
-    }
-  }
+  pnp_hyp_store<AGENT_OUT>(out, k, R, t, pnp_consensus_wave(R, t, Xw, uv, ok ? n : 0, K), ok, word);
 }
+
+// log(1 - p) of RANSACUpdateNumIters, p = 0.99 (1 - 0.99 is not 0.01 to the last bit)
+__device__ __forceinline__ double pnp_log_1mp() { return log(fmax(1. - 0.99, 2.2250738585072014e-308)); }
 
 // RANSACUpdateNumIters(p = 0.99, ep, modelPoints = 5, maxIters)
 __device__ __forceinline__ int pnp_update_iters(double ep, int maxIters) {
-  const double p = 0.99;
   ep = fmax(ep, 0.); ep = fmin(ep, 1.);
-  double num = fmax(1. - p, 2.2250738585072014e-308);
   double denom = 1. - pow(1. - ep, 5.0);
   if (denom < 2.2250738585072014e-308) return 0;
-  num = log(num);
+  const double num = pnp_log_1mp();
   denom = log(denom);
   return denom >= 0 || -num >= maxIters * (-denom) ? maxIters : (int)rint(num / denom);
-}
-
-// The iteration bound of RANSACPointSetRegistrator::run after its first m samples: samples at or beyond it can never be
-// visited (the bound only shrinks), so they need not be solved.
-__device__ __forceinline__ int pnp_bound_after(const int* cnt, const int* ok, int n, int m) {
-  int niters = PNP_HYP, maxGood = 0;
-  if (n == 5) return 1;
-  for (int iter = 0; iter < m && iter < niters; ++iter) {
-    if (!ok[iter]) continue;
-    const int g = cnt[iter];
-    if (g > max(maxGood, 4)) { maxGood = g; niters = pnp_update_iters((double)(n - g) / n, niters); }
-  }
-  return niters;
 }
 
 // pnp_update_iters's transcendental part for a sample with consensus g of n, computed by the sample's own thread ahead of the
@@ -852,98 +836,62 @@ __device__ __forceinline__ void pnp_update_terms(int g, int n, double* ld, int* 
   ep = fmax(ep, 0.); ep = fmin(ep, 1.);
   const double denom = 1. - pow(1. - ep, 5.0);
   if (denom < 2.2250738585072014e-308) { *ld = 1.0; *r = 0; return; }
-  const double num = log(fmax(1. - 0.99, 2.2250738585072014e-308));
+  const double num = pnp_log_1mp();
   *ld = log(denom);
   *r = *ld < 0 ? (int)rint(num / *ld) : 0;
 }
-// the sequential rule with those terms at hand (same decisions as pnp_select)
-__device__ __forceinline__ int pnp_select_pre(const int* cnt, const int* ok, const double* ld, const int* r, int n, int* good, int* iters) {
-  int niters = PNP_HYP, maxGood = 0, best = -1, run = 0;
-  if (n == 5) {
-    *good = ok[0] ? 5 : 0; *iters = 1;
-    return ok[0] ? 0 : -1;
-  }
-  const double num = log(fmax(1. - 0.99, 2.2250738585072014e-308));
-  for (int iter = 0; iter < niters; ++iter) {
-    ++run;
-    if (!ok[iter]) continue;
-    const int g = cnt[iter];
-    if (g > max(maxGood, 4)) {
-      maxGood = g; best = iter;
-      const double d = ld[iter];
-      if (d == 1.0) niters = 0;
-      else niters = d >= 0 || -num >= niters * (-d) ? niters : r[iter];
-    }
-  }
-  *good = maxGood; *iters = run;
-  return best;
-}
 
-// The same loop over the first m samples only: the number of samples the rule visits if it ends within them (<= m), or m + 1 if
-// it would go on - then nothing is decided yet.
-__device__ __forceinline__ int pnp_select_pre_bound(const int* cnt, const int* ok, const double* ld, const int* r, int n, int m) {
-  int niters = PNP_HYP, maxGood = 0;
-  if (n == 5) return 1;
-  const double num = log(fmax(1. - 0.99, 2.2250738585072014e-308));
-  int iter = 0;
-  for (; iter < niters; ++iter) {
-    if (iter >= m) return m + 1;
-    if (!ok[iter]) continue;
-    const int g = cnt[iter];
-    if (g > max(maxGood, 4)) {
-      maxGood = g;
-      const double d = ld[iter];
-      if (d == 1.0) niters = 0;
-      else niters = d >= 0 || -num >= niters * (-d) ? niters : r[iter];
-    }
-  }
-  return iter;   // = samples visited (niters = 0 leaves after the sample that set it)
-}
-
-// pnp_select_pre_bound and pnp_select_pre in ONE walk over the first m samples: returns what pnp_select_pre_bound returns; if that
-// is <= m - the rule ended within them - it is also pnp_select_pre's *iters, and *best / *good are its winner and consensus.
-__device__ __forceinline__ int pnp_select_pre_early(const int* cnt, const int* ok, const double* ld, const int* r, int n, int m,
-                                                    int* best_out, int* good) {
-  int niters = PNP_HYP, maxGood = 0, best = -1;
-  if (n == 5) {
-    *good = ok[0] ? 5 : 0; *best_out = ok[0] ? 0 : -1;
-    return 1;
-  }
-  const double num = log(fmax(1. - 0.99, 2.2250738585072014e-308));
-  int iter = 0;
-  for (; iter < niters; ++iter) {
-    if (iter >= m) return m + 1;
-    if (!ok[iter]) continue;
-    const int g = cnt[iter];
-    if (g > max(maxGood, 4)) {
-      maxGood = g; best = iter;
-      const double d = ld[iter];
-      if (d == 1.0) niters = 0;
-      else niters = d >= 0 || -num >= niters * (-d) ? niters : r[iter];
-    }
-  }
-  *good = maxGood; *best_out = best;
-  return iter;
-}
-
-// RANSACPointSetRegistrator::run over the precomputed samples (one thread): sample `iter` replaces the best one iff its
-// consensus is larger (and > 4), and the iteration bound shrinks with the inlier ratio.  Returns the winning sample
-// (-1: none), *good its consensus, *iters the samples visited.
-__device__ __forceinline__ int pnp_select(const int* cnt, const int* ok, int n, int* good, int* iters) {
-  int niters = PNP_HYP, maxGood = 0, best = -1, run = 0;
+// RANSACPointSetRegistrator::run over the precomputed samples (one thread), the ONE statement of the rule: sample `iter` replaces
+// the best one iff its consensus is larger (and > 4), and the iteration bound shrinks with the inlier ratio.
+//   PREPARED  the bound comes from the terms pnp_update_terms made for each sample (ld, r; ld == 1.0: the bound becomes 0) instead of
+//             pnp_update_iters (ld, r unused then) - the same decisions;
+//   m         the walk is cut in front of sample m (PNP_HYP: no cut).
+// Returns  visited  the samples the rule visits if it ends within the first m (<= m; a bound of 0 leaves after the sample that set
+//                   it), or m + 1 if it would go on - nothing is decided then, best / good are not filled in;
+//          best     the winning sample (-1: none), good its consensus;
+//          niters   the iteration bound where the walk stopped: samples at or beyond it can never be visited (the bound only
+//                   shrinks), so they need not be solved.
+struct PnpWalk { int visited, best, good, niters; };
+template <bool PREPARED>
+__device__ __forceinline__ PnpWalk pnp_walk(const int* cnt, const int* ok, const double* ld, const int* r, int n, int m) {
+  PnpWalk w = {1, -1, 0, PNP_HYP};
   if (n == 5) {   // count == modelPoints: the one model, every point an inlier
-    *good = ok[0] ? 5 : 0; *iters = 1;
-    return ok[0] ? 0 : -1;
+    w.best = ok[0] ? 0 : -1; w.good = ok[0] ? 5 : 0; w.niters = 1;
+    return w;
   }
-  for (int iter = 0; iter < niters; ++iter) {
-    ++run;
+  const double num = pnp_log_1mp();
+  int maxGood = 0, best = -1, iter = 0;
+  for (; iter < w.niters; ++iter) {
+    if (iter >= m) { w.visited = m + 1; return w; }
     if (!ok[iter]) continue;
     const int g = cnt[iter];
     if (g > max(maxGood, 4)) {
       maxGood = g; best = iter;
-      niters = pnp_update_iters((double)(n - g) / n, niters);
+      if (!PREPARED) {
+        w.niters = pnp_update_iters((double)(n - g) / n, w.niters);
+      } else {
+        const double d = ld[iter];
+        if (d == 1.0) w.niters = 0;
+        else w.niters = d >= 0 || -num >= w.niters * (-d) ? w.niters : r[iter];
+      }
     }
   }
-  *good = maxGood; *iters = run;
-  return best;
+  w.visited = iter; w.best = best; w.good = maxGood;
+  return w;
+}
+// the whole rule: svo_pnp_ransac's (pnp_select) and the tracker's, with the terms at hand (pnp_select_pre).  Returns the winning
+// sample, *good its consensus, *iters the samples visited.
+__device__ __forceinline__ int pnp_select(const int* cnt, const int* ok, int n, int* good, int* iters) {
+  const PnpWalk w = pnp_walk<false>(cnt, ok, nullptr, nullptr, n, PNP_HYP);
+  *good = w.good; *iters = w.visited;
+  return w.best;
+}
+__device__ __forceinline__ int pnp_select_pre(const int* cnt, const int* ok, const double* ld, const int* r, int n, int* good, int* iters) {
+  const PnpWalk w = pnp_walk<true>(cnt, ok, ld, r, n, PNP_HYP);
+  *good = w.good; *iters = w.visited;
+  return w.best;
+}
+// the iteration bound after the first m samples
+__device__ __forceinline__ int pnp_bound_after(const int* cnt, const int* ok, int n, int m) {
+  return pnp_walk<false>(cnt, ok, nullptr, nullptr, n, m).niters;
 }

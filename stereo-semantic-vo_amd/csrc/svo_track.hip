@@ -40,7 +40,11 @@
 // (src/pnpmatch.cc:302-337): two more launches in front of the index chain of a frame that carries boxes - k_tg_bf
 // (nearest last-frame descriptor of every keypoint) and k_tg_fmat (one wave: match filter, Hartley normalisation, normal
 // matrix, wave-parallel Jacobi, rank-2 projection; svo_fmat_dev.h).  Boxes arrive as HBM arrays in every mode
-// (svo_boxes_dev), nothing of a gated frame touches the host.
+// (svo_boxes_dev), nothing of a gated frame touches the host.  Each step is ONE body (tg_bf_body, tg_fmat_body) behind two
+// entries: per frame from the tracker state, or for a group of frames from the front-end rows (k_tg_bf_group, k_tg_fmat_group).
+// The sample kernels of the pose chain (k_tp_hyp, k_tp_hyp_exact, the k_tp_hyp_ord family) likewise share ONE gather of the
+// frame's correspondences (tp_gather_corr) and ONE replay of RANSAC's iteration bound over earlier samples (tp_bound_replay);
+// the frame part's gather also places frame 0's points and stages the LM's first chunk, and stays its own.
 //
 // This unit holds the kernels of both chains, their resources, tail_enqueue and the resets.  The entry points
 // (svo_track_entries.hip, svo_track_shard.hip), the two attachments (svo_track_dyn.hip, svo_track_map.hip) and the probes
@@ -707,20 +711,29 @@ __global__ __launch_bounds__(1024) void k_ti_resolve(TrackState* st, TrackWork* 
 // ================================================================================================
 // Semantic gating, in front of the index chain of a frame that carries detection boxes
 // ================================================================================================
+// Two steps, each ONE body with two entries that differ only in where "the last frame" comes from and where the result goes:
+//   k_tg_bf / k_tg_fmat              per frame, blockIdx.y = sequence: the last frame is in the tracker state (last_desc, last_xy,
+//                                    lastN), the result goes there too (bf_idx, bf_dist, F); nothing to do on a sequence's first frame;
+//   k_tg_bf_group / k_tg_fmat_group  a GROUP of consecutive frames of one sequence in one launch each, ahead of the index chain,
+//                                    blockIdx.y = frame of the group: the brute-force matches and F of frame f need nothing but the
+//                                    front-end results of frames f - 1 and f and frame f's boxes - no tracker state - so the 11 + 42 us
+//                                    they cost per gated frame leave the index chain (which they had made longer than the pose chain:
+//                                    122 against 117 us per frame in configs[4]).  The pointers address the group's first frame, row
+//                                    -1 is its predecessor: the group's first frame must not be the sequence's first (the caller
+//                                    starts groups at frame >= 1 of a call; frame 0 of a call keeps k_tg_bf / k_tg_fmat).  Results
+//                                    per frame in a GatePre record.
+//
 // pnpmatch::find_feature_matches (src/pnpmatch.cc:253-300): cv BruteForce-Hamming match(desc_cur, desc_last) - for every
 // keypoint of the current frame the nearest descriptor of the last frame (first minimum).  One wave per current keypoint,
-// the last frame's descriptors transposed in LDS as in k_ti_lists.  blockIdx.y = sequence.
-__global__ __launch_bounds__(256) void k_tg_bf(TrackState* st, const uint32_t* desc, const int32_t* nkp_p, int kstride,
-                                               const int32_t* nboxes) {
+// the last frame's descriptors transposed in LDS (td) as in k_ti_lists.
+__device__ __forceinline__ void tg_bf_body(const uint32_t* last_desc, int lastN, const uint32_t* cur_desc, int nkp,
+                                           int* out_idx, int* out_dist) {
   __shared__ uint32_t td[8 * TRK_MAXKP];
-  st += blockIdx.y; desc += (size_t)blockIdx.y * kstride * 8; nkp_p += blockIdx.y;
-  if (nboxes[blockIdx.y] <= 0 || st->frame_num == 0) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int nkp = min(*nkp_p, TRK_MAXKP), lastN = min(st->lastN, TRK_MAXKP);
   const int i = blockIdx.x * 4 + wv;
   if (blockIdx.x * 4 >= nkp) return;
   {
-    const uint4* d4 = reinterpret_cast<const uint4*>(st->last_desc);
+    const uint4* d4 = reinterpret_cast<const uint4*>(last_desc);
     uint4 v[TRK_MAXKP * 2 / 256];
 #pragma unroll
     for (int k = 0; k < TRK_MAXKP * 2 / 256; ++k) v[k] = d4[min(tid + 256 * k, max(2 * lastN - 1, 0))];
@@ -738,7 +751,7 @@ __global__ __launch_bounds__(256) void k_tg_bf(TrackState* st, const uint32_t* d
   if (i >= nkp) return;
   uint32_t qd[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) qd[k] = desc[8 * i + k];
+  for (int k = 0; k < 8; ++k) qd[k] = cur_desc[8 * i + k];
   uint32_t key = 0xffffffffu;
 #pragma unroll
   for (int t = 0; t < 8; ++t) {
@@ -752,30 +765,49 @@ __global__ __launch_bounds__(256) void k_tg_bf(TrackState* st, const uint32_t* d
   }
   key = wave_min_u32_dpp(key);
   if (lane == 0) {
-    st->bf_idx[i] = key == 0xffffffffu ? -1 : (int)(key & 0xffffu);
-    st->bf_dist[i] = key == 0xffffffffu ? -1 : (int)(key >> 16);
+    out_idx[i] = key == 0xffffffffu ? -1 : (int)(key & 0xffffu);
+    out_dist[i] = key == 0xffffffffu ? -1 : (int)(key >> 16);
   }
+}
+__global__ __launch_bounds__(256) void k_tg_bf(TrackState* st, const uint32_t* desc, const int32_t* nkp_p, int kstride,
+                                               const int32_t* nboxes) {
+  st += blockIdx.y; desc += (size_t)blockIdx.y * kstride * 8; nkp_p += blockIdx.y;
+  if (nboxes[blockIdx.y] <= 0 || st->frame_num == 0) return;
+  tg_bf_body(st->last_desc, min(st->lastN, TRK_MAXKP), desc, min(*nkp_p, TRK_MAXKP), st->bf_idx, st->bf_dist);
+}
+__global__ __launch_bounds__(256) void k_tg_bf_group(const uint32_t* desc, const int32_t* nkp_p, int kstride, const int32_t* nboxes,
+                                                     GatePre* pre) {
+  const int f = blockIdx.y;
+  if (nboxes[f] <= 0) return;
+  tg_bf_body(desc + (ptrdiff_t)(f - 1) * kstride * 8, min(nkp_p[f - 1], TRK_MAXKP), desc + (ptrdiff_t)f * kstride * 8,
+             min(nkp_p[f], TRK_MAXKP), pre[f].bf_idx, pre[f].bf_dist);
 }
 
 // pnpmatch::poseEstimation2D_2D (src/pnpmatch.cc:302-337) on one wave: keep the matches with distance <= max(2 min, 30)
 // (:281-299), drop those whose CURRENT point lies in a box padded by 10 px (:318-328), 8-point F from the rest (:336).
-__global__ __launch_bounds__(64) void k_tg_fmat(TrackState* st, const svo_kp* kp, const int32_t* nkp_p, int kstride,
-                                                const int32_t* boxes, const int32_t* nboxes, int bstride) {
-  __shared__ EpnpWaveLds S;
-  st += blockIdx.y; kp += (size_t)blockIdx.y * kstride; nkp_p += blockIdx.y;
+// n_boxes <= 0: nothing to do, F = 0.  last_xy(j, &x, &y): the last frame's keypoint j, from either of two places.
+struct TgLastXyState {   // TrackState::last_xy: float pairs
+  const float* xy;
+  __device__ __forceinline__ void operator()(int j, double* x, double* y) const { *x = (double)xy[2 * j]; *y = (double)xy[2 * j + 1]; }
+};
+struct TgLastXyRow {     // the front-end's svo_kp row of frame f - 1
+  const svo_kp* kp;
+  __device__ __forceinline__ void operator()(int j, double* x, double* y) const { const svo_kp k = kp[j]; *x = (double)k.x; *y = (double)k.y; }
+};
+template <typename LastXy>
+__device__ __forceinline__ void tg_fmat_body(EpnpWaveLds& S, const int* bf_idx, const int* bf_dist, const int32_t* nkp_p, const svo_kp* cur_kp,
+                                             const LastXy last_xy, const int32_t* boxes, int n_boxes, double* F_out) {
   const int lane = threadIdx.x;
-  const int n_boxes = min(max(nboxes[blockIdx.y], 0), SVO_MAX_BOXES);
-  boxes += (size_t)blockIdx.y * bstride * 4;
   double F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (n_boxes > 0 && st->frame_num > 0) {
+  if (n_boxes > 0) {
     const int nkp = min(*nkp_p, TRK_MAXKP);
     int idx[8], dist[8];
     uint32_t gmin = 0x7fffffffu;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       const int i = lane + 64 * t;
-      idx[t] = i < nkp ? st->bf_idx[i] : -1;
-      dist[t] = i < nkp ? st->bf_dist[i] : -1;
+      idx[t] = i < nkp ? bf_idx[i] : -1;
+      dist[t] = i < nkp ? bf_dist[i] : -1;
       if (idx[t] >= 0) gmin = min(gmin, (uint32_t)dist[t]);
     }
     gmin = wave_min_u32_dpp(gmin);
@@ -788,11 +820,11 @@ __global__ __launch_bounds__(64) void k_tg_fmat(TrackState* st, const svo_kp* kp
       const int i = lane + 64 * t;
       x1[t] = y1[t] = x2[t] = y2[t] = 0.0;
       if (idx[t] >= 0 && (double)dist[t] <= thr) {
-        const svo_kp k = kp[i];
+        const svo_kp k = cur_kp[i];
         if (!svo_in_boxes(k.x, k.y, boxes, n_boxes, 10)) {
           keep |= 1u << t;
           x1[t] = (double)k.x; y1[t] = (double)k.y;
-          x2[t] = (double)st->last_xy[2 * idx[t]]; y2[t] = (double)st->last_xy[2 * idx[t] + 1];
+          last_xy(idx[t], &x2[t], &y2[t]);
         }
       }
     }
@@ -802,111 +834,25 @@ __global__ __launch_bounds__(64) void k_tg_fmat(TrackState* st, const svo_kp* kp
     double v = F[0];
 #pragma unroll
     for (int k = 1; k < 9; ++k) v = lane == k ? F[k] : v;
-    st->F[lane] = v;
+    F_out[lane] = v;
   }
 }
-
-// The same two steps for a GROUP of consecutive frames of one sequence in one launch each, ahead of the index chain: the
-// brute-force matches and F of frame f need nothing but the front-end results of frames f - 1 and f and frame f's boxes -
-// no tracker state - so the 11 + 42 us they cost per gated frame leave the index chain (which they had made longer than
-// the pose chain: 122 against 117 us per frame in configs[4]).  blockIdx.y = frame of the group; the group's first frame must
-// not be the sequence's first (the caller starts groups at frame >= 1 of a call; frame 0 of a call keeps k_tg_bf / k_tg_fmat,
-// whose "last frame" is in the tracker state).  Results per frame in a GatePre record.
-__global__ __launch_bounds__(256) void k_tg_bf_group(const uint32_t* desc, const int32_t* nkp_p, int kstride, const int32_t* nboxes,
-                                                     GatePre* pre) {
-  __shared__ uint32_t td[8 * TRK_MAXKP];
-  const int f = blockIdx.y;   // relative to the pointers: they address the group's first frame, row -1 is its predecessor
-  if (nboxes[f] <= 0) return;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int nkp = min(nkp_p[f], TRK_MAXKP), lastN = min(nkp_p[f - 1], TRK_MAXKP);
-  const int i = blockIdx.x * 4 + wv;
-  if (blockIdx.x * 4 >= nkp) return;
-  const uint32_t* cur = desc + (ptrdiff_t)f * kstride * 8;
-  {
-    const uint4* d4 = reinterpret_cast<const uint4*>(desc + (ptrdiff_t)(f - 1) * kstride * 8);
-    uint4 v[TRK_MAXKP * 2 / 256];
-#pragma unroll
-    for (int k = 0; k < TRK_MAXKP * 2 / 256; ++k) v[k] = d4[min(tid + 256 * k, max(2 * lastN - 1, 0))];
-#pragma unroll
-    for (int k = 0; k < TRK_MAXKP * 2 / 256; ++k) {
-      const int q = tid + 256 * k;
-      if (q < 2 * lastN) {
-        const int j = q >> 1, w = 4 * (q & 1);
-        td[(w + 0) * TRK_MAXKP + j] = v[k].x; td[(w + 1) * TRK_MAXKP + j] = v[k].y;
-        td[(w + 2) * TRK_MAXKP + j] = v[k].z; td[(w + 3) * TRK_MAXKP + j] = v[k].w;
-      }
-    }
-  }
-  __syncthreads();
-  if (i >= nkp) return;
-  uint32_t qd[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) qd[k] = cur[8 * i + k];
-  uint32_t key = 0xffffffffu;
-#pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const int j = lane + 64 * t;
-    if (j < lastN) {
-      uint32_t d = 0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) d += __popc(qd[k] ^ td[k * TRK_MAXKP + j]);
-      key = min(key, (d << 16) | (uint32_t)j);   // ties: the lowest train index
-    }
-  }
-  key = wave_min_u32_dpp(key);
-  if (lane == 0) {
-    pre[f].bf_idx[i] = key == 0xffffffffu ? -1 : (int)(key & 0xffffu);
-    pre[f].bf_dist[i] = key == 0xffffffffu ? -1 : (int)(key >> 16);
-  }
+__global__ __launch_bounds__(64) void k_tg_fmat(TrackState* st, const svo_kp* kp, const int32_t* nkp_p, int kstride,
+                                                const int32_t* boxes, const int32_t* nboxes, int bstride) {
+  __shared__ EpnpWaveLds S;
+  st += blockIdx.y; kp += (size_t)blockIdx.y * kstride; nkp_p += blockIdx.y;
+  const int n_boxes = min(max(nboxes[blockIdx.y], 0), SVO_MAX_BOXES);
+  boxes += (size_t)blockIdx.y * bstride * 4;
+  tg_fmat_body(S, st->bf_idx, st->bf_dist, nkp_p, kp, TgLastXyState{st->last_xy}, boxes, st->frame_num > 0 ? n_boxes : 0, st->F);
 }
-
 __global__ __launch_bounds__(64) void k_tg_fmat_group(const svo_kp* kp, const int32_t* nkp_p, int kstride, const int32_t* boxes,
                                                       const int32_t* nboxes, int bstride, GatePre* pre) {
   __shared__ EpnpWaveLds S;
-  const int f = blockIdx.y, lane = threadIdx.x;
+  const int f = blockIdx.y;
   const int n_boxes = min(max(nboxes[f], 0), SVO_MAX_BOXES);
   boxes += (ptrdiff_t)f * bstride * 4;
-  const svo_kp* cur = kp + (ptrdiff_t)f * kstride;
-  const svo_kp* last = kp + (ptrdiff_t)(f - 1) * kstride;
-  double F[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  if (n_boxes > 0) {
-    const int nkp = min(nkp_p[f], TRK_MAXKP);
-    int idx[8], dist[8];
-    uint32_t gmin = 0x7fffffffu;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int i = lane + 64 * t;
-      idx[t] = i < nkp ? pre[f].bf_idx[i] : -1;
-      dist[t] = i < nkp ? pre[f].bf_dist[i] : -1;
-      if (idx[t] >= 0) gmin = min(gmin, (uint32_t)dist[t]);
-    }
-    gmin = wave_min_u32_dpp(gmin);
-    const double md = (double)min(gmin, 10000u);
-    const double thr = 2 * md > 30.0 ? 2 * md : 30.0;
-    uint32_t keep = 0;
-    double x1[8], y1[8], x2[8], y2[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      const int i = lane + 64 * t;
-      x1[t] = y1[t] = x2[t] = y2[t] = 0.0;
-      if (idx[t] >= 0 && (double)dist[t] <= thr) {
-        const svo_kp k = cur[i];
-        if (!svo_in_boxes(k.x, k.y, boxes, n_boxes, 10)) {
-          keep |= 1u << t;
-          const svo_kp kl = last[idx[t]];
-          x1[t] = (double)k.x; y1[t] = (double)k.y;
-          x2[t] = (double)kl.x; y2[t] = (double)kl.y;
-        }
-      }
-    }
-    fmat8_wave(S, keep, x1, y1, x2, y2, F);
-  }
-  if (lane < 9) {
-    double v = F[0];
-#pragma unroll
-    for (int k = 1; k < 9; ++k) v = lane == k ? F[k] : v;
-    pre[f].F[lane] = v;
-  }
+  tg_fmat_body(S, pre[f].bf_idx, pre[f].bf_dist, nkp_p + f, kp + (ptrdiff_t)f * kstride,
+               TgLastXyRow{kp + (ptrdiff_t)(f - 1) * kstride}, boxes, n_boxes, pre[f].F);
 }
 
 // ================================================================================================
@@ -942,6 +888,42 @@ __device__ __forceinline__ bool tp_wait_work(TrackState* st, const TrackWork* wo
 
 #define TP_HYP_FIRST 16
 #define TP_HYP_PRE 32   // most samples a later launch replays the adaptive rule over
+
+// The two steps every sample kernel shares (all threads of the workgroup call; both end in a barrier).
+// The frame's correspondences into LDS, widened to double: the map point's position by edge_gid, the keypoint by edge_kp.
+// PREFETCHED: the caller fetched its first entry (gid0, j0) together with the record's header.
+template <bool PREFETCHED>
+__device__ __forceinline__ void tp_gather_corr(double* Xw, double* uv, const TrackState* st, const TrackWork* work, const svo_kp* kp,
+                                               int n, int nthreads, int gid0 = 0, int j0 = 0) {
+  const float* gpos = st->gpos;
+  for (int e = threadIdx.x; e < n; e += nthreads) {
+    const bool first_e = PREFETCHED && e == (int)threadIdx.x;
+    const float* gp = gpos + 3 * (size_t)((first_e ? gid0 : ld_agent(&work->edge_gid[e])) & (TRK_GPOS - 1));
+    const svo_kp k = kp[first_e ? j0 : ld_agent(&work->edge_kp[e])];
+    Xw[3 * e] = (double)gp[0]; Xw[3 * e + 1] = (double)gp[1]; Xw[3 * e + 2] = (double)gp[2];
+    uv[2 * e] = (double)k.x; uv[2 * e + 1] = (double)k.y;
+  }
+  __syncthreads();
+}
+// The adaptive rule replayed over the first m samples, whose cnt / ok the threads have put into LDS: thread 0 walks it, everyone
+// gets the iteration bound - a sample at or beyond it can never be visited and leaves.
+__device__ __forceinline__ int tp_bound_walk(const int* cnt, const int* ok, int* bound, int n, int m) {
+  __syncthreads();
+  if (threadIdx.x == 0) *bound = pnp_bound_after(cnt, ok, n, m);
+  __syncthreads();
+  return *bound;
+}
+// ... over the first `pre` samples as earlier launches left them in hyp.  AGENT_LOADS: read at agent scope ("tail_semi", whose first
+// samples went out with agent-scope stores).
+template <bool AGENT_LOADS>
+__device__ __forceinline__ int tp_bound_replay(int* cnt, int* ok, int* bound, const PnpHyp* hyp, int n, int pre) {
+  const int tid = threadIdx.x;
+  if (tid < pre) {
+    cnt[tid] = AGENT_LOADS ? ld_agent(&hyp[tid].cnt) : hyp[tid].cnt;
+    ok[tid] = AGENT_LOADS ? ld_agent(&hyp[tid].ok) : hyp[tid].ok;
+  }
+  return tp_bound_walk(cnt, ok, bound, n, pre);
+}
 struct TpHypLds {
   double Xw[TRK_MAXKP * 3], uv[TRK_MAXKP * 2];
   EpnpWaveLds ws[4];
@@ -962,23 +944,8 @@ __global__ __launch_bounds__(256) void k_tp_hyp(TrackState* st, const TrackWork*
   const int gid0 = ld_agent(&work->edge_gid[threadIdx.x]), j0 = min(max(ld_agent(&work->edge_kp[threadIdx.x]), 0), kstride - 1);
   if (skip0 || n < 5) return;
   const int first = hyp_base + (int)blockIdx.x * (int)(blockDim.x >> 6);
-  if (hyp_base > 0) {
-    const int pre = min(hyp_base, TP_HYP_PRE);
-    if ((int)threadIdx.x < pre) { S.cnt[threadIdx.x] = st->hyp[threadIdx.x].cnt; S.ok[threadIdx.x] = st->hyp[threadIdx.x].ok; }
-    __syncthreads();
-    if (threadIdx.x == 0) S.bound = pnp_bound_after(S.cnt, S.ok, n, pre);
-    __syncthreads();
-    if (first >= S.bound) return;
-  }
-  const float* gpos = st->gpos;
-  for (int e = threadIdx.x; e < n; e += blockDim.x) {
-    const bool first_e = e == (int)threadIdx.x;
-    const float* gp = gpos + 3 * (size_t)((first_e ? gid0 : ld_agent(&work->edge_gid[e])) & (TRK_GPOS - 1));
-    const svo_kp k = kp[first_e ? j0 : ld_agent(&work->edge_kp[e])];
-    S.Xw[3 * e] = (double)gp[0]; S.Xw[3 * e + 1] = (double)gp[1]; S.Xw[3 * e + 2] = (double)gp[2];
-    S.uv[2 * e] = (double)k.x; S.uv[2 * e + 1] = (double)k.y;
-  }
-  __syncthreads();
+  if (hyp_base > 0 && first >= tp_bound_replay<false>(S.cnt, S.ok, &S.bound, st->hyp, n, min(hyp_base, TP_HYP_PRE))) return;
+  tp_gather_corr<true>(S.Xw, S.uv, st, work, kp, n, blockDim.x, gid0, j0);
   const double K[4] = {(double)st->cam.fx, (double)st->cam.fy, (double)st->cam.cx, (double)st->cam.cy};
   const long long t_gather = clock64();
   pnp_hyp_block(S.ws, S.Xw, S.uv, n, K, subsets + (size_t)min(n, 512) * 500, st->hyp, first);
@@ -1002,14 +969,7 @@ __global__ __launch_bounds__(64) void k_tp_hyp_exact(TrackState* st, TrackWork* 
   if (threadIdx.x == 0 && blockIdx.x == 0) work->rt[2] = wall_clock64();
   const int n = ld_agent(&work->n_edges);
   if (ld_agent(&work->skip_match) || n < 5) return;
-  const float* gpos = st->gpos;
-  for (int e = threadIdx.x; e < n; e += blockDim.x) {
-    const float* gp = gpos + 3 * (size_t)(ld_agent(&work->edge_gid[e]) & (TRK_GPOS - 1));
-    const svo_kp k = kp[ld_agent(&work->edge_kp[e])];
-    S.Xw[3 * e] = (double)gp[0]; S.Xw[3 * e + 1] = (double)gp[1]; S.Xw[3 * e + 2] = (double)gp[2];
-    S.uv[2 * e] = (double)k.x; S.uv[2 * e + 1] = (double)k.y;
-  }
-  __syncthreads();
+  tp_gather_corr<false>(S.Xw, S.uv, st, work, kp, n, blockDim.x);
   const double K[4] = {(double)st->cam.fx, (double)st->cam.fy, (double)st->cam.cx, (double)st->cam.cy};
   pnp_hyp_exact_wave(S.ex, S.Xw, S.uv, n, K, subsets + (size_t)min(n, 512) * 500, st->hyp, blockIdx.x);
 }
@@ -1034,11 +994,7 @@ __device__ __forceinline__ void tp_hyp_ord_body(TpHypOrdLds& S, TrackState* st, 
   if (FUSED && (force_seq >> 8) == sample + 1) return;   // test switch "debug_lose_sample": this sample never reports (the frame part's bounded wait)
   if (FUSED && semi > 0) {
     const int tid = threadIdx.x;
-    if (tid < semi) { S.cnt[tid] = ld_agent(&st->hyp[tid].cnt); S.ok[tid] = ld_agent(&st->hyp[tid].ok); }
-    __syncthreads();
-    if (tid == 0) S.bound = pnp_bound_after(S.cnt, S.ok, n, semi);
-    __syncthreads();
-    bool leave = sample >= S.bound;
+    bool leave = sample >= tp_bound_replay<true>(S.cnt, S.ok, &S.bound, st->hyp, n, semi);
     if (!leave && sample >= 2 * semi) {   // (the bound after `semi` samples reaches beyond 2 semi: all of semi .. 2 semi - 1 are being solved)
       if (tid >= semi && tid < 2 * semi) {
         int spins = 0;
@@ -1049,10 +1005,7 @@ __device__ __forceinline__ void tp_hyp_ord_body(TpHypOrdLds& S, TrackState* st, 
         const bool late = spins >= (1 << 22);
         S.cnt[tid] = late ? 0 : tp_early_cnt(w); S.ok[tid] = late ? 0 : tp_early_ok(w);   // (the word carries them: no second round trip)
       }
-      __syncthreads();
-      if (tid == 0) S.bound = pnp_bound_after(S.cnt, S.ok, n, 2 * semi);
-      __syncthreads();
-      leave = sample >= S.bound;
+      leave = sample >= tp_bound_walk(S.cnt, S.ok, &S.bound, n, 2 * semi);
     }
     if (leave) {
       if (tid == 0) {
@@ -1062,22 +1015,10 @@ __device__ __forceinline__ void tp_hyp_ord_body(TpHypOrdLds& S, TrackState* st, 
       return;
     }
   }
-  if (hyp_base > 0) {   // second launch of a many-sequence step: only the samples the adaptive bound can still reach (see k_tp_hyp)
-    const int pre = min(hyp_base, TP_HYP_PRE);   // the rule over the samples of the earlier launches (all of them done: same stream)
-    if ((int)threadIdx.x < pre) { S.cnt[threadIdx.x] = st->hyp[threadIdx.x].cnt; S.ok[threadIdx.x] = st->hyp[threadIdx.x].ok; }
-    __syncthreads();
-    if (threadIdx.x == 0) S.bound = pnp_bound_after(S.cnt, S.ok, n, pre);
-    __syncthreads();
-    if (sample >= S.bound) return;
-  }
-  const float* gpos = st->gpos;
-  for (int e = threadIdx.x; e < n; e += 64) {
-    const float* gp = gpos + 3 * (size_t)(ld_agent(&work->edge_gid[e]) & (TRK_GPOS - 1));
-    const svo_kp k = kp[ld_agent(&work->edge_kp[e])];
-    S.Xw[3 * e] = (double)gp[0]; S.Xw[3 * e + 1] = (double)gp[1]; S.Xw[3 * e + 2] = (double)gp[2];
-    S.uv[2 * e] = (double)k.x; S.uv[2 * e + 1] = (double)k.y;
-  }
-  __syncthreads();
+  // second launch of a many-sequence step: only the samples the adaptive bound can still reach (see k_tp_hyp) - the rule over the
+  // samples of the earlier launches (all of them done: same stream)
+  if (hyp_base > 0 && sample >= tp_bound_replay<false>(S.cnt, S.ok, &S.bound, st->hyp, n, min(hyp_base, TP_HYP_PRE))) return;
+  tp_gather_corr<false>(S.Xw, S.uv, st, work, kp, n, 64);
   const double K[4] = {(double)st->cam.fx, (double)st->cam.fy, (double)st->cam.cx, (double)st->cam.cy};
   if (!FUSED && sample == 0) {   // the frame kernel's copy of the correspondences (it skips its own gather: k_tp_frame, `pre_gathered`)
     for (int i = threadIdx.x; i < 3 * n; i += 64) st->Xw[i] = S.Xw[i];
@@ -1252,9 +1193,9 @@ __device__ __forceinline__ void tp_frame_body(TpLds& S, TrackState* st, TrackWor
       int l = 0;
       for (int k = 0; k < TP_EARLY; ++k) l |= S.late[k];
       S.lost = l;
-      int best = -1, good = 0;
-      S.iters = l ? 0 : pnp_select_pre_early(S.cnt, S.ok, S.upd_ld, S.upd_r, n_edges, TP_EARLY, &best, &good);
-      S.best = best; S.good = good;
+      PnpWalk w = {0, -1, 0, 0};
+      if (!l) w = pnp_walk<true>(S.cnt, S.ok, S.upd_ld, S.upd_r, n_edges, TP_EARLY);   // (visited = TP_EARLY + 1: not decided, no winner yet)
+      S.iters = w.visited; S.best = w.best; S.good = w.good;
     }
     if (tid < TP_EARLY) {
       double Tp[16];

@@ -1,13 +1,15 @@
 """RANSAC's stopping rule and consensus count on the device, through the probes svo_debug_pnp_rule and svo_debug_pnp_consensus.
 
-The rule - RANSACPointSetRegistrator::run's loop around RANSACUpdateNumIters - exists in several copies (svo_pose_dev.h): the plain
-pnp_select of svo_pnp_ransac, and what the tracker runs: pnp_update_terms (tabulated per frame, then looked up), pnp_select_pre,
-pnp_select_pre_bound / _early over the first m samples, pnp_bound_after.  All of them stand on the device's pow / log where the
+The rule - RANSACPointSetRegistrator::run's loop around RANSACUpdateNumIters - is one walker (pnp_walk, svo_pose_dev.h) with these
+instantiations: the plain pnp_select of svo_pnp_ransac (bound from pnp_update_iters), and what the tracker runs: pnp_update_terms
+(tabulated per frame, then looked up), pnp_select_pre (bound from those terms), the same walk cut at the first m samples (the fused
+tail's early decision), pnp_bound_after (the bound after m samples).  All of them stand on the device's pow / log where the
 CPU restatement stands on glibc's; tests/test_pnp_rule_cpu.py shows that the integers behind them have a relative margin of
 3.9e-7, so a correct device math library must give the restatement's integers on EVERY pair (g, n) - the table test - and the
-copies must agree with the reference loop (tests/pnp_rule_ref.py) on every vector of samples.
+instantiations must agree with the reference loop (tests/pnp_rule_ref.py) on every vector of samples.
 
-The consensus count (pnp_inlier + the wave's sum over e = lane, lane + 64, ...) is placed on its threshold on purpose: identity
+The consensus count (pnp_consensus_wave, the function every sample kernel counts with: pnp_inlier + the wave's sum over e = lane,
+lane + 64, ...) is placed on its threshold on purpose: identity
 rotation, a dyadic camera and dyadic points make the projection exact, so err == 64.0f and its float32 neighbours are met
 exactly."""
 import numpy as np
@@ -55,7 +57,7 @@ def test_table_integers_equal_the_restatements(table, orc):
     assert np.array_equal(r[small], raw[small]) and (r[~small] > 100).all()
     # ld == 1.0 marks "denominator below DBL_MIN": exactly where the restatement returns 0 (g == n)
     assert np.array_equal(ld == 1.0, raw == 0) and np.array_equal(raw == 0, g == n) and (ld[ld != 1.0] < 0).all()
-    # the decision of pnp_select_pre* with the device's ld and log(0.01), for every bound it can be asked with
+    # the decision of pnp_walk<PREPARED> with the device's ld and log(0.01), for every bound it can be asked with
     for niters in range(1, 101):
         dec = np.where((ld >= 0) | (-num >= niters * (-ld)), niters, r)
         dec = np.where(ld == 1.0, 0, dec)
@@ -81,8 +83,8 @@ def check_vectors(svo, orc, names, cnt, ok, n):
         assert sel == (best, good, iters), (key, sel, (best, good, iters))                     # pnp_select = the reference loop
         assert tuple(out["select_pre"][i]) == sel, key                                          # pnp_select_pre = pnp_select
         per = out["per_m"][i]
-        assert np.array_equal(per[:, 0], np.where(iters <= m, iters, m + 1)), key               # pnp_select_pre_bound(m)
-        assert np.array_equal(per[:, 1], per[:, 0]), key                                        # pnp_select_pre_early(m): the same value
+        assert np.array_equal(per[:, 0], np.where(iters <= m, iters, m + 1)), key               # the walk cut at m: samples visited, or m + 1
+        assert np.array_equal(per[:, 1], per[:, 0]), key                                        # (its second column: the same value)
         ended = per[:, 0] <= m
         assert (per[ended, 2] == best).all() and (per[ended, 3] == good).all(), key             # ... and pnp_select's winner where it ended
         assert np.array_equal(per[:, 4], np.array(bounds)), key                                 # pnp_bound_after(m)
