@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_ba_* (windowed bundle adjustment on the device over the map records; see
+#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_bow_* (DBoW2 bag-of-words place recognition on the device; see "bag-of-words
+                              place recognition" below); no existing entry changed.
+                              8, backward-compatible addition: svo_ba_* (windowed bundle adjustment on the device over the map records; see
                               "windowed bundle adjustment" below); no existing entry changed.
                               8, backward-compatible addition: svo_track_map_out, svo_map_obs (each tracked frame's map points and observations
                               in HBM; see "the map behind a tracked frame" below); no existing entry changed.
@@ -1249,6 +1251,86 @@ int svo_ba_windows_dev(svo_ba* ba, const svo_camera* cam, const svo_ba_params* p
  * together with n_points) holds window * max_kp / 2 records.  Synchronises. */
 int svo_ba_window(svo_ba* ba, const svo_camera* cam, const svo_ba_params* params, const svo_map_obs* obs, const int32_t* counts,
                   int obs_stride, const float* Tcw, double* Tcw_out, svo_ba_point* points, int32_t* n_points, svo_ba_stats* stats);
+
+/* ---- bag-of-words place recognition (backward-compatible addition; no existing entry changed) -------------------------------
+ * DBoW2 as ORB-SLAM2 carries it (Thirdparty/DBoW2): a vocabulary tree over the 32-byte descriptors of this library, a frame's
+ * BowVector and FeatureVector, L1Scoring::score, and for a query frame the best-scoring earlier frames.  The contract, operation
+ * by operation: DESIGN.md section 8 "Bag of words"; the numpy twin: tests/bow_ref.py.  Parity with a compiled DBoW2 is not pinned.
+ * ORB-SLAM2's published vocabulary does not fit these descriptors (it was trained on the learned rBRIEF pattern, this library
+ * describes with include/svo_brief_pattern.h): a vocabulary has to be trained on the library's own descriptors.
+ * Out of scope: an inverted index and DetectLoopCandidates' heuristics (covisibility groups, consistency over three keyframes),
+ * SearchByBoW matching through the FeatureVector, Sim3 / loop correction or any feedback into the tracker, scorings other than
+ * L1, DBoW2's binary / YAML formats, the many-sequence entries, descriptors other than 32 bytes. */
+enum { SVO_BOW_TF_IDF = 0, SVO_BOW_TF = 1, SVO_BOW_IDF = 2, SVO_BOW_BINARY = 3 };   /* DBoW2's WeightingType */
+typedef struct svo_bow_entry {     /* 16 bytes: one word of a BowVector */
+  uint32_t word, reserved;         /* reserved: 0 */
+  double value;
+} svo_bow_entry;
+typedef struct svo_bow_feature {   /* 8 bytes: one pair of a FeatureVector */
+  uint32_t node, feature;          /* the node's id as the file (or the arrays) numbered it; the feature's index in its frame */
+} svo_bow_feature;
+typedef struct svo_bow_cand {      /* 16 bytes: one candidate of a query; an unused slot is {-1, 0, 0.0} */
+  int32_t frame, reserved;
+  double score;
+} svo_bow_cand;
+typedef struct svo_bow svo_bow;
+
+/* A vocabulary for frames of up to max_kp features (1 .. 2048) and calls of up to max_frames frames (1 .. 65535), with a stream
+ * and scratch of its own (8 bytes per feature of a call).  Both constructors parse and validate on the host and touch no device:
+ * the device copy of the tree, the stream and the scratch come with the first call that needs them (SVO_E_NODEVICE / SVO_E_NOMEM
+ * are answered there), so the argument checks of every entry answer on a machine without a GPU.
+ * svo_bow_last_error(NULL): the calling thread's last failure without an object.
+ * From text: DBoW2's loadFromTextFile format, `k L scoring weighting`, then one line per node from id 1 on, `parent is_leaf
+ * b0 .. b31 weight`.  Children need not be contiguous by id; every output names nodes by the file's ids.  SVO_E_INVALID with a
+ * message naming the line: k outside 2 .. 20, L outside 1 .. 10, scoring other than 0 (L1_NORM), weighting outside 0 .. 3, a parent
+ * id not yet defined, a parent marked a leaf, more than k children of one node, an inner node without children, a malformed line.
+ * From arrays: n_nodes nodes with the root as node 0 (its parent, descriptor and weight are ignored), parents[i] < i, descriptors
+ * n_nodes x 32 bytes, weights n_nodes; a node without children is a leaf.  Words number the leaves in node-id order. */
+int svo_bow_create_from_text(int device, const char* path, int max_kp, int max_frames, svo_bow** out);
+int svo_bow_create(int device, int k, int L, int weighting, int n_nodes, const int32_t* parents, const uint8_t* descriptors,
+                   const double* weights, int max_kp, int max_frames, svo_bow** out);
+/* The text format again; weights with 17 significant digits, so a file written here loads to the same bits (DBoW2 prints 6). */
+int svo_bow_save_text(svo_bow* bow, const char* path);
+/* k, L, nodes (the root included), words, weighting; any output may be NULL. */
+int svo_bow_describe(const svo_bow* bow, int* k, int* L, int* n_nodes, int* n_words, int* weighting);
+void svo_bow_destroy(svo_bow* bow);
+int svo_bow_sync(svo_bow* bow);
+void* svo_bow_stream(svo_bow* bow);
+const char* svo_bow_last_error(const svo_bow* bow);
+
+/* B frames resident in HBM: frame f's descriptors at d_desc + f * kp_stride * 32, d_n[f] of them (the layouts
+ * svo_frontend_batch_dev writes and svo_track_tail_dev reads; a count above kp_stride is clamped on the device, a negative one is 0).
+ * Outputs, frame f at f * kp_stride elements, any of them may be NULL: d_words the word of every feature, -1 for a feature whose
+ * word's weight is not > 0 (a stop word) and for the indices from the count to kp_stride; d_vec the BowVector in ascending word
+ * order (L1-normalised) and d_vec_n its length; d_fv the FeatureVector, the pairs of the features that are not stopped by ascending
+ * (node, feature), the node being the one at level L - levelsup of the feature's walk (the root, 0, when L - levelsup <= 0; the leaf
+ * when the walk ends above that level) and d_fv_n their number.  Elements behind a frame's length are not written.
+ * Does not synchronise.  producer (may be NULL, same device): the object's stream waits ON THE DEVICE for an event recorded on
+ * svo_stream(producer), so the call runs behind the front end call that writes the descriptors; the producer waits for nothing
+ * and nothing else is enqueued on its streams.  The same call gives the same bytes.
+ * SVO_E_INVALID before a device is touched: a NULL bow, d_desc or d_n, d_desc not 4-byte aligned, kp_stride outside 1 .. max_kp,
+ * B outside 1 .. max_frames, levelsup < 0, a producer on another device. */
+int svo_bow_transform_dev(svo_bow* bow, const uint8_t* d_desc, const int32_t* d_n, int kp_stride, int B, int levelsup,
+                          int32_t* d_words, svo_bow_entry* d_vec, int32_t* d_vec_n, svo_bow_feature* d_fv, int32_t* d_fv_n,
+                          svo_ctx* producer);
+/* One frame, host to host: n (0 .. max_kp) descriptors; words n, vec and fv up to n records (vec goes with vec_n, fv with fv_n;
+ * each pair and words may be NULL).  Synchronises. */
+int svo_bow_transform(svo_bow* bow, const uint8_t* desc, int n, int levelsup, int32_t* words, svo_bow_entry* vec, int32_t* vec_n,
+                      svo_bow_feature* fv, int32_t* fv_n);
+/* L1Scoring::score(A[a], B[b]) for every pair: d_scores QA x NB doubles.  Vector i of a set at i * stride records (1 <= stride <=
+ * max_kp), its length in d_nA / d_nB (clamped to 0 .. stride); words ascending, as svo_bow_transform_dev writes them.  Vectors
+ * without a common word score -0.0.  QA 1 .. 65535, NB >= 1.  Does not synchronise (the object's stream). */
+int svo_bow_score_dev(svo_bow* bow, const svo_bow_entry* d_vecA, const int32_t* d_nA, int QA, const svo_bow_entry* d_vecB,
+                      const int32_t* d_nB, int NB, int stride, double* d_scores);
+/* For each query frame q = q0 .. q0 + Q - 1 of the N resident vectors: the top_k (1 .. 16) frames j of 0 .. q - gap - 1 with
+ * score(vec[q], vec[j]) > min_score, by descending score, equal scores by ascending j; d_cand Q x top_k records, d_cand_n Q counts.
+ * The Q x N scores are not written anywhere.  gap >= 0; min_score not a NaN.  Does not synchronise. */
+int svo_bow_query_dev(svo_bow* bow, const svo_bow_entry* d_vec, const int32_t* d_vec_n, int stride, int N, int q0, int Q, int gap,
+                      double min_score, int top_k, svo_bow_cand* d_cand, int32_t* d_cand_n);
+/* One level of the walk alone, for tests and for training: n (>= 1) descriptors against k (1 .. 20) centres of 32 bytes; d_idx
+ * the nearest centre (the earliest among equals), d_dist its Hamming distance; either may be NULL.  Runs on the object's stream,
+ * does not synchronise. */
+int svo_bow_assign_dev(svo_bow* bow, const uint8_t* d_desc, int n, const uint8_t* d_centres, int k, int32_t* d_idx, int32_t* d_dist);
 
 #ifdef __cplusplus
 }

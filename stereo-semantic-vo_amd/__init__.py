@@ -51,6 +51,12 @@ BA_STATS_DTYPE = np.dtype([("status", "<i4"), ("n_points", "<i4"), ("n_edges", "
 BA_POINT_DTYPE = np.dtype([("gid", "<i4"), ("n_obs", "<i4"), ("X", "<f8"), ("Y", "<f8"), ("Z", "<f8")])
 BA_OK, BA_EMPTY = 0, 1   # svo_ba_stats.status
 
+# svo_bow_entry / svo_bow_feature / svo_bow_cand (include/svo.h): a word of a BowVector, a pair of a FeatureVector, a query's candidate
+BOW_ENTRY_DTYPE = np.dtype([("word", "<u4"), ("reserved", "<u4"), ("value", "<f8")])
+BOW_FEATURE_DTYPE = np.dtype([("node", "<u4"), ("feature", "<u4")])
+BOW_CAND_DTYPE = np.dtype([("frame", "<i4"), ("reserved", "<i4"), ("score", "<f8")])
+BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3   # DBoW2's WeightingType
+
 # Every symbol include/svo.h declares (checked by tests/test_abi.py without a GPU).
 ABI_SYMBOLS = [
     "svo_abi_version", "svo_strerror", "svo_last_error", "svo_create", "svo_destroy", "svo_sync",
@@ -80,6 +86,9 @@ ABI_SYMBOLS = [
     "svo_rect_sync", "svo_rect_stream", "svo_rect_debug_maps",
     "svo_ba_default_params", "svo_ba_create", "svo_ba_destroy", "svo_ba_sync", "svo_ba_stream", "svo_ba_last_error",
     "svo_ba_windows_dev", "svo_ba_window",
+    "svo_bow_create_from_text", "svo_bow_create", "svo_bow_save_text", "svo_bow_describe", "svo_bow_destroy", "svo_bow_sync",
+    "svo_bow_stream", "svo_bow_last_error", "svo_bow_transform_dev", "svo_bow_transform", "svo_bow_score_dev", "svo_bow_query_dev",
+    "svo_bow_assign_dev",
 ]
 
 PNP_RULE_W = 6 + 5 * 101   # SVO_PNP_RULE_W (include/svo.h)
@@ -1388,3 +1397,126 @@ class BundleAdjuster:
     @property
     def stream(self):
         return self.lib.svo_ba_stream(self.h)
+
+
+# ---- bag-of-words place recognition (svo_bow_* in include/svo.h; the contract: DESIGN.md section 8 "Bag of words") ----------------------------
+class Vocabulary:
+    """A DBoW2 vocabulary tree on one GPU (wraps svo_bow): words, BowVectors and FeatureVectors of frames, L1 scores, and the
+    best earlier frames of a query.  An object with a stream and scratch of its own; creating it touches no device."""
+
+    def __init__(self, handle, max_kp, max_frames):
+        self.lib, self.h, self.max_kp, self.max_frames = load_library(), handle, int(max_kp), int(max_frames)
+
+    @staticmethod
+    def _bind():
+        lib = load_library()
+        lib.svo_bow_last_error.restype = C.c_char_p
+        lib.svo_bow_last_error.argtypes = [C.c_void_p]
+        lib.svo_bow_create_from_text.argtypes = [C.c_int, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        lib.svo_bow_create.argtypes = [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        lib.svo_bow_save_text.argtypes = [C.c_void_p, C.c_char_p]
+        lib.svo_bow_describe.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 5
+        lib.svo_bow_destroy.argtypes = [C.c_void_p]
+        lib.svo_bow_destroy.restype = None
+        lib.svo_bow_sync.argtypes = [C.c_void_p]
+        lib.svo_bow_stream.restype = C.c_void_p
+        lib.svo_bow_stream.argtypes = [C.c_void_p]
+        lib.svo_bow_transform_dev.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 6
+        lib.svo_bow_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+        lib.svo_bow_score_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        lib.svo_bow_query_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_double, C.c_int, C.c_void_p, C.c_void_p]
+        lib.svo_bow_assign_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        return lib
+
+    @classmethod
+    def _made(cls, lib, rc, h, what, max_kp, max_frames):
+        if rc != 0:
+            raise SvoError("%s: %s: %s" % (what, lib.svo_strerror(rc).decode(), lib.svo_bow_last_error(None).decode()))
+        return cls(h, max_kp, max_frames)
+
+    @classmethod
+    def from_text(cls, path, max_kp=500, max_frames=1, device=0):
+        """svo_bow_create_from_text: DBoW2's text format."""
+        lib, h = cls._bind(), C.c_void_p()
+        rc = lib.svo_bow_create_from_text(int(device), os.fsencode(path), int(max_kp), int(max_frames), C.byref(h))
+        return cls._made(lib, rc, h, "svo_bow_create_from_text", max_kp, max_frames)
+
+    @classmethod
+    def from_arrays(cls, k, L, weighting, parents, descriptors, weights, max_kp=500, max_frames=1, device=0):
+        """svo_bow_create: node 0 is the root; parents (n,), descriptors (n, 32) uint8, weights (n,) float64."""
+        lib, h = cls._bind(), C.c_void_p()
+        parents = np.ascontiguousarray(parents, np.int32)
+        descriptors = np.ascontiguousarray(descriptors, np.uint8)
+        weights = np.ascontiguousarray(weights, np.float64)
+        n = int(parents.shape[0])
+        if descriptors.shape != (n, 32) or weights.shape != (n,):
+            raise ValueError("descriptors must be (n, 32) and weights (n,) for n parents")
+        rc = lib.svo_bow_create(int(device), int(k), int(L), int(weighting), n, _p(parents), _p(descriptors), _p(weights), int(max_kp),
+                                int(max_frames), C.byref(h))
+        return cls._made(lib, rc, h, "svo_bow_create", max_kp, max_frames)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.svo_bow_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise SvoError("%s: %s: %s" % (what, self.lib.svo_strerror(rc).decode(), self.lib.svo_bow_last_error(self.h).decode()))
+
+    def save_text(self, path):
+        self._chk(self.lib.svo_bow_save_text(self.h, os.fsencode(path)), "svo_bow_save_text")
+
+    def describe(self):
+        """dict(k, L, nodes, words, weighting)."""
+        v = [C.c_int(0) for _ in range(5)]
+        self._chk(self.lib.svo_bow_describe(self.h, *[C.byref(x) for x in v]), "svo_bow_describe")
+        return dict(zip(("k", "L", "nodes", "words", "weighting"), (x.value for x in v)))
+
+    def transform(self, desc, levelsup=0):
+        """One frame, host to host: desc (n, 32) uint8 -> (words (n,) int32, vec BOW_ENTRY_DTYPE, fv BOW_FEATURE_DTYPE)."""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = int(desc.shape[0])
+        words = np.zeros(max(n, 1), np.int32)
+        vec = np.zeros(max(n, 1), BOW_ENTRY_DTYPE)
+        fv = np.zeros(max(n, 1), BOW_FEATURE_DTYPE)
+        nv, nf = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.svo_bow_transform(self.h, _p(desc), n, int(levelsup), _p(words), _p(vec), C.addressof(nv), _p(fv),
+                                             C.addressof(nf)), "svo_bow_transform")
+        return words[:n].copy(), vec[:nv.value].copy(), fv[:nf.value].copy()
+
+    def transform_dev(self, d_desc, d_n, kp_stride, B, levelsup=0, d_words=None, d_vec=None, d_vec_n=None, d_fv=None, d_fv_n=None,
+                      producer=None):
+        """svo_bow_transform_dev on device memory (torch tensors or device pointers as ints; any output may be None).  producer:
+        the Svo whose front end call writes the descriptors - this call runs behind it on the device.  Does not synchronise."""
+        self._chk(self.lib.svo_bow_transform_dev(self.h, _dptr(d_desc), _dptr(d_n), int(kp_stride), int(B), int(levelsup), _dptr(d_words),
+                                                 _dptr(d_vec), _dptr(d_vec_n), _dptr(d_fv), _dptr(d_fv_n),
+                                                 None if producer is None else producer.h), "svo_bow_transform_dev")
+
+    def score_dev(self, d_vecA, d_nA, QA, d_vecB, d_nB, NB, stride, d_scores):
+        """svo_bow_score_dev: d_scores (QA, NB) float64.  Does not synchronise."""
+        self._chk(self.lib.svo_bow_score_dev(self.h, _dptr(d_vecA), _dptr(d_nA), int(QA), _dptr(d_vecB), _dptr(d_nB), int(NB), int(stride),
+                                             _dptr(d_scores)), "svo_bow_score_dev")
+
+    def query_dev(self, d_vec, d_vec_n, stride, N, q0, Q, gap, min_score, top_k, d_cand, d_cand_n):
+        """svo_bow_query_dev: d_cand (Q, top_k) BOW_CAND_DTYPE records, d_cand_n (Q,) int32.  Does not synchronise."""
+        self._chk(self.lib.svo_bow_query_dev(self.h, _dptr(d_vec), _dptr(d_vec_n), int(stride), int(N), int(q0), int(Q), int(gap),
+                                             float(min_score), int(top_k), _dptr(d_cand), _dptr(d_cand_n)), "svo_bow_query_dev")
+
+    def assign_dev(self, d_desc, n, d_centres, k, d_idx, d_dist):
+        """svo_bow_assign_dev: n descriptors against k centres -> index and distance.  Does not synchronise."""
+        self._chk(self.lib.svo_bow_assign_dev(self.h, _dptr(d_desc), int(n), _dptr(d_centres), int(k), _dptr(d_idx), _dptr(d_dist)),
+                  "svo_bow_assign_dev")
+
+    def sync(self):
+        self._chk(self.lib.svo_bow_sync(self.h), "svo_bow_sync")
+
+    @property
+    def stream(self):
+        return self.lib.svo_bow_stream(self.h)

@@ -139,6 +139,7 @@ Tracking::~Tracking() {
   }
   if (rect) svo_rect_destroy(rect);
   if (ba) svo_ba_destroy(ba);
+  if (bow) svo_bow_destroy(bow);
   if (ctx_batch) svo_destroy(ctx_batch);
   if (ctx_map) svo_destroy(ctx_map);
   svo_destroy(ctx);
@@ -147,6 +148,7 @@ Tracking::~Tracking() {
 void Tracking::TrackBatch(const uint8_t* L, const uint8_t* R, int stride, int n, const double* timestamps,
                           const std::vector<std::vector<std::vector<int>>>& detection_box, bool bgr) {
   if (n < 1) return;
+  if (bow) throw std::runtime_error("TrackBatch: the pipelined mode keeps no descriptors on the host, so it has no bag of words (LoadVocabulary goes with Track())");
   if (n > batch_capacity) throw std::runtime_error("TrackBatch: more frames than batch_capacity");
   if (!ctx_batch) {
     if (svo_create(&ctx_batch, device, width, height, 500, batch_capacity) != SVO_OK) throw std::runtime_error("svo_create failed");
@@ -268,6 +270,39 @@ Tracking::LocalBAResult Tracking::LocalBA(size_t first_frame, const svo_ba_param
     throw std::runtime_error(std::string("Tracking::LocalBA: ") + svo_ba_last_error(ba));
   r.points.resize((size_t)n);
   return r;
+}
+void Tracking::LoadVocabulary(const std::string& path) {
+  if (bow) { svo_bow_destroy(bow); bow = nullptr; }
+  if (svo_bow_create_from_text(device, path.c_str(), 500, 1, &bow) != SVO_OK)
+    throw std::runtime_error(std::string("Tracking::LoadVocabulary: ") + svo_bow_last_error(nullptr));
+}
+std::vector<svo_bow_cand> Tracking::LoopCandidates(size_t frame_id, int gap, int top_k, double min_score) {
+  if (!bow) throw std::runtime_error("Tracking::LoopCandidates: no vocabulary (LoadVocabulary)");
+  if (frame_id >= bow_vectors.size()) throw std::runtime_error("Tracking::LoopCandidates: no such frame (Track() called?)");
+  if (top_k < 1 || top_k > 16) throw std::runtime_error("Tracking::LoopCandidates: top_k must be 1 .. 16");
+  const size_t N = frame_id + 1, stride = 500;     // the frames up to the query, in the layout svo_bow_query_dev takes
+  std::vector<svo_bow_entry> vec(N * stride, svo_bow_entry{});
+  std::vector<int32_t> cnt(N);
+  for (size_t f = 0; f < N; ++f) {
+    std::copy(bow_vectors[f].begin(), bow_vectors[f].end(), vec.begin() + f * stride);
+    cnt[f] = (int32_t)bow_vectors[f].size();
+  }
+  std::vector<svo_bow_cand> out((size_t)top_k);
+  int32_t n = 0;
+  uint8_t* d = nullptr;
+  const size_t bv = vec.size() * sizeof(svo_bow_entry), bn = N * sizeof(int32_t), bc = out.size() * sizeof(svo_bow_cand);
+  if (!svo_bow_stream(bow)) throw std::runtime_error(std::string("Tracking::LoopCandidates: ") + svo_bow_last_error(bow));
+  if (hipMalloc(reinterpret_cast<void**>(&d), bv + bn + bc + 16) != hipSuccess) throw std::runtime_error("Tracking::LoopCandidates: out of device memory");
+  uint8_t *d_n = d + bv, *d_c = d_n + ((bn + 15) & ~(size_t)15), *d_cn = d_c + bc;
+  bool ok = hipMemcpy(d, vec.data(), bv, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_n, cnt.data(), bn, hipMemcpyHostToDevice) == hipSuccess;
+  ok = ok && svo_bow_query_dev(bow, reinterpret_cast<svo_bow_entry*>(d), reinterpret_cast<int32_t*>(d_n), (int)stride, (int)N, (int)frame_id, 1,
+                               gap, min_score, top_k, reinterpret_cast<svo_bow_cand*>(d_c), reinterpret_cast<int32_t*>(d_cn)) == SVO_OK;
+  ok = ok && svo_bow_sync(bow) == SVO_OK && hipMemcpy(out.data(), d_c, bc, hipMemcpyDeviceToHost) == hipSuccess &&
+       hipMemcpy(&n, d_cn, sizeof n, hipMemcpyDeviceToHost) == hipSuccess;
+  (void)hipFree(d);
+  if (!ok) throw std::runtime_error(std::string("Tracking::LoopCandidates: ") + svo_bow_last_error(bow));
+  out.resize((size_t)n);
+  return out;
 }
 const svo_map_obs* Tracking::ObservationOf(size_t frame_id, int kp) const {
   const std::vector<svo_map_obs>& o = Observations(frame_id);   // (ascending kp)
@@ -428,6 +463,18 @@ void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, co
     currentframe->disp2Depth(bf);
   }
   currentframe->id = frame_num;
+  if (bow) {                              // this frame's words and vectors (ORB-SLAM2's Frame::ComputeBoW: levelsup 4)
+    const int n = (int)std::min<size_t>(currentframe->keypoints_l.size(), 500);     // (f_descriptor keeps its capacity of N rows)
+    std::vector<int32_t> w((size_t)n);
+    std::vector<svo_bow_entry> v((size_t)n);
+    std::vector<svo_bow_feature> fv((size_t)n);
+    int32_t nv = 0, nf = 0;
+    if (svo_bow_transform(bow, currentframe->f_descriptor.data(), n, 4, w.data(), v.data(), &nv, fv.data(), &nf) != SVO_OK)
+      throw std::runtime_error(std::string("svo_bow_transform: ") + svo_bow_last_error(bow));
+    v.resize((size_t)nv);
+    fv.resize((size_t)nf);
+    bow_words.push_back(std::move(w)); bow_vectors.push_back(std::move(v)); bow_features.push_back(std::move(fv));
+  }
   Tracklastframe();
   SaveTrajectoryAndDraw(f, f2);
   if (frame_num > 0) GetVelocity();

@@ -52,6 +52,17 @@ class Tracking {
   // the window's refined poses (Tcw, window x 16 float64) and points; nothing feeds back into the tracker.
   struct LocalBAResult { std::vector<double> Tcw; std::vector<svo_ba_point> points; svo_ba_stats stats; };
   LocalBAResult LocalBA(size_t first_frame, const svo_ba_params& params);
+  // Bag-of-words place recognition (svo_bow_*): loads a vocabulary in DBoW2's text format (trained on this library's descriptors:
+  // tools/bow_train.py).  From then on the frame-by-frame Track() computes every frame's words, BowVector and FeatureVector from
+  // frame::f_descriptor (svo_bow_transform, levelsup 4 as ORB-SLAM2's Frame::ComputeBoW) and keeps them: bow_vectors[k],
+  // bow_features[k], bow_words[k].  LoopCandidates(k, gap, top_k) are the top_k (1 .. 16) best-scoring frames of 0 .. k - gap - 1
+  // with a score above min_score (svo_bow_query_dev over the kept vectors).  Nothing feeds back into the tracker.  TrackBatch()
+  // keeps no descriptors on the host: with a vocabulary loaded it throws.
+  void LoadVocabulary(const std::string& path);
+  std::vector<svo_bow_cand> LoopCandidates(size_t frame_id, int gap, int top_k, double min_score = 0.0);
+  std::vector<std::vector<svo_bow_entry>> bow_vectors;
+  std::vector<std::vector<svo_bow_feature>> bow_features;
+  std::vector<std::vector<int32_t>> bow_words;
   // Raw (unrectified) input: reads LEFT.K / .D / .R / .P and RIGHT.* - or the flat Camera.k1 / k2 / p1 / p2 [/ k3] keys - of the
   // settings file (rect_settings.h), builds the maps on the device (svo_rect_create; the images' size is the context's) and
   // makes the left P's fx', fy', cx', cy' the tracker's camera (bf as the file has it).  From then on Track() rectifies every
@@ -101,6 +112,7 @@ class Tracking {
   struct DynCall { std::vector<float> lists; std::vector<int32_t> counts, dropped; };   // one TrackBatch()'s svo_track_dynamic_out arrays
   std::vector<std::unique_ptr<DynCall>> batch_dyn_calls;                               // (complete after svo_sync: FinishBatches collects them)
   svo_rect* rect = nullptr;               // LoadRectification
+  svo_bow* bow = nullptr;                 // LoadVocabulary (500 features a frame)
   svo_ba* ba = nullptr;                   // LocalBA's adjuster (500 records a frame, one window), made on first use
   struct RectBatch;                       // TrackBatch's device buffers behind the rectifier (Tracking.cc)
   RectBatch* rect_batch = nullptr;

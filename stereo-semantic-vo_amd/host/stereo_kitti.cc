@@ -19,6 +19,9 @@
 // --dynamic-dev / --dynamic-dev-bgr (with --pipelined only): the same loop inside the device-resident tracker (svo_track_dynamic,
 // Tracking::dynamic_dev), on gray or - needs --colour - on the colour left images; --write-dynamic writes the same files.
 // --dynamic-lk-bgr (implies --dynamic-lk; needs --colour): the same loop on the colour left images, svo_lk_track_bgr.
+// --bow <voc.txt> [--write-bow <dir>] [--loop-candidates <file> [--loop-gap G] [--loop-top K]] (frame by frame): bag-of-words place
+// recognition (svo_bow_*) with a vocabulary trained on this library's descriptors (tools/bow_train.py); each frame's vectors and
+// its best-scoring earlier frames.  The positional vocabulary argument stays ignored.
 // --write-map <dir> / --write-cloud <file.ply> (any mode): each frame's map points and observations (svo_track_map_out,
 // Tracking::map_out) to <dir>/NNNNNN.txt, "gid kp new u v depth X Y Z" per line; every new point of the run as an ASCII PLY.
 // --rectify <settings.yaml> (any mode, gray and --colour): the sequence's images are RAW; the file's LEFT.* / RIGHT.* blocks (or its
@@ -179,6 +182,24 @@ int main(int argc, char** argv) {
     argc -= take;
   }
   const bool map_out = !map_dir.empty() || !cloud_file.empty();
+  // --bow <voc.txt> (frame by frame): a vocabulary in DBoW2's text format (Tracking::LoadVocabulary; the positional vocabulary
+  // argument stays ignored); --write-bow <dir>: each frame's words, BowVector and FeatureVector to <dir>/NNNNNN.txt - "n_features
+  // n_words n_pairs", the words in one line, then "word value" (%.17g) per entry and "node feature" per pair;
+  // --loop-candidates <file> [--loop-gap G, default 100] [--loop-top K, default 4]: per frame "frame count", then "frame score".
+  std::string bow_voc, bow_dir, loop_file;
+  int loop_gap = 100, loop_top = 4;
+  for (int i = 1; i < argc;) {
+    const std::string a = argv[i];
+    int take = 0;
+    if (a == "--bow" && i + 1 < argc) { bow_voc = argv[i + 1]; take = 2; }
+    else if (a == "--write-bow" && i + 1 < argc) { bow_dir = argv[i + 1]; take = 2; }
+    else if (a == "--loop-candidates" && i + 1 < argc) { loop_file = argv[i + 1]; take = 2; }
+    else if (a == "--loop-gap" && i + 1 < argc) { loop_gap = atoi(argv[i + 1]); take = 2; }
+    else if (a == "--loop-top" && i + 1 < argc) { loop_top = atoi(argv[i + 1]); take = 2; }
+    if (!take) { ++i; continue; }
+    for (int j = i; j + take < argc; ++j) argv[j] = argv[j + take];
+    argc -= take;
+  }
   std::string rectify;   // --rectify <settings.yaml>
   for (int i = 1; i + 1 < argc; ++i)
     if (std::string(argv[i]) == "--rectify") {
@@ -210,6 +231,12 @@ int main(int argc, char** argv) {
     std::cerr << "--rectify with --pipelined: not with --dynamic-dev / --dynamic-dev-bgr / --write-map / --write-cloud" << std::endl;
     return 1;
   }
+  if (!bow_voc.empty() && pipelined) {
+    std::cerr << "--bow: frame by frame only (the pipelined mode keeps no descriptors on the host)" << std::endl;
+    return 1;
+  }
+  if ((!bow_dir.empty() || !loop_file.empty()) && bow_voc.empty()) { std::cerr << "--write-bow / --loop-candidates need --bow" << std::endl; return 1; }
+  if (!bow_voc.empty() && (loop_gap < 0 || loop_top < 1 || loop_top > 16)) { std::cerr << "--loop-gap G: >= 0; --loop-top K: 1 .. 16" << std::endl; return 1; }
   if (ba_window && (!pipelined || map_dir.empty())) { std::cerr << "--local-ba needs --pipelined and --write-map" << std::endl; return 1; }
   if (ba_window && !ba_step) ba_step = ba_window;
   if (ba_window && (ba_window < 2 || ba_window > 8 || ba_fixed < 1 || ba_fixed >= ba_window || ba_step < 1)) {
@@ -217,7 +244,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--rectify settings.yaml] [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--write-map dir] [--write-cloud file.ply] [--pipelined] [--local-ba W [--ba-step S] [--ba-fixed F]] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--rectify settings.yaml] [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--write-map dir] [--write-cloud file.ply] [--pipelined] [--local-ba W [--ba-step S] [--ba-fixed F]] [--bow voc.txt [--write-bow dir] [--loop-candidates file [--loop-gap G] [--loop-top K]]] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -257,6 +284,48 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if (!bow_voc.empty()) {
+    try {
+      mpTracker->LoadVocabulary(bow_voc);
+    } catch (const std::exception& e) {
+      std::cerr << e.what() << std::endl;
+      return 1;
+    }
+  }
+  std::ofstream loops;
+  if (!loop_file.empty()) {
+    loops.open(loop_file);
+    if (!loops) { std::cerr << "cannot write " << loop_file << std::endl; return 1; }
+  }
+  auto write_bow = [&](int ni) {
+    if (!bow_dir.empty()) {
+      std::stringstream ss;
+      ss << bow_dir << "/" << std::setfill('0') << std::setw(6) << ni << ".txt";
+      FILE* o = fopen(ss.str().c_str(), "w");
+      if (!o) { std::cerr << "cannot write " << ss.str() << std::endl; return false; }
+      const auto& w = mpTracker->bow_words[(size_t)ni];
+      const auto& v = mpTracker->bow_vectors[(size_t)ni];
+      const auto& fv = mpTracker->bow_features[(size_t)ni];
+      fprintf(o, "%zu %zu %zu\n", w.size(), v.size(), fv.size());
+      for (size_t i = 0; i < w.size(); ++i) fprintf(o, "%d%s", w[i], i + 1 == w.size() ? "" : " ");
+      fprintf(o, "\n");
+      for (const svo_bow_entry& e : v) fprintf(o, "%u %.17g\n", e.word, e.value);
+      for (const svo_bow_feature& e : fv) fprintf(o, "%u %u\n", e.node, e.feature);
+      fclose(o);
+    }
+    if (loops.is_open()) {
+      try {
+        const std::vector<svo_bow_cand> c = mpTracker->LoopCandidates((size_t)ni, loop_gap, loop_top);
+        loops << ni << " " << c.size() << "\n";
+        char buf[64];
+        for (const svo_bow_cand& e : c) { snprintf(buf, sizeof buf, "%d %.17g\n", e.frame, e.score); loops << buf; }
+      } catch (const std::exception& e) {
+        std::cerr << e.what() << std::endl;
+        return false;
+      }
+    }
+    return true;
+  };
   std::vector<svo_map_obs> cloud;
   auto write_map = [&](int ni) {
     const std::vector<svo_map_obs>& obs = mpTracker->Observations((size_t)ni);
@@ -409,6 +478,7 @@ int main(int argc, char** argv) {
     vTimesTrack[ni] = (float)std::chrono::duration_cast<std::chrono::duration<double>>(t2 - t1).count();
     if (!dynamic_dir.empty() && !write_dynamic(ni, mpTracker->lastframe.DY_keypoints)) return 1;
     if (map_out && !write_map(ni)) return 1;
+    if (!bow_voc.empty() && !write_bow(ni)) return 1;
   }
   if (!write_cloud()) return 1;
   f.close(); f2.close();
