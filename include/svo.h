@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_bow_* (DBoW2 bag-of-words place recognition on the device; see "bag-of-words
+#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_loop_* (SearchByBoW matching and the fixed-scale Sim3Solver on the device; see
+                              "loop verification" below); no existing entry changed.
+                              8, backward-compatible addition: svo_bow_* (DBoW2 bag-of-words place recognition on the device; see "bag-of-words
                               place recognition" below); no existing entry changed.
                               8, backward-compatible addition: svo_ba_* (windowed bundle adjustment on the device over the map records; see
                               "windowed bundle adjustment" below); no existing entry changed.
@@ -1259,8 +1261,8 @@ int svo_ba_window(svo_ba* ba, const svo_camera* cam, const svo_ba_params* params
  * ORB-SLAM2's published vocabulary does not fit these descriptors (it was trained on the learned rBRIEF pattern, this library
  * describes with include/svo_brief_pattern.h): a vocabulary has to be trained on the library's own descriptors.
  * Out of scope: an inverted index and DetectLoopCandidates' heuristics (covisibility groups, consistency over three keyframes),
- * SearchByBoW matching through the FeatureVector, Sim3 / loop correction or any feedback into the tracker, scorings other than
- * L1, DBoW2's binary / YAML formats, the many-sequence entries, descriptors other than 32 bytes. */
+ * loop correction or any feedback into the tracker, scorings other than L1, DBoW2's binary / YAML formats, the many-sequence
+ * entries, descriptors other than 32 bytes.  (SearchByBoW and the fixed-scale Sim3Solver: "loop verification" below.) */
 enum { SVO_BOW_TF_IDF = 0, SVO_BOW_TF = 1, SVO_BOW_IDF = 2, SVO_BOW_BINARY = 3 };   /* DBoW2's WeightingType */
 typedef struct svo_bow_entry {     /* 16 bytes: one word of a BowVector */
   uint32_t word, reserved;         /* reserved: 0 */
@@ -1331,6 +1333,107 @@ int svo_bow_query_dev(svo_bow* bow, const svo_bow_entry* d_vec, const int32_t* d
  * the nearest centre (the earliest among equals), d_dist its Hamming distance; either may be NULL.  Runs on the object's stream,
  * does not synchronise. */
 int svo_bow_assign_dev(svo_bow* bow, const uint8_t* d_desc, int n, const uint8_t* d_centres, int k, int32_t* d_idx, int32_t* d_dist);
+
+/* ---- loop verification (backward-compatible addition; no existing entry changed) --------------------------------------------
+ * What ORB-SLAM2's LoopClosing::ComputeSim3 does with a candidate, for stereo (scale fixed to 1): ORBmatcher::SearchByBoW over
+ * the two frames' FeatureVectors, then Sim3Solver - RANSAC over Horn's closed-form alignment of the matched map points.  The
+ * contract, operation by operation: DESIGN.md section 8 "Loop verification"; the numpy twin: tests/loop_ref.py.  Parity with a
+ * compiled ORB-SLAM2 is not pinned.  Two stated departures from it: samples come from splitmix64(seed + 3 * iteration + draw)
+ * instead of rand(), and the rotation is taken from the quaternion directly instead of through atan2 and cv::Rodrigues.
+ * Inputs are what the other entries leave in HBM: descriptors and keypoints (svo_frontend_batch_dev), FeatureVectors
+ * (svo_bow_transform_dev), candidates (svo_bow_query_dev), map records (svo_track_map_out) and the tracked poses.
+ * Out of scope: SearchBySim3, OptimizeSim3, scale estimation, covisibility consistency, loop correction and any feedback into
+ * the tracker; the many-sequence entries. */
+enum { SVO_LOOP_OK = 0, SVO_LOOP_FEW = 1, SVO_LOOP_REJECTED = 2, SVO_LOOP_SKIPPED = 3 };   /* svo_loop_result.status */
+typedef struct svo_loop_params {
+  int32_t th_low;             /* SearchByBoW: best distance < th_low, 1 .. 256 */
+  float nn_ratio;             /* and (float)best < nn_ratio * (float)second, (0, 1] */
+  int32_t check_orientation;  /* 1: keep the three fullest bins of the rotation histogram */
+  double prob;                /* RANSAC probability, (0, 1) */
+  int32_t min_inliers;        /* >= 3 */
+  int32_t max_iterations;     /* 1 .. 1024 */
+  uint64_t seed;              /* of the samples */
+  double chi2;                /* maxerr = chi2 * sigma2[octave] */
+  float scale_factor;         /* ORBextractor's, for sigma2 */
+  int32_t refine;             /* 1: one more alignment over all inliers of the result (not ORB-SLAM2) */
+} svo_loop_params;
+/* 50, 0.75f, 1, 0.99, 20, 300, seed 0x5eed5eed5eed5eed, 9.210, 1.2f, 0: what LoopClosing passes */
+int svo_loop_default_params(svo_loop_params* p);
+typedef struct svo_loop_result {   /* 168 bytes */
+  int32_t status;       /* OK: a hypothesis with more than min_inliers inliers ended the search; REJECTED: the bound was reached, the
+                           best so far is reported; FEW: fewer than min_inliers correspondences, the solver did not run; SKIPPED: a
+                           negative frame index.  FEW and SKIPPED: bound 0, visited 0, winner -1, n_inliers 0, sample -1, T12 = I */
+  int32_t n_matches;    /* N: the correspondences, matches whose two keypoints both have a map record */
+  int32_t bound;        /* iterations admitted for N */
+  int32_t visited;      /* iterations the sequential rule looked at */
+  int32_t winner;       /* the result's iteration */
+  int32_t n_inliers;
+  int32_t sample[3];    /* the winner's three correspondences (indices into the ascending-i1 list) */
+  int32_t reserved;     /* 0 */
+  double T12[16];       /* row-major 4 x 4: takes b's camera coordinates to a's */
+} svo_loop_result;
+typedef struct svo_loop svo_loop;
+
+/* A verifier for frames of up to max_kp keypoints (1 .. 2048) and calls of up to max_pairs pairs (1 .. 65535), with a stream and
+ * scratch of its own (96 bytes per keypoint of a pair).  Touches no device: the stream and the scratch come with the first call
+ * that needs them (SVO_E_NODEVICE / SVO_E_NOMEM are answered there), so the argument checks of every entry answer on a machine
+ * without a GPU.  svo_loop_last_error(NULL): the calling thread's last failure without an object. */
+int svo_loop_create(int device, int max_kp, int max_pairs, svo_loop** out);
+void svo_loop_destroy(svo_loop* loop);
+int svo_loop_sync(svo_loop* loop);
+void* svo_loop_stream(svo_loop* loop);
+const char* svo_loop_last_error(const svo_loop* loop);
+/* Records an event on `stream` (a hipStream_t of the object's device: svo_stream(ctx), svo_bow_stream(bow), ...) and makes the
+ * object's stream wait for it ON THE DEVICE: the calls that follow run behind the work enqueued on `stream` so far.  Nothing else
+ * is enqueued on `stream` and nothing of its owner waits. */
+int svo_loop_wait(svo_loop* loop, void* stream);
+/* The iteration bound of Sim3Solver::SetRansacParameters for N = 0 .. n_max correspondences (bounds holds n_max + 1 values; 0
+ * where N < min_inliers), with the host's log and pow.  Needs no object and no device: it is the table the device looks up. */
+int svo_loop_bounds(const svo_loop_params* params, int n_max, int32_t* bounds);
+
+/* The candidates of svo_bow_query_dev (Q x top_k records, Q counts; queries q0 .. q0 + Q - 1) as pairs: d_pairs holds
+ * Q * top_k x 2 int32, slot i * top_k + t is (q0 + i, cand.frame) for t < the count (clamped to 0 .. top_k) and a frame >= 0,
+ * else (-1, -1).  Q * top_k <= max_pairs, top_k 1 .. 16.  Does not synchronise. */
+int svo_loop_pairs_dev(svo_loop* loop, const svo_bow_cand* d_cand, const int32_t* d_cand_n, int q0, int Q, int top_k,
+                       int32_t* d_pairs);
+/* SearchByBoW(KF1 = a, KF2 = b) for n_pairs pairs (a, b) = d_pairs[2 p], d_pairs[2 p + 1] of frames resident in HBM: frame f's
+ * descriptors, keypoints and FeatureVector at f * kp_stride elements (d_n[f] keypoints, d_fv_n[f] pairs), its map records at
+ * f * obs_stride (d_obs_n[f] of them, ascending kp).  A count above its stride is clamped on the device, a negative one is 0.
+ * Outputs: d_match n_pairs x kp_stride int32 - for keypoint i1 of a the matched keypoint of b or -1, -1 from a's count to the
+ * stride; d_match_n n_pairs counts.  A pair with a negative frame index: all -1 and 0.  Does not synchronise. */
+int svo_loop_match_dev(svo_loop* loop, const svo_loop_params* params, const uint8_t* d_desc, const svo_kp* d_kp, const int32_t* d_n,
+                       int kp_stride, const svo_bow_feature* d_fv, const int32_t* d_fv_n, const svo_map_obs* d_obs,
+                       const int32_t* d_obs_n, int obs_stride, const int32_t* d_pairs, int n_pairs, int32_t* d_match,
+                       int32_t* d_match_n);
+/* The relative pose of every pair from its row of d_match (any -1 / index array of that layout; an entry outside 0 .. kp_stride - 1
+ * or naming a keypoint without a map record is no correspondence; this entry is not given the keypoint counts, so a record counts
+ * when its kp lies in 0 .. kp_stride - 1, where svo_loop_match_dev asks for kp below the frame's count d_n[f]).  Frame f's float32 4 x 4 Tcw stands at the start of element f
+ * of d_Tcw, elements pose_stride_bytes apart (as in svo_ba_windows_dev).  d_result n_pairs records; d_inliers (may be NULL)
+ * n_pairs x kp_stride bytes, 1 for the keypoints of a whose correspondence is an inlier of the result, all kp_stride written.
+ * A change of prob, min_inliers or max_iterations between calls rebuilds the bound table and synchronises the object's stream once;
+ * otherwise the call does not synchronise.  The same call gives the same bytes. */
+int svo_loop_solve_dev(svo_loop* loop, const svo_camera* cam, const svo_loop_params* params, const svo_kp* d_kp,
+                       const svo_map_obs* d_obs, const int32_t* d_obs_n, int obs_stride, const void* d_Tcw, int pose_stride_bytes,
+                       const int32_t* d_pairs, int n_pairs, const int32_t* d_match, int kp_stride, svo_loop_result* d_result,
+                       uint8_t* d_inliers);
+/* Both stages, one behind the other on the object's stream.
+ * SVO_E_INVALID before a device is touched, for the three entries above (svo_loop_last_error names the argument): a NULL
+ * pointer (d_inliers excepted), d_desc not 4-byte, d_fv not 8-byte, d_obs not 16-byte aligned, kp_stride or obs_stride outside
+ * 1 .. max_kp, n_pairs outside 1 .. max_pairs, th_low outside 1 .. 256, nn_ratio not in (0, 1], min_inliers < 3, max_iterations
+ * outside 1 .. 1024, prob not in (0, 1), a non-finite or non-positive chi2 or scale_factor, a non-finite camera value, fx or
+ * fy <= 0, a pose stride below 64 or not a multiple of 4. */
+int svo_loop_verify_dev(svo_loop* loop, const svo_camera* cam, const svo_loop_params* params, const uint8_t* d_desc,
+                        const svo_kp* d_kp, const int32_t* d_n, int kp_stride, const svo_bow_feature* d_fv, const int32_t* d_fv_n,
+                        const svo_map_obs* d_obs, const int32_t* d_obs_n, int obs_stride, const void* d_Tcw, int pose_stride_bytes,
+                        const int32_t* d_pairs, int n_pairs, int32_t* d_match, int32_t* d_match_n, svo_loop_result* d_result,
+                        uint8_t* d_inliers);
+/* One pair host to host: every array holds frame a, then frame b (desc 2 x kp_stride x 32 bytes, kp and fv 2 x kp_stride records,
+ * obs 2 x obs_stride records, the counts 2 values, Tcw 2 x 16 float32); match (kp_stride, may be NULL), result, inliers
+ * (kp_stride, may be NULL).  Synchronises. */
+int svo_loop_verify(svo_loop* loop, const svo_camera* cam, const svo_loop_params* params, const uint8_t* desc, const svo_kp* kp,
+                    const int32_t* n, int kp_stride, const svo_bow_feature* fv, const int32_t* fv_n, const svo_map_obs* obs,
+                    const int32_t* obs_n, int obs_stride, const float* Tcw, int32_t* match, svo_loop_result* result,
+                    uint8_t* inliers);
 
 #ifdef __cplusplus
 }

@@ -57,6 +57,11 @@ BOW_FEATURE_DTYPE = np.dtype([("node", "<u4"), ("feature", "<u4")])
 BOW_CAND_DTYPE = np.dtype([("frame", "<i4"), ("reserved", "<i4"), ("score", "<f8")])
 BOW_TF_IDF, BOW_TF, BOW_IDF, BOW_BINARY = 0, 1, 2, 3   # DBoW2's WeightingType
 
+# svo_loop_result (include/svo.h): the relative pose of a verified pair (svo_loop_solve_dev)
+LOOP_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_matches", "<i4"), ("bound", "<i4"), ("visited", "<i4"), ("winner", "<i4"),
+                              ("n_inliers", "<i4"), ("sample", "<i4", (3,)), ("reserved", "<i4"), ("T12", "<f8", (16,))])
+LOOP_OK, LOOP_FEW, LOOP_REJECTED, LOOP_SKIPPED = 0, 1, 2, 3   # svo_loop_result.status
+
 # Every symbol include/svo.h declares (checked by tests/test_abi.py without a GPU).
 ABI_SYMBOLS = [
     "svo_abi_version", "svo_strerror", "svo_last_error", "svo_create", "svo_destroy", "svo_sync",
@@ -89,6 +94,9 @@ ABI_SYMBOLS = [
     "svo_bow_create_from_text", "svo_bow_create", "svo_bow_save_text", "svo_bow_describe", "svo_bow_destroy", "svo_bow_sync",
     "svo_bow_stream", "svo_bow_last_error", "svo_bow_transform_dev", "svo_bow_transform", "svo_bow_score_dev", "svo_bow_query_dev",
     "svo_bow_assign_dev",
+    "svo_loop_default_params", "svo_loop_create", "svo_loop_destroy", "svo_loop_sync", "svo_loop_stream", "svo_loop_last_error",
+    "svo_loop_wait", "svo_loop_bounds", "svo_loop_pairs_dev", "svo_loop_match_dev", "svo_loop_solve_dev", "svo_loop_verify_dev",
+    "svo_loop_verify",
 ]
 
 PNP_RULE_W = 6 + 5 * 101   # SVO_PNP_RULE_W (include/svo.h)
@@ -1520,3 +1528,147 @@ class Vocabulary:
     @property
     def stream(self):
         return self.lib.svo_bow_stream(self.h)
+
+
+# ---- loop verification (svo_loop_* in include/svo.h; the contract: DESIGN.md section 8 "Loop verification") ---------------------------------
+class LoopParams(C.Structure):
+    """svo_loop_params; LoopParams.default() is svo_loop_default_params, keyword arguments replace single fields."""
+    _fields_ = [("th_low", C.c_int32), ("nn_ratio", C.c_float), ("check_orientation", C.c_int32), ("prob", C.c_double),
+                ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("seed", C.c_uint64), ("chi2", C.c_double),
+                ("scale_factor", C.c_float), ("refine", C.c_int32)]
+
+    @classmethod
+    def default(cls, **kw):
+        p = cls()
+        rc = load_library().svo_loop_default_params(C.byref(p))
+        if rc != 0:
+            raise SvoError("svo_loop_default_params failed (%d)" % rc)
+        for k, v in kw.items():
+            if k not in dict(cls._fields_):
+                raise TypeError("LoopParams has no field %r" % k)
+            setattr(p, k, v)
+        return p
+
+
+def loop_bounds(params, n_max):
+    """svo_loop_bounds: the iteration bound for N = 0 .. n_max correspondences ((n_max + 1,) int32).  Needs no device."""
+    lib = LoopVerifier._bind()
+    out = np.zeros(int(n_max) + 1, np.int32)
+    rc = lib.svo_loop_bounds(C.addressof(params), int(n_max), _p(out))
+    if rc != 0:
+        raise SvoError("svo_loop_bounds: %s: %s" % (lib.svo_strerror(rc).decode(), lib.svo_loop_last_error(None).decode()))
+    return out
+
+
+class LoopVerifier:
+    """Loop verification on one GPU (wraps svo_loop): SearchByBoW matches of frame pairs through their FeatureVectors and the
+    relative pose of each pair by RANSAC over Horn's alignment of the matched map points.  An object with a stream and scratch of
+    its own; creating it touches no device."""
+
+    @staticmethod
+    def _bind():
+        lib = load_library()
+        lib.svo_loop_last_error.restype = C.c_char_p
+        lib.svo_loop_last_error.argtypes = [C.c_void_p]
+        lib.svo_loop_default_params.argtypes = [C.c_void_p]
+        lib.svo_loop_create.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        lib.svo_loop_destroy.argtypes = [C.c_void_p]
+        lib.svo_loop_destroy.restype = None
+        lib.svo_loop_sync.argtypes = [C.c_void_p]
+        lib.svo_loop_stream.restype = C.c_void_p
+        lib.svo_loop_stream.argtypes = [C.c_void_p]
+        lib.svo_loop_wait.argtypes = [C.c_void_p, C.c_void_p]
+        lib.svo_loop_bounds.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        lib.svo_loop_pairs_dev.argtypes = [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]
+        lib.svo_loop_match_dev.argtypes = [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.svo_loop_solve_dev.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p]
+        lib.svo_loop_verify_dev.argtypes = [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                                                            C.c_int] + [C.c_void_p] * 4
+        lib.svo_loop_verify.argtypes = [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 4
+        return lib
+
+    def __init__(self, max_kp=500, max_pairs=1, device=0):
+        self.lib = lib = self._bind()
+        self.max_kp, self.max_pairs = int(max_kp), int(max_pairs)
+        h = C.c_void_p()
+        rc = lib.svo_loop_create(int(device), self.max_kp, self.max_pairs, C.byref(h))
+        if rc != 0:
+            raise SvoError("svo_loop_create: %s: %s" % (lib.svo_strerror(rc).decode(), lib.svo_loop_last_error(None).decode()))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.svo_loop_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            raise SvoError("%s: %s: %s" % (what, self.lib.svo_strerror(rc).decode(), self.lib.svo_loop_last_error(self.h).decode()))
+
+    def wait(self, stream):
+        """svo_loop_wait: the calls that follow run behind what `stream` (a hipStream_t as an int, e.g. Svo.stream or
+        Vocabulary.stream) holds so far; nothing of its owner waits."""
+        self._chk(self.lib.svo_loop_wait(self.h, C.c_void_p(stream)), "svo_loop_wait")
+
+    def pairs_dev(self, d_cand, d_cand_n, q0, Q, top_k, d_pairs):
+        """svo_loop_pairs_dev: the candidates of Vocabulary.query_dev as (Q * top_k, 2) int32 pairs.  Does not synchronise."""
+        self._chk(self.lib.svo_loop_pairs_dev(self.h, _dptr(d_cand), _dptr(d_cand_n), int(q0), int(Q), int(top_k), _dptr(d_pairs)),
+                  "svo_loop_pairs_dev")
+
+    def match_dev(self, params, d_desc, d_kp, d_n, kp_stride, d_fv, d_fv_n, d_obs, d_obs_n, obs_stride, d_pairs, n_pairs, d_match,
+                  d_match_n):
+        """svo_loop_match_dev on device memory (torch tensors or device pointers as ints).  Does not synchronise."""
+        self._chk(self.lib.svo_loop_match_dev(self.h, C.addressof(params), _dptr(d_desc), _dptr(d_kp), _dptr(d_n), int(kp_stride),
+                                              _dptr(d_fv), _dptr(d_fv_n), _dptr(d_obs), _dptr(d_obs_n), int(obs_stride), _dptr(d_pairs),
+                                              int(n_pairs), _dptr(d_match), _dptr(d_match_n)), "svo_loop_match_dev")
+
+    def solve_dev(self, cam, params, d_kp, d_obs, d_obs_n, obs_stride, d_Tcw, pose_stride_bytes, d_pairs, n_pairs, d_match, kp_stride,
+                  d_result, d_inliers=None):
+        """svo_loop_solve_dev: d_result (n_pairs,) LOOP_RESULT_DTYPE records, d_inliers (n_pairs, kp_stride) uint8 or None."""
+        self._chk(self.lib.svo_loop_solve_dev(self.h, C.addressof(cam), C.addressof(params), _dptr(d_kp), _dptr(d_obs), _dptr(d_obs_n),
+                                              int(obs_stride), _dptr(d_Tcw), int(pose_stride_bytes), _dptr(d_pairs), int(n_pairs),
+                                              _dptr(d_match), int(kp_stride), _dptr(d_result), _dptr(d_inliers)), "svo_loop_solve_dev")
+
+    def verify_dev(self, cam, params, d_desc, d_kp, d_n, kp_stride, d_fv, d_fv_n, d_obs, d_obs_n, obs_stride, d_Tcw, pose_stride_bytes,
+                   d_pairs, n_pairs, d_match, d_match_n, d_result, d_inliers=None):
+        """svo_loop_verify_dev: both stages on the object's stream.  Does not synchronise."""
+        self._chk(self.lib.svo_loop_verify_dev(self.h, C.addressof(cam), C.addressof(params), _dptr(d_desc), _dptr(d_kp), _dptr(d_n),
+                                               int(kp_stride), _dptr(d_fv), _dptr(d_fv_n), _dptr(d_obs), _dptr(d_obs_n), int(obs_stride),
+                                               _dptr(d_Tcw), int(pose_stride_bytes), _dptr(d_pairs), int(n_pairs), _dptr(d_match),
+                                               _dptr(d_match_n), _dptr(d_result), _dptr(d_inliers)), "svo_loop_verify_dev")
+
+    def verify(self, cam, params, desc, kp, n, fv, fv_n, obs, obs_n, Tcw):
+        """One pair (a, b) host to host: desc (2, S, 32) uint8, kp (2, S) KP_DTYPE, n (2,), fv (2, S) BOW_FEATURE_DTYPE, fv_n (2,),
+        obs (2, So) MAP_OBS_DTYPE, obs_n (2,), Tcw (2, 4, 4) -> (match (S,) int32, result (LOOP_RESULT_DTYPE scalar),
+        inliers (S,) uint8).  Synchronises."""
+        desc = np.ascontiguousarray(desc, np.uint8)
+        if desc.ndim != 3 or desc.shape[0] != 2 or desc.shape[2] != 32:
+            raise ValueError("desc must be (2, kp_stride, 32)")
+        S = int(desc.shape[1])
+        kp = np.ascontiguousarray(kp, KP_DTYPE)
+        fv = np.ascontiguousarray(fv, BOW_FEATURE_DTYPE)
+        obs = np.ascontiguousarray(obs, MAP_OBS_DTYPE)
+        if kp.shape != (2, S) or fv.shape != (2, S) or obs.ndim != 2 or obs.shape[0] != 2:
+            raise ValueError("kp and fv must be (2, kp_stride), obs (2, obs_stride)")
+        n, fv_n, obs_n = (np.ascontiguousarray(x, np.int32).reshape(2) for x in (n, fv_n, obs_n))
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(2, 16)
+        match = np.zeros(S, np.int32)
+        res = np.zeros(1, LOOP_RESULT_DTYPE)
+        inl = np.zeros(S, np.uint8)
+        self._chk(self.lib.svo_loop_verify(self.h, C.addressof(cam), C.addressof(params), _p(desc), _p(kp), _p(n), S, _p(fv), _p(fv_n),
+                                           _p(obs), _p(obs_n), int(obs.shape[1]), _p(T), _p(match), _p(res), _p(inl)), "svo_loop_verify")
+        return match, res[0], inl
+
+    def sync(self):
+        self._chk(self.lib.svo_loop_sync(self.h), "svo_loop_sync")
+
+    @property
+    def stream(self):
+        return self.lib.svo_loop_stream(self.h)

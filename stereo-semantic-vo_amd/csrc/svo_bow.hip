@@ -21,7 +21,7 @@
 // every run.
 //
 // Not here: an inverted index and ORB-SLAM2's DetectLoopCandidates heuristics (covisibility groups, consistency over three
-// keyframes), SearchByBoW matching through the FeatureVector, Sim3 / loop correction or any feedback into the tracker, scorings
+// keyframes), loop correction or any feedback into the tracker (SearchByBoW and the fixed-scale Sim3Solver: svo_loop.hip), scorings
 // other than L1, DBoW2's binary / YAML formats, the many-sequence entries, descriptors other than 32 bytes.
 #include <errno.h>
 #include <limits.h>

@@ -140,6 +140,7 @@ Tracking::~Tracking() {
   if (rect) svo_rect_destroy(rect);
   if (ba) svo_ba_destroy(ba);
   if (bow) svo_bow_destroy(bow);
+  if (loop) svo_loop_destroy(loop);
   if (ctx_batch) svo_destroy(ctx_batch);
   if (ctx_map) svo_destroy(ctx_map);
   svo_destroy(ctx);
@@ -304,6 +305,43 @@ std::vector<svo_bow_cand> Tracking::LoopCandidates(size_t frame_id, int gap, int
   out.resize((size_t)n);
   return out;
 }
+svo_loop_result Tracking::VerifyLoop(size_t frame_id, size_t cand_frame, const svo_loop_params& params, std::vector<int32_t>* match) {
+  if (!bow) throw std::runtime_error("Tracking::VerifyLoop: no vocabulary (LoadVocabulary)");
+  if (!map_out) throw std::runtime_error("Tracking::VerifyLoop: needs map_out (set before the first Track())");
+  const size_t have = std::min(std::min(loop_keypoints.size(), bow_features.size()), std::min(observations.size(), map_poses.size()));
+  if (frame_id >= have || cand_frame >= have) throw std::runtime_error("Tracking::VerifyLoop: no such frame (Track() called?)");
+  const size_t S = 500, fr[2] = {frame_id, cand_frame};
+  std::vector<uint8_t> desc(2 * S * 32, 0);
+  std::vector<svo_kp> kp(2 * S, svo_kp{});
+  std::vector<svo_bow_feature> fv(2 * S, svo_bow_feature{});
+  std::vector<svo_map_obs> obs(2 * S, svo_map_obs{});
+  std::vector<float> Tcw(32);
+  int32_t n[2], fv_n[2], obs_n[2];
+  for (int s = 0; s < 2; ++s) {
+    const size_t f = fr[s];
+    const std::vector<svo_kp>& k = loop_keypoints[f];
+    const std::vector<svo_map_obs>& o = observations[f];
+    if (k.size() > S || bow_features[f].size() > S || o.size() > S) throw std::runtime_error("Tracking::VerifyLoop: more than 500 keypoints in a frame");
+    for (const svo_map_obs& r : o)      // the device tracker's keypoint list is the classes': a record's kp names the same keypoint
+      if (r.kp < 0 || (size_t)r.kp >= k.size() || k[(size_t)r.kp].x != r.u || k[(size_t)r.kp].y != r.v)
+        throw std::runtime_error("Tracking::VerifyLoop: an observation does not name the kept keypoint");
+    std::copy(k.begin(), k.end(), kp.begin() + s * S);
+    std::copy(loop_descriptors[f].begin(), loop_descriptors[f].end(), desc.begin() + s * S * 32);
+    std::copy(bow_features[f].begin(), bow_features[f].end(), fv.begin() + s * S);
+    std::copy(o.begin(), o.end(), obs.begin() + s * S);
+    std::copy(map_poses[f].begin(), map_poses[f].end(), Tcw.begin() + s * 16);
+    n[s] = (int32_t)k.size(); fv_n[s] = (int32_t)bow_features[f].size(); obs_n[s] = (int32_t)o.size();
+  }
+  if (!loop && svo_loop_create(device, (int)S, 1, &loop) != SVO_OK)
+    throw std::runtime_error(std::string("Tracking::VerifyLoop: ") + svo_loop_last_error(nullptr));
+  std::vector<int32_t> m(S, -1);
+  svo_loop_result r;
+  if (svo_loop_verify(loop, &K, &params, desc.data(), kp.data(), n, (int)S, fv.data(), fv_n, obs.data(), obs_n, (int)S, Tcw.data(),
+                      m.data(), &r, nullptr) != SVO_OK)
+    throw std::runtime_error(std::string("Tracking::VerifyLoop: ") + svo_loop_last_error(loop));
+  if (match) match->assign(m.begin(), m.begin() + n[0]);
+  return r;
+}
 const svo_map_obs* Tracking::ObservationOf(size_t frame_id, int kp) const {
   const std::vector<svo_map_obs>& o = Observations(frame_id);   // (ascending kp)
   const auto it = std::lower_bound(o.begin(), o.end(), kp, [](const svo_map_obs& r, int j) { return r.kp < j; });
@@ -334,6 +372,7 @@ void Tracking::MapFrame(const GrayImage& imLeft, const GrayImage& imRight, const
   if (rc != SVO_OK) throw std::runtime_error(std::string("Tracking::map_out: ") + svo_last_error(ctx_map));
   obs.resize((size_t)count);
   observations.push_back(std::move(obs));
+  map_poses.emplace_back(res.Tcw, res.Tcw + 16);
 }
 
 void Tracking::init() {
@@ -474,6 +513,10 @@ void Tracking::TrackImages(const GrayImage& imLeft, const GrayImage& imRight, co
     v.resize((size_t)nv);
     fv.resize((size_t)nf);
     bow_words.push_back(std::move(w)); bow_vectors.push_back(std::move(v)); bow_features.push_back(std::move(fv));
+    if (map_out) {                        // what VerifyLoop reads next to the FeatureVector
+      loop_keypoints.emplace_back(currentframe->keypoints_l.begin(), currentframe->keypoints_l.begin() + n);
+      loop_descriptors.emplace_back(currentframe->f_descriptor.begin(), currentframe->f_descriptor.begin() + (size_t)n * 32);
+    }
   }
   Tracklastframe();
   SaveTrajectoryAndDraw(f, f2);

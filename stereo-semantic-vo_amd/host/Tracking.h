@@ -59,6 +59,18 @@ class Tracking {
   // with a score above min_score (svo_bow_query_dev over the kept vectors).  Nothing feeds back into the tracker.  TrackBatch()
   // keeps no descriptors on the host: with a vocabulary loaded it throws.
   void LoadVocabulary(const std::string& path);
+  // Loop verification (svo_loop_verify; ORB-SLAM2's ComputeSim3 for stereo): is cand_frame the place of frame_id, and where did
+  // the camera stand?  SearchByBoW over the two frames' kept FeatureVectors (bow_features), then RANSAC over Horn's alignment of
+  // the matched map points: KF1 = frame_id, KF2 = cand_frame, the result's T12 takes cand_frame's camera coordinates to
+  // frame_id's.  Host to host from what Track() keeps per frame once a vocabulary is loaded and map_out is set: keypoints and
+  // descriptors (loop_keypoints, loop_descriptors: the device tracker beside the classes extracts the same list, so an
+  // Observations record's kp indexes them - checked on u, v), Observations and the device tracker's poses (map_poses, the world
+  // Observations' positions live in).  match (may be null): per keypoint of frame_id the matched keypoint of cand_frame or -1.
+  // Needs map_out and a vocabulary, throws otherwise.  Nothing feeds back into the tracker.
+  svo_loop_result VerifyLoop(size_t frame_id, size_t cand_frame, const svo_loop_params& params, std::vector<int32_t>* match = nullptr);
+  std::vector<std::vector<svo_kp>> loop_keypoints;
+  std::vector<std::vector<uint8_t>> loop_descriptors;
+  std::vector<std::vector<float>> map_poses;   // per tracked frame: svo_track_result.Tcw of Track()'s device tracker (map_out)
   std::vector<svo_bow_cand> LoopCandidates(size_t frame_id, int gap, int top_k, double min_score = 0.0);
   std::vector<std::vector<svo_bow_entry>> bow_vectors;
   std::vector<std::vector<svo_bow_feature>> bow_features;
@@ -113,6 +125,7 @@ class Tracking {
   std::vector<std::unique_ptr<DynCall>> batch_dyn_calls;                               // (complete after svo_sync: FinishBatches collects them)
   svo_rect* rect = nullptr;               // LoadRectification
   svo_bow* bow = nullptr;                 // LoadVocabulary (500 features a frame)
+  svo_loop* loop = nullptr;               // VerifyLoop's verifier (500 keypoints a frame, one pair), made on first use
   svo_ba* ba = nullptr;                   // LocalBA's adjuster (500 records a frame, one window), made on first use
   struct RectBatch;                       // TrackBatch's device buffers behind the rectifier (Tracking.cc)
   RectBatch* rect_batch = nullptr;

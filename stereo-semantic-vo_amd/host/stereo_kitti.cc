@@ -19,7 +19,8 @@
 // --dynamic-dev / --dynamic-dev-bgr (with --pipelined only): the same loop inside the device-resident tracker (svo_track_dynamic,
 // Tracking::dynamic_dev), on gray or - needs --colour - on the colour left images; --write-dynamic writes the same files.
 // --dynamic-lk-bgr (implies --dynamic-lk; needs --colour): the same loop on the colour left images, svo_lk_track_bgr.
-// --bow <voc.txt> [--write-bow <dir>] [--loop-candidates <file> [--loop-gap G] [--loop-top K]] (frame by frame): bag-of-words place
+// --bow <voc.txt> [--write-bow <dir>] [--loop-candidates <file> [--loop-gap G] [--loop-top K] [--loop-verify <file>]] (frame by
+// frame; --loop-verify, with --write-map: every candidate through Tracking::VerifyLoop - matches, inliers, T12): bag-of-words place
 // recognition (svo_bow_*) with a vocabulary trained on this library's descriptors (tools/bow_train.py); each frame's vectors and
 // its best-scoring earlier frames.  The positional vocabulary argument stays ignored.
 // --write-map <dir> / --write-cloud <file.ply> (any mode): each frame's map points and observations (svo_track_map_out,
@@ -186,7 +187,9 @@ int main(int argc, char** argv) {
   // argument stays ignored); --write-bow <dir>: each frame's words, BowVector and FeatureVector to <dir>/NNNNNN.txt - "n_features
   // n_words n_pairs", the words in one line, then "word value" (%.17g) per entry and "node feature" per pair;
   // --loop-candidates <file> [--loop-gap G, default 100] [--loop-top K, default 4]: per frame "frame count", then "frame score".
-  std::string bow_voc, bow_dir, loop_file;
+  // --loop-verify <file> (with --loop-candidates and --write-map): every candidate through Tracking::VerifyLoop with the default
+  // parameters, one line each: "frame candidate status n_matches n_inliers" and T12's 16 values (%.17g)
+  std::string bow_voc, bow_dir, loop_file, verify_file;
   int loop_gap = 100, loop_top = 4;
   for (int i = 1; i < argc;) {
     const std::string a = argv[i];
@@ -194,6 +197,7 @@ int main(int argc, char** argv) {
     if (a == "--bow" && i + 1 < argc) { bow_voc = argv[i + 1]; take = 2; }
     else if (a == "--write-bow" && i + 1 < argc) { bow_dir = argv[i + 1]; take = 2; }
     else if (a == "--loop-candidates" && i + 1 < argc) { loop_file = argv[i + 1]; take = 2; }
+    else if (a == "--loop-verify" && i + 1 < argc) { verify_file = argv[i + 1]; take = 2; }
     else if (a == "--loop-gap" && i + 1 < argc) { loop_gap = atoi(argv[i + 1]); take = 2; }
     else if (a == "--loop-top" && i + 1 < argc) { loop_top = atoi(argv[i + 1]); take = 2; }
     if (!take) { ++i; continue; }
@@ -236,6 +240,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   if ((!bow_dir.empty() || !loop_file.empty()) && bow_voc.empty()) { std::cerr << "--write-bow / --loop-candidates need --bow" << std::endl; return 1; }
+  if (!verify_file.empty() && (loop_file.empty() || map_dir.empty())) { std::cerr << "--loop-verify needs --loop-candidates and --write-map" << std::endl; return 1; }
   if (!bow_voc.empty() && (loop_gap < 0 || loop_top < 1 || loop_top > 16)) { std::cerr << "--loop-gap G: >= 0; --loop-top K: 1 .. 16" << std::endl; return 1; }
   if (ba_window && (!pipelined || map_dir.empty())) { std::cerr << "--local-ba needs --pipelined and --write-map" << std::endl; return 1; }
   if (ba_window && !ba_step) ba_step = ba_window;
@@ -244,7 +249,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   if (argc != 4) {
-    std::cerr << "Usage: ./stereo_kitti [--rectify settings.yaml] [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--write-map dir] [--write-cloud file.ply] [--pipelined] [--local-ba W [--ba-step S] [--ba-fixed F]] [--bow voc.txt [--write-bow dir] [--loop-candidates file [--loop-gap G] [--loop-top K]]] path_to_vocabulary"
+    std::cerr << "Usage: ./stereo_kitti [--rectify settings.yaml] [--detect cfg weights [threshold]] [--write-boxes dir] [--colour] [--depth-source 0..3] [--sgbm-colour] [--sgbm-mode sgbm|hh] [--dynamic-lk | --dynamic-lk-bgr | --dynamic-dev | --dynamic-dev-bgr] [--write-dynamic dir] [--write-map dir] [--write-cloud file.ply] [--pipelined] [--local-ba W [--ba-step S] [--ba-fixed F]] [--bow voc.txt [--write-bow dir] [--loop-candidates file [--loop-gap G] [--loop-top K] [--loop-verify file]]] path_to_vocabulary"
                  " path_to_settings path_to_sequence [frames_per_call]" << std::endl;
     return 1;
   }
@@ -297,6 +302,11 @@ int main(int argc, char** argv) {
     loops.open(loop_file);
     if (!loops) { std::cerr << "cannot write " << loop_file << std::endl; return 1; }
   }
+  std::ofstream verified;
+  if (!verify_file.empty()) {
+    verified.open(verify_file);
+    if (!verified) { std::cerr << "cannot write " << verify_file << std::endl; return 1; }
+  }
   auto write_bow = [&](int ni) {
     if (!bow_dir.empty()) {
       std::stringstream ss;
@@ -319,6 +329,16 @@ int main(int argc, char** argv) {
         loops << ni << " " << c.size() << "\n";
         char buf[64];
         for (const svo_bow_cand& e : c) { snprintf(buf, sizeof buf, "%d %.17g\n", e.frame, e.score); loops << buf; }
+        if (verified.is_open()) {
+          svo_loop_params lp;
+          svo_loop_default_params(&lp);
+          for (const svo_bow_cand& e : c) {
+            const svo_loop_result r = mpTracker->VerifyLoop((size_t)ni, (size_t)e.frame, lp);
+            verified << ni << " " << e.frame << " " << r.status << " " << r.n_matches << " " << r.n_inliers;
+            for (int j = 0; j < 16; ++j) { snprintf(buf, sizeof buf, " %.17g", r.T12[j]); verified << buf; }
+            verified << "\n";
+          }
+        }
       } catch (const std::exception& e) {
         std::cerr << e.what() << std::endl;
         return false;
