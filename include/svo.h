@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_loop_* (SearchByBoW matching and the fixed-scale Sim3Solver on the device; see
+#define SVO_ABI_VERSION 8   /* 8, backward-compatible addition: svo_debug_msa_plan (which kernels the last MSA tree aggregation ran as; a host-side
+                              probe, see there); no existing entry changed.
+                              8, backward-compatible addition: svo_loop_* (SearchByBoW matching and the fixed-scale Sim3Solver on the device; see
                               "loop verification" below); no existing entry changed.
                               8, backward-compatible addition: svo_bow_* (DBoW2 bag-of-words place recognition on the device; see "bag-of-words
                               place recognition" below); no existing entry changed.
@@ -787,6 +789,16 @@ int svo_msa_solve(svo_ctx* ctx, const uint8_t* bgrL, const uint8_t* bgrR, int wi
  * calls of svo_msa_solve with scale 1.  Synchronises before it returns. */
 int svo_msa_batch_dev(svo_ctx* ctx, const uint8_t* d_L, const uint8_t* d_R, int stride, int width, int height, int B, int d,
                       float* d_disp);
+
+/* Diagnostics (a backward-compatible ABI-8 addition; host side only, touches no device state): how the LAST tree aggregation
+ * planned on this context ran - svo_msa_tree_dp, svo_msa_solve or a chunk of svo_msa_batch_dev.  out[0] = 1: one launch per
+ * aggregation (a workgroup per disparity walks the levels, level values in LDS), 0: one launch per level (the widest level or
+ * the level table does not fit 150 KB of LDS, a node has more than 255 children, the sequence does not list siblings in
+ * child-list order, the transposing gather's tile 64 * (D + 1) * 4 bytes exceeds 64 KB, or SVO_MSA_LEVEL_LAUNCHES is set),
+ * -1: nothing planned yet.  out[1] = the widest level over the trees, out[2] = the deepest tree's number of levels, out[3] =
+ * the LDS bytes the one-launch kernel needs for those two (8 * (256 + 2 * out[1]) + 4 * (out[2] + 2)), out[4] = the state of
+ * its opt-in above 64 KB on this context (0 not tried, 1 granted, -1 refused). */
+int svo_debug_msa_plan(svo_ctx* ctx, int32_t out[5]);
 
 /* ---- semi-global block matching (ABI-7 additions; no existing entry changed) -----------------------------------------------
  * The reference's third dense solver: the body of frame::ElasMatch (src/frame.cc:94-120) is cv::StereoSGBM::create(0, 16, 3)

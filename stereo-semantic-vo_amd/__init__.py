@@ -75,7 +75,7 @@ ABI_SYMBOLS = [
     "svo_frontend_batch_dev", "svo_track_batch_dev", "svo_profile_enable", "svo_profile_reset",
     "svo_profile_get",
     "svo_elas_default_params", "svo_elas_process", "svo_elas_process_ex", "svo_elas_delaunay",
-    "svo_ctmf", "svo_track_multi_reset", "svo_track_multi_step_dev", "svo_track_tail_dev", "svo_track_overflowed", "svo_track_epnp_fallbacks", "svo_debug_stream_probe", "svo_debug_stream_pipes", "svo_track_sharded_dev", "svo_elas_batch_dev", "svo_msa_init", "svo_msa_tree", "svo_msa_tree_dp", "svo_msa_wta", "svo_msa_lrcheck", "svo_msa_solve", "svo_msa_batch_dev",
+    "svo_ctmf", "svo_track_multi_reset", "svo_track_multi_step_dev", "svo_track_tail_dev", "svo_track_overflowed", "svo_track_epnp_fallbacks", "svo_debug_stream_probe", "svo_debug_stream_pipes", "svo_track_sharded_dev", "svo_elas_batch_dev", "svo_msa_init", "svo_msa_tree", "svo_msa_tree_dp", "svo_msa_wta", "svo_msa_lrcheck", "svo_msa_solve", "svo_msa_batch_dev", "svo_debug_msa_plan",
     "svo_create_ex", "svo_stream_mode", "svo_track_batch_host", "svo_track_sharded_host", "svo_frontend_batch_host",
     "svo_bgr_to_gray", "svo_track_frame_bgr", "svo_track_batch_bgr_dev", "svo_track_batch_bgr_host",
     "svo_det_describe", "svo_det_last_error", "svo_det_create", "svo_det_destroy", "svo_det_detect", "svo_det_batch_dev",
@@ -755,6 +755,14 @@ class Svo:
         out = np.zeros((H, W), np.uint8)
         self._chk(self.lib.svo_msa_solve(self.h, _p(a), _p(b), W, H, 3 * W, int(d), int(scale), _p(out)))
         return out
+
+    def msa_plan(self):
+        """svo_debug_msa_plan: how the last tree aggregation planned on this context ran - dict(bfs = 1 one launch per aggregation /
+        0 one launch per level / -1 none yet, maxw, levels, lds = bytes the one-launch kernel needs, lds_state = its opt-in above
+        64 KB: 0 not tried, 1 granted, -1 refused)."""
+        out = (C.c_int32 * 5)()
+        self._chk(self.lib.svo_debug_msa_plan(self.h, out))
+        return dict(zip(("bfs", "maxw", "levels", "lds", "lds_state"), (int(v) for v in out)))
 
     # ---- semi-global block matching (include/svo.h: svo_sgbm_*; the body of the reference's frame::ElasMatch) ----
     # mode: SGBM_MODE_SGBM (0, five directions, what the reference sets) or SGBM_MODE_HH (1, all eight directions in two passes)

@@ -176,6 +176,7 @@ struct svo_ctx {
   std::vector<hipEvent_t> ev_frame;        // index chain of frame f finished (recorded on `stream_idx`)
   uint16_t* d_pnp_subsets = nullptr;   // [513][100][5]: RANSAC sample indices of cv::RNG((uint64)-1) for every point count
   int msa_lds_state = 0;         // k_msa_dp_bfs opted into > 64 KB of dynamic LDS: 0 not tried, 1 yes, -1 refused
+  int32_t msa_plan[4] = {-1, 0, 0, 0};   // the last MsaDpPlan::decide on this ctx (host only, svo_debug_msa_plan): bfs, maxw, levels, lds() bytes
   int pose_lds_state = 0;       // > 64 KB dynamic-LDS opt-in of the pose kernels: 0 untried, 1 granted, -1 refused
   int track_lds_state = 0;      // same for the tracker's kernels
   std::vector<SvoPyrGroup> pyr_plan;  // the pyramid as fused launches (svo_create); empty: one launch per level

@@ -328,6 +328,11 @@ struct MsaDpPlan {
   }
   size_t lds() const { return sizeof(double) * (256 + 2 * (size_t)maxw) + sizeof(int) * (width.size() + 2); }
   void decide(svo_ctx* ctx, int D) {
+    choose(ctx, D);
+    const int32_t rec[4] = {bfs ? 1 : 0, maxw, (int32_t)width.size(), (int32_t)lds()};   // what svo_debug_msa_plan reports
+    memcpy(ctx->msa_plan, rec, sizeof rec);
+  }
+  void choose(svo_ctx* ctx, int D) {
     if (msa_level_launches() || lds() > 150 * 1024 || (size_t)64 * (D + 1) * sizeof(float) > 64 * 1024) { bfs = false; return; }
     if (ctx->msa_lds_state == 0)
       ctx->msa_lds_state = hipFuncSetAttribute(reinterpret_cast<const void*>(k_msa_dp_bfs<kMsaDpThreads>),
@@ -335,6 +340,13 @@ struct MsaDpPlan {
     bfs = bfs && (ctx->msa_lds_state > 0 || lds() <= 64 * 1024);
   }
 };
+
+extern "C" int svo_debug_msa_plan(svo_ctx* ctx, int32_t out[5]) {
+  if (!ctx || !out) return SVO_E_INVALID;
+  memcpy(out, ctx->msa_plan, sizeof ctx->msa_plan);
+  out[4] = ctx->msa_lds_state;
+  return SVO_OK;
+}
 // One aggregation (both sweeps) of the trees tabs[0 .. ntrees): two launches, or two per level
 static void msa_aggregate(hipStream_t s, const MsaTab* d_tabs, int ntrees, int N, int D, const double* d_Exp, const MsaDpPlan& p) {
   const int L = (int)p.width.size();
